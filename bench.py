@@ -122,6 +122,41 @@ def source_hash() -> str:
     return h.hexdigest()[:16]
 
 
+DUMP_BYTES_SAMPLE = 8 << 20     # float32 -> 32 MB
+DUMP_BUCKETS_SAMPLE = 1 << 20   # 3 float64 columns -> 24 MB
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir: str, index, suffix: str = "") -> dict:
+    """What the timed path hands its caller is the index the last step left. Written as .npy files (at most 64 MB in all) so that two
+    builds of the project can be compared output for output:
+      summary            float64 [count, buckets, serialized bytes]
+      index_sha256       float64 [32]: the SHA-256 of the serialized index (the bytes `save_to_file` writes), one byte per element
+      index_bytes        float32: the serialized bytes at DUMP_BYTES_SAMPLE ascending positions drawn with DUMP_SEED (all of them when fewer)
+      buckets            float64 [rows, 3]: (prefix, length, kind) of the bucket table at DUMP_BUCKETS_SAMPLE rows drawn with DUMP_SEED
+    `suffix` tells the ranks of a sharded run apart. Returns {name: shape}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    blob = index.serialize_np()
+    prefix, length, kind = index.bucket_table_np()
+
+    def rows(n, m):  # a generator of its own per array: a sample depends on that array's length alone
+        return np.arange(n, dtype=np.int64) if n <= m else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+
+    pos = rows(blob.size, DUMP_BYTES_SAMPLE)
+    brow = rows(prefix.size, DUMP_BUCKETS_SAMPLE)
+    arrays = {
+        "summary": np.array([index.count(), index.num_buckets(), blob.size], dtype=np.float64),
+        "index_sha256": np.frombuffer(hashlib.sha256(memoryview(blob)).digest(), dtype=np.uint8).astype(np.float64),
+        "index_bytes": blob[pos].astype(np.float32),
+        "buckets": np.stack([prefix[brow], length[brow], kind[brow]], axis=1).astype(np.float64),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in arrays.items()}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -161,6 +196,9 @@ def parse_args(argv=None):
     ap.add_argument("--recv-groups", type=int, default=0, help="N > 1, native bins protocol: groups per rank of the receiver (0 = default 4, 1 = ungrouped)")
     ap.add_argument("--force-sharded", action="store_true", help="dev: run the N-GPU code path on a 1-rank RCCL group")
     ap.add_argument("--shared-gpu", action="store_true", help="dry run: all ranks on GPU 0, exchange staged through gloo")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left in the index as DIR/<name>.npy (float32 / float64, at most 64 MB): "
+                         "see dump_outputs()")
     args = ap.parse_args(argv)
     if args.config is None:
         args.config = "cfg2" if args.gpus == 1 else "cfg3"
@@ -706,6 +744,10 @@ def main():
         stage_units = last().stage_units()  # words per stage over the timed steps (the bucket classes split them)
         units_alg = (count_a + count_b) * args.steps  # words of the merged runs
         extra["merge"]["words_union"] = count
+    if args.dump_outputs:  # after the timed region's figures are read, before any later leg clears or reuses the index
+        dumped = dump_outputs(args.dump_outputs, cbl if args.kind == "build" else last(), f"_rank{rank}" if world > 1 else "")
+        if rank == 0:
+            extra["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     total_units = allreduce_sum(units_per_rank_step) * args.steps
     value = total_units / dt
 

@@ -89,3 +89,20 @@ def test_full_size_parity_leg_of_the_merge_at_a_small_size():
     assert o["equal"] is True and o["sha256"] == o["sha256_oracle"] and 0 < o["bytes"] < p["bytes"]
     assert p["distinct_kmers"] == p["distinct_kmers_oracle"] == out["merge"]["words_union"]
     assert out["cpu_baseline"]["kind"] == "port" and out["cpu_baseline"]["value"] > 0 and "merge" in out["cpu_baseline"]["sample"]
+
+
+def test_dump_outputs_is_the_timed_index_and_repeats(tmp_path):
+    """`--dump-outputs DIR`: the index the last timed step left, as .npy files; the same arguments give the same files."""
+    import numpy as np
+
+    argv = ("--config", "cfg2", "--reads", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-h2d", "--no-serialize")
+    outs = [_run(*argv, "--dump-outputs", str(tmp_path / d)) for d in ("a", "b")]
+    assert all(o["steps"] == 2 and o["ms_per_step"] > 0 for o in outs)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(n + ".npy" for n in outs[0]["dump_outputs"]["arrays"]) == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert sum((tmp_path / "a" / n).stat().st_size for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    count, nbuckets, nbytes = np.load(tmp_path / "a" / "summary.npy").tolist()
+    assert count == outs[0]["distinct_kmers_in_index"] > 0 and nbuckets > 0 and nbytes > 0

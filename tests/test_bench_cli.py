@@ -98,3 +98,74 @@ def test_launcher_deadline_and_clean_exit(capsys):
     procs = [_child("import sys; sys.stdout.write('x' * 300000 + '\\n{\"ok\": 1}\\n')", stdout=subprocess.PIPE), _child("import time; time.sleep(1)")]
     assert bench.supervise_ranks(procs, 60.0) == 0
     assert capsys.readouterr().out.rstrip().endswith('{"ok": 1}')
+
+
+class _FakeIndex:
+    """Stands in for cbl_amd.CBL in dump_outputs: serialized bytes and a bucket table of the given sizes."""
+
+    def __init__(self, nbytes, nbuckets, seed=0):
+        import numpy as np
+
+        r = np.random.default_rng(seed)
+        self.blob = r.integers(0, 256, nbytes, dtype=np.uint8)
+        self.prefix = np.sort(r.choice(1 << 28, nbuckets, replace=False)).astype(np.uint32)
+        self.length = r.integers(1, 5000, nbuckets, dtype=np.uint32)
+        self.kind = r.integers(0, 2, nbuckets, dtype=np.uint8)
+
+    def serialize_np(self):
+        return self.blob
+
+    def bucket_table_np(self):
+        return self.prefix, self.length, self.kind
+
+    def count(self):
+        return int(self.length.sum())
+
+    def num_buckets(self):
+        return int(self.prefix.size)
+
+
+def test_dump_outputs_option():
+    assert bench.parse_args([]).dump_outputs is None
+    a = bench.parse_args(["--dump-outputs", "out", "--steps", "7"])
+    assert (a.dump_outputs, a.steps) == ("out", 7)
+
+
+def test_dump_outputs_small_index_is_written_whole(tmp_path):
+    import hashlib
+
+    import numpy as np
+
+    idx = _FakeIndex(5000, 300)
+    shapes = bench.dump_outputs(str(tmp_path), idx)
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(n + ".npy" for n in shapes)
+    got = {n: np.load(tmp_path / (n + ".npy")) for n in shapes}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["summary"].tolist() == [idx.count(), 300, 5000]
+    assert bytes(got["index_sha256"].astype(np.uint8)) == hashlib.sha256(idx.blob.tobytes()).digest()
+    assert np.array_equal(got["index_bytes"], idx.blob.astype(np.float32))
+    assert np.array_equal(got["buckets"], np.stack([idx.prefix, idx.length, idx.kind], axis=1).astype(np.float64))
+    bench.dump_outputs(str(tmp_path), idx, "_rank1")
+    assert (tmp_path / "summary_rank1.npy").exists()
+
+
+def test_dump_outputs_large_index_is_sampled_within_64mb(tmp_path, monkeypatch):
+    import numpy as np
+
+    # the real caps on a scaled-down index: the same rule at a size a test can afford
+    monkeypatch.setattr(bench, "DUMP_BYTES_SAMPLE", 1000)
+    monkeypatch.setattr(bench, "DUMP_BUCKETS_SAMPLE", 100)
+    idx = _FakeIndex(200_000, 5000)
+    bench.dump_outputs(str(tmp_path / "a"), idx)
+    bench.dump_outputs(str(tmp_path / "b"), idx)
+    for n in ("summary", "index_sha256", "index_bytes", "buckets"):  # the same index gives the same files
+        assert np.array_equal(np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy")))
+    b = np.load(tmp_path / "a" / "index_bytes.npy")
+    rows = np.load(tmp_path / "a" / "buckets.npy")
+    assert b.shape == (1000,) and rows.shape == (100, 3)
+    assert np.all(np.diff(rows[:, 0]) > 0)  # rows keep the table's ascending prefix order
+    assert set(rows[:, 0].astype(np.int64)) <= set(idx.prefix.astype(np.int64))
+
+
+def test_dump_outputs_caps_add_up_to_at_most_64mb():
+    assert bench.DUMP_BYTES_SAMPLE * 4 + bench.DUMP_BUCKETS_SAMPLE * 3 * 8 + (3 + 32) * 8 <= 64 << 20

@@ -20,6 +20,8 @@ import cbl_amd  # noqa: E402
 from cbl_amd import synth  # noqa: E402
 from oracle import Oracle  # noqa: E402
 
+import rank_threads  # noqa: E402  (tests/: the ranks of the one-GPU multi-rank tests in at most 5 processes)
+
 
 def _need_gpu():
     if not torch.cuda.is_available():
@@ -1739,14 +1741,11 @@ def test_parallel_index_loader(k, pb, canonical, threads, monkeypatch):
 
 
 # ---- the N-GPU code path with real device steps on ONE GPU: two processes share cuda:0, the collectives go through gloo ----
-def _two_rank_worker(rank, world, port, k, pb, canonical, protocol, per, L, q):
-    import torch.distributed as dist
-
+def _two_rank_worker(rank, world, port, k, pb, canonical, protocol, per, L, q, threaded=False):
     from cbl_amd import sharded
 
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist = rank_threads.group(rank, world, port, threaded)
     try:
         g = cbl_amd.CBL(k, pb, canonical=canonical, device=0)
         sb = sharded.ShardedBuilder(g, sharded.HostStagedGroup(dist), slices=3, protocol=protocol)
@@ -1758,7 +1757,7 @@ def _two_rank_worker(rank, world, port, k, pb, canonical, protocol, per, L, q):
         if rank == 0:
             q.put((blob, [int(x) for x in sb.bounds], g.count()))
     finally:
-        dist.destroy_process_group()
+        rank_threads.release(dist)
 
 
 @pytest.mark.parametrize("world,k,pb,canonical,protocol", [(2, 31, 24, False, "sorted"), (2, 31, 24, True, "words"), (2, 59, 28, False, "sorted"),
@@ -1778,7 +1777,7 @@ def test_two_ranks_on_one_gpu_through_a_gloo_shim(world, k, pb, canonical, proto
     s.close()
     ctx = _spawn_context()
     q = ctx.Queue()
-    procs = [ctx.Process(target=_two_rank_worker, args=(r, world, port, k, pb, canonical, protocol, per, L, q)) for r in range(world)]
+    procs = rank_threads.processes(ctx, _two_rank_worker, world, lambda r: (r, world, port, k, pb, canonical, protocol, per, L, q))
     for p in procs:
         p.start()
     blob, bounds, count0 = q.get(timeout=900)
@@ -1927,16 +1926,13 @@ def test_load_rejects_malformed_trie_and_empty_vec():
     assert e.value.code == cbl_amd.EFORMAT
 
 
-def _sharded_index_worker(rank, world, port, k, pb, canonical, per, L, slices, tmp, q):
+def _sharded_index_worker(rank, world, port, k, pb, canonical, per, L, slices, tmp, q, threaded=False):
     import sys
-
-    import torch.distributed as dist
 
     from cbl_amd import sharded
 
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist = rank_threads.group(rank, world, port, threaded)
     sharded.MAX_MSG_BYTES = 1 << 16
     try:
         grp = sharded.HostStagedGroup(dist)
@@ -1980,7 +1976,7 @@ def _sharded_index_worker(rank, world, port, k, pb, canonical, per, L, slices, t
         if rank == 0:
             q.put({n: open(os.path.join(tmp, n + ".cbl"), "rb").read() for n in "abecd"})
     finally:
-        dist.destroy_process_group()
+        rank_threads.release(dist)
 
 
 @pytest.mark.parametrize("world,k,pb,canonical,per,L,slices", [(2, 31, 24, False, 3000, 150, 2), (3, 11, 8, False, 6, 7000, 3), (2, 59, 28, True, 600, 250, 1),
@@ -2001,7 +1997,7 @@ def test_sharded_index_merge_load_save_on_one_gpu(world, k, pb, canonical, per, 
     s.close()
     ctx = _spawn_context()
     q = ctx.Queue()
-    procs = [ctx.Process(target=_sharded_index_worker, args=(r, world, port, k, pb, canonical, per, L, slices, str(tmp_path), q)) for r in range(world)]
+    procs = rank_threads.processes(ctx, _sharded_index_worker, world, lambda r: (r, world, port, k, pb, canonical, per, L, slices, str(tmp_path), q))
     for p in procs:
         p.start()
     files = q.get(timeout=1200)
@@ -2165,14 +2161,11 @@ def test_native_sharded_insert_single_rank_rccl():
     comm.close()
 
 
-def _native_worker(rank, world, port, k, pb, canonical, per, L, path, q, protocol="bins", groups=0):
-    import torch.distributed as dist
-
+def _native_worker(rank, world, port, k, pb, canonical, per, L, path, q, protocol="bins", groups=0, threaded=False):
     from cbl_amd import sharded
 
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist = rank_threads.group(rank, world, port, threaded)
     try:
         comm = cbl_amd.Comm.over_group(dist, rank, world, 0)  # host callbacks: the ranks share this GPU
         comm.set_recv_groups(groups)  # 0: the default (4 groups per rank), 1: the ungrouped receiver
@@ -2205,7 +2198,7 @@ def _native_worker(rank, world, port, k, pb, canonical, per, L, path, q, protoco
             q.put((blob, [int(x) for x in sb.bounds], g.count(), fblob, sb.stats["sent_bytes"], used, fine))
         comm.close()
     finally:
-        dist.destroy_process_group()
+        rank_threads.release(dist)
 
 
 @pytest.mark.parametrize("world,k,pb,canonical,protocol,groups", [
@@ -2244,7 +2237,7 @@ def test_native_sharded_insert_on_one_gpu_through_callbacks(world, k, pb, canoni
     s.close()
     ctx = _spawn_context()
     q = ctx.Queue()
-    procs = [ctx.Process(target=_native_worker, args=(r, world, port, k, pb, canonical, per, L, path, q, protocol, groups)) for r in range(world)]
+    procs = rank_threads.processes(ctx, _native_worker, world, lambda r: (r, world, port, k, pb, canonical, per, L, path, q, protocol, groups))
     for p in procs:
         p.start()
     blob, bounds, count0, fblob, sent, used, fine = q.get(timeout=420)
