@@ -21,6 +21,7 @@ from cbl_amd import synth  # noqa: E402
 from oracle import Oracle  # noqa: E402
 
 import rank_threads  # noqa: E402  (tests/: the ranks of the one-GPU multi-rank tests in at most 5 processes)
+import dirty_reads  # noqa: E402  (tests/: N, lower case, IUPAC ... at fixed stream positions, the same on every rank and for the oracle)
 
 
 def _need_gpu():
@@ -1741,7 +1742,7 @@ def test_parallel_index_loader(k, pb, canonical, threads, monkeypatch):
 
 
 # ---- the N-GPU code path with real device steps on ONE GPU: two processes share cuda:0, the collectives go through gloo ----
-def _two_rank_worker(rank, world, port, k, pb, canonical, protocol, per, L, q, threaded=False):
+def _two_rank_worker(rank, world, port, k, pb, canonical, protocol, per, L, q, dirty=None, threaded=False):
     from cbl_amd import sharded
 
     torch.cuda.set_device(0)
@@ -1752,6 +1753,8 @@ def _two_rank_worker(rank, world, port, k, pb, canonical, protocol, per, L, q, t
         for batch, n in enumerate(per[rank]):  # two batches; the second reuses the first one's splitters
             first = sum(per[r][bb] for r in range(world) for bb in range(batch)) + sum(per[r][batch] for r in range(rank))
             d_b, d_o = synth.reads_torch(23, n, L, first_read=first, device="cuda:0")
+            if dirty:
+                d_b = dirty_reads.dirty_torch(d_b, first * L, n * L, **dirty)
             sb.insert_seqs_device(d_b, d_o, n)
         blob = sharded.gather_serialized(g.serialize(), dist)
         if rank == 0:
@@ -1760,9 +1763,42 @@ def _two_rank_worker(rank, world, port, k, pb, canonical, protocol, per, L, q, t
         rank_threads.release(dist)
 
 
-@pytest.mark.parametrize("world,k,pb,canonical,protocol", [(2, 31, 24, False, "sorted"), (2, 31, 24, True, "words"), (2, 59, 28, False, "sorted"),
-                                                         (2, 25, 12, False, "sorted"), (4, 31, 24, False, "sorted"), (3, 31, 24, False, "words"), (8, 31, 24, False, "sorted")])
-def test_two_ranks_on_one_gpu_through_a_gloo_shim(world, k, pb, canonical, protocol):
+def _dirty_spec(per, L, k, slices, seed=17, all_n_rank=None):
+    """The dirt of a multi-rank test's job (tests/dirty_reads.py): bytes around every rank's slice cuts of every batch, and
+    optionally every byte of rank `all_n_rank`'s first batch `N` (it has reads, and contributes no k-mer)."""
+    all_n = []
+    if all_n_rank is not None:
+        a = sum(per[r][0] for r in range(all_n_rank))
+        all_n = [(a * L, (a + per[all_n_rank][0]) * L)]
+    return dict(seed=seed, L=L, k=k, cuts=dirty_reads.slice_cuts(per, L, slices), all_n=all_n)
+
+
+def _job_oracle(k, pb, canonical, per, L, seed, slices=3, dirty=None):
+    """The one-process oracle of a two-batch job: per batch, slice-major then rank-minor (the stream order of the sharded build)."""
+    from cbl_amd.sharded import ShardedBuilder
+
+    world = len(per)
+    one = Oracle(k, pb, canonical)
+    for batch in range(2):
+        first = sum(per[r][bb] for r in range(world) for bb in range(batch))
+        starts = [first + sum(per[rr][batch] for rr in range(r)) for r in range(world)]
+        sl = [ShardedBuilder.slice_bounds(per[r][batch], slices) for r in range(world)]
+        for c in range(slices):
+            for r in range(world):
+                a, b = sl[r][c]
+                if b > a:
+                    hb, ho = synth.reads(seed, b - a, L, first_read=starts[r] + a)
+                    if dirty:
+                        hb = dirty_reads.dirty_np(hb, (starts[r] + a) * L, **dirty)
+                    one.insert_seqs(hb, ho)
+    return one
+
+
+@pytest.mark.parametrize("world,k,pb,canonical,protocol,dirty", dirty_reads.cases(
+    [(2, 31, 24, False, "sorted"), (2, 31, 24, True, "words"), (2, 59, 28, False, "sorted"), (2, 25, 12, False, "sorted"), (4, 31, 24, False, "sorted"),
+     (3, 31, 24, False, "words"), (8, 31, 24, False, "sorted")],
+    [(3, 59, 28, True, "sorted"), (2, 31, 24, False, "words")]))  # N, lower case, IUPAC ... (tests/dirty_reads.py)
+def test_two_ranks_on_one_gpu_through_a_gloo_shim(world, k, pb, canonical, protocol, dirty):
     _need_gpu()
     import socket
 
@@ -1777,7 +1813,8 @@ def test_two_ranks_on_one_gpu_through_a_gloo_shim(world, k, pb, canonical, proto
     s.close()
     ctx = _spawn_context()
     q = ctx.Queue()
-    procs = rank_threads.processes(ctx, _two_rank_worker, world, lambda r: (r, world, port, k, pb, canonical, protocol, per, L, q))
+    spec = _dirty_spec(per, L, k, 3) if dirty else None
+    procs = rank_threads.processes(ctx, _two_rank_worker, world, lambda r: (r, world, port, k, pb, canonical, protocol, per, L, q, spec))
     for p in procs:
         p.start()
     blob, bounds, count0 = q.get(timeout=900)
@@ -1794,6 +1831,8 @@ def test_two_ranks_on_one_gpu_through_a_gloo_shim(world, k, pb, canonical, proto
                 a, b = sl[r][c]
                 if b > a:
                     hb, ho = synth.reads(23, b - a, L, first_read=starts[r] + a)
+                    if spec:
+                        hb = dirty_reads.dirty_np(hb, (starts[r] + a) * L, **spec)
                     one.insert_seqs(hb, ho)
     assert blob == one.serialize()
     assert len(bounds) == world - 1 and 0 < count0 < one.count()  # rank 0 owns part of the index, not all of it
@@ -2161,7 +2200,7 @@ def test_native_sharded_insert_single_rank_rccl():
     comm.close()
 
 
-def _native_worker(rank, world, port, k, pb, canonical, per, L, path, q, protocol="bins", groups=0, threaded=False):
+def _native_worker(rank, world, port, k, pb, canonical, per, L, path, q, protocol="bins", groups=0, dirty=None, files=None, threaded=False):
     from cbl_amd import sharded
 
     torch.cuda.set_device(0)
@@ -2171,13 +2210,16 @@ def _native_worker(rank, world, port, k, pb, canonical, per, L, path, q, protoco
         comm.set_recv_groups(groups)  # 0: the default (4 groups per rank), 1: the ungrouped receiver
         g = cbl_amd.CBL(k, pb, canonical=canonical, device=0)
         sb = sharded.ShardedBuilder(g, dist, slices=3, comm=comm, protocol=protocol)
-        used, fine = [], []
+        used, fine, protos = [], [], []
         for batch, n in enumerate(per[rank]):  # two batches; the second reuses the first one's splitters (and meets a non-empty index)
             first = sum(per[r][bb] for r in range(world) for bb in range(batch)) + sum(per[r][batch] for r in range(rank))
             d_b, d_o = synth.reads_torch(23, n, L, first_read=first, device="cuda:0")
+            if dirty:  # (tests/dirty_reads.py: the bytes the oracle is given for this range)
+                d_b = dirty_reads.dirty_torch(d_b, first * L, n * L, **dirty)
             sb.insert_seqs_device(d_b, d_o, n)
             used.append(comm.groups_used())
             fine.append(comm.groups_fine())
+            protos.append(comm.protocol_used())
         blob = sharded.gather_serialized(g.serialize(), dist)
         fblob = None
         if path:
@@ -2185,7 +2227,7 @@ def _native_worker(rank, world, port, k, pb, canonical, per, L, path, q, protoco
             # small file is cut into many; a given block size, then the library's choice (block = 0), then a FASTQ file
             os.environ["CBLX_FASTX_REGION_BYTES"] = "3000"
             fblob = []
-            for pth, blk in ((path, 5), (path, 0), (path + ".fq", 0), (path + ".short", 4)):
+            for pth, blk in (files or ((path, 5), (path, 0), (path + ".fq", 0), (path + ".short", 4))):
                 h = cbl_amd.CBL(k, pb, canonical=canonical, device=0)
                 sf = sharded.ShardedBuilder(h, dist, slices=3, comm=comm, protocol=protocol)
                 try:
@@ -2195,7 +2237,7 @@ def _native_worker(rank, world, port, k, pb, canonical, per, L, path, q, protoco
                     fblob.append(("error", e.code))
                     break
         if rank == 0:
-            q.put((blob, [int(x) for x in sb.bounds], g.count(), fblob, sb.stats["sent_bytes"], used, fine))
+            q.put((blob, [int(x) for x in sb.bounds], g.count(), fblob, sb.stats["sent_bytes"], used, fine) + ((protos,) if dirty else ()))
         comm.close()
     finally:
         rank_threads.release(dist)
@@ -2277,6 +2319,59 @@ def test_native_sharded_insert_on_one_gpu_through_callbacks(world, k, pb, canoni
     assert fblob[2] == (len(qrecs), oq.serialize())
 
 
+@pytest.mark.parametrize("world,k,pb,canonical,protocol,all_n_rank,fastx", [
+    (2, 31, 24, False, "bins", None, True), (3, 31, 28, True, "bins", None, False),  # (FINE bins at PREFIX_BITS > 24)
+    (4, 59, 28, False, "sorted", None, True),
+    (2, 31, 26, True, "replicate", None, True), (3, 25, 12, False, "replicate", 1, False), (4, 33, 27, False, "replicate", None, False),  # (16-byte records)
+    (8, 31, 24, False, "auto", None, False)])
+def test_native_sharded_insert_of_dirty_reads_on_one_gpu_through_callbacks(world, k, pb, canonical, protocol, all_n_rank, fastx, tmp_path):
+    """The native multi-rank build on reads with N, lower case, IUPAC and other skipped bytes (tests/dirty_reads.py: single bytes,
+    N runs up to 3 K, reads all N or with fewer than K bases, a skipped byte among the first K, dirt on both sides of every slice
+    cut, where "replicate" packs a plane group into two parts): byte-identical to the oracle on the same bytes. "replicate" builds the
+    validity plane on the device (k_pack_planes) and filters the first K bytes of a read from planes that crossed the wire; the other
+    protocols take the encode kernel's dirty chunks (k_encode_dirty_wave) through their prefix-range filter. And dirty FASTA / FASTQ
+    files through the shared parse (cblx_stage_fastx_blocks_comm), an N run across a cut into 3000-byte regions."""
+    _need_gpu()
+    import socket
+
+    L = 150 if k < 59 else 250
+    per = [(700, 2), (300, 450), (1, 600), (512, 0), (64, 64), (0, 900), (333, 5), (90, 90)][:world]
+    spec = _dirty_spec(per, L, k, 3, seed=29 + world, all_n_rank=all_n_rank)
+    path, files = None, None
+    if fastx:
+        path = str(tmp_path / "dirty.fa")
+        recs = dirty_reads.write_dirty_fastx(path, 61, 37, k=k)
+        qrecs = dirty_reads.write_dirty_fastx(path + ".fq", 62, 23, fastq=True, k=k)
+        files = ((path, 3), (path, 0), (path + ".fq", 0))
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    ctx = _spawn_context()
+    q = ctx.Queue()
+    procs = rank_threads.processes(ctx, _native_worker, world, lambda r: (r, world, port, k, pb, canonical, per, L, path, q, protocol, 0, spec, files))
+    for p in procs:
+        p.start()
+    blob, bounds, count0, fblob, sent, used, fine, protos = q.get(timeout=420)
+    for p in procs:
+        p.join(timeout=300)
+        assert p.exitcode == 0
+    # what ran: "auto" resolved; "replicate" on the empty index of batch 1, "bins" once the index is not empty (comm.hpp)
+    first = cbl_amd.Comm.auto_protocol(world) if protocol == "auto" else protocol
+    assert protos == [first, "bins" if first == "replicate" else first], protos
+    one = _job_oracle(k, pb, canonical, per, L, 23, dirty=spec)
+    assert blob == one.serialize()
+    assert len(bounds) == world - 1 and 0 < count0 < one.count() and sent > 0
+    if fastx:
+        of, oq = Oracle(k, pb, canonical), Oracle(k, pb, canonical)
+        for r in recs:
+            of.insert_seq(r)
+        for r in qrecs:
+            oq.insert_seq(r)
+        assert fblob[0] == (len(recs), of.serialize()) and fblob[1] == (len(recs), of.serialize())
+        assert fblob[2] == (len(qrecs), oq.serialize())
+
+
 @pytest.mark.parametrize("world,k,pb,canonical,groups,slices,gbps,deep", [
     (4, 31, 24, False, 0, 2, 0.0, None), (4, 31, 24, False, 1, 3, 0.0, None), (8, 31, 28, True, 6, 1, 2.0, None), (3, 59, 28, False, 4, 2, 0.0, None),
     (8, 31, 28, False, 4, 3, 0.0, "fine=0"), (2, 31, 26, True, 4, 2, 0.0, None), (8, 31, 28, False, 0, 3, 0.0, None),  # FINE bins off (three passes of 7 + 7 + 6 bits) / on
@@ -2333,8 +2428,11 @@ def test_rehearsal_of_rank_0_on_recorded_senders(world, k, pb, canonical, groups
     assert nxt >= int(bounds[0])
 
 
-@pytest.mark.parametrize("world,k,pb,canonical,tgt,slices,gbps", [(2, 31, 28, False, 1, 1, 0.0), (3, 31, 24, True, 0, 2, 1.0), (4, 59, 27, False, 2, 3, 0.0), (2, 25, 12, False, 0, 1, 0.0)])
-def test_rehearsal_of_any_rank_on_the_replicate_protocol(world, k, pb, canonical, tgt, slices, gbps, monkeypatch):
+@pytest.mark.parametrize("world,k,pb,canonical,tgt,slices,gbps,dirty", dirty_reads.cases(
+    [(2, 31, 28, False, 1, 1, 0.0), (3, 31, 24, True, 0, 2, 1.0), (4, 59, 27, False, 2, 3, 0.0), (2, 25, 12, False, 0, 1, 0.0)],
+    # N, lower case, IUPAC ... (tests/dirty_reads.py), dirt on the part cuts: the rehearsed rank in the middle, at the end
+    [(3, 31, 26, True, 1, 3, 0.0), (4, 25, 24, False, 3, 2, 0.0)]))
+def test_rehearsal_of_any_rank_on_the_replicate_protocol(world, k, pb, canonical, tgt, slices, gbps, dirty, monkeypatch):
     """"replicate" under the one-GPU rehearsal (what tools/emulate_wire.py --protocol replicate times): the other ranks record the planes and offsets
     they would send, the rehearsed rank transforms every rank's reads and keeps its prefix range — exactly the buckets of that range of the
     one-process oracle's index (stream order slice-major, rank-minor), paced wire or not."""
@@ -2344,8 +2442,11 @@ def test_rehearsal_of_any_rank_on_the_replicate_protocol(world, k, pb, canonical
     bounds = np.zeros(world - 1, dtype=np.uint32)
     valid = False
     cuts = [nr * s // slices for s in range(slices + 1)]
+    spec = dict(seed=5 + world, L=L, k=k, cuts=[(r * nr + c) * L for r in range(world) for c in cuts]) if dirty else None
     for r in [x for x in range(world) if x != tgt] + [tgt]:
         d_b, d_o = synth.reads_torch(91, nr, L, first_read=r * nr, device="cuda")
+        if spec:
+            d_b = dirty_reads.dirty_torch(d_b, r * nr * L, nr * L, **spec)
         cm = cbl_amd.Comm.sim(r, world, store, gbps if r == tgt else 0.0)
         cm.set_protocol("replicate")
         g = cbl_amd.CBL(k, pb, canonical=canonical)
@@ -2364,6 +2465,8 @@ def test_rehearsal_of_any_rank_on_the_replicate_protocol(world, k, pb, canonical
         for r in range(world):
             if cuts[c + 1] > cuts[c]:
                 hb, ho = synth.reads(91, cuts[c + 1] - cuts[c], L, first_read=r * nr + cuts[c])
+                if spec:
+                    hb = dirty_reads.dirty_np(hb, (r * nr + cuts[c]) * L, **spec)
                 one.insert_seqs(hb, ho)
     full = cbl_amd.CBL(k, pb, canonical=canonical)
     full.load(one.serialize())

@@ -19,6 +19,7 @@ from cbl_amd import synth  # noqa: E402
 from oracle import Oracle  # noqa: E402
 
 import rank_threads  # noqa: E402
+import dirty_reads  # noqa: E402  (tests/)
 
 
 def _ngpu():
@@ -33,7 +34,7 @@ def _port():
     return p
 
 
-def _worker(rank, world, port, k, pb, canonical, protocol, native, per, L, q, groups=0, shared=False, threaded=False):
+def _worker(rank, world, port, k, pb, canonical, protocol, native, per, L, q, groups=0, shared=False, dirty=None, threaded=False):
     """One rank. shared=False: its own GPU, RCCL. shared=True: GPU 0 with the other ranks, collectives staged through gloo."""
     import torch.distributed as dist
 
@@ -64,6 +65,8 @@ def _worker(rank, world, port, k, pb, canonical, protocol, native, per, L, q, gr
         for batch, n in enumerate(per[rank]):
             first = sum(per[r][bb] for r in range(world) for bb in range(batch)) + sum(per[r][batch] for r in range(rank))
             d_b, d_o = synth.reads_torch(23, n, L, first_read=first, device=f"cuda:{dev}")
+            if dirty:
+                d_b = dirty_reads.dirty_torch(d_b, first * L, n * L, **dirty)
             sb.insert_seqs_device(d_b, d_o, n)
         blob = sharded.gather_serialized(g.serialize(), dist)
         # cfg 5: a second index at other bounds, re-shard + merge
@@ -85,15 +88,16 @@ def _worker(rank, world, port, k, pb, canonical, protocol, native, per, L, q, gr
         rank_threads.release(dist)
 
 
-@pytest.mark.parametrize("world,k,pb,canonical,protocol,native,groups", [
+@pytest.mark.parametrize("world,k,pb,canonical,protocol,native,groups,dirty", dirty_reads.cases([
     (2, 31, 24, False, "sorted", False, 0), (2, 31, 24, True, "words", False, 0), (2, 59, 28, False, "sorted", True, 0),
     (4, 31, 24, False, "sorted", True, 0), (8, 31, 28, False, "sorted", False, 0),
     (2, 31, 24, False, "bins", True, 0), (4, 59, 28, True, "bins", True, 0), (8, 31, 28, False, "bins", True, 0),
     (2, 31, 24, False, "bins", True, 1), (8, 31, 28, False, "bins", True, 1), (4, 31, 24, True, "bins", True, 3),
     (2, 31, 28, False, "auto", True, 0), (8, 31, 26, True, "auto", True, 0),  # the library's choice ("replicate" on 2 - 3 ranks, "sorted" on 4); FINE bins at PREFIX_BITS > 24 on 8
     # "replicate" (round 6): the reads cross as bit planes (one grouped exchange of planes and offsets), every rank transforms all of them
-    (2, 31, 24, False, "replicate", True, 0), (3, 59, 28, True, "replicate", True, 0), (4, 31, 28, False, "replicate", True, 3), (8, 31, 26, False, "replicate", True, 0)])
-def test_sharded_build_and_merge_on_real_rccl(world, k, pb, canonical, protocol, native, groups):
+    (2, 31, 24, False, "replicate", True, 0), (3, 59, 28, True, "replicate", True, 0), (4, 31, 28, False, "replicate", True, 3), (8, 31, 26, False, "replicate", True, 0)], [
+    (2, 31, 26, True, "auto", True, 0)]))  # N, lower case, IUPAC ... (tests/dirty_reads.py), dirt on the slice cuts: "replicate" packs its planes on the device
+def test_sharded_build_and_merge_on_real_rccl(world, k, pb, canonical, protocol, native, groups, dirty):
     if _ngpu() == 0:
         pytest.fail("no GPU visible: the -m gpu tests must run on the MI355X box")
     # RCCL: a GPU and a process per rank. Otherwise every rank on GPU 0, the exchange through gloo, at most 5 processes
@@ -111,7 +115,8 @@ def test_sharded_build_and_merge_on_real_rccl(world, k, pb, canonical, protocol,
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _port()
-    procs = rank_threads.processes(ctx, _worker, world, lambda r: (r, world, port, k, pb, canonical, protocol, native, per, L, q, groups, shared))
+    spec = dict(seed=37, L=L, k=k, cuts=dirty_reads.slice_cuts(per, L, 3), all_n=[]) if dirty else None
+    procs = rank_threads.processes(ctx, _worker, world, lambda r: (r, world, port, k, pb, canonical, protocol, native, per, L, q, groups, shared, spec))
     for p in procs:
         p.start()
     blob, mblob, sent = q.get(timeout=900)
@@ -128,6 +133,8 @@ def test_sharded_build_and_merge_on_real_rccl(world, k, pb, canonical, protocol,
                 a, b = sl[r][c]
                 if b > a:
                     hb, ho = synth.reads(23, b - a, L, first_read=starts[r] + a)
+                    if spec:
+                        hb = dirty_reads.dirty_np(hb, (starts[r] + a) * L, **spec)
                     one.insert_seqs(hb, ho)
     assert blob == one.serialize() and sent > 0
 

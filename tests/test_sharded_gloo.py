@@ -14,9 +14,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
 from shard_standin import OracleEngine  # noqa: E402  (CPU stand-in for cbl_amd.sharded.GpuEngine)
+import dirty_reads  # noqa: E402  (N, lower case, IUPAC ... at fixed stream positions)
 
 
-def _worker(rank, world, port, k, pb, nreads, L, slices, protocol, q):
+def _worker(rank, world, port, k, pb, nreads, L, slices, protocol, q, dirty=None):
     sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import torch
@@ -31,6 +32,8 @@ def _worker(rank, world, port, k, pb, nreads, L, slices, protocol, q):
     try:
         per = nreads // world
         bases, offsets = synth.reads(7, per, L, first_read=rank * per)
+        if dirty:  # tests/dirty_reads.py: the same bytes the one-process build below is given
+            bases = dirty_reads.dirty_np(bases, rank * per * L, **dirty)
         orc = Oracle(k, pb)
 
         class _Cbl:  # the two attributes ShardedBuilder reads from a CBL
@@ -66,9 +69,10 @@ def _free_port():
 
 
 @pytest.mark.parametrize("protocol", ["sorted", "words"])
-@pytest.mark.parametrize("world,k,pb,nreads,L,slices", [(2, 31, 24, 240, 150, 1), (2, 31, 24, 240, 150, 3), (3, 9, 4, 600, 100, 4),
-                                                        (2, 59, 28, 120, 250, 2)])
-def test_sharded_build_equals_single_process(world, k, pb, nreads, L, slices, protocol):
+@pytest.mark.parametrize("world,k,pb,nreads,L,slices,dirty", dirty_reads.cases([(2, 31, 24, 240, 150, 1), (2, 31, 24, 240, 150, 3), (3, 9, 4, 600, 100, 4),
+                                                                                  (2, 59, 28, 120, 250, 2)],
+                                                                                 [(3, 31, 24, 1500, 150, 3)]))  # N, lower case, IUPAC ... (tests/dirty_reads.py), dirt on the slice cuts
+def test_sharded_build_equals_single_process(world, k, pb, nreads, L, slices, protocol, dirty):
     import torch.multiprocessing as mp
 
     from cbl_amd import synth
@@ -77,7 +81,16 @@ def test_sharded_build_equals_single_process(world, k, pb, nreads, L, slices, pr
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, k, pb, nreads, L, slices, protocol, q)) for r in range(world)]
+    from cbl_amd.sharded import ShardedBuilder
+
+    per = nreads // world
+    h = per // 2
+    spec = None
+    if dirty:
+        cuts = sorted({(r * per + a + c) * L for r in range(world) for a, b in ((0, h), (h, per)) for sl in ShardedBuilder.slice_bounds(b - a, slices)
+                       for c in sl})
+        spec = dict(seed=13, L=L, k=k, cuts=cuts, all_n=[((per + h) * L, (2 * per) * L)])  # rank 1's second batch: reads, no k-mer
+    procs = [ctx.Process(target=_worker, args=(r, world, port, k, pb, nreads, L, slices, protocol, q, spec)) for r in range(world)]
     for p in procs:
         p.start()
     blob, bounds, counts = q.get(timeout=300)
@@ -85,15 +98,13 @@ def test_sharded_build_equals_single_process(world, k, pb, nreads, L, slices, pr
         p.join(timeout=60)
         assert p.exitcode == 0
     # one-process build. Stream order of the sharded job: per batch, slice-major then rank-minor.
-    from cbl_amd.sharded import ShardedBuilder
-
-    per = nreads // world
-    h = per // 2
     one = Oracle(k, pb)
     for a, b in ((0, h), (h, per)):
         for sa, sb_ in ShardedBuilder.slice_bounds(b - a, slices):
             for r in range(world):
                 bases, offsets = synth.reads(7, sb_ - sa, L, first_read=r * per + a + sa)
+                if spec:
+                    bases = dirty_reads.dirty_np(bases, (r * per + a + sa) * L, **spec)
                 one.insert_seqs(bases, offsets)
     assert blob == one.serialize()
     assert len(bounds) == world - 1 and bounds == sorted(bounds)
@@ -225,14 +236,19 @@ def _worker_file(rank, world, port, k, pb, path, block, protocol, q):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,k,pb,nrec,block,protocol", [(2, 31, 24, 57, 5, "sorted"), (3, 15, 8, 40, 1, "words"), (2, 31, 24, 9, 100, "sorted"), (3, 25, 12, 2, 1, "sorted")])
-def test_sharded_build_from_one_file_has_file_order(world, k, pb, nrec, block, protocol, tmp_path):
+@pytest.mark.parametrize("world,k,pb,nrec,block,protocol,dirty", dirty_reads.cases([(2, 31, 24, 57, 5, "sorted"), (3, 15, 8, 40, 1, "words"), (2, 31, 24, 9, 100, "sorted"),
+                                                                                    (3, 25, 12, 2, 1, "sorted")],
+                                                                                   [(2, 31, 24, 30, 3, "sorted"), (3, 31, 24, 30, 2, "words")]))  # N runs, lower case, IUPAC, CRLF
+def test_sharded_build_from_one_file_has_file_order(world, k, pb, nrec, block, protocol, dirty, tmp_path):
     import torch.multiprocessing as mp
 
     from oracle import Oracle
 
     path = str(tmp_path / "reads.fa")
-    recs = _write_fasta(path, 5 + nrec, nrec)
+    if dirty:
+        recs = dirty_reads.write_dirty_fastx(path, 5 + nrec, nrec, k=k)
+    else:
+        recs = _write_fasta(path, 5 + nrec, nrec)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
