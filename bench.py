@@ -17,11 +17,16 @@ one rank; started plainly (`python bench.py --gpus 8`) this process only LAUNCHE
 quantile ranges, one exchange of the partitioned words over RCCL (cbl_amd/sharded.py); per-GPU work is fixed as N grows
 ("weak"). `--shared-gpu` runs the N ranks on ONE GPU with the exchange staged through gloo (dry run of the N-rank code).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints ONE JSON line on rank 0: the headline figure
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) with what the timed steps themselves left behind:
   roofline     - the dominant kernel group of the step (algorithmic bytes / HIP-event time vs the 8 TB/s HBM peak), and
-                 `kernels`: the same figures for every kernel group of the step
-  cpu_baseline - the CPU oracle (a C++ port of the reference algorithm, oracle/) timed on a bounded sample, 1 thread
+                 `kernels`: the same figures for every kernel group of the step (the events are recorded inside the timed steps)
   exchange     - (N > 1) world size as the process group reports it, bytes sent / received per rank, effective GB/s
+`--full` adds every leg that takes a run of its own, before or after the timed region (each with a `--no-...` switch):
+  cpu_baseline - the CPU oracle (a C++ port of the reference algorithm, oracle/) timed on a bounded sample, 1 thread
+  parity_sample, set_check (N > 1), parity_full_size (`--cpu-full`) - the index bytes / the sharded set against the oracle
+  sharded_overhead, one_gpu_same_config - the direct build of the same reads beside the N-GPU code path
+  serialize, h2d_inclusive, fasta_inclusive, per_record - the paths either side of the kernels, never `value`
 """
 from __future__ import annotations
 
@@ -179,6 +184,10 @@ def parse_args(argv=None):
                          "slice overlaps the next slice's kernels)")
     ap.add_argument("--transport", choices=["torch", "native"], default="native",
                     help="N > 1: exchange driven from Python over torch.distributed, or the whole sharded insert inside libcblx on RCCL directly")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the timed steps: cpu_baseline, parity_sample, set_check, sharded_overhead, serialize, h2d_inclusive, "
+                         "fasta_inclusive, per_record (each has a --no-... switch of its own). Without it a run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line; --cpu-full implies it")
     ap.add_argument("--cpu-sample-reads", type=int, default=None,
                     help="reads of the CPU leg (default: about 20-30 s of CPU work: 1 M at PREFIX_BITS <= 24, 125 k at 28, 60 k at K = 59)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0,
@@ -200,6 +209,10 @@ def parse_args(argv=None):
                     help="after the timed steps, write what the last step left in the index as DIR/<name>.npy (float32 / float64, at most 64 MB): "
                          "see dump_outputs()")
     args = ap.parse_args(argv)
+    args.full = args.full or args.cpu_full
+    if not args.full:  # a plain run: the timed steps and the line they give, no leg beside them
+        args.no_cpu_baseline = args.no_parity_sample = args.no_set_check = args.no_serialize = True
+        args.no_h2d = args.no_fasta = args.no_per_record = True
     if args.config is None:
         args.config = "cfg2" if args.gpus == 1 else "cfg3"
     if args.protocol is None:
@@ -849,7 +862,7 @@ def main():
 
     # what the N-GPU code path costs a rank over the direct build of the same reads (no exchange, no slices): the direct steps
     # run AFTER the timed region, each rank on its own reads
-    if args.kind == "build" and engine is not None:
+    if args.kind == "build" and engine is not None and args.full:
         cbl.clear()
         cbl.insert_seqs_device(d_bases, d_offsets, NR)  # warm-up of the direct path's allocations
         fence()

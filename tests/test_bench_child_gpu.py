@@ -1,6 +1,7 @@
 """bench.py run the way the driver runs it — a child process, the launcher's own rank children — on one GPU: `--gpus 2 --shared-gpu`
 is the dry run of the N-rank line (ranks share GPU 0, exchange staged through gloo), `--cpu-full` the full-size parity leg at a size
-the oracle finishes in seconds. First contact of `python bench.py --gpus N` must not be the 8-GPU box."""
+the oracle finishes in seconds. First contact of `python bench.py --gpus N` must not be the 8-GPU box. A plain run carries the headline
+figure alone; the legs beside the timed steps are asked for with `--full`."""
 import json
 import os
 import subprocess
@@ -23,7 +24,7 @@ def _run(*argv, timeout=900):
 
 @pytest.mark.parametrize("config", ["cfg3", "cfg2", "merge"])
 def test_two_rank_line_through_the_launcher(config):
-    out = _run("--gpus", "2", "--shared-gpu", "--config", config, "--reads", "20000", "--steps", "1", "--warmup", "0",
+    out = _run("--full", "--gpus", "2", "--shared-gpu", "--config", config, "--reads", "20000", "--steps", "1", "--warmup", "0",
                "--cpu-sample-reads", "2000", "--launch-timeout", "600")
     assert out["n_gpus"] == 2 and out["steps"] == 1 and out["scaling"] == "weak" and out["value"] > 0
     assert out["roofline"] and out["roofline"]["bound"] == "hbm" and out["roofline"]["kernels"]
@@ -53,9 +54,33 @@ def test_two_rank_line_through_the_launcher(config):
     assert all(r["frac"] is None or r["frac"] <= 1.0 for r in out["roofline"]["kernels"])
 
 
+# what a leg beside the timed steps puts on the line: a plain run has none of them
+SIDE_LEGS = ("parity_sample", "parity_full_size", "set_check", "sharded_overhead", "one_gpu_same_config", "scaling_vs_one_gpu_same_config",
+             "serialize", "fasta_inclusive", "per_record")
+
+
+def test_plain_line_is_the_headline_figure_alone():
+    """Without `--full` a run times its steps and prints the line: the headline keys mean what they always did, the figures the timed steps
+    leave behind (roofline, count) are there, and no leg that takes a run of its own has run. `--full` brings them back."""
+    argv = ("--gpus", "1", "--config", "cfg2", "--reads", "40000", "--steps", "2", "--warmup", "1")
+    out = _run(*argv)
+    assert out["metric"] == "k-mers inserted/sec (build index)" and out["unit"] == "k-mers/s" and out["higher_is_better"] is True and out["dtype"] == "u64"
+    assert (out["n_gpus"], out["steps"], out["warmup"]) == (1, 2, 1) and out["ms_per_step"] > 0
+    # value = k-mers of a step / time of a step (ms_per_step is rounded to a microsecond: well within 1 % at this size)
+    assert abs(out["value"] - 40000 * 120 / (out["ms_per_step"] * 1e-3)) <= 0.01 * out["value"]
+    assert 0 < out["distinct_kmers_in_index"] <= 40000 * 120
+    assert out["roofline"] and out["roofline"]["kernels"] and "roofline_error" not in out
+    assert out["cpu_baseline"] is None and out["h2d_inclusive"] is None and out["value_h2d_inclusive"] is None and out["exchange"] is None
+    assert not [k for k in SIDE_LEGS if k in out]
+    full = _run(*argv, "--full", "--cpu-sample-reads", "5000", "--no-h2d")
+    assert full["cpu_baseline"]["value"] > 0 and full["serialize"]["bytes"] > 0 and full["parity_sample"]["equal"] is True
+    same = ("metric", "unit", "higher_is_better", "dtype", "config", "distinct_kmers_in_index")
+    assert {k: full[k] for k in same} == {k: out[k] for k in same}
+
+
 def test_default_line_carries_parity_sample():
-    """The driver's N = 1 line: the CPU leg's sample is built once more on the GPU after the timed region and byte-compared with the oracle's index of it."""
-    out = _run("--config", "cfg2", "--reads", "40000", "--steps", "1", "--warmup", "0", "--cpu-sample-reads", "5000", "--no-h2d")
+    """The N = 1 line of a `--full` run: the CPU leg's sample is built once more on the GPU after the timed region and byte-compared with the oracle's index of it."""
+    out = _run("--full", "--config", "cfg2", "--reads", "40000", "--steps", "1", "--warmup", "0", "--cpu-sample-reads", "5000", "--no-h2d")
     ps = out["parity_sample"]
     assert ps["equal"] is True and ps["reads"] == 5000 and ps["sha256"] == ps["sha256_oracle"] and ps["bytes"] == ps["bytes_oracle"] > 0
     assert ps["distinct_kmers"] == ps["distinct_kmers_oracle"] <= 5000 * 120
@@ -72,7 +97,7 @@ def test_launcher_reports_a_failing_rank():
 
 
 def test_full_size_parity_leg_at_a_small_size():
-    out = _run("--config", "cfg2", "--reads", "30000", "--steps", "1", "--warmup", "0", "--cpu-full", "--no-h2d")
+    out = _run("--full", "--config", "cfg2", "--reads", "30000", "--steps", "1", "--warmup", "0", "--cpu-full", "--no-h2d")
     p = out["parity_full_size"]
     assert p["equal"] is True and p["sha256"] == p["sha256_oracle"] and p["bytes"] == p["bytes_oracle"] > 0
     assert p["distinct_kmers"] == p["distinct_kmers_oracle"] == out["distinct_kmers_in_index"]
@@ -82,7 +107,7 @@ def test_full_size_parity_leg_at_a_small_size():
 def test_full_size_parity_leg_of_the_merge_at_a_small_size():
     """`--config merge --cpu-full`: the oracle builds both operands, merges them, and BOTH resulting indexes are byte-compared (the merged one
     and other, whose Vec buckets the merge sorted); the CPU baseline of that line is the oracle's merge."""
-    out = _run("--config", "merge", "--reads", "30000", "--steps", "2", "--warmup", "1", "--cpu-full", "--no-h2d")
+    out = _run("--full", "--config", "merge", "--reads", "30000", "--steps", "2", "--warmup", "1", "--cpu-full", "--no-h2d")
     p = out["parity_full_size"]
     assert p["equal"] is True and p["sha256"] == p["sha256_oracle"] and p["bytes"] == p["bytes_oracle"] > 0
     o = p["other_after_merge"]

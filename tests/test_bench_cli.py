@@ -27,6 +27,19 @@ def test_defaults_follow_the_contract():
     assert (a.steps, a.warmup) == (3, 1)
 
 
+def test_legs_beside_the_timed_steps_run_with_full_only():
+    legs = ("no_cpu_baseline", "no_parity_sample", "no_set_check", "no_serialize", "no_h2d", "no_fasta", "no_per_record")
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and all(getattr(a, n) for n in legs)
+    a = bench.parse_args(["--full"])
+    assert a.full is True and not any(getattr(a, n) for n in legs)
+    a = bench.parse_args(["--full", "--no-h2d", "--no-serialize"])  # a leg's own switch still takes it out of a full run
+    assert [n for n in legs if getattr(a, n)] == ["no_serialize", "no_h2d"]
+    a = bench.parse_args(["--cpu-full"])  # the oracle on the whole workload is a leg of the full run: asking for it asks for that
+    assert a.full is True and a.cpu_full is True and not a.no_cpu_baseline
+    assert bench.parse_args(["--no-cpu-baseline", "--no-h2d"]).full is False
+
+
 def test_algorithmic_bytes_of_cfg2():
     alg = bench.stage_alg_bytes(31, 24, 150)
     assert alg["radix_scatter"] == 18 + 17 + 16  # pass A reads 9 + writes 8 (+1 side channel), B 8 + 8 + 1, C 8 + 8

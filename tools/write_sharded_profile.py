@@ -21,7 +21,7 @@ for f in sorted(glob.glob(f"gpurun_out/{tag}/sharded_*.json")):
     rows.append((cfg, proto, so["direct_ms"], so["sharded_ms"], so["ratio"], extra))
 rows.sort()
 md = [f"# {rnd} — what the N-GPU code path costs ONE rank (1-rank RCCL group on one MI355X)\n",
-      "`python bench.py --gpus 1 --force-sharded --config <cfg> --protocol <p> --transport native|torch --steps 5 --warmup 2` (tools/r3_lines.sh sharded).",
+      "`python bench.py --full --gpus 1 --force-sharded --config <cfg> --protocol <p> --transport native|torch --steps 5 --warmup 2` (tools/r3_lines.sh sharded).",
       "`direct` = `cblx_insert_seqs_device` of the same reads in the same process, after the timed region. One rank: every word is an \"own\" word, so the",
       "figures are the protocol's fixed costs (slices, bins / batches, receive arena, piece tables, merge), not the wire.\n",
       "| config | protocol | direct ms | sharded ms | ratio | stages that differ by >= 0.3 ms (sharded - direct) |", "|---|---|---|---|---|---|"]
