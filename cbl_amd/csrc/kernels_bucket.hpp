@@ -123,10 +123,7 @@ __device__ __forceinline__ bool dir_lookup(const DirView& d, u32 p, u64& rank) {
 enum { CLS_M16 = 0, CLS_M64 = 1, CLS_M128 = 2, CLS_M256 = 3, CLS_M512 = 4, CLS_M1024 = 5, CLS_HUGE = 6, CLS_S16 = 7, CLS_S32 = 8, CLS_BIG = 9, CLS_M32 = 10, CLS_N = 11 };
 // CLS_M32 (round 6, the build only): runs of 129 - 256 words as 64 threads x FOUR slots. In the 512-slot class they paid for eight slots per lane
 // — the phases are unrolled over the slots — and at PREFIX_BITS = 28 nearly all of that class is this short (cfg 3: 3.97 M of its 4.02 M runs):
-// 3.51 -> 2.53 ms on the same runs (tools/dev_msd_bench.cpp -DMSD_BENCH_SPLIT). 0 = the classes of rounds 1 - 5.
-#ifndef CBLX_CLASS_256
-#define CBLX_CLASS_256 1
-#endif
+// 3.51 -> 2.53 ms on the same runs (tools/dev_msd_bench.cpp -DMSD_BENCH_SPLIT).
 // Runs longer than one workgroup's LDS sort takes (> 4096) and up to BIG_MAX: split by the top suffix bits into sub-ranges of
 // about a thousand words in scratch, each sorted + deduplicated by k_bucket_msd, then collected in order (k_big_*). Such
 // buckets are the rule, not the exception, once an index holds tens of millions of reads at PREFIX_BITS = 24 (one rank of an
@@ -179,8 +176,7 @@ static const int CLASSIFY_THREADS = 1024;
 
 __global__ __launch_bounds__(CLASSIFY_THREADS) void k_classify(u64 nb, u32 lds_max /* longest run one workgroup sorts in LDS */, const u32* __restrict__ bucket_prefix, const u64* __restrict__ raw_start,
                                                                 DirView old, u32* __restrict__ res_count, u8* __restrict__ res_kind, u32* __restrict__ out_count,
-                                                                u8* __restrict__ out_kind, BDesc* __restrict__ lists /* [CLS_N][nb] */, u32* __restrict__ list_n,
-                                                                const u8* __restrict__ span_done = nullptr /* buckets a clean span settled already (k_bucket_span) */) {
+                                                                u8* __restrict__ out_kind, BDesc* __restrict__ lists /* [CLS_N][nb] */, u32* __restrict__ list_n) {
     const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     int cls = -1;
     u64 c = 0;
@@ -192,8 +188,7 @@ __global__ __launch_bounds__(CLASSIFY_THREADS) void k_classify(u64 nb, u32 lds_m
         if (dir_lookup(old, bucket_prefix[r], orank)) { rc = old.count[orank]; rk = old.kind[orank]; }
         res_count[r] = rc;
         res_kind[r] = rk;
-        if (span_done && span_done[r]) {  // no repeat in the whole span it belongs to: count and kind are written, the words stay where they are
-        } else if (rc != 0 && c == rc) {  // untouched by this batch: keep as is (src/wordset/mod.rs:213-214 only re-checks touched buckets)
+        if (rc != 0 && c == rc) {  // untouched by this batch: keep as is (src/wordset/mod.rs:213-214 only re-checks touched buckets)
             out_count[r] = rc;
             out_kind[r] = rk;
         } else if (c == 1 && rc == 0) {  // a single new word: nothing to deduplicate, it already sits in its slot
@@ -201,7 +196,7 @@ __global__ __launch_bounds__(CLASSIFY_THREADS) void k_classify(u64 nb, u32 lds_m
             out_kind[r] = KIND_VEC;
         } else if (c <= SMALL_MAX && rk != KIND_TRIE) cls = c <= 16 ? CLS_S16 : CLS_S32;  // lanes per bucket: 16 / 32
         else if (c <= 16 * MED_ITEMS) cls = CLS_M16;
-        else if (CBLX_CLASS_256 && c <= 32 * MED_ITEMS) cls = CLS_M32;  // one wave, four slots per lane
+        else if (c <= 32 * MED_ITEMS) cls = CLS_M32;  // one wave, four slots per lane
         else if (c <= 64 * MED_ITEMS) cls = CLS_M64;    // workgroup size follows the run length: THREADS = CAP / 8
         else if (c <= 128 * MED_ITEMS) cls = CLS_M128;
         else if (c <= 256 * MED_ITEMS && c <= lds_max) cls = CLS_M256;
@@ -927,142 +922,14 @@ __global__ __launch_bounds__(THREADS) void k_bucket_medium(const BDesc* __restri
     }
 }
 
-// ---- clean spans (round 6; a measured switch, OFF by default: CBLX_SPANS=1): many SHORT runs settled by one workgroup, when none holds a repeat ----
-// At PREFIX_BITS = 28 a bucket holds 90 words: 14 M one-wave workgroups at cfg 3 on one GPU, each a chain of launch -> scalar loads -> the
-// HBM round trip of 600 bytes -> a dozen LDS phases (3.2 us of wave life at 96 % occupancy, DESIGN_HISTORY.md §3.13) — for runs that, in a
-// batch of distinct k-mers, need NOTHING: no repeat means count = run length, kind = Vec, the words stay where they are. A SPAN is a maximal
-// stretch of consecutive buckets that are all short new runs (2 .. SPAN_MAX_RUN words, empty index) and start inside one aligned block of
-// SPAN_BLOCK arena positions: at most SPAN_CAP words. One workgroup loads the span's words coalesced and inserts a 64-bit fingerprint of
-// (bucket number inside the span, suffix) of every word into an LDS table (compare-and-swap, linear probing, two slots per word): if no
-// fingerprint was there already, no two words of any bucket of the span are equal — exact — and all its buckets are final. Any hit (a
-// repeat, or two words sharing a fingerprint: 2^-43 per span) leaves the span to the kernels below, bucket by bucket, untouched: this kernel
-// writes counts and kinds only, never a word. Spans of fewer than SPAN_MIN_RUNS buckets are left alone too (one bucket per workgroup is what
-// the other kernels do). k_classify then skips the settled buckets.
-static const u32 SPAN_BLOCK = 1024, SPAN_MAX_RUN = 512, SPAN_CAP = SPAN_BLOCK + SPAN_MAX_RUN, SPAN_MIN_RUNS = 3, SPAN_THREADS = 256, SPAN_SLOTS = 4096;
-__device__ __forceinline__ bool span_eligible(const u64* __restrict__ raw_start, u64 nb, u64 r) {
-    if (r >= nb) return false;
-    const u64 c = raw_start[r + 1] - raw_start[r];
-    return c >= 2 && c <= SPAN_MAX_RUN;
-}
-// span heads: an eligible bucket whose predecessor is not eligible or starts in another block; cont[r] = bucket r continues its predecessor's span
-__global__ __launch_bounds__(CLASSIFY_THREADS) void k_span_heads(u64 nb, const u64* __restrict__ raw_start, u32* __restrict__ heads, u32* __restrict__ nheads, u8* __restrict__ cont) {
-    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    int cls = -1;
-    if (r < nb) {
-        const bool el = span_eligible(raw_start, nb, r);
-        const bool head = el && (r == 0 || !span_eligible(raw_start, nb, r - 1) || raw_start[r - 1] / SPAN_BLOCK != raw_start[r] / SPAN_BLOCK);
-        cont[r] = el && !head ? 1 : 0;
-        if (head) cls = 0;
-    }
-    const u32 slot = block_append<CLASSIFY_THREADS, 1>(cls, nheads);
-    if (cls == 0) heads[slot] = (u32)r;
-}
-// (32-bit fingerprints: two words of a span share one with probability n^2 / 2^33 — 3 spans in 10 000 go the long way for nothing — and the table
-// is 16 KB: eight workgroups per CU. The chain of dependent HBM round trips is what a span costs, so everything a workgroup needs is requested at
-// once: the continuation flags and starts of the buckets behind the head, and SPAN_CAP words from the head's first word on, before it knows where
-// the span ends.)
-template <bool WS, typename HiT>
-__global__ __launch_bounds__(SPAN_THREADS) void k_bucket_span(const u32* __restrict__ heads, const u32* __restrict__ nheads, u64 nb, const u64* __restrict__ raw_start,
-                                                            const u8* __restrict__ cont, const u64* __restrict__ lo, const HiT* __restrict__ hi, u32 SB, u32* __restrict__ out_count,
-                                                            u8* __restrict__ out_kind, u8* __restrict__ span_done) {
-    constexpr int ITEMS = (SPAN_CAP + SPAN_THREADS - 1) / SPAN_THREADS;  // 6
-    constexpr int LOOK = (SPAN_BLOCK / 2 + 2 + SPAN_THREADS - 1) / SPAN_THREADS;  // buckets behind the head, per thread (runs of two words: 513 of them) = 3
-    constexpr u32 HW = SPAN_CAP / 64 + 1;
-    __shared__ u32 s_tab[SPAN_SLOTS];
-    __shared__ u64 s_heads[HW + 1];  // bit q: a bucket starts at word q of the span
-    __shared__ u32 s_hpre[HW + 1];
-    __shared__ u32 s_r1, s_end, s_hit;
-    if (blockIdx.x >= *nheads) return;
-    const u32 tid = threadIdx.x;
-    const u64 r0 = heads[blockIdx.x];
-    const u64 total = raw_start[nb];
-    const u64 a0 = raw_start[r0];
-    if (tid == 0) { s_r1 = 0xFFFFFFFFu; s_end = 0; s_hit = 0; }
-    for (u32 i = tid; i < HW + 1; i += SPAN_THREADS) s_heads[i] = 0;
-    for (u32 i = tid * 4; i < SPAN_SLOTS; i += SPAN_THREADS * 4) *reinterpret_cast<uint4*>(&s_tab[i]) = uint4{~0u, ~0u, ~0u, ~0u};
-    // -- one batch of requests: flags + starts of the buckets behind the head, the words
-    u32 ct[LOOK];
-    u64 st[LOOK];
-#pragma unroll
-    for (int k = 0; k < LOOK; ++k) {
-        const u64 r = r0 + 1 + tid + (u32)k * SPAN_THREADS;
-        ct[k] = r < nb ? cont[r] : 0u;
-        st[k] = raw_start[r <= nb ? r : nb];
-    }
-    const u64* __restrict__ wl = lo + a0;
-    const HiT* __restrict__ wh = WS ? hi + a0 : nullptr;
-    Sfx<WS> key[ITEMS];
-    const u32 nmax = total - a0 < SPAN_CAP ? (u32)(total - a0) : SPAN_CAP;
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-        const u32 e = j * SPAN_THREADS + tid;
-        key[j] = load_sfx<WS, HiT>(wl, wh, e < nmax ? e : 0u, SB);
-    }
-    __syncthreads();
-    // -- the span's members: buckets r0 .. r0 + s_r1 (s_r1 = the first bucket behind the head that does not continue it)
-#pragma unroll
-    for (int k = 0; k < LOOK; ++k)
-        if (!ct[k]) { atomicMin(&s_r1, tid + (u32)k * SPAN_THREADS); break; }
-    __syncthreads();
-    const u32 nruns = s_r1 + 1u;
-    if (nruns < SPAN_MIN_RUNS) return;
-#pragma unroll
-    for (int k = 0; k < LOOK; ++k) {
-        const u32 i = tid + (u32)k * SPAN_THREADS;
-        if (i < s_r1) atomicOr(reinterpret_cast<unsigned long long*>(&s_heads[(st[k] - a0) >> 6]), 1ull << ((st[k] - a0) & 63));
-        else if (i == s_r1) s_end = (u32)(st[k] - a0);  // where the bucket behind the span starts
-    }
-    __syncthreads();
-    const u32 n = s_end;  // <= SPAN_CAP
-    if (tid < 64) {  // exclusive prefix of the bucket-start bits per 64-bit word
-        const u32 v = tid < HW ? (u32)__builtin_popcountll(s_heads[tid]) : 0u;
-        const u32 inc = wave_inclusive_scan(v);
-        if (tid < HW) s_hpre[tid] = inc - v;
-    }
-    __syncthreads();
-    bool hit = false;
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-        const u32 e = j * SPAN_THREADS + tid;
-        if (e < n && !*reinterpret_cast<volatile u32*>(&s_hit)) {
-            // bucket number of word e inside the span = bucket starts at or before e (the head's own start carries no bit)
-            const u32 b = s_hpre[e >> 6] + (u32)__builtin_popcountll(s_heads[e >> 6] & ((e & 63) == 63 ? ~0ull : ((2ull << (e & 63)) - 1ull)));
-            u64 f64 = key[j].lo * 0x9E3779B97F4A7C15ull + (u64)b * 0xD6E8FEB86659FD93ull;
-            if constexpr (WS) f64 ^= (key[j].hi + 0x2545F4914F6CDD1Dull) * 0xBF58476D1CE4E5B9ull;
-            f64 ^= f64 >> 29; f64 *= 0x94D049BB133111EBull; f64 ^= f64 >> 32;
-            u32 f = (u32)f64;
-            if (f == ~0u) f = 0;  // (the empty mark)
-            u32 h = (u32)(f64 >> 40) & (SPAN_SLOTS - 1);
-            for (;;) {
-                const u32 old = atomicCAS(&s_tab[h], ~0u, f);
-                if (old == ~0u) break;
-                if (old == f) { hit = true; break; }
-                h = (h + 1u) & (SPAN_SLOTS - 1);
-            }
-            if (hit) s_hit = 1u;  // (the others stop early: a batch full of repeats pays for a fraction of its spans)
-        }
-    }
-    if (__syncthreads_or((hit || s_hit) ? 1 : 0)) return;  // a repeat (or a shared fingerprint): the span's buckets take the kernels below
-    // (the members' lengths from the starts this thread holds: bucket r0 + 1 + i runs from st[k] to its successor's start — re-read, L2-warm)
-    for (u32 i = tid; i < nruns; i += SPAN_THREADS) {
-        const u64 r = r0 + i;
-        out_count[r] = (u32)(raw_start[r + 1] - raw_start[r]);
-        out_kind[r] = KIND_VEC;
-        span_done[r] = 1;
-    }
-}
-
 // ---- KRN-3 fast path: one workgroup per bucket, run <= CAP. Suffixes of one prefix are close to uniformly spread,
 // so one counting-sort step on their top ceil(log2 c) bits leaves sub-buckets of ~1 element; each element then ranks
 // itself inside its sub-bucket by (suffix, stream index) with a handful of compares. O(c) LDS work instead of
 // SUFFIX_BITS/8 radix passes. A bucket whose largest sub-bucket exceeds MSD_LIMIT (heavy duplication / repeats) is
 // handed to the radix kernel through `retry` untouched. -------------------------------------------------------------
-#ifndef CBLX_MSD_LIMIT
-#define CBLX_MSD_LIMIT 48
-#endif
 // (suffixes wider than 64 bits — K >= 57 or so — come with longer reads and clusters of up to K mates: their fallback is a radix sort
 // of 13 passes, so they give up later: cfg 4 at the bucket depth of an 8-GPU job 87 -> 73 ms)
-static const u32 MSD_LIMIT = CBLX_MSD_LIMIT, MSD_LIMIT_WIDE = 2 * CBLX_MSD_LIMIT, MSD_LIMIT_HASHED = 16;
+static const u32 MSD_LIMIT = 48, MSD_LIMIT_WIDE = 2 * MSD_LIMIT, MSD_LIMIT_HASHED = 16;
 
 template <bool WS> __device__ __forceinline__ u32 sfx_top_bits(const Sfx<WS>& k, u32 SB, u32 nbits) {
     if constexpr (WS) {
@@ -1103,40 +970,9 @@ template <bool WS> __device__ __forceinline__ bool sfx_less(const Sfx<WS>& a, u3
 // PACKED (SUFFIX_BITS + 12 <= 64, narrow suffix): an element is ONE u64 = suffix << 12 | stream index, so every LDS
 // access, compare and move handles key and index together (the kernel is LDS-throughput-bound).
 static const u32 PK_BITS = 12;  // CAP <= 4096
-#ifndef CBLX_MSD_TRIP
-#define CBLX_MSD_TRIP 3  // measured at cfg 2: 2 -> 6.87 ms, 3 -> 6.66 ms, 4 -> 6.86 ms, 8 -> +0.8 ms
-#endif
-static const int MSD_TRIP = CBLX_MSD_TRIP;  // sub-bucket entries read per trip of the ranking loop (<= the 4 slack entries)
-#ifndef CBLX_MSD_REUSE_BASE
-#define CBLX_MSD_REUSE_BASE 0  // measured (profiles/r02_variants.md): +0.15 ms — eight more live registers cost more than the LDS read
-#endif
-#ifndef CBLX_MSD_SKIP_SELF
-#define CBLX_MSD_SKIP_SELF 0  // measured (cfg 2): 6.73 -> 8.23 ms — per-read lane masks cost more issue time than the bank conflicts they avoid
-#endif
-#ifndef CBLX_MSD_SKIP_SINGLE
-#define CBLX_MSD_SKIP_SINGLE 1  // a lane alone in its sub-bucket does not enter the ranking loop
-#endif
-#ifndef CBLX_MSD_PROBE
-#define CBLX_MSD_PROBE 0  // > 0: timing probes that leave phases out (tools/variants.sh); never in the product build
-#endif
-#ifndef CBLX_MSD_PROBE_MERGE
-#define CBLX_MSD_PROBE_MERGE 0  // 1: probes 1 - 3 only touch `self |= other` launches (the two indexes in front of a merge bench stay right); 4 / 5 are merge-only anyway
-#endif
-#if (CBLX_MSD_PROBE || CBLX_ENC_PROBE) && !defined(CBLX_TIMING_PROBES)
-#error "CBLX_MSD_PROBE / CBLX_ENC_PROBE leave phases out and produce wrong results: timing builds only (-DCBLX_TIMING_PROBES)"
-#endif
-#ifndef CBLX_MSD_MERGE_REUSE
-#define CBLX_MSD_MERGE_REUSE 0
-#endif
-#ifndef CBLX_MSD_MERGE_WAVES
-#define CBLX_MSD_MERGE_WAVES 7
-#endif
-#ifndef CBLX_MSD_PRECHECK
-#define CBLX_MSD_PRECHECK 0  // measured (round 6, tools/dev_msd_bench.cpp at PREFIX_BITS = 28): 4.203 against 4.209 ms — the class is not bound by what follows the loads
-#endif
-#ifndef CBLX_MSD_WAVES
-#define CBLX_MSD_WAVES 7  // waves per SIMD the register allocation aims at (LDS allows 7 workgroups of the 256-thread class; 76 -> 72 VGPRs: 7.28 -> 7.10 ms)
-#endif
+static const int MSD_TRIP = 3;  // sub-bucket entries read per trip of the ranking loop (<= the 4 slack entries); measured at cfg 2: 2 -> 6.87 ms, 3 -> 6.66 ms, 4 -> 6.86 ms, 8 -> +0.8 ms
+// waves per SIMD the register allocation aims at (LDS allows 7 workgroups of the 256-thread class; 76 -> 72 VGPRs: 7.28 -> 7.10 ms)
+static const int MSD_WAVES = 7, MSD_MERGE_WAVES = 7;
 
 // MERGE: the instantiation `self |= other` launches (its epilogue keeps a dozen more registers live, which the build's
 // instantiation must not pay for: 6.8 -> 7.0 ms at cfg 2 when the two shared one kernel)
@@ -1153,13 +989,13 @@ template <bool WS> __host__ __device__ inline bool msd_takes(u32 SB) { return !W
 // The occupancy every instantiation is compiled FOR = what the register allocator can meet (round 5: all of them asked for 7 and 26 of
 // them got 4 - 6 with a warning each, so a register regression in one of them would have gone unnoticed): 16-byte elements (WS) take 4
 // waves per SIMD (5 in the shortest build class that has them), the unpacked 2048- and 4096-slot classes and the packed 4096-slot one
-// 5 - 6, everything else CBLX_MSD_WAVES.
+// 5 - 6, everything else MSD_WAVES.
 template <int CAP, bool PACKED, bool WS, bool MERGE> constexpr int msd_waves() {
-    if (WS) return CAP <= 128 ? CBLX_MSD_WAVES : ((CAP <= 512 && !MERGE) ? 5 : 4);
+    if (WS) return CAP <= 128 ? MSD_WAVES : ((CAP <= 512 && !MERGE) ? 5 : 4);
     if (CAP >= 4096) return PACKED ? 6 : 5;
     if (CAP >= 2048 && !PACKED) return MERGE ? 5 : 6;
-    if (MERGE && CAP > 128) return CBLX_MSD_MERGE_WAVES;
-    return CBLX_MSD_WAVES;
+    if (MERGE && CAP > 128) return MSD_MERGE_WAVES;
+    return MSD_WAVES;
 }
 template <int THREADS, int CAP, bool PACKED, bool WS, typename HiT, bool MERGE = false>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_waves<CAP, PACKED, WS, MERGE>(), 8))) void k_bucket_msd(const BDesc* __restrict__ list, const u32* __restrict__ list_n,
@@ -1183,9 +1019,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
     __shared__ u32 s_max;
     __shared__ u32 s_sel[MERGE ? NW : 1];  // merge epilogue: per-wave counts of its three selections (10-bit fields)
     static_assert(!MERGE || 64 * ITEMS < 1024, "the merge epilogue counts a wave's selections in 10-bit fields: a wave owns fewer than 1024 slots");
-    // distinctness pre-check of the shortest class (below): 2^15 bits
-    constexpr bool PRECHECK = CBLX_MSD_PRECHECK && CAP <= 128 && !MERGE;
-    __shared__ u32 s_bits[PRECHECK ? 1024 : 1];
 
     if (blockIdx.x >= *list_n) return;
     const BDesc dsc = list[blockIdx.x];
@@ -1275,28 +1108,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
             key[j] = load_sfx<WS, HiT>(lo, hi, s0 + ee, SB);
         }
     }
-    if constexpr (PRECHECK) {
-        // (measured switch, off) A run of at most 128 words that can only end up a Vec (cfg 3 on one GPU: 9.8 M of them, 77 words each, a wave
-        // per run) and holds no repeat needs none of the phases below: nothing is written, the count is the run length. A test that can only err
-        // on the safe side: every word sets the bit of a 15-bit hash of its suffix in a 4 KB LDS table (atomicOr returns the old word); if no bit
-        // was already set, no two suffixes are equal (91 % of the runs of 77 distinct words) and the run is done; otherwise the counting sort
-        // decides exactly as before. Bit-identical, and worth nothing: the wave's life (3.2 us at 96 % occupancy) is its launch, its scalar loads
-        // and the HBM round trip of its words, not the 400 instructions this saves (DESIGN_HISTORY.md §3.13).
-        if (vec_only) {
-            for (u32 i = tid * 4; i < 1024; i += THREADS * 4) *reinterpret_cast<uint4*>(&s_bits[i]) = uint4{0, 0, 0, 0};
-            __syncthreads();
-            bool hit = false;
-#pragma unroll
-            for (int j = 0; j < ITEMS; ++j) {
-                const u32 h = sfx_hash_bits<WS>(key[j], 15);
-                if (valid[j]) hit |= (atomicOr(&s_bits[h >> 5], 1u << (h & 31u)) >> (h & 31u)) & 1u;
-            }
-            if (!__syncthreads_or(hit ? 1 : 0)) {
-                if (tid == 0) { out_count[r] = c; out_kind[r] = KIND_VEC; }
-                return;
-            }
-        }
-    }
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
         sub[j] = vec_only ? sfx_hash_bits<WS>(key[j], nbits) : sfx_bits_below<WS>(key[j], SB, skip, nbits);
@@ -1336,12 +1147,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
         }
     }
     __syncthreads();
-#if CBLX_MSD_PROBE == 3  // timing probe only: loads, counting atomics and scan alone
-    if (!CBLX_MSD_PROBE_MERGE || merging) {
-        if (tid == 0) { out_count[r] = c; out_kind[r] = KIND_VEC; }
-        if (key[0].lo != 0x1234567ull) return;
-    }
-#endif
     if (tid == 0) s_off[NB] = (u16)c;
     if constexpr (PACKED) { if (tid < 4) s_klo[c + tid] = ~0ull; }  // the slack the ranking loop may read compares greater than every element
     if constexpr (WP) { if (tid < 4) s_kw[c + tid] = W128{~0ull, ~0ull}; }
@@ -1353,16 +1158,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
     const u32 sl3 = slot0();
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
-#if CBLX_MSD_SKIP_SELF
-        arr[j] += sbase[j];  // the element's own slot, kept for the ranking loop (same register as the arrival order)
-#endif
         if (valid[j]) {
             const u32 e = sl3 + j * 64;
-#if CBLX_MSD_SKIP_SELF
-            const u32 p = arr[j];
-#else
             const u32 p = sbase[j] + arr[j];
-#endif
             if constexpr (PACKED) {
                 s_klo[p] = (key[j].lo << PK_BITS) | e;
             } else if constexpr (WP) {
@@ -1381,8 +1179,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
     u32 sa[ITEMS], sb[ITEMS];  // sub-bucket bounds of every item, fetched in one batch of independent LDS reads
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
-        if constexpr (CBLX_MSD_REUSE_BASE || (MERGE && CBLX_MSD_MERGE_REUSE)) sa[j] = sbase[j];  // the offsets did not change since the scatter read them: one LDS read per item less
-        else sa[j] = s_off[sub[j]];
+        sa[j] = s_off[sub[j]];  // (re-read: keeping sbase[] alive from the scatter cost eight live registers, +0.15 ms, profiles/r02_variants.md)
         sb[j] = s_off[sub[j] + 1];
     }
     const u32 sl4 = slot0();
@@ -1392,41 +1189,15 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
         fin[j] = 0;
         if (valid[j]) {
             const u32 e = sl4 + j * 64;
-#if CBLX_MSD_PROBE >= 1 && CBLX_MSD_PROBE <= 2  // timing probe only (wrong order): no ranking reads
-            const u32 b = sb[j], a = (!CBLX_MSD_PROBE_MERGE || merging) ? b : ((b - sa[j] > 1u) ? sa[j] : b);
+            const u32 b = sb[j], a = (b - sa[j] > 1u) ? sa[j] : b;  // alone in its sub-bucket: rank 0, no duplicate, nothing to read
             const u32 a0 = sa[j];
-#elif CBLX_MSD_SKIP_SINGLE
-            const u32 b = sb[j], a = (b - sa[j] > 1u) ? sa[j] : b;  // alone: rank 0, no duplicate, nothing to read
-            const u32 a0 = sa[j];
-#else
-            const u32 a = sa[j], b = sb[j], a0 = a;
-#endif
             u32 rank = 0;
             bool dup = false;
             // four entries per trip: the reads are independent, so a sub-bucket (1.5 elements on average, 4-5 for the
             // slowest lane of a wave) costs one LDS round trip instead of one per element
             if constexpr (PACKED) {
                 const u64 me = (key[j].lo << PK_BITS) | e;
-#if CBLX_MSD_SKIP_SELF
-                // only the OTHER entries of the sub-bucket are read, under the lane's own mask: a lane alone in its
-                // sub-bucket (about half of them) issues no LDS access at all, one with a single mate issues one — the
-                // kernel is bound by the bank conflicts of these random reads (profiles/r02_sq_counters.md)
-                for (u32 q = a; q < b; q += MSD_TRIP) {
-                    u64 o[MSD_TRIP];
-#pragma unroll
-                    for (int k = 0; k < MSD_TRIP; ++k) {
-                        const u32 ix = q + k;
-                        o[k] = ~0ull;  // compares greater than every element
-                        if (ix < b && ix != arr[j]) o[k] = s_klo[ix];
-                    }
-#pragma unroll
-                    for (int k = 0; k < MSD_TRIP; ++k) {
-                        const bool less = o[k] < me;
-                        rank += less ? 1u : 0u;
-                        dup |= less && ((o[k] >> PK_BITS) == key[j].lo);
-                    }
-                }
-#else
+                // (reading only the OTHER entries under a per-read lane mask was measured slower, cfg 2: 6.73 -> 8.23 ms)
                 if (vec_only) {  // hashed sub-buckets: what follows a sub-bucket is unrelated, entries past b are masked
                     for (u32 q = a; q < b; q += MSD_TRIP) {
                         u64 o[MSD_TRIP];
@@ -1453,7 +1224,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
                         }
                     }
                 }
-#endif
             } else if constexpr (WP) {
                 const W128 me = w128_pack(key[j], e);
                 if (vec_only) {  // hashed sub-buckets: what follows a sub-bucket is unrelated, entries past b are masked
@@ -1510,10 +1280,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
         // came from, and whether it is the first of its suffix (the ranking loop's `dup`: an equal suffix with a smaller index — the
         // other side's copy of a word self holds). Round 5: the slots carried the 12-bit index instead, every thread read its slot AND
         // the one in front of it to find the heads again, and the (up to) three compactions each had their own pair of barriers.
-#if CBLX_MSD_PROBE == 4  // timing probe only: no merge epilogue at all
-        if (tid == 0) { out_count[r] = c; out_kind[r] = KIND_VEC; }
-        if (fin[0] != 0x12345u) return;
-#endif
         __syncthreads();  // every read of the sub-bucket order is done
         const u32 sl5 = slot0();
 #pragma unroll
@@ -1580,10 +1346,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
         u64* shi = reinterpret_cast<u64*>(hi);
         const u64 obase = mg.ostart[r];
         runB += cs_m;  // B follows self's cs elements
-#if CBLX_MSD_PROBE == 5  // timing probe only: the merge epilogue without its global stores
-        if (tid == 0) { out_count[r] = c; out_kind[r] = KIND_VEC; }
-        if (runO + runA + runB + fl[0] != 0x12345u) return;
-#endif
 #pragma unroll
         for (int j = 0; j < ITEMS; ++j) {
             const u64 balO = __ballot((fl[j] & 1u) != 0), balA = __ballot((fl[j] & (1u << 10)) != 0), balB = __ballot((fl[j] & (1u << 20)) != 0);
@@ -1615,11 +1377,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
     }
     __syncthreads();
     const u32 d = s_wtot[NW];
-#if CBLX_MSD_PROBE == 2  // timing probe only: no sorted write-back (and no ranking reads)
-    const bool trie = false;
-#else
     const bool trie = d > VEC_THRESHOLD || res_trie;
-#endif
     if (!trie) {
         // Vec: first occurrences in stream order, straight from registers (slots are in stream order). Without a
         // duplicate (d == c) every element already sits in its slot and nothing is written.
@@ -1706,21 +1464,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
 // gathered run; both parts hold distinct words, so a repeat is other's copy of a word self holds and sits right behind it in the sorted
 // order. The rules of /root/reference/src/trievec/set_ops.rs:43-71 are then ordered selections of the sorted slots, as in k_bucket_msd's
 // merge epilogue: what a slot says about its element is whether it came from self (index < cs) and whether it is the first of its value.
-#ifndef CBLX_SORTED_WAVES
-#define CBLX_SORTED_WAVES 7
-#endif
-#ifndef CBLX_SORTED_BALANCE
-#define CBLX_SORTED_BALANCE 0  // the chunks of a workgroup dealt to its lanes in order of their span (measured: see DESIGN_HISTORY.md §3.13)
-#endif
-#ifndef CBLX_SORTED_PERBODY
-#define CBLX_SORTED_PERBODY 0  // every phase instantiated per slots-per-lane, not the walk alone (measured: 3.471 against 3.449 ms, DESIGN_HISTORY.md §3.13)
-#endif
-#ifndef CBLX_SORTED_PROBE
-#define CBLX_SORTED_PROBE 0  // > 0: timing probes that leave phases out (wrong results); never in the product build
-#endif
-#if CBLX_SORTED_PROBE && !defined(CBLX_TIMING_PROBES)
-#error "CBLX_SORTED_PROBE leaves phases out and produces wrong results: timing builds only (-DCBLX_TIMING_PROBES)"
-#endif
+static const int SORTED_WAVES = 7;  // waves per SIMD the register allocation aims at
 // The element of the walk: suffix << 12 | stream index. Narrow (SUFFIX_BITS + 12 <= 64): one u64 in an array padded by one slot per
 // eight — the 64 lanes' slots of one step are 8 slots apart, 9 with the padding: every bank pair is hit four times, the best a
 // 64 x 8-byte access can do. Wide (SUFFIX_BITS + 12 <= 128): one 16-byte slot (ds_read_b128), slot index XORed with its block-of-eight
@@ -1753,7 +1497,7 @@ template <> struct WalkEl<true> {
         return (u32)(v >> (PK_BITS + sh)) & ((1u << nbits) - 1u);
     }
 };
-template <int CAP, bool WS> constexpr int sorted_waves() { return WS ? (CAP <= 128 ? CBLX_SORTED_WAVES : 4) : (CAP >= 4096 ? 6 : CBLX_SORTED_WAVES); }
+template <int CAP, bool WS> constexpr int sorted_waves() { return WS ? (CAP <= 128 ? SORTED_WAVES : 4) : (CAP >= 4096 ? 6 : SORTED_WAVES); }
 template <int THREADS, int CAP, bool WS, typename HiT, bool MERGE = false>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_waves<CAP, WS>(), 8))) void k_bucket_sorted(
     const BDesc* __restrict__ list, const u32* __restrict__ list_n, u64* __restrict__ lo, HiT* __restrict__ hi, u32 SB, u32* __restrict__ out_count, u8* __restrict__ out_kind,
@@ -1800,14 +1544,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
     for (u32 i = tid; i < NB / 2 + 1; i += THREADS) s_off32[i] = 0;
     if (tid == 0) s_max = 0;
     __syncthreads();
-    // (CBLX_SORTED_PERBODY=1 instantiates everything below per `per` = slots a lane owns, uniform over the workgroup — a run of 1 300 words on 256
-    // threads then issues six slots per lane in every phase, not eight; the masked slots turned out to cost nothing outside the walk)
+    // `per` = slots a lane owns, uniform over the workgroup. Only the walk is instantiated per `per`: a run of 1 300 words on 256 threads issues
+    // eight slots per lane in every other phase, and the masked slots cost nothing there (3.471 against 3.449 ms, DESIGN_HISTORY.md §3.13)
     const u32 per = (c + THREADS - 1) / THREADS;  // <= ITEMS
-    auto body = [&](auto per_tag) {
-    constexpr int PI = decltype(per_tag)::value;
+    auto body = [&] {  // (a lambda on purpose: written straight into the kernel, every instantiation compiles to other code and other register counts)
     {
-        Sfx<WS> key[PI];
-        u32 sub[PI], arr[PI];
+        Sfx<WS> key[ITEMS];
+        u32 sub[ITEMS], arr[ITEMS];
         // all loads first, unconditionally (slots past the run re-read its first word): eight independent global loads in flight per lane
         if constexpr (MERGE) {
             // element e is word e of `pa` (e < split) or of `pb` (other's pointer moved back by the split: no subtraction per slot)
@@ -1827,7 +1570,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
                 }
             }
 #pragma unroll
-            for (int j = 0; j < PI; ++j) {
+            for (int j = 0; j < ITEMS; ++j) {
                 const u32 e = j * THREADS + tid, ee = e < c ? e : 0u;
                 const bool in_a = ee < split;
                 key[j] = load_sfx<WS, u64>(in_a ? pa : pb, in_a ? ha : hb, ee, SB);
@@ -1836,13 +1579,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
             const u64* __restrict__ run_lo = lo + s0;
             const HiT* __restrict__ run_hi = WS ? hi + s0 : nullptr;
 #pragma unroll
-            for (int j = 0; j < PI; ++j) {
+            for (int j = 0; j < ITEMS; ++j) {
                 const u32 e = j * THREADS + tid;
                 key[j] = load_sfx<WS, HiT>(run_lo, run_hi, e < c ? e : 0u, SB);
             }
         }
 #pragma unroll
-        for (int j = 0; j < PI; ++j) {
+        for (int j = 0; j < ITEMS; ++j) {
             const u32 e = j * THREADS + tid;
             sub[j] = sfx_bits_below<WS>(key[j], SB, skip, nbits);
             arr[j] = 0;
@@ -1850,17 +1593,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
         }
         bool crowded = false;  // an arrival number of `crowd` = a sub-bucket of more than `crowd` entries
 #pragma unroll
-        for (int j = 0; j < PI; ++j) {
+        for (int j = 0; j < ITEMS; ++j) {
             arr[j] = (arr[j] >> ((sub[j] & 1u) * 16u)) & 0xFFFFu;
             crowded |= arr[j] >= crowd;
         }
         if (crowded) s_max = crowd + 1u;  // benign race: every writer stores the same value
         __syncthreads();
         if (s_max > crowd) { give_up(); return; }  // repeats (or a cluster beyond the limit): claim table (build) / radix kernel (merge, sub-ranges)
-#if CBLX_SORTED_PROBE == 1  // timing probe only: loads and counting atomics
-        if (tid == 0) { out_count[r] = c; out_kind[r] = KIND_TRIE; }
-        if (s_off32[tid] != 0x12345678u) return;
-#endif
         {   // exclusive scan of the NB counts; each thread owns `per` consecutive entries
             const u32 per_nb = (NB + THREADS - 1) / THREADS;  // <= ITEMS
             const u32 b0 = tid * per_nb;
@@ -1879,59 +1618,23 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
         __syncthreads();
         if (tid == 0) s_off[NB] = (u16)c;
         if (tid < 4) s_k[EL::phys(c + tid)] = EL::ones();  // what a walk may read behind the run compares greater than every element
-        u32 sbase[PI];
+        u32 sbase[ITEMS];
 #pragma unroll
-        for (int j = 0; j < PI; ++j) sbase[j] = s_off[sub[j]];
+        for (int j = 0; j < ITEMS; ++j) sbase[j] = s_off[sub[j]];
 #pragma unroll
-        for (int j = 0; j < PI; ++j) {
+        for (int j = 0; j < ITEMS; ++j) {
             const u32 e = j * THREADS + tid;
             if (e < c) s_k[EL::phys(sbase[j] + arr[j])] = EL::pack(key[j], e);
         }
     }
     __syncthreads();
-#if CBLX_SORTED_PROBE == 2  // timing probe only: everything up to the scatter
-    if (tid == 0) { out_count[r] = c; out_kind[r] = KIND_TRIE; }
-    if (s_off32[tid] != 0x1234567u) return;
-#endif
     // -- the walk: lane t owns slots [t per, t per + per) of the sub-bucket order
-    u32 chunk = tid;
-#if CBLX_SORTED_BALANCE
-    if constexpr (NW > 1 && THREADS <= 256) {
-        // The wave's longest span is what its walk costs (2.2 x the mean): the chunks are dealt to the lanes in order of their span, so that a wave's
-        // lanes walk spans of about one length (a counting sort of the THREADS chunks on min(span, 127))
-        __shared__ u32 s_bins32[64];
-        __shared__ u8 s_perm[THREADS];
-        u16* s_bins = reinterpret_cast<u16*>(s_bins32);
-        if (tid < 64) s_bins32[tid] = 0;
-        const u32 q0 = tid * per;
-        u32 span = 0;
-        if (q0 < c) {
-            const u32 q1 = (q0 + per < c ? q0 + per : c) - 1u;
-            const E f = s_k[EL::phys(q0)], l = s_k[EL::phys(q1)];
-            span = s_off[EL::sub(l, sub_sh, nbits) + 1u] - (s_off[EL::sub(f, sub_sh, nbits)] & ~1u);
-        }
-        const u32 bin = span < 127u ? span : 127u;
-        __syncthreads();
-        const u32 arr = (atomicAdd(&s_bins32[bin >> 1], 1u << ((bin & 1u) * 16u)) >> ((bin & 1u) * 16u)) & 0xFFFFu;
-        __syncthreads();
-        if (tid < 64) {  // exclusive scan of the 128 counts, two per lane
-            const u32 a = s_bins[2 * tid], b = s_bins[2 * tid + 1];
-            const u32 inc = wave_inclusive_scan(a + b);
-            s_bins[2 * tid] = (u16)(inc - a - b);
-            s_bins[2 * tid + 1] = (u16)(inc - b);
-        }
-        __syncthreads();
-        s_perm[s_bins[bin] + arr] = (u8)tid;
-        __syncthreads();
-        chunk = s_perm[tid];
-    }
-#endif
-    const u32 p0 = chunk * per;
+    const u32 p0 = tid * per;
     const u32 n_own = p0 < c ? (c - p0 < per ? c - p0 : per) : 0u;
-    E me[PI];
-    u32 fin[PI];
+    E me[ITEMS];
+    u32 fin[ITEMS];
 #pragma unroll
-    for (int i = 0; i < PI; ++i) {
+    for (int i = 0; i < ITEMS; ++i) {
         const u32 p = p0 + i;
         me[i] = s_k[EL::phys(p < c ? p : c)];  // (slots past the lane's share read the all-ones slot or a neighbour's entry: never written back)
         fin[i] = 0;
@@ -1940,22 +1643,11 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
     if (n_own) {
         E last = me[0];
 #pragma unroll
-        for (int i = 1; i < PI; ++i) if ((u32)i < n_own) last = me[i];
+        for (int i = 1; i < ITEMS; ++i) if ((u32)i < n_own) last = me[i];
         // (rounded down to an even slot: the entry in front of the sub-bucket is smaller than every entry of mine, it counts like the rest in front)
         A = s_off[EL::sub(me[0], sub_sh, nbits)] & ~1u;
         B = s_off[EL::sub(last, sub_sh, nbits) + 1u];
     }
-#ifdef CBLX_SORTED_STATS  // dev: span statistics into retry_n[0..7] as u64 (tools/dev_msd_bench.cpp)
-    {
-        unsigned long long* st = reinterpret_cast<unsigned long long*>(retry_n);
-        const u32 span = B - A;
-        u32 mx = span;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const u32 t = __shfl_xor(mx, o, 64); mx = t > mx ? t : mx; }
-        const u32 sm = wave_reduce_sum(span), na = wave_reduce_sum(n_own ? 1u : 0u);
-        if (lane == 0) { atomicAdd(&st[0], (unsigned long long)sm); atomicAdd(&st[1], (unsigned long long)mx); atomicAdd(&st[2], (unsigned long long)na); atomicAdd(&st[3], 1ull); }
-    }
-#endif
     // (an entry read behind B belongs to a later sub-bucket, or is all ones: greater than every entry of mine.) The comparisons are
     // what this kernel is made of (two VALU instructions per pair, 28.8 steps of the wave's longest span at cfg 2): the loop is
     // instantiated per `per` — uniform over the workgroup — so that a run of 1300 words (per = 6) does not pay for eight slots
@@ -1975,44 +1667,33 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
             for (int i = 0; i < PER; ++i) fin[i] += (EL::less(o0, me[i]) ? 1u : 0u) + (EL::less(o1, me[i]) ? 1u : 0u);
         }
     };
-#if CBLX_SORTED_PERBODY
-    walk(std::integral_constant<int, PI>());
-#else
-    if constexpr (PI == 8) {
+    if constexpr (ITEMS == 8) {
         switch (per) {
             case 8: walk(std::integral_constant<int, 8>()); break;
             case 7: walk(std::integral_constant<int, 7>()); break;
             case 6: walk(std::integral_constant<int, 6>()); break;
             case 5: walk(std::integral_constant<int, 5>()); break;
-            default: walk(std::integral_constant<int, 4>()); break;
+            default: walk(std::integral_constant<int, 4>()); break;  // (per <= 4: a short run of a class above its length, e.g. a sub-range of a long run)
         }
     } else {
-        walk(std::integral_constant<int, PI>());
+        walk(std::integral_constant<int, ITEMS>());
     }
-#endif
-#if CBLX_SORTED_PROBE == 3  // timing probe only: everything up to the walk
-    if (tid == 0) { out_count[r] = c; out_kind[r] = KIND_TRIE; }
-    { u32 t = 0;
-#pragma unroll
-      for (int i = 0; i < PI; ++i) t += fin[i];
-      if (t != 0x12345678u) return; }
-#endif
     __syncthreads();  // every read of the sub-bucket order is done
 #pragma unroll
-    for (int i = 0; i < PI; ++i)
+    for (int i = 0; i < ITEMS; ++i)
         if ((u32)i < n_own) s_k[EL::phys(A + fin[i])] = me[i];
     __syncthreads();
     const u32 EPW = 64 * per;  // wave-contiguous slices of the sorted slots: ballots then compact in order
-    Sfx<WS> val[PI];
+    Sfx<WS> val[ITEMS];
     if constexpr (MERGE) if (merging) {
         // three ordered selections of the sorted slots, counted and written together (k_bucket_msd's merge epilogue):
         //   O = other's elements (back to other's arena, sorted)            A = Trie |= x: the heads (sorted union); Vec |= x: self's elements
         //   B = Vec |= x only: other's heads = other \ self, behind self's   (every self element is a head)
         const bool o_vec = mg.okind[r] == KIND_VEC;  // the reference's iter_sorted leaves other's Vec sorted
-        u32 fl[PI];
+        u32 fl[ITEMS];
         u32 nO = 0;
 #pragma unroll
-        for (int j = 0; j < PI; ++j) {
+        for (int j = 0; j < ITEMS; ++j) {
             const u32 p = w * EPW + j * 64 + lane;
             const bool live = (u32)j < per && p < c;
             const u32 pc = live ? p : 0u;
@@ -2039,7 +1720,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
         const u64 obase = mg.ostart[r];
         runB += cs_m;  // B follows self's cs elements
 #pragma unroll
-        for (int j = 0; j < PI; ++j) {
+        for (int j = 0; j < ITEMS; ++j) {
             const u64 balO = __ballot((fl[j] & 1u) != 0), balA = __ballot((fl[j] & (1u << 10)) != 0), balB = __ballot((fl[j] & (1u << 20)) != 0);
             if (fl[j] & 1u) {
                 const u32 q = runO + mbcnt(balO);
@@ -2062,10 +1743,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
         return;
     }
     // -- heads (the first slot of every suffix value), counted, then compacted slot by slot
-    bool head[PI];
+    bool head[ITEMS];
     u32 wh = 0;
 #pragma unroll
-    for (int j = 0; j < PI; ++j) {
+    for (int j = 0; j < ITEMS; ++j) {
         const u32 p = w * EPW + j * 64 + lane;
         const bool live = (u32)j < per && p < c;
         const u32 pc = live ? p : 0u;
@@ -2088,13 +1769,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
     HiT* __restrict__ out_hi = WS ? hi + s0 : nullptr;
     if (d == c) {  // no repeat in the run (the usual case): every slot is a head and keeps its place
 #pragma unroll
-        for (int j = 0; j < PI; ++j) {
+        for (int j = 0; j < ITEMS; ++j) {
             const u32 p = w * EPW + j * 64 + lane;
             if ((u32)j < per && p < c) store_sfx<WS, HiT>(out_lo, out_hi, p, val[j]);
         }
     } else {
 #pragma unroll
-        for (int j = 0; j < PI; ++j) {
+        for (int j = 0; j < ITEMS; ++j) {
             const u64 bal = __ballot(head[j]);
             if (head[j]) store_sfx<WS, HiT>(out_lo, out_hi, run + mbcnt(bal), val[j]);
             run += (u32)__builtin_popcountll(bal);
@@ -2105,21 +1786,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
         out_kind[r] = KIND_TRIE;
     }
     };
-#if CBLX_SORTED_PERBODY
-    if constexpr (ITEMS == 8) {
-        switch (per) {
-            case 8: body(std::integral_constant<int, 8>()); break;
-            case 7: body(std::integral_constant<int, 7>()); break;
-            case 6: body(std::integral_constant<int, 6>()); break;
-            case 5: body(std::integral_constant<int, 5>()); break;
-            default: body(std::integral_constant<int, 4>()); break;  // (per <= 4: a short run of a class above its length, e.g. a sub-range of a long run)
-        }
-    } else {
-        body(std::integral_constant<int, ITEMS>());
-    }
-#else
-    body(std::integral_constant<int, ITEMS>());
-#endif
+    body();
 }
 
 // ---- KRN-3 for runs full of repeats (one batch at high coverage: every k-mer arrives dozens of times). The counting sort

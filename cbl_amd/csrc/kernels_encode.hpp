@@ -89,15 +89,6 @@ __global__ __launch_bounds__(256) void k_pack_planes(const u8* __restrict__ asci
     valid[g - g0] = (u16)ok;
 }
 
-#ifndef CBLX_ENC_UNIFORM
-#define CBLX_ENC_UNIFORM 1
-#endif
-#ifndef CBLX_ENC_HIST_VOTE
-#define CBLX_ENC_HIST_VOTE 0  // measured (cfg 2): encode 4.69 -> 7.10 ms — the scalar vote loop is a serial dependency chain per wave
-#endif
-#ifndef CBLX_ENC_HIST_RUNS
-#define CBLX_ENC_HIST_RUNS 0  // measured (profiles/r02_variants.md): +0.3 ms — the kernel is VALU-bound, the dozen instructions cost more than the serialised atomics
-#endif
 static const u32 ENC_TILE_BYTES = 4096;
 static const u32 ENC_THREADS = 256;
 static const u32 ENC_MAX_CHUNKS = 1024;                                    // >= 4096 / min chunk length (K >= 5)
@@ -303,9 +294,6 @@ __global__ void k_tile_first_chunk(const u64* __restrict__ chunk_start, u64 nchu
     tile_first[t] = (u32)lo;
 }
 
-#ifndef CBLX_ENC_PROBE
-#define CBLX_ENC_PROBE 0
-#endif
 // ---- word of one k-mer ---------------------------------------------------------------------------------
 template <bool WIDE> struct KmerT;
 template <> struct KmerT<false> { typedef u64 type; };
@@ -419,7 +407,6 @@ __global__ __launch_bounds__(ENC_THREADS) void k_encode(BaseView B, u64 total_ba
     }
     __syncthreads();
     const u32 Q = s_koff[nc];
-#if CBLX_ENC_UNIFORM
     // Reads of one length back to back (the common input): every chunk of the tile has nk0 k-mers and starts len0 bases
     // after its predecessor, so chunk and position of k-mer q follow from q by arithmetic and the k-mer loop never reads
     // the chunk tables.
@@ -428,10 +415,6 @@ __global__ __launch_bounds__(ENC_THREADS) void k_encode(BaseView B, u64 total_ba
     // (a dirty chunk carries bit 31 in s_cstart: chunk 1 must be tested for it explicitly, len0 is defined by its start)
     for (u32 i = tid; i < nc; i += ENC_THREADS) uni = uni && s_koff[i + 1] == (i + 1) * nk0 && s_cstart[i] == cs0 + i * len0 && !(s_cstart[i] >> 31);
     const bool uniform = __syncthreads_and(uni ? 1 : 0) != 0;
-#else
-    const bool uniform = false;
-    const u32 nk0 = 1, cs0 = 0, len0 = 0;
-#endif
 
     auto find_chunk = [&](u32 q) -> u32 {  // last i with s_koff[i] <= q
         u32 lo = 0, hi = nc;
@@ -495,44 +478,14 @@ __global__ __launch_bounds__(ENC_THREADS) void k_encode(BaseView B, u64 total_ba
             }
             u64 lo, hi;
             kmer_word<WIDE>(x, PK, rc, lo, hi);
-#if CBLX_ENC_PROBE == 1  // timing probe only (tools/dev_encode_probe.py): one byte per k-mer instead of the word
-            reinterpret_cast<u8*>(out_lo)[obase + drel] = (u8)lo ^ (u8)hi;
-#else
             out_lo[obase + drel] = lo;
             st_hi<HiT>(out_hi, obase + drel, hi);
-#endif
             if (eh.counts) {
+                // The first-pass digit is the skewed one: a wave's 64 updates hit a handful of counters, which the LDS serialises address by
+                // address. Merging them first (a scalar vote per value: encode 4.69 -> 7.10 ms at cfg 2; one update per run of equal keys:
+                // +0.3 ms, profiles/r02_variants.md) costs more than that: the kernel is VALU-bound.
                 const u32 key = ((hbase + drel) / ENC_HIST_WINDOW) * 256 + eh.digit(lo, hi, s_cut, cut_staged);
-#if CBLX_ENC_HIST_VOTE
-                // The first-pass digit is the skewed one: a wave's 64 keys are a handful of distinct values (2-3 on
-                // average), which per-lane LDS atomics serialise address by address. Instead the wave votes value by
-                // value on the scalar unit: broadcast the first unsettled lane's key, ballot who shares it, one lane adds
-                // the count. The loop is scalar work plus one compare per round.
-                u64 todo = __ballot(true);
-                while (todo) {
-                    const u32 k0 = (u32)__builtin_amdgcn_readlane((int)key, (int)__builtin_ctzll(todo));
-                    const u64 same = __ballot(key == k0);
-                    if ((tid & 63u) == (u32)__builtin_ctzll(todo)) atomicAdd(&s_hist[k0], (u32)__builtin_popcountll(same));
-                    todo &= ~same;
-                }
-#elif CBLX_ENC_HIST_RUNS
-                // Neighbouring lanes hold consecutive k-mers of a read: their necklaces share the leading bits, and the
-                // first-pass digit is the skewed one — a wave's 64 updates hit a handful of counters, which the LDS
-                // serialises address by address. One update per RUN of equal keys instead: the first lane of a run adds
-                // the run's length (lanes that sit this iteration out break a run).
-                const u64 act = __ballot(true);
-                const u32 lane = tid & 63u;
-                const u32 prev = (u32)__builtin_amdgcn_update_dpp((int)~key, (int)key, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-                const bool lead = lane == 0 || !((act >> (lane - 1)) & 1ull) || prev != key;
-                const u64 leaders = __ballot(lead);
-                if (lead) {
-                    const u64 above = lane == 63 ? 0ull : ((leaders | ~act) >> (lane + 1));  // next leader or inactive lane ends the run
-                    const u32 len = above ? (u32)__builtin_ctzll(above) + 1u : 64u - lane;
-                    atomicAdd(&s_hist[key], len);
-                }
-#else
                 atomicAdd(&s_hist[key], 1u);
-#endif
             }
         };
         if (uniform) {
@@ -564,11 +517,7 @@ __global__ __launch_bounds__(ENC_THREADS) void k_encode(BaseView B, u64 total_ba
         if (P.K == 59) kmer_loop(std::integral_constant<u32, 59>());
         else kmer_loop(std::integral_constant<u32, 0>());
     }
-#if CBLX_ENC_PROBE == 2  // timing probe only (wrong histogram): what the flush of the tile's counts costs
-    if (false) {
-#else
     if (eh.counts) {  // the first-pass digit is the skewed one: only a few dozen bins per window are non-zero
-#endif
         __syncthreads();
         for (u32 i = tid; i < ENC_HIST_WINDOWS * 256; i += ENC_THREADS) {
             const u32 v = s_hist[i];

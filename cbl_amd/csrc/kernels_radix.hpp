@@ -197,14 +197,8 @@ __device__ __forceinline__ void tile_rank_packed(u32 (&dp)[ITEMS], u32* s_wcnt, 
         if ((u32)j < rounds) { const u32 d = dp[j] >> 16; dp[j] += s_dbase[d] + my[d]; }
 }
 
-#ifndef CBLX_RDX_THREADS
-#define CBLX_RDX_THREADS 512
-#endif
-#ifndef CBLX_RDX_ITEMS
-#define CBLX_RDX_ITEMS 8
-#endif
-static const int RDX_THREADS = CBLX_RDX_THREADS;
-static const int RDX_ITEMS = CBLX_RDX_ITEMS;
+static const int RDX_THREADS = 512;
+static const int RDX_ITEMS = 8;
 static const int RDX_TILE = RDX_THREADS * RDX_ITEMS;  // 4096 records per workgroup
 
 // digit of a record: a bit field of the word (LSD passes) ...
@@ -297,17 +291,10 @@ struct OwnWindow {
 // relied on for correctness): XCD x then walks the CONTIGUOUS tile range [x * per, (x + 1) * per) in order, so the runs
 // that neighbouring tiles append to the same bin are written through the same L2 close in time and their partial
 // cache lines merge there instead of reaching HBM twice. Launch xcd_grid(ntiles) workgroups.
-#ifndef CBLX_XCD_MAP
-#define CBLX_XCD_MAP 1
-#endif
 __host__ __device__ inline u32 xcd_grid(u32 ntiles) { return ((ntiles + 7u) / 8u) * 8u; }
 __device__ __forceinline__ u32 xcd_tile(u32 b, u32 ntiles) {
-#if CBLX_XCD_MAP
     const u32 per = (ntiles + 7u) / 8u;
     return (b & 7u) * per + (b >> 3);
-#else
-    return b;
-#endif
 }
 
 // Where the tiles of a pass live. Plain passes cut [0, n) into RDX_TILE-record tiles. After the first (most significant

@@ -107,10 +107,7 @@ __host__ __device__ inline void necklace_pos_halves(nk_u128 x, unsigned BITS, nk
 
 // x must already be masked to BITS bits, BITS < 8 * sizeof(T). T = uint64_t (BITS <= 62) or nk_u128 (BITS <= 118).
 template <typename T> __host__ __device__ inline void necklace_pos_fast(T x, unsigned BITS, T& necklace, unsigned& pos) {
-#ifndef CBLX_NK_HALVES
-#define CBLX_NK_HALVES 1
-#endif
-    if constexpr (CBLX_NK_HALVES && sizeof(T) == 16) {
+    if constexpr (sizeof(T) == 16) {
         if ((BITS & 1u) == 0 && BITS < 128) {
             nk_u128 nk;
             necklace_pos_halves((nk_u128)x, BITS, nk, pos);

@@ -4,10 +4,6 @@
 #include "ctx.hpp"
 #include "kernels_kmer.hpp"
 
-#ifndef CBLX_CLAIM_FIRST
-#define CBLX_CLAIM_FIRST 0  // measured: the claim table as FIRST kernel of the runs <= 1024 words costs cfg 2 (no repeats) +0.25 ms and saves the 30x-coverage workload 2.4 ms
-#endif
-
 namespace {
 
 // ---- the sort + directory + per-bucket pipeline over N records (lo/hi), resident records first -------------
@@ -48,9 +44,6 @@ struct DirWindow {
 };
 
 // the LSD passes behind pass A: digit widths and shifts (relative to SUFFIX_BITS) of the remaining prefix bits
-#ifndef CBLX_PREFIX_SPLIT
-#define CBLX_PREFIX_SPLIT 1  // PREFIX_BITS > 24: the last PB - 24 bits by k_prefix_split instead of a third LSD pass (0: three LSD passes of 7 + 7 + 6 bits)
-#endif
 struct LsdPlan {
     u32 npass = 0, wid[4] = {0, 0, 0, 0}, sh[5] = {0, 0, 0, 0, 0};
     u32 xb = 0;  // lowest prefix bits left to k_prefix_split (the passes sort the PB - xb bits above them)
@@ -63,10 +56,10 @@ inline LsdPlan lsd_plan(const Consts& P, bool split_ok = true) {
     // Up to two passes: 8 bits, then the rest (the group-cut tiles of the last pass are built for that shape). PREFIX_BITS > 24:
     // 8 + 8 bits by two passes with the directory of 2^24 "super-prefixes" from the second one's tables, and the last 1 .. 4 bits
     // by k_prefix_split (a run of equal 24-bit prefix staged in LDS, written back in order: copy speed, DESIGN_HISTORY.md §3.11). Three passes
-    // of 7 + 7 + 6 bits before that (CBLX_PREFIX_SPLIT=0): a pass costs nearly the same whatever its width.
+    // of 7 + 7 + 6 bits before that, and still without `split_ok`: a pass costs nearly the same whatever its width.
     LsdPlan L;
     const u32 RB = P.PB - std::min(8u, P.PB);
-    if (CBLX_PREFIX_SPLIT && split_ok && P.PB > 24) {
+    if (split_ok && P.PB > 24) {
         L.xb = P.PB - 24;
         L.npass = 2;
         L.wid[0] = L.wid[1] = 8;
@@ -432,8 +425,8 @@ __global__ void k_sum_list_counts(const BDesc* __restrict__ list, u32 n, const u
 // segments, out of the arena into a twin buffer at the same positions; sub-ranges sorted + deduplicated in place there by
 // k_bucket_msd; what cannot be finished that way takes the general kernel on the (untouched) arena run. The finished runs stay
 // in the twin: finish_twin decides which buffer becomes the arena.
-// CBLX_SORTED_KERNEL=0: the runs that end up sorted take k_bucket_msd as they did until round 5 instead of k_bucket_sorted (tests compare both
-// routes); read per call
+// CBLX_SORTED_KERNEL=0: the runs that end up sorted take k_bucket_msd as they did until round 5 instead of k_bucket_sorted (the previous
+// route, for A/B runs by hand: no test sets it); read per call
 inline bool sorted_kernel() {
     const char* e = std::getenv("CBLX_SORTED_KERNEL");
     return !(e && e[0] == '0');
@@ -585,15 +578,7 @@ template <typename C> void finish_twin(cblx_ctx* c, Resident& nr, Twin& tw, int 
 // KRN-3 over the runs of `nr` (run of a prefix = [its resident suffixes as stored][the new words in stream order]) in the
 // arena a_lo / a_hi: per-bucket dedup / sort by size class; fills nr.cnt, nr.kind, nr.count. `old` = the resident index
 // the runs were built against (tells which buckets are untouched and which are Tries already).
-// CBLX_SPANS=1: the clean-span pre-filter in front of the classification (kernels_bucket.hpp: k_bucket_span). OFF by default — measured (round 6, one
-// MI355X): cfg 3 38.71 against 38.80 ms, cfg 4 50.9 against 51.6, cfg 2 +0.4 ms, 30 x coverage +2.4 ms: a span's life is its chain of dependent HBM
-// round trips (head -> first start -> flags, starts and words) just as a bucket's is, and eight 1 500-word spans per CU keep no more bytes in flight
-// per microsecond than thirty-two 77-word waves (DESIGN_HISTORY.md §3.13). Tests run both routes; read per call
-inline bool spans_enabled() {
-    const char* e = std::getenv("CBLX_SPANS");
-    return e && e[0] == '1';
-}
-// CBLX_REPEAT_PREPASS=0 switches the pre-pass of the long runs off (tests compare both routes); read per call
+// CBLX_REPEAT_PREPASS=0 switches the pre-pass of the long runs off (the previous route, for A/B runs by hand: no test sets it); read per call
 bool repeat_prepass() {
     const char* e = std::getenv("CBLX_REPEAT_PREPASS");
     return !(e && e[0] == '0');
@@ -620,29 +605,10 @@ template <typename C> void bucket_stage(cblx_ctx* c, Resident& nr, const DirView
     CBLX_HIP(hipMemsetAsync(list_n.get(), 0, CLS_N * 4, c->stream));
     // (suffixes wider than 64 bits: an element takes 18 bytes of LDS, the 4096-word workgroup 82 KB = one per CU, and the Trie
     // classes cost 60 ps per word on 2000-word buckets against 10 on short ones. Sending runs over 2048 / 1024 words down the
-    // long-run path instead was measured — CBLX_LDS_MAX_WS — and is slower: 134 -> 143 / 165 ms per 1.2 G words at K = 59, the
-    // cost is the ranking inside clusters of up to K mates, whatever the workgroup)
-    static const u32 lds_max_ws = [] { const char* e = std::getenv("CBLX_LDS_MAX_WS"); const u32 v = e ? (u32)std::strtoul(e, nullptr, 10) : 0; return v ? v : 4096u; }();
-    // clean spans (kernels_bucket.hpp: k_bucket_span; a measured switch, off by default): on an empty index, stretches of consecutive short runs
-    // without a single repeat are settled by one workgroup each before anything is classified
-    Buf<u8> span_done;
-    if ((old.bv == nullptr || old.nb == 0) && nb >= SPAN_MIN_RUNS && spans_enabled()) {
-        StageTimer t(c, ST_BSMALL);
-        span_done = Buf<u8>(c->pool, nb + 1);
-        Buf<u32> heads(c->pool, nb + 1), nheads(c->pool, 1);
-        Buf<u8> cont(c->pool, nb + 1);
-        CBLX_HIP(hipMemsetAsync(span_done.get(), 0, nb + 1, c->stream));
-        CBLX_HIP(hipMemsetAsync(nheads.get(), 0, 4, c->stream));
-        hipLaunchKernelGGL(k_span_heads, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, (const u64*)nr.start.get(), heads.get(), nheads.get(), cont.get());
-        const u32 nh = d2h<u32>(c, nheads.get());
-        if (nh)
-            hipLaunchKernelGGL((k_bucket_span<C::WS, HiT>), dim3(nh), dim3(SPAN_THREADS), 0, c->stream, (const u32*)heads.get(), (const u32*)nheads.get(), nb, (const u64*)nr.start.get(),
-                               (const u8*)cont.get(), (const u64*)a_lo, (const HiT*)a_hi, P.SB, nr.cnt.get(), nr.kind.get(), span_done.get());
-        CBLX_HIP(hipGetLastError());
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // heads die here
-    }
-    hipLaunchKernelGGL(k_classify, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, C::WS ? lds_max_ws : 4096u, nr.prefix.get(), nr.start.get(), old,
-                       res_count.get(), res_kind.get(), nr.cnt.get(), nr.kind.get(), lists.get(), list_n.get(), (const u8*)span_done.get());
+    // long-run path instead was measured and is slower: 134 -> 143 / 165 ms per 1.2 G words at K = 59, the cost is the ranking
+    // inside clusters of up to K mates, whatever the workgroup — so k_classify's `lds_max` is 4096 for every suffix width)
+    hipLaunchKernelGGL(k_classify, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, 4096u, nr.prefix.get(), nr.start.get(), old,
+                       res_count.get(), res_kind.get(), nr.cnt.get(), nr.kind.get(), lists.get(), list_n.get());
     std::vector<u32> ln = d2h_vec<u32>(c, list_n.get(), CLS_N);
     if (ln[CLS_S32] | ln[CLS_S16]) {
         StageTimer t(c, ST_BSMALL);
@@ -697,7 +663,8 @@ template <typename C> void bucket_stage(cblx_ctx* c, Resident& nr, const DirView
                 constexpr int T = decltype(thr)::value, CAPV = decltype(cap)::value;
                 const int cls = MCLS[k];
                 if (!ln[cls]) return;
-                if ((CBLX_CLAIM_FIRST && CAPV <= (int)VEC_THRESHOLD) || repeat_mode) {
+                // (the claim table as FIRST kernel of every run <= 1024 words, measured: cfg 2, no repeats, +0.25 ms; the 30x-coverage workload -2.4 ms)
+                if (repeat_mode) {
                     hipLaunchKernelGGL((k_bucket_claim<T, CAPV, C::WS, HiT>), dim3(ln[cls]), dim3(T), 0, c->stream, lists.get() + (size_t)cls * nb, list_n.get() + cls, a_lo, a_hi, P.SB,
                                        nr.cnt.get(), nr.kind.get(), retry2.get(), r2n, (const u8*)nullptr);
                     return;
@@ -738,7 +705,7 @@ template <typename C> void bucket_stage(cblx_ctx* c, Resident& nr, const DirView
             claim(std::integral_constant<int, 128>(), std::integral_constant<int, 1024>(), 3);
             claim(std::integral_constant<int, 256>(), std::integral_constant<int, 2048>(), 4);
             claim(std::integral_constant<int, 512>(), std::integral_constant<int, 4096>(), 5);
-            if (CBLX_CLAIM_FIRST || repeat_mode || any_of(any)) {
+            if (repeat_mode || any_of(any)) {
                 // what the claim tables left for the sorted layout: distinct words now, at most 4096 per run
                 const u32 n2 = d2h<u32>(c, r2n);
                 if (n2) {

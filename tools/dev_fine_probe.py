@@ -1,5 +1,5 @@
-"""Dev probe (round 5): stage times of ONE fine-bins build at cfg 3 / cfg 4 size for the library given by CBLX_LIB_PATH. A timing-probe
-library (-DCBLX_ENC_PROBE=2: KRN-1 without the flush of its tile counts) fails behind KRN-1 by design; its encode time is still recorded."""
+"""Dev probe (round 5): stage times of ONE fine-bins build at cfg 3 / cfg 4 size for the library given by CBLX_LIB_PATH. A build
+that fails behind KRN-1 still has its encode time recorded."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

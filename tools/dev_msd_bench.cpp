@@ -1,7 +1,7 @@
 // Dev harness (not shipped): k_bucket_msd alone, every length class, on the REAL buckets of a K = 31 build (necklace clusters and all):
 // words from libcblx's KRN-1 (cblx_seq_words_device), a stable sort by prefix (rocPRIM, setup only), run lengths classified as k_classify
 // does, then the instantiation of every class timed over pristine copies of the arena. The kernels come from THIS translation unit
-// (kernels_bucket.hpp compiled with the -D switches of the variant under test), libcblx.so only supplies the words. Prints per class:
+// (kernels_bucket.hpp as it stands, or with the patch of the variant under test applied), libcblx.so only supplies the words. Prints per class:
 // buckets, words, ms, and a checksum of (counts, kinds, arena) that must not change between variants.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I cbl_amd/csrc -I include tools/dev_msd_bench.cpp -o tools/dev_msd_bench.bin -L cbl_amd -lcblx -Wl,-rpath,'$ORIGIN/../cbl_amd'
 //   tools/dev_msd_bench.bin [reads = 10000000] [prefix_bits = 24] [reps = 5]
@@ -226,15 +226,7 @@ int main(int argc, char** argv) {
             CK(hipMemset(bail_any, 0, 32));
             CK(hipDeviceSynchronize());
             CK(hipEventRecord(e0));
-#ifdef CBLX_SORTED_STATS
-            static unsigned long long* d_st = dalloc<unsigned long long>(8);
-            CK(hipMemset(d_st, 0, 64));
-            hipLaunchKernelGGL((k_bucket_sorted<T, CAPV, false, u8>), dim3(ln[k]), dim3(T), 0, 0, lists + (size_t)k * nruns, list_n + k, arena, (u8*)nullptr, SB, cnt, kind, (BDesc*)nullptr, (u32*)d_st, bail, bail_any);
-            if (rep == reps) { unsigned long long h[4]; CK(hipMemcpy(h, d_st, 32, hipMemcpyDeviceToHost));
-                printf("  span: mean per owning lane %.1f, mean of the wave maxima %.1f (%llu waves)\n", (double)h[0] / h[2], (double)h[1] / h[3], h[3]); }
-#else
             hipLaunchKernelGGL((k_bucket_sorted<T, CAPV, false, u8>), dim3(ln[k]), dim3(T), 0, 0, lists + (size_t)k * nruns, list_n + k, arena, (u8*)nullptr, SB, cnt, kind, (BDesc*)nullptr, (u32*)nullptr, bail, bail_any);
-#endif
             CK(hipEventRecord(e1));
             CK(hipEventSynchronize(e1));
             CK(hipGetLastError());

@@ -15,9 +15,6 @@ for w in $WHAT; do
     tests) timeout 1500 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "deep_buckets or threshold or merge or repeat" > $OUT/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest.log ;;
     emul)  timeout 800 python tools/emulate_rank.py --reads 10000000 --protocol words --merge > $OUT/cfg2x8_words.json 2> $OUT/cfg2x8_words.err; echo "cfg2x8 rc=$?"; show $OUT/cfg2x8_words.json
            timeout 800 python tools/emulate_rank.py --protocol words --merge > $OUT/cfg5_words.json 2> $OUT/cfg5_words.err; echo "cfg5 rc=$?"; show $OUT/cfg5_words.json ;;
-    ws)    for v in 4096 2048 1024; do
-             CBLX_LDS_MAX_WS=$v timeout 800 python tools/emulate_rank.py --k 59 --prefix-bits 28 --reads 6250000 --read-len 250 --protocol words > $OUT/cfg4_ws_$v.json 2> $OUT/cfg4_ws_$v.err; echo "cfg4 depth lds_max=$v rc=$?"; show $OUT/cfg4_ws_$v.json
-           done ;;
     lim)   for v in "" lim96 lim160; do
              L=""; [ -n "$v" ] && L=$R/tools/libcblx_$v.so
              CBLX_LIB_PATH=$L timeout 800 python tools/emulate_rank.py --k 59 --prefix-bits 28 --reads 6250000 --read-len 250 --protocol words > $OUT/cfg4_words_$v.json 2> $OUT/cfg4_words_$v.err; echo "cfg4 depth [$v] rc=$?"; show $OUT/cfg4_words_$v.json
