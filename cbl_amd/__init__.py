@@ -68,6 +68,8 @@ BUCKET_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.
 ABI_VERSION = 3  # include/cblx.h CBLX_ABI_VERSION
 
 # name -> (restype, argtypes): every symbol include/cblx.h declares
+SETOPS = {"or": 0, "and": 1, "sub": 2, "xor": 3}  # CBLX_SETOP_* of include/cblx.h
+
 SIGNATURES = {
     "cblx_abi_version": (C.c_uint32, []),
     "cblx_last_global_error": (C.c_char_p, []),
@@ -129,6 +131,8 @@ SIGNATURES = {
     "cblx_load_from_file": (C.c_int, [C.c_void_p, C.c_char_p]),
     "cblx_merge_assign": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cblx_merge_from": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cblx_set_op": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "cblx_get_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "cblx_stage_units": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]),
     "cblx_export_buckets": (C.c_int, [C.c_void_p, BUCKET_CB, C.c_void_p]),
     "cblx_contains_seq": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -772,6 +776,43 @@ class CBL:
         """self = what `a |= b` would leave in a, with a untouched (b as `|=` leaves it): `self = a.clone(); self |= b` without the copy."""
         self._chk(self._L.cblx_merge_from(self._h, a._h, b._h))
         return self
+
+    # ---- src/cbl.rs:411-431, 451-471, 491-511, 531-551: the operator forms `&mut a OP &mut b` ---------------------
+    @staticmethod
+    def set_op(a: "CBL", b: "CBL", op: str, out: "CBL" = None) -> "CBL":
+        """`a OP b` into a new index (op: "or" | "and" | "sub" | "xor"), or into `out`, whose content is replaced. A bucket only one operand
+        holds is cloned as stored; a bucket both hold becomes an ascending Vec and is dropped when empty. `a` and `b` keep their sets; their
+        Vec buckets on the prefixes both hold end up sorted, as the reference leaves them."""
+        if op not in SETOPS:
+            raise ValueError("set_op: op must be one of %s" % ", ".join(repr(o) for o in SETOPS))
+        if out is None:
+            out = CBL(a.k, a.prefix_bits, canonical=a.is_canonical(), device=a.device())
+        out._chk(out._L.cblx_set_op(out._h, a._h, b._h, SETOPS[op]))
+        return out
+
+    def device(self) -> int:
+        """The HIP device ordinal the index lives on (`device=-1` resolved when it was created)."""
+        v = C.c_int32(0)
+        self._chk(self._L.cblx_get_device(self._h, C.byref(v)))
+        return v.value
+
+    def __or__(self, other: "CBL") -> "CBL":
+        return CBL.set_op(self, other, "or")
+
+    def __and__(self, other: "CBL") -> "CBL":
+        return CBL.set_op(self, other, "and")
+
+    def __sub__(self, other: "CBL") -> "CBL":
+        return CBL.set_op(self, other, "sub")
+
+    def __xor__(self, other: "CBL") -> "CBL":
+        return CBL.set_op(self, other, "xor")
+
+    def _no_assigning_form(self, other):
+        # without these Python would rebind `a = a & b`, which is the operator's bucket layout under the assigning form's name
+        raise NotImplementedError("the assigning forms `&=`, `-=` and `^=` have the reference's remove_sorted_iter bucket layout, which is not built; use `a = a & b` for the operator form")
+
+    __iand__ = __isub__ = __ixor__ = _no_assigning_form
 
     # ---- inspection -------------------------------------------------------------------------------------------
     def consts(self) -> dict:

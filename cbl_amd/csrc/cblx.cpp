@@ -907,6 +907,37 @@ int cblx_merge_from(cblx_ctx* dst, cblx_ctx* self, cblx_ctx* other) {
         }
     });
 }
+int cblx_set_op(cblx_ctx* dst, cblx_ctx* a, cblx_ctx* b, uint32_t op) {
+    return guard(dst, [&] {
+        if (!a || !b) throw Error(CBLX_EINVAL, "null argument");
+        if (dst == a || dst == b || a == b) throw Error(CBLX_EINVAL, "set_op: dst, a and b must be three different contexts");
+        for (cblx_ctx* x : {a, b})
+            if (dst->P.K != x->P.K || dst->P.PB != x->P.PB) throw Error(CBLX_EINVAL, "set_op: K / PREFIX_BITS mismatch");
+        if (a->P.canonical != b->P.canonical) throw Error(CBLX_EINVAL, "One of the index is canonical while the other isn't");
+        if (op > CBLX_SETOP_XOR) throw Error(CBLX_EINVAL, "set_op: unknown operation " + std::to_string(op));
+        if (dst->device != a->device || dst->device != b->device) throw Error(CBLX_EINVAL, "set_op: dst, a and b must live on the same device");
+        CBLX_HIP(hipStreamSynchronize(dst->stream));
+        dst->res = Resident();
+        dst->batch = SortedBatch();
+        ingest_drop(dst);
+        dst->P.canonical = a->P.canonical;  // the result is as canonical as its operands
+        for (cblx_ctx* x : {a, b}) {  // an observer: pending inserts are part of the sets
+            flush(x);
+            CBLX_HIP(hipStreamSynchronize(x->stream));
+        }
+        const bool ea = a->res.count == 0, eb = b->res.count == 0;
+        if (ea || eb) {  // no prefix is held by both: nothing is sorted, what the op keeps is cloned as stored
+            const bool keep_a = !ea && op != CBLX_SETOP_AND, keep_b = !eb && (op == CBLX_SETOP_OR || op == CBLX_SETOP_XOR);
+            if (keep_a) dst->res = clone_resident(dst, a);
+            else if (keep_b) dst->res = clone_resident(dst, b);
+            return;
+        }
+        dispatch(dst->P, [&](auto cfg) { set_op_direct<decltype(cfg)>(dst, a->res, b->res, op); });
+        collect_events(dst);
+        CBLX_HIP(hipStreamSynchronize(dst->stream));
+    });
+}
+int cblx_get_device(const cblx_ctx* c, int32_t* out) { if (!c || !out) return CBLX_EINVAL; *out = (int32_t)c->device; return CBLX_OK; }
 int cblx_merge_assign(cblx_ctx* self, cblx_ctx* other) {
     return guard(self, [&] {
         if (!other) throw Error(CBLX_EINVAL, "null argument");

@@ -517,6 +517,266 @@ __global__ __launch_bounds__(UNI_THREADS) void k_bucket_union(const BDesc* __res
     if (tid == 0) { out_count[r] = written; out_kind[r] = KIND_TRIE; }
 }
 
+// ---- `&mut a OP &mut b` into a new index (cblx_set_op; /root/reference/src/wordset/set_ops.rs:78-121, 159-190, 241-279, 319-364 walk the
+// two prefix bitvectors, src/trievec/set_ops.rs:5-41, 73-99, 131-161, 189-224 the buckets): a bucket only one side holds is cloned as
+// stored, a bucket both hold becomes TrieOrVec::Vec(sorted OP of the two sorted iterators) — always a Vec, ascending, dropped when empty;
+// iter_sorted leaves the Vec buckets of either operand sorted on the prefixes both hold. --------------------------------------------------
+static const u32 SETOP_OR = 0, SETOP_AND = 1, SETOP_SUB = 2, SETOP_XOR = 3;  // = CBLX_SETOP_* of include/cblx.h
+// candidate prefixes of the result: AND needs both sides, SUB needs a's (what only b holds yields nothing), OR / XOR either
+__global__ void k_setop_bv(u64 nwords, const u64* __restrict__ a, const u64* __restrict__ b, u32 op, u64* __restrict__ out, u32* __restrict__ popc) {
+    const u64 w = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= nwords) return;
+    const u64 v = op == SETOP_AND ? (a[w] & b[w]) : op == SETOP_SUB ? a[w] : (a[w] | b[w]);
+    out[w] = v;
+    popc[w] = (u32)__builtin_popcountll(v);
+}
+// One thread per candidate prefix, after k_merge_table (cap = cs + co on entry): the run capacity becomes the op's upper bound, a one-sided bucket
+// gets its final count and kind (it is cloned as stored), a both-sided one joins the `both` list, and each of its Vec sides of two words or more
+// joins the list of the sorting class of its length ([side][0]: one workgroup's LDS radix sort, [side][1]: the general kernel) with the run in the
+// OPERAND's arena as its descriptor — sorted in place there, which is the side effect the reference has.
+static const u32 SETOP_SORT_LDS = 512 * MED_ITEMS;  // k_bucket_medium<512>'s capacity
+__global__ __launch_bounds__(CLASSIFY_THREADS) void k_setop_plan(u64 nb, u32 op, u32* __restrict__ cap, const u32* __restrict__ m_cs, u32* __restrict__ m_co,
+                                                                  const u64* __restrict__ m_sstart, const u64* __restrict__ m_ostart, const u8* __restrict__ m_skind,
+                                                                  const u8* __restrict__ m_okind, u32* __restrict__ out_count, u8* __restrict__ out_kind,
+                                                                  BDesc* __restrict__ sort_lists /* [2 sides][2 classes][nb] */, BDesc* __restrict__ both_list,
+                                                                  u32* __restrict__ list_n /* [4] sort lists, [1] both */) {
+    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    int cls_a = -1, cls_b = -1, cls_both = -1;
+    u32 cs = 0, co = 0;
+    if (r < nb) {
+        cs = m_cs[r];
+        co = cap[r] - cs;
+        m_co[r] = co;
+        if (cs != 0 && co != 0) {
+            cap[r] = op == SETOP_AND ? (cs < co ? cs : co) : op == SETOP_SUB ? cs : cs + co;
+            out_count[r] = 0;  // (written by k_bucket_setop)
+            out_kind[r] = KIND_VEC;
+            cls_both = 0;
+            if (m_skind[r] == KIND_VEC && cs > 1) cls_a = cs <= SETOP_SORT_LDS ? 0 : 1;
+            if (m_okind[r] == KIND_VEC && co > 1) cls_b = co <= SETOP_SORT_LDS ? 0 : 1;
+        } else {  // one-sided (never for AND, never b's side for SUB: such prefixes are no candidates)
+            cap[r] = cs + co;
+            out_count[r] = cs + co;
+            out_kind[r] = cs ? m_skind[r] : m_okind[r];
+        }
+    }
+    const u32 slot_a = block_append<CLASSIFY_THREADS, 2>(cls_a, list_n);
+    if (cls_a >= 0) sort_lists[(u64)cls_a * nb + slot_a] = BDesc{m_sstart[r], cs | BDESC_TRIE, (u32)r};  // (TRIE: the kernel leaves the run sorted)
+    __syncthreads();  // block_append's tables are reused
+    const u32 slot_b = block_append<CLASSIFY_THREADS, 2>(cls_b, list_n + 2);
+    if (cls_b >= 0) sort_lists[(u64)(2 + cls_b) * nb + slot_b] = BDesc{m_ostart[r], co | BDESC_TRIE, (u32)r};
+    const u32 slot = block_append<CLASSIFY_THREADS, 1>(cls_both, list_n + 4);
+    if (cls_both >= 0) both_list[slot] = BDesc{0, 0, (u32)r};
+}
+// LPB lanes per candidate: a one-sided bucket is copied into its run as stored
+template <bool WS, int LPB>
+__global__ __launch_bounds__(256) void k_setop_gather(u64 nb, const u64* __restrict__ start, const u32* __restrict__ m_cs, const u32* __restrict__ m_co,
+                                                      const u64* __restrict__ m_sstart, const u64* __restrict__ m_ostart, const u64* __restrict__ s_lo,
+                                                      const u64* __restrict__ s_hi, const u64* __restrict__ o_lo, const u64* __restrict__ o_hi,
+                                                      u64* __restrict__ out_lo, u64* __restrict__ out_hi) {
+    const u64 r = ((u64)blockIdx.x * 256 + threadIdx.x) / LPB;
+    if (r >= nb) return;
+    const u32 lane = threadIdx.x & (LPB - 1);
+    const u32 cs = m_cs[r], co = m_co[r];
+    if (cs != 0 && co != 0) return;
+    const u64 d0 = start[r], src = cs ? m_sstart[r] : m_ostart[r];
+    const u64* __restrict__ lo = cs ? s_lo : o_lo;
+    const u64* __restrict__ hi = cs ? s_hi : o_hi;
+    for (u32 j = lane; j < cs + co; j += LPB) {
+        out_lo[d0 + j] = lo[src + j];
+        if constexpr (WS) out_hi[d0 + j] = hi[src + j];
+    }
+}
+// Both-sided buckets: k_bucket_union's rounds (two staging rings, co-rank on the round's diagonal, register merge network, ordered compaction by
+// ballot) with another keep-predicate. Both lists are duplicate-free, so a value occurs once or twice in the merged sequence, a's copy first:
+//   OR keeps what differs from its predecessor, AND what equals it (the second of a pair), XOR what differs from both neighbours, SUB what
+//   differs from both neighbours and came from a.
+// ORIGIN (SUB): the merge network loses it. No tag bit is used — a bit above the suffix is free below 64 bits and in the high half of a wide
+// suffix, but not at SUFFIX_BITS = 64, and a tagged all-ones suffix would have to be kept apart from the network's padding value. Instead the
+// thread that merged an output knows how many of its outputs came from a (the difference of its two co-ranks) and still holds exactly those
+// candidates in registers: an output that equals none of them came from b. (One that equals one of them is a's copy or b's copy of a PAIR, which SUB
+// drops on its neighbours alone, so the answer is exact wherever it is used.) The same code serves every suffix width; the flags travel to the
+// compaction through one LDS word per thread.
+// ROUND EDGES: a's copy of a pair may be the last output of a round and b's copy the first of the next. The last output of every round is therefore
+// HELD BACK — its value, whether it equals its predecessor and where it came from stay in registers — and is decided as the first element of the
+// next round, when its successor is known; after the last round it has no successor. A round thus emits [held-back value, outputs 0 .. nout-2].
+template <bool WS, u32 OP>
+__global__ __launch_bounds__(UNI_THREADS) void k_bucket_setop(const BDesc* __restrict__ list, const u32* __restrict__ list_n, const u32* __restrict__ m_cs,
+                                                              const u32* __restrict__ m_co, const u64* __restrict__ m_sstart, const u64* __restrict__ m_ostart,
+                                                              const u64* __restrict__ s_lo, const u64* __restrict__ s_hi, const u64* __restrict__ o_lo,
+                                                              const u64* __restrict__ o_hi, const u64* __restrict__ run_start, u64* __restrict__ out_lo,
+                                                              u64* __restrict__ out_hi, u32 SB, u32* __restrict__ out_count, u8* __restrict__ out_kind) {
+    typedef UniE<WS> E;
+    constexpr int NW = UNI_THREADS / 64;
+    constexpr u32 T = UNI_TILE;
+    static_assert((T & (T - 1)) == 0, "the staging rings index by g mod T");
+    static_assert(UNI_ITEMS <= 32, "one origin bit per output in a 32-bit word");
+    constexpr u32 SLOTS = T * 2 + (T * 2) / 8 + 8;
+    __shared__ u64 s_in[SLOTS];
+    __shared__ u64 s_inh[WS ? SLOTS : 1];
+    __shared__ u32 s_org[OP == SETOP_SUB ? UNI_THREADS : 1];  // bit k of word t: output t * UNI_ITEMS + k of the round came from a
+    __shared__ u32 s_split[NW + 1];
+    __shared__ u32 s_wtot[NW + 1];
+    if (blockIdx.x >= *list_n) return;
+    const u32 r = list[blockIdx.x].r, cs = m_cs[r], co = m_co[r];
+    const u64 a_self = m_sstart[r], a_oth = m_ostart[r], d_run = run_start[r];
+    const u64* __restrict__ A = s_lo + a_self;
+    const u64* __restrict__ B = o_lo + a_oth;
+    const u64* __restrict__ Ah = WS ? s_hi + a_self : nullptr;
+    const u64* __restrict__ Bh = WS ? o_hi + a_oth : nullptr;
+    u64* __restrict__ dst = out_lo + d_run;
+    u64* __restrict__ dsth = WS ? out_hi + d_run : nullptr;
+    const u64 mask = WS ? ((1ull << (SB - 64)) - 1ull) : (SB >= 64 ? ~0ull : ((1ull << SB) - 1ull));
+    const u32 tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    auto get = [&](u32 slot) { E e; e.lo = s_in[slot]; if constexpr (WS) e.hi = s_inh[slot]; return e; };
+    auto put = [&](u32 slot, const E& e) { s_in[slot] = e.lo; if constexpr (WS) s_inh[slot] = e.hi; };
+    auto keep_rule = [](bool eqp, bool eqn, bool from_a) {
+        return OP == SETOP_OR ? !eqp : OP == SETOP_AND ? eqp : OP == SETOP_XOR ? (!eqp && !eqn) : (from_a && !eqp && !eqn);
+    };
+    u32 ia = 0, ib = 0, written = 0;
+    u32 ha = 0, hb = 0;
+    E carry = uni_inf<WS>();  // the held-back output
+    bool have_carry = false, carry_eqp = false, carry_a = false;
+    auto ra = [&](u32 g) { return uni_pad(g & (T - 1)); };
+    auto rb = [&](u32 g) { return uni_pad(T + (g & (T - 1))); };
+    while (ia < cs || ib < co) {
+        const u32 na = cs - ia < T ? cs - ia : T, nb = co - ib < T ? co - ib : T, nout = na + nb < T ? na + nb : T;
+        for (u32 g = ia + ha + tid; g < ia + na; g += UNI_THREADS) {
+            if constexpr (WS) { s_in[ra(g)] = A[g]; s_inh[ra(g)] = Ah[g] & mask; }
+            else s_in[ra(g)] = A[g] & mask;
+        }
+        for (u32 g = ib + hb + tid; g < ib + nb; g += UNI_THREADS) {
+            if constexpr (WS) { s_in[rb(g)] = B[g]; s_inh[rb(g)] = Bh[g] & mask; }
+            else s_in[rb(g)] = B[g] & mask;
+        }
+        __syncthreads();
+        const u32 d0 = tid * UNI_ITEMS < nout ? tid * UNI_ITEMS : nout, d1 = (tid + 1) * UNI_ITEMS < nout ? (tid + 1) * UNI_ITEMS : nout;
+        u32 lo = d1 > nb ? d1 - nb : 0u, hi = d1 < na ? d1 : na;
+        while (lo < hi) {
+            const u32 mid = (lo + hi) >> 1;
+            if (!uni_lt<WS>(get(rb(ib + d1 - 1 - mid)), get(ra(ia + mid)))) lo = mid + 1; else hi = mid;  // ties take a's copy first
+        }
+        const u32 i1 = lo;
+        if (lane == 63) s_split[w + 1] = i1;
+        if (tid == 0) s_split[0] = 0;
+        __syncthreads();
+        u32 i0 = __shfl_up(i1, 1, 64);
+        if (lane == 0) i0 = s_split[w];
+        const u32 iend = s_split[NW];
+        const u32 j0 = d0 - i0;
+        E a[UNI_ITEMS], b[UNI_ITEMS];
+#pragma unroll
+        for (int k = 0; k < UNI_ITEMS; ++k) {
+            const u32 x = i0 + k, y = j0 + k;
+            a[k] = uni_sel<WS>(x < na, get(ra(ia + (x < na ? x : 0u))), uni_inf<WS>());
+            b[k] = uni_sel<WS>(y < nb, get(rb(ib + (y < nb ? y : 0u))), uni_inf<WS>());
+        }
+        E o[UNI_ITEMS];
+#pragma unroll
+        for (int k = 0; k < UNI_ITEMS; ++k) o[k] = uni_sel<WS>(uni_lt<WS>(a[k], b[UNI_ITEMS - 1 - k]), a[k], b[UNI_ITEMS - 1 - k]);
+#pragma unroll
+        for (int st = UNI_ITEMS / 2; st >= 1; st >>= 1)
+#pragma unroll
+            for (int k = 0; k < UNI_ITEMS; ++k)
+                if ((k & st) == 0) uni_cmpx<WS>(o[k], o[k + st]);
+        u32 org = 0;
+        if constexpr (OP == SETOP_SUB) {
+            const u32 from_a = i1 - i0;  // a[0 .. from_a) are the thread's outputs that came from a
+#pragma unroll
+            for (int k = 0; k < UNI_ITEMS; ++k) {
+                bool fa = false;
+#pragma unroll
+                for (int j = 0; j < UNI_ITEMS; ++j) fa = fa || ((u32)j < from_a && uni_eq<WS>(o[k], a[j]));
+                org |= fa ? 1u << k : 0u;
+            }
+        }
+        __syncthreads();  // every read of the chunks is done: the outputs take the place of what the round consumed
+        auto oslot = [&](u32 q) { return q < iend ? ra(ia + q) : rb(ib + (q - iend)); };
+#pragma unroll
+        for (int k = 0; k < UNI_ITEMS; ++k) {
+            const u32 q = tid * UNI_ITEMS + k;
+            if (q < nout) put(oslot(q), o[k]);
+        }
+        if constexpr (OP == SETOP_SUB) s_org[tid] = org;
+        __syncthreads();
+        auto org_of = [&](u32 q) { return OP == SETOP_SUB ? ((s_org[q / UNI_ITEMS] >> (q % UNI_ITEMS)) & 1u) != 0 : false; };
+        // emit slot e of the round holds output e - 1 (slot 0: the value held back); its successor is output e
+        E v[UNI_ITEMS];
+        bool keep[UNI_ITEMS];
+        u32 wh = 0;
+#pragma unroll
+        for (int j = 0; j < UNI_ITEMS; ++j) {
+            const u32 e = w * (64 * UNI_ITEMS) + j * 64 + lane;
+            const bool in = e < nout;
+            const E succ = get(oslot(in ? e : 0u));
+            const E x1 = get(oslot(in && e >= 1 ? e - 1 : 0u)), x2 = get(oslot(in && e >= 2 ? e - 2 : 0u));
+            v[j] = uni_sel<WS>(e >= 1, x1, carry);
+            const E pred = uni_sel<WS>(e >= 2, x2, carry);
+            const bool eqp = e == 0 ? carry_eqp : ((e >= 2 || have_carry) && uni_eq<WS>(v[j], pred));
+            const bool from_a = e == 0 ? carry_a : org_of(in && e >= 1 ? e - 1 : 0u);
+            keep[j] = in && (e >= 1 || have_carry) && keep_rule(eqp, uni_eq<WS>(v[j], succ), from_a);
+            wh += (u32)__builtin_popcountll(__ballot(keep[j]));
+        }
+        // the round's last output is held back
+        const E last = get(oslot(nout - 1));
+        const E before = uni_sel<WS>(nout >= 2, get(oslot(nout >= 2 ? nout - 2 : 0u)), carry);
+        const bool last_eqp = (nout >= 2 || have_carry) && uni_eq<WS>(last, before);
+        const bool last_a = org_of(nout - 1);
+        if (lane == 0) s_wtot[w] = wh;
+        __syncthreads();
+        u32 run = 0, tot = 0;
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) { const u32 t = s_wtot[ww]; if ((u32)ww < w) run += t; tot += t; }
+#pragma unroll
+        for (int j = 0; j < UNI_ITEMS; ++j) {
+            const u64 bal = __ballot(keep[j]);
+            if (keep[j]) {
+                dst[written + run + mbcnt(bal)] = v[j].lo;
+                if constexpr (WS) dsth[written + run + mbcnt(bal)] = v[j].hi;
+            }
+            run += (u32)__builtin_popcountll(bal);
+        }
+        carry = last;
+        carry_eqp = last_eqp;
+        carry_a = last_a;
+        have_carry = true;
+        written += tot;
+        ha = na - iend;
+        hb = nb - (nout - iend);
+        ia += iend;
+        ib += nout - iend;
+        __syncthreads();  // the next round refills the freed slots and rewrites the split table
+    }
+    if (tid == 0) {
+        if (have_carry && keep_rule(carry_eqp, false, carry_a)) {  // the last value of the merged sequence has no successor
+            dst[written] = carry.lo;
+            if constexpr (WS) dsth[written] = carry.hi;
+            ++written;
+        }
+        out_count[r] = written;
+        out_kind[r] = KIND_VEC;
+    }
+}
+// the candidates that keep at least one word stay in the directory
+__global__ void k_setop_live(u64 nb, const u32* __restrict__ cnt, u32* __restrict__ live) {
+    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < nb) live[r] = cnt[r] != 0 ? 1u : 0u;
+}
+// ... and move to their new rank (ascending prefixes stay ascending); their bits make up the result's bitvector (zeroed by the caller)
+__global__ void k_setop_compact(u64 nb, const u32* __restrict__ cnt, const u64* __restrict__ new_rank, const u32* __restrict__ prefix, const u64* __restrict__ start,
+                                const u8* __restrict__ kind, u32* __restrict__ o_prefix, u64* __restrict__ o_start, u32* __restrict__ o_cnt, u8* __restrict__ o_kind,
+                                u64* __restrict__ bv) {
+    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nb || cnt[r] == 0) return;
+    const u64 n = new_rank[r];
+    const u32 p = prefix[r];
+    o_prefix[n] = p;
+    o_start[n] = start[r];
+    o_cnt[n] = cnt[r];
+    o_kind[n] = kind[r];
+    atomicOr((unsigned long long*)&bv[p >> 6], 1ull << (p & 63));
+}
+
 // ---- suffix access --------------------------------------------------------------------------------------
 // narrow suffix (SB <= 64): suffix = lo & mask. wide (SB > 64): (hi & mask(SB-64), lo).
 template <bool WS> struct Sfx;

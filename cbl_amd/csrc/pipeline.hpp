@@ -1609,5 +1609,141 @@ template <typename C> void merge_direct(cblx_ctx* c, const Resident& s, const Re
     c->res = std::move(nr);
 }
 
+// ---- `&mut a OP &mut b` into a new index, all three resident on this device (src/cbl.rs:411-431, 451-471, 491-511, 531-551 -> src/wordset/set_ops.rs) ----
+// The result becomes c->res. `a` and `b` keep their sets; their Vec buckets on the prefixes both hold are sorted in their own arenas (iter_sorted's side
+// effect). Both operands are non-empty (the caller answers the other cases with a clone or an empty index).
+// The arena keeps slack inside the runs of the both-sided buckets (a run is as long as the op's upper bound), as the results of `|=` do: the serializer,
+// cblx_validate and the queries read start[r] and cnt[r] only.
+template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, u32 op) {
+    typedef typename C::HiT HiT;
+    constexpr bool WS = C::WS;
+    const Consts& P = c->P;
+    const u64 nprefix = 1ull << P.PB, nwords = std::max<u64>(1, nprefix / 64);
+    Resident nr;
+    Buf<u32> cap, m_cs, m_co, popc(c->pool, nwords);
+    Buf<u64> m_sstart, m_ostart;
+    Buf<u8> m_skind, m_okind;
+    Buf<BDesc> sort_lists, both_list;
+    Buf<u32> list_n(c->pool, 5);
+    u64 N = 0;
+    {
+        StageTimer t(c, ST_DIR);
+        nr.bv = Buf<u64>(c->pool, nwords);
+        nr.rank_dir = Buf<u64>(c->pool, nwords + 1);
+        hipLaunchKernelGGL(k_setop_bv, grid1(nwords, 256), dim3(256), 0, c->stream, nwords, a.bv.get(), b.bv.get(), op, nr.bv.get(), popc.get());
+        nr.nb = exclusive_scan<u64>(c, popc.get(), nwords, nr.rank_dir.get());
+        if (nr.nb == 0) { c->res = Resident(); return; }  // (AND of indexes that share no prefix)
+        const u64 nb = nr.nb;
+        nr.prefix = Buf<u32>(c->pool, nb + 1);
+        nr.start = Buf<u64>(c->pool, nb + 1);
+        nr.cnt = Buf<u32>(c->pool, nb + 1);
+        nr.kind = Buf<u8>(c->pool, nb + 1);
+        cap = Buf<u32>(c->pool, nb + 1);
+        m_cs = Buf<u32>(c->pool, nb + 1);
+        m_co = Buf<u32>(c->pool, nb + 1);
+        m_sstart = Buf<u64>(c->pool, nb + 1);
+        m_ostart = Buf<u64>(c->pool, nb + 1);
+        m_skind = Buf<u8>(c->pool, nb + 1);
+        m_okind = Buf<u8>(c->pool, nb + 1);
+        sort_lists = Buf<BDesc>(c->pool, 4 * nb);
+        both_list = Buf<BDesc>(c->pool, nb);
+        CBLX_HIP(hipMemsetAsync(list_n.get(), 0, 5 * 4, c->stream));
+        hipLaunchKernelGGL(k_merge_table, grid1(nprefix, 256), dim3(256), 0, c->stream, nprefix, nr.bv.get(), nr.rank_dir.get(), a.view(), b.view(), nr.prefix.get(),
+                           cap.get(), m_cs.get(), m_sstart.get(), m_ostart.get(), m_skind.get(), m_okind.get());
+        hipLaunchKernelGGL(k_setop_plan, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, op, cap.get(), m_cs.get(), m_co.get(), m_sstart.get(),
+                           m_ostart.get(), m_skind.get(), m_okind.get(), nr.cnt.get(), nr.kind.get(), sort_lists.get(), both_list.get(), list_n.get());
+        N = exclusive_scan<u64>(c, cap.get(), nb, nr.start.get());
+        hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, nr.start.get() + nb, N);
+        CBLX_HIP(hipGetLastError());
+    }
+    const u64 nb = nr.nb;
+    nr.a_lo = Buf<u64>(c->pool, N + 2);
+    if (WS) nr.a_hi = Buf<u64>(c->pool, N + 2);
+    {
+        StageTimer t(c, ST_EXPAND);
+        with_lpb(N, nb, [&](auto lpb) {
+            constexpr int LPB = decltype(lpb)::value;
+            hipLaunchKernelGGL((k_setop_gather<WS, LPB>), lpb_grid(nb, LPB), dim3(256), 0, c->stream, nb, nr.start.get(), m_cs.get(), m_co.get(), m_sstart.get(), m_ostart.get(),
+                               (const u64*)a.a_lo.get(), (const u64*)a.a_hi.get(), (const u64*)b.a_lo.get(), (const u64*)b.a_hi.get(), nr.a_lo.get(), nr.a_hi.get());
+        });
+        CBLX_HIP(hipGetLastError());
+    }
+    const std::vector<u32> ln = d2h_vec<u32>(c, list_n.get(), 5);
+    {
+        // step 1: the Vec sides of the both-sided buckets, sorted where they are stored. Runs of up to 4096 words take the LDS radix sort, longer ones (a Vec
+        // left by an earlier `|=` or set operation has no length limit) the general kernel; both are asked for the sorted layout and write the count and
+        // kind they find — the operand's own, unchanged: its words are distinct — into a table nobody reads.
+        Resident junk;
+        junk.cnt = Buf<u32>(c->pool, nb + 1);
+        junk.kind = Buf<u8>(c->pool, nb + 1);
+        for (int side = 0; side < 2; ++side) {
+            Resident& x = side ? b : a;
+            u64* x_lo = x.a_lo.get();
+            HiT* x_hi = WS ? (HiT*)x.a_hi.get() : (HiT*)nullptr;
+            const BDesc* l_lds = sort_lists.get() + (size_t)(2 * side) * nb;
+            const BDesc* l_gen = sort_lists.get() + (size_t)(2 * side + 1) * nb;
+            if (ln[2 * side]) {
+                StageTimer t(c, ST_BMED);
+                hipLaunchKernelGGL((k_bucket_medium<512, WS, HiT>), dim3(ln[2 * side]), dim3(512), 0, c->stream, l_lds, list_n.get() + 2 * side, x_lo, x_hi, P.SB, junk.cnt.get(),
+                                   junk.kind.get(), MergeArgs{});
+                CBLX_HIP(hipGetLastError());
+            }
+            huge_stage<C>(c, l_gen, list_n.get() + 2 * side + 1, ln[2 * side + 1], x_lo, x_hi, junk, MergeArgs{});
+        }
+        CBLX_HIP(hipStreamSynchronize(c->stream));  // `junk` dies here
+    }
+    if (ln[4]) {
+        // step 2: both lists ascending now, whatever their kinds
+        StageTimer t(c, ST_BBIG);
+        auto go = [&](auto opc) {
+            constexpr u32 OP = decltype(opc)::value;
+            hipLaunchKernelGGL((k_bucket_setop<WS, OP>), dim3(ln[4]), dim3(UNI_THREADS), 0, c->stream, both_list.get(), list_n.get() + 4, m_cs.get(), m_co.get(), m_sstart.get(),
+                               m_ostart.get(), (const u64*)a.a_lo.get(), (const u64*)a.a_hi.get(), (const u64*)b.a_lo.get(), (const u64*)b.a_hi.get(), (const u64*)nr.start.get(),
+                               nr.a_lo.get(), nr.a_hi.get(), P.SB, nr.cnt.get(), nr.kind.get());
+        };
+        if (op == SETOP_OR) go(std::integral_constant<u32, SETOP_OR>());
+        else if (op == SETOP_AND) go(std::integral_constant<u32, SETOP_AND>());
+        else if (op == SETOP_SUB) go(std::integral_constant<u32, SETOP_SUB>());
+        else go(std::integral_constant<u32, SETOP_XOR>());
+        CBLX_HIP(hipGetLastError());
+    }
+    {
+        // buckets that came out empty leave the directory (never for OR)
+        StageTimer t(c, ST_DIR);
+        Buf<u32> live(c->pool, nb);
+        Buf<u64> new_rank(c->pool, nb);
+        hipLaunchKernelGGL(k_setop_live, grid1(nb, 256), dim3(256), 0, c->stream, nb, nr.cnt.get(), live.get());
+        const u64 kept = exclusive_scan<u64>(c, live.get(), nb, new_rank.get());
+        if (kept == 0) { CBLX_HIP(hipStreamSynchronize(c->stream)); c->res = Resident(); return; }
+        if (kept != nb) {
+            Resident cr;
+            cr.nb = kept;
+            cr.bv = Buf<u64>(c->pool, nwords);
+            cr.rank_dir = Buf<u64>(c->pool, nwords + 1);
+            cr.prefix = Buf<u32>(c->pool, kept + 1);
+            cr.start = Buf<u64>(c->pool, kept + 1);
+            cr.cnt = Buf<u32>(c->pool, kept + 1);
+            cr.kind = Buf<u8>(c->pool, kept + 1);
+            CBLX_HIP(hipMemsetAsync(cr.bv.get(), 0, nwords * 8, c->stream));
+            hipLaunchKernelGGL(k_setop_compact, grid1(nb, 256), dim3(256), 0, c->stream, nb, nr.cnt.get(), new_rank.get(), nr.prefix.get(), nr.start.get(), nr.kind.get(),
+                               cr.prefix.get(), cr.start.get(), cr.cnt.get(), cr.kind.get(), cr.bv.get());
+            hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, cr.start.get() + kept, N);
+            hipLaunchKernelGGL(k_popc_words, grid1(nwords, 256), dim3(256), 0, c->stream, nwords, cr.bv.get(), popc.get());
+            CBLX_HIP(hipGetLastError());
+            if (exclusive_scan<u64>(c, popc.get(), nwords, cr.rank_dir.get()) != kept) throw Error(CBLX_EDEVICE, "set_op: the compacted directory does not match its bitvector (internal error)");
+            cr.a_lo = std::move(nr.a_lo);
+            cr.a_hi = std::move(nr.a_hi);
+            CBLX_HIP(hipStreamSynchronize(c->stream));  // the old tables die here
+            nr = std::move(cr);
+        }
+    }
+    {
+        Buf<u64> total(c->pool, 1);
+        CBLX_HIP(hipMemsetAsync(total.get(), 0, 8, c->stream));
+        hipLaunchKernelGGL(k_sum_u32, dim3((unsigned)std::min<u64>(2048, std::max<u64>(1, ceil_div(nr.nb, 256)))), dim3(256), 0, c->stream, nr.cnt.get(), nr.nb, total.get());
+        nr.count = d2h<u64>(c, total.get());
+    }
+    c->res = std::move(nr);
+}
 
 }  // namespace

@@ -27,7 +27,8 @@ extern "C" {
 
 /* 3: cblx_merge_from, cblx_stage_units, cblx_fine_builds, cblx_comm_groups_fine, cblx_comm_protocol_used, CBLX_PROTO_AUTO (the default of a new
  * communicator: an unchanged 2 - 4 rank caller no longer runs BINS), CBLX_PROTO_REPLICATE; empty PREFIX_BITS > 24 builds take the FINE route. A binding
- * built against this header must refuse a library that reports less. */
+ * built against this header must refuse a library that reports less.
+ * Added under 3 (a new symbol is compatible): cblx_set_op with CBLX_SETOP_OR / AND / SUB / XOR, and cblx_get_device. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -301,6 +302,22 @@ int cblx_merge_assign(cblx_ctx* self, cblx_ctx* other);
  * (/root/reference/src/cbl.rs:433-449) without the copy: the device merge writes a new arena anyway. dst's previous content is dropped;
  * dst, self and other are three different contexts of equal K / PREFIX_BITS / canonical, dst and self on the same device. */
 int cblx_merge_from(cblx_ctx* dst, cblx_ctx* self, cblx_ctx* other);
+
+/* dst = what `&mut a OP &mut b` returns (/root/reference/src/cbl.rs:411-431, 451-471, 491-511, 531-551 -> src/wordset/set_ops.rs:78-121, 159-190,
+ * 241-279, 319-364 -> src/trievec/set_ops.rs): a bucket only one operand holds is cloned as stored (kind and order kept; AND keeps none, SUB only
+ * a's), a bucket both hold becomes a Vec of the result in ascending order whatever its length, and is dropped when empty. a and b keep their sets and
+ * are left as the reference leaves them: on every prefix both hold, a Vec bucket of either is sorted ascending (also where the result is empty).
+ * Pending inserts of a and b are applied first. dst's previous content and pending work are dropped as cblx_merge_from drops them; dst takes a's
+ * canonical flag. CBLX_EINVAL, with the three contexts unchanged: dst, a and b not three different contexts, K / PREFIX_BITS differ, a and b differ in
+ * `canonical`, op > 3, or the contexts live on different devices. On any other error (a flush of a or b that fails, CBLX_ENOMEM) dst's previous
+ * content is lost, as with cblx_merge_from. The assigning forms (`&=`, `-=`, `^=`) have another bucket layout and are not offered. */
+#define CBLX_SETOP_OR 0
+#define CBLX_SETOP_AND 1
+#define CBLX_SETOP_SUB 2
+#define CBLX_SETOP_XOR 3
+int cblx_set_op(cblx_ctx* dst, cblx_ctx* a, cblx_ctx* b, uint32_t op);
+/* The HIP device ordinal the context lives on (cblx_params.device = -1 resolved at creation). */
+int cblx_get_device(const cblx_ctx* ctx, int32_t* out);
 
 /* Walk the resident buckets in ascending prefix order (lets a Rust shim rebuild a WordSet, and tests
  * compare bucket contents): kind 0 = Vec (stored = first-occurrence order), 1 = Trie (ascending).

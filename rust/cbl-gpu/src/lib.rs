@@ -20,7 +20,7 @@
 use std::collections::BTreeMap;
 use std::ffi::{CStr, CString};
 use std::marker::PhantomData;
-use std::ops::BitOrAssign;
+use std::ops::{BitAnd, BitOr, BitOrAssign, BitXor, Sub};
 use std::os::raw::c_int;
 use std::path::Path;
 
@@ -389,6 +389,49 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         let s = Self::with(self.is_canonical());
         s.check(unsafe { sys::cblx_merge_from(s.ctx, self.ctx, other.ctx) });
         s
+    }
+}
+
+impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BITS> {
+    /// `&mut a OP &mut b` (`src/cbl.rs:411-431, 451-471, 491-511, 531-551`): a new set; both operands keep theirs, with their Vec buckets on the
+    /// prefixes both hold sorted (`iter_sorted`).
+    fn set_op(&mut self, other: &mut Self, op: u32) -> Self {
+        assert_eq!(self.is_canonical(), other.is_canonical(), "One of the index is canonical while the other isn't");
+        let s = Self::with(self.is_canonical());
+        s.check(unsafe { sys::cblx_set_op(s.ctx, self.ctx, other.ctx, op) });
+        s
+    }
+}
+
+impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> BitAnd<Self> for &mut CBL<K, T, PREFIX_BITS> {
+    type Output = CBL<K, T, PREFIX_BITS>;
+    /// Intersection (`src/cbl.rs:451-471`).
+    fn bitand(self, other: Self) -> Self::Output {
+        self.set_op(other, sys::CBLX_SETOP_AND)
+    }
+}
+
+impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> Sub<Self> for &mut CBL<K, T, PREFIX_BITS> {
+    type Output = CBL<K, T, PREFIX_BITS>;
+    /// Difference (`src/cbl.rs:491-511`).
+    fn sub(self, other: Self) -> Self::Output {
+        self.set_op(other, sys::CBLX_SETOP_SUB)
+    }
+}
+
+impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> BitXor<Self> for &mut CBL<K, T, PREFIX_BITS> {
+    type Output = CBL<K, T, PREFIX_BITS>;
+    /// Symmetric difference (`src/cbl.rs:531-551`).
+    fn bitxor(self, other: Self) -> Self::Output {
+        self.set_op(other, sys::CBLX_SETOP_XOR)
+    }
+}
+
+impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> BitOr<Self> for &mut CBL<K, T, PREFIX_BITS> {
+    type Output = CBL<K, T, PREFIX_BITS>;
+    /// Union into a new set (`src/cbl.rs:411-431`); `|=` is the in-place form.
+    fn bitor(self, other: Self) -> Self::Output {
+        self.set_op(other, sys::CBLX_SETOP_OR)
     }
 }
 

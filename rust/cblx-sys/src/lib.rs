@@ -24,6 +24,10 @@ pub const CBLX_PROTO_SORTED: u32 = 0;
 pub const CBLX_PROTO_BINS: u32 = 1;
 pub const CBLX_PROTO_AUTO: u32 = 2;
 pub const CBLX_PROTO_REPLICATE: u32 = 3;
+pub const CBLX_SETOP_OR: u32 = 0;
+pub const CBLX_SETOP_AND: u32 = 1;
+pub const CBLX_SETOP_SUB: u32 = 2;
+pub const CBLX_SETOP_XOR: u32 = 3;
 
 #[repr(C)]
 pub struct cblx_ctx {
@@ -266,6 +270,8 @@ extern "C" {
 
     pub fn cblx_merge_assign(this: *mut cblx_ctx, other: *mut cblx_ctx) -> c_int;
     pub fn cblx_merge_from(dst: *mut cblx_ctx, this: *mut cblx_ctx, other: *mut cblx_ctx) -> c_int;
+    pub fn cblx_set_op(dst: *mut cblx_ctx, a: *mut cblx_ctx, b: *mut cblx_ctx, op: u32) -> c_int;
+    pub fn cblx_get_device(ctx: *const cblx_ctx, out: *mut i32) -> c_int;
     pub fn cblx_stage_units(ctx: *mut cblx_ctx, units: *mut u64, cap: u32, n: *mut u32) -> c_int;
 
     pub fn cblx_export_buckets(ctx: *mut cblx_ctx, cb: cblx_bucket_cb, user: *mut c_void) -> c_int;
