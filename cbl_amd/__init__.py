@@ -132,6 +132,7 @@ SIGNATURES = {
     "cblx_merge_assign": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cblx_merge_from": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cblx_set_op": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "cblx_set_op_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "cblx_get_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "cblx_stage_units": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]),
     "cblx_export_buckets": (C.c_int, [C.c_void_p, BUCKET_CB, C.c_void_p]),
@@ -808,9 +809,21 @@ class CBL:
     def __xor__(self, other: "CBL") -> "CBL":
         return CBL.set_op(self, other, "xor")
 
+    # ---- src/cbl.rs:473-489, 513-529, 553-569: the assigning forms `a OP= &mut b` --------------------------------------
+    def set_op_assign(self, other: "CBL", op: str) -> "CBL":
+        """`self OP= other` in place (op: "and" | "sub" | "xor" | "or"; "or" is `|=`), as the reference's `&=`, `-=`, `^=` leave both operands:
+        a bucket both hold keeps self's kind — a Trie stays ascending, a Vec gets the reference's swap_remove order — and is dropped when empty;
+        `other` keeps its set, its Vec buckets on the prefixes both hold end up sorted. Returns self."""
+        if op not in SETOPS:
+            raise ValueError("set_op_assign: op must be one of %s" % ", ".join(repr(o) for o in SETOPS))
+        if op == "or":
+            return self.__ior__(other)
+        self._chk(self._L.cblx_set_op_assign(self._h, other._h, SETOPS[op]))
+        return self
+
     def _no_assigning_form(self, other):
         # without these Python would rebind `a = a & b`, which is the operator's bucket layout under the assigning form's name
-        raise NotImplementedError("the assigning forms `&=`, `-=` and `^=` have the reference's remove_sorted_iter bucket layout, which is not built; use `a = a & b` for the operator form")
+        raise NotImplementedError("`&=`, `-=` and `^=` are spelled a.set_op_assign(b, \"and\" | \"sub\" | \"xor\") (the reference's in-place bucket layout); `a = a & b` is the operator form")
 
     __iand__ = __isub__ = __ixor__ = _no_assigning_form
 

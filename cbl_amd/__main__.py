@@ -1,5 +1,5 @@
-"""`python -m cbl_amd <command>` — the build / insert / merge / count / query / list subcommands of the reference CLI
-(/root/reference/examples/cbl.rs:147-167,230-249,270-279,168-229) on the MI355X path.
+"""`python -m cbl_amd <command>` — the build / insert / merge / inter / diff / sym-diff / count / query / list subcommands of the reference CLI
+(/root/reference/examples/cbl.rs:147-167,230-249,270-309,168-229) on the MI355X path.
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
 here they are flags with the same defaults (K=25, PREFIX_BITS=24). Index files are interchangeable with the reference's.
@@ -28,6 +28,11 @@ def main(argv=None):
     m.add_argument("first_index")
     m.add_argument("second_index")
     m.add_argument("-o", "--output")
+    for name, what in (("inter", "intersection"), ("diff", "difference"), ("sym-diff", "symmetric difference")):  # examples/cbl.rs:280-309
+        s = sub.add_parser(name, help=f"Compute the {what} of two indexes")
+        s.add_argument("first_index")
+        s.add_argument("second_index")
+        s.add_argument("-o", "--output")
     c = sub.add_parser("count", help="Count the k-mers contained in an index")
     c.add_argument("index")
     q = sub.add_parser("query", help="Query an index for every k-mer contained in a FASTA/Q file")
@@ -57,6 +62,13 @@ def main(argv=None):
         cbl = CBL.load_from_file(a.first_index, a.k, a.prefix_bits, device=a.device)
         cbl2 = CBL.load_from_file(a.second_index, a.k, a.prefix_bits, device=a.device)
         cbl |= cbl2
+        if a.output:
+            print(f"Writing the index to {a.output}", file=sys.stderr)
+            cbl.save_to_file(a.output)
+    elif a.cmd in ("inter", "diff", "sym-diff"):  # `cbl &= &mut cbl2`, `cbl -= &mut cbl2`, `cbl ^= &mut cbl2`
+        cbl = CBL.load_from_file(a.first_index, a.k, a.prefix_bits, device=a.device)
+        cbl2 = CBL.load_from_file(a.second_index, a.k, a.prefix_bits, device=a.device)
+        cbl.set_op_assign(cbl2, {"inter": "and", "diff": "sub", "sym-diff": "xor"}[a.cmd])
         if a.output:
             print(f"Writing the index to {a.output}", file=sys.stderr)
             cbl.save_to_file(a.output)

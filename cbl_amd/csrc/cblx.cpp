@@ -937,6 +937,31 @@ int cblx_set_op(cblx_ctx* dst, cblx_ctx* a, cblx_ctx* b, uint32_t op) {
         CBLX_HIP(hipStreamSynchronize(dst->stream));
     });
 }
+int cblx_set_op_assign(cblx_ctx* a, cblx_ctx* b, uint32_t op) {
+    const int rc = guard(a, [&] {
+        if (!a || !b) throw Error(CBLX_EINVAL, "null argument");
+        if (a == b) throw Error(CBLX_EINVAL, "set_op_assign: a and b must be two different contexts");
+        if (a->P.K != b->P.K || a->P.PB != b->P.PB) throw Error(CBLX_EINVAL, "set_op_assign: K / PREFIX_BITS mismatch");
+        if (a->P.canonical != b->P.canonical) throw Error(CBLX_EINVAL, "One of the index is canonical while the other isn't");
+        if (op > CBLX_SETOP_XOR) throw Error(CBLX_EINVAL, "set_op_assign: unknown operation " + std::to_string(op));
+        if (a->device != b->device) throw Error(CBLX_EINVAL, "set_op_assign: a and b must live on the same device");
+        if (op == CBLX_SETOP_OR) return;  // `|=` has its own path, taken below once nothing above refused
+        for (cblx_ctx* x : {a, b}) {  // pending inserts are part of the sets
+            flush(x);
+            CBLX_HIP(hipStreamSynchronize(x->stream));
+        }
+        const bool ea = a->res.count == 0, eb = b->res.count == 0;
+        if (ea || eb) {  // no prefix is held by both: nothing is sorted
+            if (ea && !eb && op == CBLX_SETOP_XOR) a->res = clone_resident(a, b);  // every bucket only b holds: cloned as stored
+            else if (!ea && eb && op == CBLX_SETOP_AND) a->res = Resident();
+            return;
+        }
+        dispatch(a->P, [&](auto cfg) { set_op_assign_direct<decltype(cfg)>(a, b->res, op); });
+        collect_events(a);
+        CBLX_HIP(hipStreamSynchronize(a->stream));
+    });
+    return rc == CBLX_OK && op == CBLX_SETOP_OR ? cblx_merge_assign(a, b) : rc;
+}
 int cblx_get_device(const cblx_ctx* c, int32_t* out) { if (!c || !out) return CBLX_EINVAL; *out = (int32_t)c->device; return CBLX_OK; }
 int cblx_merge_assign(cblx_ctx* self, cblx_ctx* other) {
     return guard(self, [&] {

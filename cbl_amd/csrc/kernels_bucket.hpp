@@ -754,7 +754,7 @@ __global__ __launch_bounds__(UNI_THREADS) void k_bucket_setop(const BDesc* __res
             ++written;
         }
         out_count[r] = written;
-        out_kind[r] = KIND_VEC;
+        if (out_kind) out_kind[r] = KIND_VEC;  // (null: the bucket keeps the kind the plan gave it)
     }
 }
 // the candidates that keep at least one word stay in the directory
@@ -775,6 +775,181 @@ __global__ void k_setop_compact(u64 nb, const u32* __restrict__ cnt, const u64* 
     o_cnt[n] = cnt[r];
     o_kind[n] = kind[r];
     atomicOr((unsigned long long*)&bv[p >> 6], 1ull << (p & 63));
+}
+
+// ---- `a &= &mut b`, `a -= &mut b`, `a ^= &mut b` (cblx_set_op_assign; src/wordset/set_ops.rs:192-239, 281-317, 366-410 walk the prefixes,
+// src/trievec/set_ops.rs:101-129, 163-187, 226-257 the buckets). A bucket both hold keeps a's KIND. A Trie is the ascending result (Trie::remove
+// prunes empty nodes, so the trie is a function of its set): k_bucket_setop's output. A Vec is sorted by iter_sorted, takes the ascending words
+// only b holds at its end (`^=`: insert_sorted_iter) and loses its deletions through remove_sorted_iter: swap_remove on ascending indices in
+// reverse (src/trievec/mod.rs:146-168). With v the Vec remove_sorted_iter scans, n = len(v), D the deleted indices (all inside sorted a),
+// m = |D|, L = n - m and dl(p) the number of deleted indices below p, the result r of length L is
+//     r[i] = v[i]                       for i < L outside D
+//     r[h] = v[s], s = next*(L + dl(h)) for a hole h < L in D, with next(p) = p outside D and L + dl(p) inside D, followed to its fixed point
+// (L + dl(p) = n - |{d in D: d >= p}|: where the last word stood when index p was removed). Chains live in [L, n) and can be as long as m, so
+// they are settled by pointer doubling (next = next o next until nothing moves), never walked by one lane.
+// One thread per candidate prefix, as k_setop_plan: a both-sided bucket keeps a's kind and joins the list of its kernel — [0] a's side a Trie
+// (k_bucket_setop), [1] a's side a Vec of up to SA_LDS words (tables in LDS), [2] a longer Vec (tables in `scratch`, 3 cs + 1 words from
+// BDesc.start on; the sum of those goes to scratch_n).
+static const int SA_THREADS = 256;
+static const u32 SA_LDS = 1024;
+__global__ __launch_bounds__(CLASSIFY_THREADS) void k_setop_assign_plan(u64 nb, u32 op, u32* __restrict__ cap, const u32* __restrict__ m_cs, u32* __restrict__ m_co,
+                                                                         const u64* __restrict__ m_sstart, const u64* __restrict__ m_ostart, const u8* __restrict__ m_skind,
+                                                                         const u8* __restrict__ m_okind, u32* __restrict__ out_count, u8* __restrict__ out_kind,
+                                                                         BDesc* __restrict__ sort_lists /* [2 sides][2 classes][nb] */,
+                                                                         BDesc* __restrict__ both_lists /* [3][nb] */, u32* __restrict__ list_n /* [4] sort lists, [3] both */,
+                                                                         unsigned long long* __restrict__ scratch_n) {
+    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    int cls_a = -1, cls_b = -1, cls_both = -1;
+    u32 cs = 0, co = 0;
+    u64 off = 0;
+    if (r < nb) {
+        cs = m_cs[r];
+        co = cap[r] - cs;
+        m_co[r] = co;
+        if (cs != 0 && co != 0) {
+            cap[r] = op == SETOP_AND ? (cs < co ? cs : co) : op == SETOP_SUB ? cs : cs + co;
+            out_count[r] = 0;  // (written by the bucket's kernel)
+            out_kind[r] = m_skind[r];
+            cls_both = m_skind[r] == KIND_TRIE ? 0 : cs <= SA_LDS ? 1 : 2;
+            if (cls_both == 2) off = atomicAdd(scratch_n, 3ull * cs + 1ull);  // (long Vecs are rare: one atomic each)
+            if (m_skind[r] == KIND_VEC && cs > 1) cls_a = cs <= SETOP_SORT_LDS ? 0 : 1;
+            if (m_okind[r] == KIND_VEC && co > 1) cls_b = co <= SETOP_SORT_LDS ? 0 : 1;
+        } else {  // one-sided (never for AND, never b's side for SUB: such prefixes are no candidates): cloned as stored
+            cap[r] = cs + co;
+            out_count[r] = cs + co;
+            out_kind[r] = cs ? m_skind[r] : m_okind[r];
+        }
+    }
+    const u32 slot_a = block_append<CLASSIFY_THREADS, 2>(cls_a, list_n);
+    if (cls_a >= 0) sort_lists[(u64)cls_a * nb + slot_a] = BDesc{m_sstart[r], cs | BDESC_TRIE, (u32)r};  // (TRIE: the kernel leaves the run sorted)
+    __syncthreads();  // block_append's tables are reused
+    const u32 slot_b = block_append<CLASSIFY_THREADS, 2>(cls_b, list_n + 2);
+    if (cls_b >= 0) sort_lists[(u64)(2 + cls_b) * nb + slot_b] = BDesc{m_ostart[r], co | BDESC_TRIE, (u32)r};
+    const u32 slot = block_append<CLASSIFY_THREADS, 3>(cls_both, list_n + 4);
+    if (cls_both >= 0) both_lists[(u64)cls_both * nb + slot] = BDesc{off, 0, (u32)r};
+}
+template <bool WS> __device__ __forceinline__ UniE<WS> sa_load(const u64* __restrict__ lo, const u64* __restrict__ hi, u32 i, u64 mask) {
+    UniE<WS> e;
+    if constexpr (WS) { e.lo = lo[i]; e.hi = hi[i] & mask; }
+    else e.lo = lo[i] & mask;
+    return e;
+}
+// is x one of the n ascending words of (lo, hi)?
+template <bool WS> __device__ __forceinline__ bool sa_member(const u64* __restrict__ lo, const u64* __restrict__ hi, u32 n, u64 mask, const UniE<WS>& x) {
+    u32 l = 0, h = n;
+    while (l < h) {
+        const u32 mid = l + ((h - l) >> 1);
+        if (uni_lt<WS>(sa_load<WS>(lo, hi, mid, mask), x)) l = mid + 1; else h = mid;
+    }
+    return l < n && uni_eq<WS>(sa_load<WS>(lo, hi, l, mask), x);
+}
+// One workgroup per both-sided bucket whose a side is a Vec; both runs are ascending in their arenas (a's was sorted there, as b's if it is a Vec).
+//   1. every word of a is looked up in b by binary search — its index in sorted a is the index remove_sorted_iter finds, so no merge has to carry
+//      it: deleted = absent (AND) / present (SUB, XOR); an ordered count of the flags gives dl[0 .. cs], dl[cs] = m;
+//   2. XOR: the words of b that a lacks, in order, go to dst[cs ..) — the places insert_sorted_iter pushes them to;
+//   3. next[] over the tail [L, cs) of sorted a (beyond cs nothing is deleted: a fixed point), doubled until no entry moves;
+//   4. dst[i], i < min(L, cs): a[i] if it stays, else v[next*(L + dl(i))], read from a below cs and from the pushed words (dst itself, at or
+//      beyond cs, where step 4 writes nothing) above.
+// BIG: dl and the two copies of next[] sit in global memory instead of LDS; the steps are the same.
+template <bool WS, u32 OP, bool BIG>
+__global__ __launch_bounds__(SA_THREADS) void k_bucket_setop_assign(const BDesc* __restrict__ list, const u32* __restrict__ list_n, const u32* __restrict__ m_cs,
+                                                                    const u32* __restrict__ m_co, const u64* __restrict__ m_sstart, const u64* __restrict__ m_ostart,
+                                                                    const u64* __restrict__ s_lo, const u64* __restrict__ s_hi, const u64* __restrict__ o_lo,
+                                                                    const u64* __restrict__ o_hi, const u64* __restrict__ run_start, u64* out_lo, u64* out_hi, u32 SB,
+                                                                    u32* __restrict__ out_count, u8* __restrict__ out_kind, u32* scratch) {
+    typedef UniE<WS> E;
+    static_assert(OP == SETOP_AND || OP == SETOP_SUB || OP == SETOP_XOR, "`|=` is cblx_merge_assign");
+    constexpr int NW = SA_THREADS / 64;
+    __shared__ u32 s_dl[BIG ? 1 : SA_LDS + 1];
+    __shared__ u32 s_nx[BIG ? 1 : 2 * SA_LDS];
+    __shared__ u32 s_wtot[NW];
+    if (blockIdx.x >= *list_n) return;
+    const BDesc dsc = list[blockIdx.x];
+    const u32 r = dsc.r, cs = m_cs[r], co = m_co[r];
+    const u64 a_self = m_sstart[r], a_oth = m_ostart[r], d_run = run_start[r];
+    const u64* __restrict__ A = s_lo + a_self;
+    const u64* __restrict__ B = o_lo + a_oth;
+    const u64* __restrict__ Ah = WS ? s_hi + a_self : nullptr;
+    const u64* __restrict__ Bh = WS ? o_hi + a_oth : nullptr;
+    u64* dst = out_lo + d_run;
+    u64* dsth = WS ? out_hi + d_run : nullptr;
+    const u64 mask = WS ? ((1ull << (SB - 64)) - 1ull) : (SB >= 64 ? ~0ull : ((1ull << SB) - 1ull));
+    const u32 tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    u32 *dl, *nx0, *nx1;
+    if constexpr (BIG) { dl = scratch + dsc.start; nx0 = dl + cs + 1; nx1 = nx0 + cs; }
+    else { dl = s_dl; nx0 = s_nx; nx1 = s_nx + SA_LDS; }
+    // flags of the workgroup's threads in thread order: -> how many are set in front of this thread; returns how many are set in all
+    auto count_before = [&](bool f, u32& before) {
+        const u64 bal = __ballot(f);
+        if (lane == 0) s_wtot[w] = (u32)__builtin_popcountll(bal);
+        __syncthreads();
+        u32 run = 0, tot = 0;
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) { const u32 t = s_wtot[ww]; if ((u32)ww < w) run += t; tot += t; }
+        before = run + mbcnt(bal);
+        __syncthreads();  // s_wtot is rewritten by the next call
+        return tot;
+    };
+    u32 m = 0;
+    for (u32 base = 0; base < cs; base += SA_THREADS) {
+        const u32 i = base + tid;
+        bool del = false;
+        if (i < cs) del = sa_member<WS>(B, Bh, co, mask, sa_load<WS>(A, Ah, i, mask)) != (OP == SETOP_AND);
+        u32 before;
+        const u32 tot = count_before(del, before);
+        if (i < cs) dl[i] = m + before;
+        m += tot;
+    }
+    if (tid == 0) dl[cs] = m;
+    u32 ins = 0;
+    if constexpr (OP == SETOP_XOR) {
+        for (u32 base = 0; base < co; base += SA_THREADS) {
+            const u32 j = base + tid;
+            E y = uni_inf<WS>();
+            bool push = false;
+            if (j < co) { y = sa_load<WS>(B, Bh, j, mask); push = !sa_member<WS>(A, Ah, cs, mask, y); }
+            u32 before;
+            const u32 tot = count_before(push, before);
+            if (push) {
+                dst[cs + ins + before] = y.lo;
+                if constexpr (WS) dsth[cs + ins + before] = y.hi;
+            }
+            ins += tot;
+        }
+    }
+    const u32 L = cs + ins - m, low = L < cs ? L : cs;
+    __syncthreads();
+    u32* cur = nx0;
+    if (L < cs) {
+        const u32 T = cs - L;
+        for (u32 q = tid; q < T; q += SA_THREADS) {
+            const u32 p = L + q, d0 = dl[p];
+            nx0[q] = dl[p + 1] != d0 ? L + d0 : p;
+        }
+        __syncthreads();
+        u32* nxt = nx1;
+        for (;;) {
+            bool moved = false;
+            for (u32 q = tid; q < T; q += SA_THREADS) {
+                const u32 v = cur[q], v2 = v < cs ? cur[v - L] : v;
+                nxt[q] = v2;
+                moved = moved || v2 != v;
+            }
+            u32* const t = cur; cur = nxt; nxt = t;
+            if (!__syncthreads_or(moved)) break;
+        }
+    }
+    for (u32 i = tid; i < low; i += SA_THREADS) {
+        const u32 d0 = dl[i];
+        u32 s = i;
+        if (dl[i + 1] != d0) { s = L + d0; if (s < cs) s = cur[s - L]; }
+        E e;
+        if (s < cs) e = sa_load<WS>(A, Ah, s, mask);
+        else { e.lo = dst[s]; if constexpr (WS) e.hi = dsth[s]; }
+        dst[i] = e.lo;
+        if constexpr (WS) dsth[i] = e.hi;
+    }
+    if (tid == 0) { out_count[r] = L; out_kind[r] = KIND_VEC; }
 }
 
 // ---- suffix access --------------------------------------------------------------------------------------

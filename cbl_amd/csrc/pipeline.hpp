@@ -1614,7 +1614,11 @@ template <typename C> void merge_direct(cblx_ctx* c, const Resident& s, const Re
 // effect). Both operands are non-empty (the caller answers the other cases with a clone or an empty index).
 // The arena keeps slack inside the runs of the both-sided buckets (a run is as long as the op's upper bound), as the results of `|=` do: the serializer,
 // cblx_validate and the queries read start[r] and cnt[r] only.
-template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, u32 op) {
+// `assign`: the layout of the ASSIGNING forms `a &= &mut b`, `a -= &mut b`, `a ^= &mut b` (src/cbl.rs:473-489, 513-529, 553-569 -> src/wordset/set_ops.rs:192-239,
+// 281-317, 366-410 -> src/trievec/set_ops.rs:101-129, 163-187, 226-257): same candidates, same one-sided buckets, same sorts, but a both-sided bucket keeps a's kind
+// — a Trie is the ascending result, a Vec is what remove_sorted_iter's swap_remove leaves (k_bucket_setop_assign). The file holds neither container ids nor the
+// tiered vector nor empty_containers, so the result is this per-bucket function of the operands.
+template <typename C> Resident set_op_build(cblx_ctx* c, Resident& a, Resident& b, u32 op, bool assign) {
     typedef typename C::HiT HiT;
     constexpr bool WS = C::WS;
     const Consts& P = c->P;
@@ -1623,8 +1627,9 @@ template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, 
     Buf<u32> cap, m_cs, m_co, popc(c->pool, nwords);
     Buf<u64> m_sstart, m_ostart;
     Buf<u8> m_skind, m_okind;
-    Buf<BDesc> sort_lists, both_list;
-    Buf<u32> list_n(c->pool, 5);
+    Buf<BDesc> sort_lists, both_list;  // both_list: [1][nb], or [3][nb] by the kernel that takes the bucket (assign)
+    Buf<u32> list_n(c->pool, 7);
+    Buf<unsigned long long> scratch_n(c->pool, 1);  // (assign) words of global tables the long Vec buckets need
     u64 N = 0;
     {
         StageTimer t(c, ST_DIR);
@@ -1632,7 +1637,7 @@ template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, 
         nr.rank_dir = Buf<u64>(c->pool, nwords + 1);
         hipLaunchKernelGGL(k_setop_bv, grid1(nwords, 256), dim3(256), 0, c->stream, nwords, a.bv.get(), b.bv.get(), op, nr.bv.get(), popc.get());
         nr.nb = exclusive_scan<u64>(c, popc.get(), nwords, nr.rank_dir.get());
-        if (nr.nb == 0) { c->res = Resident(); return; }  // (AND of indexes that share no prefix)
+        if (nr.nb == 0) return Resident();  // (AND of indexes that share no prefix)
         const u64 nb = nr.nb;
         nr.prefix = Buf<u32>(c->pool, nb + 1);
         nr.start = Buf<u64>(c->pool, nb + 1);
@@ -1646,12 +1651,17 @@ template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, 
         m_skind = Buf<u8>(c->pool, nb + 1);
         m_okind = Buf<u8>(c->pool, nb + 1);
         sort_lists = Buf<BDesc>(c->pool, 4 * nb);
-        both_list = Buf<BDesc>(c->pool, nb);
-        CBLX_HIP(hipMemsetAsync(list_n.get(), 0, 5 * 4, c->stream));
+        both_list = Buf<BDesc>(c->pool, (assign ? 3 : 1) * nb);
+        CBLX_HIP(hipMemsetAsync(list_n.get(), 0, 7 * 4, c->stream));
+        CBLX_HIP(hipMemsetAsync(scratch_n.get(), 0, 8, c->stream));
         hipLaunchKernelGGL(k_merge_table, grid1(nprefix, 256), dim3(256), 0, c->stream, nprefix, nr.bv.get(), nr.rank_dir.get(), a.view(), b.view(), nr.prefix.get(),
                            cap.get(), m_cs.get(), m_sstart.get(), m_ostart.get(), m_skind.get(), m_okind.get());
-        hipLaunchKernelGGL(k_setop_plan, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, op, cap.get(), m_cs.get(), m_co.get(), m_sstart.get(),
-                           m_ostart.get(), m_skind.get(), m_okind.get(), nr.cnt.get(), nr.kind.get(), sort_lists.get(), both_list.get(), list_n.get());
+        if (assign)
+            hipLaunchKernelGGL(k_setop_assign_plan, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, op, cap.get(), m_cs.get(), m_co.get(), m_sstart.get(),
+                               m_ostart.get(), m_skind.get(), m_okind.get(), nr.cnt.get(), nr.kind.get(), sort_lists.get(), both_list.get(), list_n.get(), scratch_n.get());
+        else
+            hipLaunchKernelGGL(k_setop_plan, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, op, cap.get(), m_cs.get(), m_co.get(), m_sstart.get(),
+                               m_ostart.get(), m_skind.get(), m_okind.get(), nr.cnt.get(), nr.kind.get(), sort_lists.get(), both_list.get(), list_n.get());
         N = exclusive_scan<u64>(c, cap.get(), nb, nr.start.get());
         hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, nr.start.get() + nb, N);
         CBLX_HIP(hipGetLastError());
@@ -1668,7 +1678,7 @@ template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, 
         });
         CBLX_HIP(hipGetLastError());
     }
-    const std::vector<u32> ln = d2h_vec<u32>(c, list_n.get(), 5);
+    const std::vector<u32> ln = d2h_vec<u32>(c, list_n.get(), 7);
     {
         // step 1: the Vec sides of the both-sided buckets, sorted where they are stored. Runs of up to 4096 words take the LDS radix sort, longer ones (a Vec
         // left by an earlier `|=` or set operation has no length limit) the general kernel; both are asked for the sorted layout and write the count and
@@ -1699,12 +1709,32 @@ template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, 
             constexpr u32 OP = decltype(opc)::value;
             hipLaunchKernelGGL((k_bucket_setop<WS, OP>), dim3(ln[4]), dim3(UNI_THREADS), 0, c->stream, both_list.get(), list_n.get() + 4, m_cs.get(), m_co.get(), m_sstart.get(),
                                m_ostart.get(), (const u64*)a.a_lo.get(), (const u64*)a.a_hi.get(), (const u64*)b.a_lo.get(), (const u64*)b.a_hi.get(), (const u64*)nr.start.get(),
-                               nr.a_lo.get(), nr.a_hi.get(), P.SB, nr.cnt.get(), nr.kind.get());
+                               nr.a_lo.get(), nr.a_hi.get(), P.SB, nr.cnt.get(), assign ? (u8*)nullptr : nr.kind.get());  // (assign: a's side is a Trie and stays one)
         };
         if (op == SETOP_OR) go(std::integral_constant<u32, SETOP_OR>());
         else if (op == SETOP_AND) go(std::integral_constant<u32, SETOP_AND>());
         else if (op == SETOP_SUB) go(std::integral_constant<u32, SETOP_SUB>());
         else go(std::integral_constant<u32, SETOP_XOR>());
+        CBLX_HIP(hipGetLastError());
+    }
+    Buf<u32> scratch;
+    if (assign && (ln[5] || ln[6])) {
+        // step 2, a's side a Vec: membership, the pushed words of `^=` and the swap_remove layout in one kernel; tables in LDS up to SA_LDS words, else in `scratch`
+        StageTimer t(c, ST_BSMALL);
+        if (ln[6]) scratch = Buf<u32>(c->pool, d2h<unsigned long long>(c, scratch_n.get()) + 1);
+        auto go = [&](auto opc, auto big) {
+            constexpr u32 OP = decltype(opc)::value;
+            constexpr bool BIG = decltype(big)::value;
+            const u32 n = ln[BIG ? 6 : 5];
+            if (n)
+                hipLaunchKernelGGL((k_bucket_setop_assign<WS, OP, BIG>), dim3(n), dim3(SA_THREADS), 0, c->stream, both_list.get() + (size_t)(BIG ? 2 : 1) * nb, list_n.get() + (BIG ? 6 : 5),
+                                   m_cs.get(), m_co.get(), m_sstart.get(), m_ostart.get(), (const u64*)a.a_lo.get(), (const u64*)a.a_hi.get(), (const u64*)b.a_lo.get(),
+                                   (const u64*)b.a_hi.get(), (const u64*)nr.start.get(), nr.a_lo.get(), nr.a_hi.get(), P.SB, nr.cnt.get(), nr.kind.get(), scratch.get());
+        };
+        auto both = [&](auto opc) { go(opc, std::false_type()); go(opc, std::true_type()); };
+        if (op == SETOP_AND) both(std::integral_constant<u32, SETOP_AND>());
+        else if (op == SETOP_SUB) both(std::integral_constant<u32, SETOP_SUB>());
+        else both(std::integral_constant<u32, SETOP_XOR>());
         CBLX_HIP(hipGetLastError());
     }
     {
@@ -1714,7 +1744,7 @@ template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, 
         Buf<u64> new_rank(c->pool, nb);
         hipLaunchKernelGGL(k_setop_live, grid1(nb, 256), dim3(256), 0, c->stream, nb, nr.cnt.get(), live.get());
         const u64 kept = exclusive_scan<u64>(c, live.get(), nb, new_rank.get());
-        if (kept == 0) { CBLX_HIP(hipStreamSynchronize(c->stream)); c->res = Resident(); return; }
+        if (kept == 0) { CBLX_HIP(hipStreamSynchronize(c->stream)); return Resident(); }
         if (kept != nb) {
             Resident cr;
             cr.nb = kept;
@@ -1743,6 +1773,13 @@ template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, 
         hipLaunchKernelGGL(k_sum_u32, dim3((unsigned)std::min<u64>(2048, std::max<u64>(1, ceil_div(nr.nb, 256)))), dim3(256), 0, c->stream, nr.cnt.get(), nr.nb, total.get());
         nr.count = d2h<u64>(c, total.get());
     }
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // the lists and tables of this call die here
+    return nr;
+}
+template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, u32 op) { c->res = set_op_build<C>(c, a, b, op, false); }
+// `a OP= &mut b` for AND / SUB / XOR, a = c->res: built beside a from a and b, then moved into a, as merge_direct does for `|=`
+template <typename C> void set_op_assign_direct(cblx_ctx* c, Resident& b, u32 op) {
+    Resident nr = set_op_build<C>(c, c->res, b, op, true);
     c->res = std::move(nr);
 }
 

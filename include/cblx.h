@@ -28,7 +28,7 @@ extern "C" {
 /* 3: cblx_merge_from, cblx_stage_units, cblx_fine_builds, cblx_comm_groups_fine, cblx_comm_protocol_used, CBLX_PROTO_AUTO (the default of a new
  * communicator: an unchanged 2 - 4 rank caller no longer runs BINS), CBLX_PROTO_REPLICATE; empty PREFIX_BITS > 24 builds take the FINE route. A binding
  * built against this header must refuse a library that reports less.
- * Added under 3 (a new symbol is compatible): cblx_set_op with CBLX_SETOP_OR / AND / SUB / XOR, and cblx_get_device. */
+ * Added under 3 (a new symbol is compatible): cblx_set_op with CBLX_SETOP_OR / AND / SUB / XOR, cblx_get_device, and cblx_set_op_assign. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -310,12 +310,21 @@ int cblx_merge_from(cblx_ctx* dst, cblx_ctx* self, cblx_ctx* other);
  * Pending inserts of a and b are applied first. dst's previous content and pending work are dropped as cblx_merge_from drops them; dst takes a's
  * canonical flag. CBLX_EINVAL, with the three contexts unchanged: dst, a and b not three different contexts, K / PREFIX_BITS differ, a and b differ in
  * `canonical`, op > 3, or the contexts live on different devices. On any other error (a flush of a or b that fails, CBLX_ENOMEM) dst's previous
- * content is lost, as with cblx_merge_from. The assigning forms (`&=`, `-=`, `^=`) have another bucket layout and are not offered. */
+ * content is lost, as with cblx_merge_from. The assigning forms (`&=`, `-=`, `^=`) have another bucket layout: cblx_set_op_assign. */
 #define CBLX_SETOP_OR 0
 #define CBLX_SETOP_AND 1
 #define CBLX_SETOP_SUB 2
 #define CBLX_SETOP_XOR 3
 int cblx_set_op(cblx_ctx* dst, cblx_ctx* a, cblx_ctx* b, uint32_t op);
+/* a OP= &mut b: a holds what the reference's `a &= &mut b` (CBLX_SETOP_AND), `a -= &mut b` (SUB) or `a ^= &mut b` (XOR) leaves in a, b what it leaves in b
+ * (src/cbl.rs:473-489, 513-529, 553-569 -> src/wordset/set_ops.rs:192-239, 281-317, 366-410 -> src/trievec/set_ops.rs:101-129, 163-187, 226-257).
+ * A bucket only a holds is dropped (AND) or kept as stored (SUB, XOR); a bucket only b holds is cloned as stored (XOR). A bucket both hold keeps a's kind:
+ * a Trie holds the result in ascending order whatever its length, a Vec is sorted, takes the words only b holds in ascending order at its end (XOR) and loses
+ * its deletions by swap_remove on ascending indices in reverse (src/trievec/mod.rs:146-168), so it stays a Vec above 1024 words; a bucket that comes out
+ * empty leaves the index. On every prefix both hold, a Vec bucket of b ends up sorted ascending; b's other buckets and a's untouched buckets keep their order.
+ * CBLX_SETOP_OR is cblx_merge_assign(a, b). Pending inserts of a and b are applied first. CBLX_EINVAL, with both contexts unchanged: a == b, K /
+ * PREFIX_BITS differ, a and b differ in `canonical`, op > 3, or the contexts live on different devices. */
+int cblx_set_op_assign(cblx_ctx* a, cblx_ctx* b, uint32_t op);
 /* The HIP device ordinal the context lives on (cblx_params.device = -1 resolved at creation). */
 int cblx_get_device(const cblx_ctx* ctx, int32_t* out);
 

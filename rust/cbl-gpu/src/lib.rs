@@ -20,7 +20,7 @@
 use std::collections::BTreeMap;
 use std::ffi::{CStr, CString};
 use std::marker::PhantomData;
-use std::ops::{BitAnd, BitOr, BitOrAssign, BitXor, Sub};
+use std::ops::{BitAnd, BitAndAssign, BitOr, BitOrAssign, BitXor, BitXorAssign, Sub, SubAssign};
 use std::os::raw::c_int;
 use std::path::Path;
 
@@ -424,6 +424,36 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> BitXor<Self> for &m
     /// Symmetric difference (`src/cbl.rs:531-551`).
     fn bitxor(self, other: Self) -> Self::Output {
         self.set_op(other, sys::CBLX_SETOP_XOR)
+    }
+}
+
+impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BITS> {
+    /// `a OP= &mut b` (`src/cbl.rs:473-489, 513-529, 553-569`): in place, with the reference's bucket layout; `other` keeps its set, with its Vec
+    /// buckets on the prefixes both hold sorted (`iter_sorted`).
+    fn set_op_assign(&mut self, other: &mut Self, op: u32) {
+        assert_eq!(self.is_canonical(), other.is_canonical(), "One of the index is canonical while the other isn't");
+        self.check(unsafe { sys::cblx_set_op_assign(self.ctx, other.ctx, op) });
+    }
+}
+
+impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> BitAndAssign<&mut Self> for CBL<K, T, PREFIX_BITS> {
+    /// Intersection in place (`src/cbl.rs:473-489`).
+    fn bitand_assign(&mut self, other: &mut Self) {
+        self.set_op_assign(other, sys::CBLX_SETOP_AND)
+    }
+}
+
+impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> SubAssign<&mut Self> for CBL<K, T, PREFIX_BITS> {
+    /// Difference in place (`src/cbl.rs:513-529`).
+    fn sub_assign(&mut self, other: &mut Self) {
+        self.set_op_assign(other, sys::CBLX_SETOP_SUB)
+    }
+}
+
+impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> BitXorAssign<&mut Self> for CBL<K, T, PREFIX_BITS> {
+    /// Symmetric difference in place (`src/cbl.rs:553-569`).
+    fn bitxor_assign(&mut self, other: &mut Self) {
+        self.set_op_assign(other, sys::CBLX_SETOP_XOR)
     }
 }
 

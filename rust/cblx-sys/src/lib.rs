@@ -271,6 +271,7 @@ extern "C" {
     pub fn cblx_merge_assign(this: *mut cblx_ctx, other: *mut cblx_ctx) -> c_int;
     pub fn cblx_merge_from(dst: *mut cblx_ctx, this: *mut cblx_ctx, other: *mut cblx_ctx) -> c_int;
     pub fn cblx_set_op(dst: *mut cblx_ctx, a: *mut cblx_ctx, b: *mut cblx_ctx, op: u32) -> c_int;
+    pub fn cblx_set_op_assign(a: *mut cblx_ctx, b: *mut cblx_ctx, op: u32) -> c_int;
     pub fn cblx_get_device(ctx: *const cblx_ctx, out: *mut i32) -> c_int;
     pub fn cblx_stage_units(ctx: *mut cblx_ctx, units: *mut u64, cap: u32, n: *mut u32) -> c_int;
 
