@@ -133,6 +133,7 @@ SIGNATURES = {
     "cblx_merge_from": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cblx_set_op": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "cblx_set_op_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "cblx_set_op_many": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]),
     "cblx_get_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "cblx_stage_units": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]),
     "cblx_export_buckets": (C.c_int, [C.c_void_p, BUCKET_CB, C.c_void_p]),
@@ -790,6 +791,33 @@ class CBL:
             out = CBL(a.k, a.prefix_bits, canonical=a.is_canonical(), device=a.device())
         out._chk(out._L.cblx_set_op(out._h, a._h, b._h, SETOPS[op]))
         return out
+
+    # ---- src/cbl.rs:106-124: CBL::merge / CBL::intersect of many indexes ------------------------------------------------
+    @staticmethod
+    def _set_op_many(cbls, op: str, out: "CBL" = None) -> "CBL":
+        cbls = list(cbls)
+        if not cbls:
+            raise ValueError("%s: at least one index" % ("merge" if op == "or" else "intersect"))
+        if len(set(map(id, cbls))) != len(cbls):
+            raise ValueError("%s: the same index twice" % ("merge" if op == "or" else "intersect"))
+        if out is None:
+            a = cbls[0]
+            out = CBL(a.k, a.prefix_bits, canonical=a.is_canonical(), device=a.device())
+        srcs = (C.c_void_p * len(cbls))(*[c._h for c in cbls])
+        out._chk(out._L.cblx_set_op_many(out._h, srcs, len(cbls), SETOPS[op]))
+        return out
+
+    @staticmethod
+    def merge(cbls, out: "CBL" = None) -> "CBL":
+        """The union of up to 64 indexes into a new one (or into `out`, whose content is replaced), as the reference's `CBL::merge`: a bucket one index
+        holds is cloned as stored; a bucket several hold becomes an ascending Vec, and the Vec buckets of exactly those holders end up sorted."""
+        return CBL._set_op_many(cbls, "or", out)
+
+    @staticmethod
+    def intersect(cbls, out: "CBL" = None) -> "CBL":
+        """The k-mers all of up to 64 indexes hold, as the reference's `CBL::intersect`: only prefixes every index holds are visited; there every Vec
+        bucket ends up sorted and the result is an ascending Vec, dropped when empty."""
+        return CBL._set_op_many(cbls, "and", out)
 
     def device(self) -> int:
         """The HIP device ordinal the index lives on (`device=-1` resolved when it was created)."""

@@ -1,5 +1,6 @@
 """`python -m cbl_amd <command>` — the build / insert / merge / inter / diff / sym-diff / count / query / list subcommands of the reference CLI
-(/root/reference/examples/cbl.rs:147-167,230-249,270-309,168-229) on the MI355X path.
+(/root/reference/examples/cbl.rs:147-167,230-249,270-309,168-229) on the MI355X path, and merge-all / inter-all: the library's `CBL::merge` and
+`CBL::intersect` (src/cbl.rs:106-124) over two or more index files, which the reference's CLI does not expose.
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
 here they are flags with the same defaults (K=25, PREFIX_BITS=24). Index files are interchangeable with the reference's.
@@ -32,6 +33,10 @@ def main(argv=None):
         s = sub.add_parser(name, help=f"Compute the {what} of two indexes")
         s.add_argument("first_index")
         s.add_argument("second_index")
+        s.add_argument("-o", "--output")
+    for name, what in (("merge-all", "union"), ("inter-all", "intersection")):  # CBL::merge / CBL::intersect, src/cbl.rs:106-124
+        s = sub.add_parser(name, help=f"Compute the {what} of two or more indexes")
+        s.add_argument("indexes", nargs="+", metavar="index")
         s.add_argument("-o", "--output")
     c = sub.add_parser("count", help="Count the k-mers contained in an index")
     c.add_argument("index")
@@ -69,6 +74,14 @@ def main(argv=None):
         cbl = CBL.load_from_file(a.first_index, a.k, a.prefix_bits, device=a.device)
         cbl2 = CBL.load_from_file(a.second_index, a.k, a.prefix_bits, device=a.device)
         cbl.set_op_assign(cbl2, {"inter": "and", "diff": "sub", "sym-diff": "xor"}[a.cmd])
+        if a.output:
+            print(f"Writing the index to {a.output}", file=sys.stderr)
+            cbl.save_to_file(a.output)
+    elif a.cmd in ("merge-all", "inter-all"):
+        if len(a.indexes) < 2:
+            ap.error(f"{a.cmd} takes two or more index files")
+        cbls = [CBL.load_from_file(path, a.k, a.prefix_bits, device=a.device) for path in a.indexes]
+        cbl = CBL.merge(cbls) if a.cmd == "merge-all" else CBL.intersect(cbls)
         if a.output:
             print(f"Writing the index to {a.output}", file=sys.stderr)
             cbl.save_to_file(a.output)

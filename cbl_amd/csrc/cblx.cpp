@@ -937,6 +937,41 @@ int cblx_set_op(cblx_ctx* dst, cblx_ctx* a, cblx_ctx* b, uint32_t op) {
         CBLX_HIP(hipStreamSynchronize(dst->stream));
     });
 }
+int cblx_set_op_many(cblx_ctx* dst, cblx_ctx* const* srcs, uint32_t n, uint32_t op) {
+    return guard(dst, [&] {
+        if (!dst || !srcs) throw Error(CBLX_EINVAL, "null argument");
+        if (n == 0 || n > CBLX_SETOP_MAX_OPERANDS) throw Error(CBLX_EINVAL, "set_op_many: 1 to " + std::to_string(CBLX_SETOP_MAX_OPERANDS) + " operands, not " + std::to_string(n));
+        if (op != CBLX_SETOP_OR && op != CBLX_SETOP_AND) throw Error(CBLX_EINVAL, "set_op_many: the operation is CBLX_SETOP_OR (merge) or CBLX_SETOP_AND (intersect), not " + std::to_string(op));
+        for (uint32_t i = 0; i < n; ++i) {
+            cblx_ctx* x = srcs[i];
+            if (!x) throw Error(CBLX_EINVAL, "null argument");
+            if (x == dst) throw Error(CBLX_EINVAL, "set_op_many: dst must not be one of the operands");
+            for (uint32_t j = 0; j < i; ++j)
+                if (srcs[j] == x) throw Error(CBLX_EINVAL, "set_op_many: the operands must be different contexts");
+            if (dst->P.K != x->P.K || dst->P.PB != x->P.PB) throw Error(CBLX_EINVAL, "set_op_many: K / PREFIX_BITS mismatch");
+            if (x->P.canonical != srcs[0]->P.canonical) throw Error(CBLX_EINVAL, "One of the index is canonical while the other isn't");
+            if (dst->device != x->device) throw Error(CBLX_EINVAL, "set_op_many: dst and the operands must live on the same device");
+        }
+        CBLX_HIP(hipStreamSynchronize(dst->stream));
+        dst->res = Resident();
+        dst->batch = SortedBatch();
+        ingest_drop(dst);
+        dst->P.canonical = srcs[0]->P.canonical;  // the result is as canonical as its operands
+        std::vector<cblx_ctx*> live;  // an empty operand holds no prefix: nothing to a merge, the end of an intersection
+        for (uint32_t i = 0; i < n; ++i) {  // an observer: pending inserts are part of the sets
+            flush(srcs[i]);
+            CBLX_HIP(hipStreamSynchronize(srcs[i]->stream));
+            if (srcs[i]->res.count != 0) live.push_back(srcs[i]);
+        }
+        if (live.empty() || (op == CBLX_SETOP_AND && live.size() != n)) return;  // no prefix is visited: nothing is sorted
+        if (op == CBLX_SETOP_OR && live.size() == 1) { dst->res = clone_resident(dst, live[0]); return; }  // every bucket has one holder: cloned as stored
+        std::vector<Resident*> xs;
+        for (cblx_ctx* x : live) xs.push_back(&x->res);
+        dispatch(dst->P, [&](auto cfg) { set_op_many_direct<decltype(cfg)>(dst, xs, op); });
+        collect_events(dst);
+        CBLX_HIP(hipStreamSynchronize(dst->stream));
+    });
+}
 int cblx_set_op_assign(cblx_ctx* a, cblx_ctx* b, uint32_t op) {
     const int rc = guard(a, [&] {
         if (!a || !b) throw Error(CBLX_EINVAL, "null argument");

@@ -777,6 +777,304 @@ __global__ void k_setop_compact(u64 nb, const u32* __restrict__ cnt, const u64* 
     atomicOr((unsigned long long*)&bv[p >> 6], 1ull << (p & 63));
 }
 
+// ---- CBL::merge / CBL::intersect of n operands (cblx_set_op_many; /root/reference/src/cbl.rs:106-124 -> src/wordset/set_ops.rs:11-42, 49-75) ----------
+// Per distinct prefix the reference gets the operands that hold it. merge: one holder -> cloned as stored; two or more -> every holder's Vec is sorted
+// (iter_sorted) and the result is Vec(ascending union), whatever its length. intersect: only prefixes ALL operands hold; every holder's Vec is sorted, the
+// result is Vec(ascending intersection), dropped when empty — also for n = 1, which turns every bucket into an ascending Vec.
+// A candidate bucket carries a 64-bit holder mask (hence at most 64 operands); nothing of size [buckets][operands] exists: a holder's rank in its own
+// directory is rank_dir[word] + popc(bits below), recomputed where its run is needed.
+static const u32 MANY_MAX = 64;  // = CBLX_SETOP_MAX_OPERANDS
+// words of all holders of a bucket that k_bucket_setop_many stages in LDS: up to MANY_SMALL one wave and 2 KB (4 KB wide), up to MANY_LDS four waves and
+// 24 KB (40 KB wide: 6 / 4 workgroups per CU); longer buckets are folded pairwise by k_bucket_setop (tests/test_gpu_setops_many.py mirrors both)
+static const u32 MANY_SMALL = 256, MANY_LDS = 2048;
+struct ManyOp { DirView d; const u64* lo; const u64* hi; };  // one operand: its directory and its arena
+
+__global__ void k_many_bv(u64 nwords, const ManyOp* __restrict__ ops, u32 n, u32 op, u64* __restrict__ out, u32* __restrict__ popc) {
+    const u64 w = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= nwords) return;
+    u64 v = ops[0].d.bv[w];
+    for (u32 i = 1; i < n; ++i) { const u64 x = ops[i].d.bv[w]; v = op == SETOP_AND ? (v & x) : (v | x); }
+    out[w] = v;
+    popc[w] = (u32)__builtin_popcountll(v);
+}
+// One thread per prefix slot of the candidate bitvector: holder mask, run capacity (merge: sum of the holders' counts, intersect: the smallest) and the
+// bucket's fate — a merge bucket with one holder gets its final count and kind (k_many_gather clones it), every other one joins the list of its route:
+// [0] up to MANY_SMALL words of all holders, [1] up to MANY_LDS, [2] longer. BDesc.c = words of all holders.
+__global__ __launch_bounds__(CLASSIFY_THREADS) void k_many_table(u64 nprefix, const u64* __restrict__ bv, const u64* __restrict__ rank_dir, const ManyOp* __restrict__ ops, u32 n,
+                                                                  u32 op, u64 nb, u32* __restrict__ bucket_prefix, u64* __restrict__ hmask, u32* __restrict__ cap,
+                                                                  u32* __restrict__ out_count, u8* __restrict__ out_kind, BDesc* __restrict__ lists /* [3][nb] */,
+                                                                  u32* __restrict__ list_n) {
+    const u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    int cls = -1;
+    u64 r = 0;
+    u32 sum = 0;
+    if (p < nprefix) {
+        const u64 w = bv[p >> 6];
+        if ((w >> (p & 63)) & 1ull) {
+            r = rank_dir[p >> 6] + (u64)__builtin_popcountll(w & ((1ull << (p & 63)) - 1ull));
+            u64 mask = 0;
+            u32 mn = 0xFFFFFFFFu;
+            u8 k0 = KIND_VEC;
+            for (u32 i = 0; i < n; ++i) {
+                u64 rank;
+                if (!dir_lookup(ops[i].d, (u32)p, rank)) continue;
+                const u32 c = ops[i].d.count[rank];
+                if (!mask) k0 = ops[i].d.kind[rank];
+                mask |= 1ull << i;
+                sum += c;
+                mn = c < mn ? c : mn;
+            }
+            bucket_prefix[r] = (u32)p;
+            hmask[r] = mask;
+            if (op == SETOP_OR && (mask & (mask - 1ull)) == 0) {
+                cap[r] = sum;
+                out_count[r] = sum;
+                out_kind[r] = k0;
+            } else {
+                cap[r] = op == SETOP_AND ? mn : sum;
+                out_count[r] = 0;  // (written by the bucket's kernel)
+                out_kind[r] = KIND_VEC;
+                cls = sum <= MANY_SMALL ? 0 : sum <= MANY_LDS ? 1 : 2;
+            }
+        }
+    }
+    const u32 slot = block_append<CLASSIFY_THREADS, 3>(cls, list_n);
+    if (cls >= 0) lists[(u64)cls * nb + slot] = BDesc{0, sum, (u32)r};
+}
+// LPB lanes per candidate (merge): a bucket one operand holds is copied into its run as stored — k_setop_gather's n-ary twin
+template <bool WS, int LPB>
+__global__ __launch_bounds__(256) void k_many_gather(u64 nb, const u64* __restrict__ start, const u32* __restrict__ bucket_prefix, const u64* __restrict__ hmask,
+                                                     const ManyOp* __restrict__ ops, u64* __restrict__ out_lo, u64* __restrict__ out_hi) {
+    const u64 r = ((u64)blockIdx.x * 256 + threadIdx.x) / LPB;
+    if (r >= nb) return;
+    const u32 lane = threadIdx.x & (LPB - 1);
+    const u64 mask = hmask[r];
+    if (mask & (mask - 1ull)) return;
+    const ManyOp o = ops[__builtin_ctzll(mask)];
+    u64 rank;
+    if (!dir_lookup(o.d, bucket_prefix[r], rank)) return;
+    const u64 d0 = start[r], src = o.d.start[rank];
+    const u32 c = o.d.count[rank];
+    for (u32 j = lane; j < c; j += LPB) {
+        out_lo[d0 + j] = o.lo[src + j];
+        if constexpr (WS) out_hi[d0 + j] = o.hi[src + j];
+    }
+}
+// One thread per candidate, once per operand: the operand's Vec bucket of two words or more on a prefix the reference visits with iter_sorted (merge: two
+// holders or more; intersect: every candidate) joins the list of its sorting class, with the run in the OPERAND's arena as descriptor (as k_setop_plan)
+__global__ __launch_bounds__(CLASSIFY_THREADS) void k_many_sortplan(u64 nb, const u32* __restrict__ bucket_prefix, const u64* __restrict__ hmask, u32 op,
+                                                                     const ManyOp* __restrict__ ops, u32 i, BDesc* __restrict__ sort_lists /* [2][nb] */,
+                                                                     u32* __restrict__ list_n) {
+    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    int cls = -1;
+    u64 st = 0;
+    u32 c = 0;
+    if (r < nb) {
+        const u64 mask = hmask[r];
+        u64 rank;
+        if (((mask >> i) & 1ull) && (op == SETOP_AND || (mask & (mask - 1ull)) != 0) && dir_lookup(ops[i].d, bucket_prefix[r], rank)) {
+            c = ops[i].d.count[rank];
+            st = ops[i].d.start[rank];
+            if (ops[i].d.kind[rank] == KIND_VEC && c > 1) cls = c <= SETOP_SORT_LDS ? 0 : 1;
+        }
+    }
+    const u32 slot = block_append<CLASSIFY_THREADS, 2>(cls, list_n);
+    if (cls >= 0) sort_lists[(u64)cls * nb + slot] = BDesc{st, c | BDESC_TRIE, (u32)r};  // (TRIE: the kernel leaves the run sorted)
+}
+// One workgroup per bucket of up to CAP words over all its m holders, whose runs are ascending and duplicate-free by now. The runs are staged back to back
+// in LDS (lane t of the first wave looks up operand t; a wave scan of the counts gives the offsets).
+//   OR: every element finds its position in the merged multiset by one binary search per other run — runs of lower index count their elements <= it, runs of
+//       higher index those < it, so the lowest holder's copy of a value comes first — and the searches in the lower runs also say whether one of them holds
+//       the value: then this copy is not kept. (element index, kept) goes to the merged position; an ordered compaction by ballot / mbcnt / wave totals writes
+//       the kept ones out. No tag bit in the suffix and no padding value: SUFFIX_BITS = 64 has no free bit and all-ones is a legal suffix.
+//   AND: the elements of the shortest holder (the lowest one on ties) are searched in every other run and kept when all hold them; same compaction.
+template <bool WS, u32 OP, u32 CAP, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_bucket_setop_many(const BDesc* __restrict__ list, const u32* __restrict__ list_n, const u32* __restrict__ bucket_prefix,
+                                                               const u64* __restrict__ hmask, const ManyOp* __restrict__ ops, const u64* __restrict__ run_start,
+                                                               u64* __restrict__ out_lo, u64* __restrict__ out_hi, u32 SB, u32* __restrict__ out_count) {
+    typedef UniE<WS> E;
+    static_assert(OP == SETOP_OR || OP == SETOP_AND, "the reference has no n-ary SUB / XOR");
+    static_assert(THREADS % 64 == 0, "whole waves");
+    constexpr int NW = THREADS / 64;
+    __shared__ u64 s_lo[CAP];
+    __shared__ u64 s_hi[WS ? CAP : 1];
+    __shared__ u32 s_perm[OP == SETOP_OR ? CAP : 1];  // merged position -> element | kept << 31
+    __shared__ u64 s_src[MANY_MAX];                    // holder k: first arena slot of its run,
+    __shared__ u32 s_opi[MANY_MAX];                    // its operand,
+    __shared__ u32 s_off[MANY_MAX + 1];                // and where its run starts in s_lo; [m] = words of all holders
+    __shared__ u32 s_wtot[NW];
+    if (blockIdx.x >= *list_n) return;
+    const u32 r = list[blockIdx.x].r;
+    const u64 holders = hmask[r];
+    const u32 p = bucket_prefix[r], m = (u32)__builtin_popcountll(holders);
+    const u64 mask = WS ? ((1ull << (SB - 64)) - 1ull) : (SB >= 64 ? ~0ull : ((1ull << SB) - 1ull));
+    const u32 tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    if (tid < 64) {
+        const bool holds = ((holders >> tid) & 1ull) != 0;
+        u32 c = 0;
+        u64 st = 0, rank;
+        if (holds && dir_lookup(ops[tid].d, p, rank)) { c = ops[tid].d.count[rank]; st = ops[tid].d.start[rank]; }
+        u32 inc = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const u32 t = __shfl_up(inc, d, 64); if ((int)lane >= d) inc += t; }
+        if (holds) {
+            const u32 k = (u32)__builtin_popcountll(holders & ((1ull << tid) - 1ull));
+            s_off[k] = inc - c;
+            s_src[k] = st;
+            s_opi[k] = tid;
+        }
+        if (tid == 63) s_off[m] = inc;
+    }
+    __syncthreads();
+    const u32 total = s_off[m] < CAP ? s_off[m] : CAP;  // (the list's class says total <= CAP)
+    auto run_of = [&](u32 e) { u32 k = 0; while (k + 1 < m && s_off[k + 1] <= e) ++k; return k; };
+    auto get = [&](u32 i) { E e; e.lo = s_lo[i]; if constexpr (WS) e.hi = s_hi[i]; return e; };
+    for (u32 e = tid; e < total; e += THREADS) {
+        const u32 k = run_of(e);
+        const ManyOp& o = ops[s_opi[k]];
+        const u64 g = s_src[k] + (e - s_off[k]);
+        if constexpr (WS) { s_lo[e] = o.lo[g]; s_hi[e] = o.hi[g] & mask; }
+        else s_lo[e] = o.lo[g] & mask;
+        if constexpr (OP == SETOP_OR) s_perm[e] = 0;
+    }
+    __syncthreads();
+    u64* __restrict__ dst = out_lo + run_start[r];
+    u64* __restrict__ dsth = WS ? out_hi + run_start[r] : nullptr;
+    // first index in [a, b) whose element is not below v (UPPER: is above v)
+    auto bound = [&](u32 a, u32 b, const E& v, bool upper) {
+        while (a < b) {
+            const u32 mid = (a + b) >> 1;
+            const E x = get(mid);
+            if (upper ? !uni_lt<WS>(v, x) : uni_lt<WS>(x, v)) a = mid + 1; else b = mid;
+        }
+        return a;
+    };
+    u32 ks = 0, len = total;
+    if constexpr (OP == SETOP_OR) {
+        for (u32 e = tid; e < total; e += THREADS) {
+            const u32 k = run_of(e);
+            const E v = get(e);
+            u32 pos = e - s_off[k];
+            bool dup = false;
+            for (u32 kk = 0; kk < m; ++kk) {
+                if (kk == k) continue;
+                const u32 a = s_off[kk], at = bound(a, s_off[kk + 1] < total ? s_off[kk + 1] : total, v, kk < k);
+                pos += at - a;
+                if (kk < k && at > a && uni_eq<WS>(get(at - 1), v)) dup = true;
+            }
+            if (pos < total) s_perm[pos] = e | (dup ? 0u : 0x80000000u);
+        }
+        __syncthreads();
+    } else {
+        len = s_off[1] - s_off[0];
+        for (u32 k = 1; k < m; ++k) { const u32 c = s_off[k + 1] - s_off[k]; if (c < len) { len = c; ks = k; } }
+        if (s_off[ks] + len > total) len = 0;
+    }
+    u32 written = 0;
+    for (u32 base = 0; base < len; base += THREADS) {
+        const u32 q = base + tid;
+        bool keep = q < len;
+        u32 src = 0;
+        if constexpr (OP == SETOP_OR) {
+            const u32 pe = keep ? s_perm[q] : 0u;
+            keep = (pe >> 31) != 0;
+            src = pe & 0x7FFFFFFFu;
+        } else if (keep) {
+            src = s_off[ks] + q;
+            const E v = get(src);
+            for (u32 kk = 0; kk < m && keep; ++kk) {
+                if (kk == ks) continue;
+                const u32 b = s_off[kk + 1] < total ? s_off[kk + 1] : total, at = bound(s_off[kk], b, v, false);
+                keep = at < b && uni_eq<WS>(get(at), v);
+            }
+        }
+        const u64 bal = __ballot(keep);
+        if (lane == 0) s_wtot[w] = (u32)__builtin_popcountll(bal);
+        __syncthreads();
+        u32 run = 0, tot = 0;
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) { const u32 t = s_wtot[ww]; if ((u32)ww < w) run += t; tot += t; }
+        if (keep) {
+            dst[written + run + mbcnt(bal)] = s_lo[src];
+            if constexpr (WS) dsth[written + run + mbcnt(bal)] = s_hi[src];
+        }
+        written += tot;
+        __syncthreads();  // s_wtot is rewritten
+    }
+    if (tid == 0) out_count[r] = written;
+}
+// ---- the long route: a bucket whose holders have more than MANY_LDS words is folded holder by holder with k_bucket_setop over two scratch runs of
+// sum-of-counts words each (X at sc_start[q], Y at S + sc_start[q]; q = the bucket's place in the long list). acc_side[q] says which one holds the
+// accumulator: a step whose operand does not hold the bucket leaves it where it is.
+// the accumulator starts as the lowest holder's run (ascending by now), suffix bits only
+template <bool WS>
+__global__ __launch_bounds__(256) void k_many_long_init(const BDesc* __restrict__ list, u32 nlong, const u32* __restrict__ bucket_prefix, const u64* __restrict__ hmask,
+                                                        const ManyOp* __restrict__ ops, const u64* __restrict__ sc_start, u64* __restrict__ sc_lo, u64* __restrict__ sc_hi,
+                                                        u32 SB, u32* __restrict__ acc_cnt, u8* __restrict__ acc_side) {
+    const u32 q = blockIdx.x;
+    if (q >= nlong) return;
+    const u32 r = list[q].r;
+    const ManyOp o = ops[__builtin_ctzll(hmask[r])];
+    u64 rank;
+    if (!dir_lookup(o.d, bucket_prefix[r], rank)) return;
+    const u64 mask = WS ? ((1ull << (SB - 64)) - 1ull) : (SB >= 64 ? ~0ull : ((1ull << SB) - 1ull));
+    const u64 src = o.d.start[rank], d0 = sc_start[q];
+    const u32 c = o.d.count[rank];
+    for (u32 j = threadIdx.x; j < c; j += 256) {
+        if constexpr (WS) { sc_lo[d0 + j] = o.lo[src + j]; sc_hi[d0 + j] = o.hi[src + j] & mask; }
+        else sc_lo[d0 + j] = o.lo[src + j] & mask;
+    }
+    if (threadIdx.x == 0) { acc_cnt[q] = c; acc_side[q] = 0; }
+}
+__global__ void k_many_long_words(const BDesc* __restrict__ list, u32 nlong, u32* __restrict__ words) {
+    const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nlong) words[q] = list[q].c;
+}
+// step i of the fold: the long buckets operand i holds (beyond their first holder, and unless an intersection is empty already) get k_bucket_setop's
+// tables — a = the accumulator, b = operand i's run, output = the other scratch run — and change sides
+__global__ __launch_bounds__(CLASSIFY_THREADS) void k_many_long_plan(const BDesc* __restrict__ list, u32 nlong, const u32* __restrict__ bucket_prefix,
+                                                                      const u64* __restrict__ hmask, const ManyOp* __restrict__ ops, u32 i, u32 op,
+                                                                      const u64* __restrict__ sc_start, u64 S, const u32* __restrict__ acc_cnt, u8* __restrict__ acc_side,
+                                                                      u32* __restrict__ t_cs, u32* __restrict__ t_co, u64* __restrict__ t_sstart, u64* __restrict__ t_ostart,
+                                                                      u64* __restrict__ t_run, BDesc* __restrict__ step_list, u32* __restrict__ step_n) {
+    const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
+    int cls = -1;
+    if (q < nlong) {
+        const u32 r = list[q].r;
+        const u64 mask = hmask[r];
+        u64 rank;
+        if (((mask >> i) & 1ull) && (u32)__builtin_ctzll(mask) != i && !(op == SETOP_AND && acc_cnt[q] == 0) && dir_lookup(ops[i].d, bucket_prefix[r], rank)) {
+            const u8 side = acc_side[q];
+            t_cs[q] = acc_cnt[q];
+            t_co[q] = ops[i].d.count[rank];
+            t_sstart[q] = sc_start[q] + (side ? S : 0ull);
+            t_ostart[q] = ops[i].d.start[rank];
+            t_run[q] = sc_start[q] + (side ? 0ull : S);
+            acc_side[q] = side ^ 1;
+            cls = 0;
+        }
+    }
+    const u32 slot = block_append<CLASSIFY_THREADS, 1>(cls, step_n);
+    if (cls >= 0) step_list[slot] = BDesc{0, 0, q};
+}
+// the accumulator becomes the result bucket
+template <bool WS>
+__global__ __launch_bounds__(256) void k_many_long_finish(const BDesc* __restrict__ list, u32 nlong, const u64* __restrict__ sc_start, u64 S, const u64* __restrict__ sc_lo,
+                                                          const u64* __restrict__ sc_hi, const u32* __restrict__ acc_cnt, const u8* __restrict__ acc_side,
+                                                          const u64* __restrict__ run_start, const u32* __restrict__ cap, u64* __restrict__ out_lo, u64* __restrict__ out_hi,
+                                                          u32* __restrict__ out_count) {
+    const u32 q = blockIdx.x;
+    if (q >= nlong) return;
+    const u32 r = list[q].r;
+    const u32 c = acc_cnt[q] < cap[r] ? acc_cnt[q] : cap[r];  // (an intersection is no longer than its shortest holder, a union than all of them)
+    const u64 src = sc_start[q] + (acc_side[q] ? S : 0ull), d0 = run_start[r];
+    for (u32 j = threadIdx.x; j < c; j += 256) {
+        out_lo[d0 + j] = sc_lo[src + j];
+        if constexpr (WS) out_hi[d0 + j] = sc_hi[src + j];
+    }
+    if (threadIdx.x == 0) out_count[r] = c;
+}
+
 // ---- `a &= &mut b`, `a -= &mut b`, `a ^= &mut b` (cblx_set_op_assign; src/wordset/set_ops.rs:192-239, 281-317, 366-410 walk the prefixes,
 // src/trievec/set_ops.rs:101-129, 163-187, 226-257 the buckets). A bucket both hold keeps a's KIND. A Trie is the ascending result (Trie::remove
 // prunes empty nodes, so the trie is a function of its set): k_bucket_setop's output. A Vec is sorted by iter_sorted, takes the ascending words

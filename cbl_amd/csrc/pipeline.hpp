@@ -1609,6 +1609,63 @@ template <typename C> void merge_direct(cblx_ctx* c, const Resident& s, const Re
     c->res = std::move(nr);
 }
 
+// The Vec buckets of one operand that a set operation visits with iter_sorted, sorted where they are stored: runs of up to 4096 words (`l_lds`, list_n[0]) take
+// the LDS radix sort, longer ones (`l_gen`, list_n[1]) the general kernel; `junk` takes the counts and kinds they report.
+template <typename C> void sort_vec_sides(cblx_ctx* c, Resident& x, const BDesc* l_lds, const BDesc* l_gen, const u32* list_n, u32 n_lds, u32 n_gen, Resident& junk) {
+    typedef typename C::HiT HiT;
+    constexpr bool WS = C::WS;
+    u64* x_lo = x.a_lo.get();
+    HiT* x_hi = WS ? (HiT*)x.a_hi.get() : (HiT*)nullptr;
+    if (n_lds) {
+        StageTimer t(c, ST_BMED);
+        hipLaunchKernelGGL((k_bucket_medium<512, WS, HiT>), dim3(n_lds), dim3(512), 0, c->stream, l_lds, list_n, x_lo, x_hi, c->P.SB, junk.cnt.get(), junk.kind.get(), MergeArgs{});
+        CBLX_HIP(hipGetLastError());
+    }
+    huge_stage<C>(c, l_gen, list_n + 1, n_gen, x_lo, x_hi, junk, MergeArgs{});
+}
+// The end of a set operation into a new index: candidates that came out empty leave the directory, the k-mers are counted. `popc` is scratch of nwords
+// counters, N the arena's length. false: nothing is left (the result is the empty index).
+inline bool set_op_tail(cblx_ctx* c, Resident& nr, Buf<u32>& popc, u64 nwords, u64 N) {
+    const u64 nb = nr.nb;
+    {
+        // buckets that came out empty leave the directory (never for OR)
+        StageTimer t(c, ST_DIR);
+        Buf<u32> live(c->pool, nb);
+        Buf<u64> new_rank(c->pool, nb);
+        hipLaunchKernelGGL(k_setop_live, grid1(nb, 256), dim3(256), 0, c->stream, nb, nr.cnt.get(), live.get());
+        const u64 kept = exclusive_scan<u64>(c, live.get(), nb, new_rank.get());
+        if (kept == 0) { CBLX_HIP(hipStreamSynchronize(c->stream)); return false; }
+        if (kept != nb) {
+            Resident cr;
+            cr.nb = kept;
+            cr.bv = Buf<u64>(c->pool, nwords);
+            cr.rank_dir = Buf<u64>(c->pool, nwords + 1);
+            cr.prefix = Buf<u32>(c->pool, kept + 1);
+            cr.start = Buf<u64>(c->pool, kept + 1);
+            cr.cnt = Buf<u32>(c->pool, kept + 1);
+            cr.kind = Buf<u8>(c->pool, kept + 1);
+            CBLX_HIP(hipMemsetAsync(cr.bv.get(), 0, nwords * 8, c->stream));
+            hipLaunchKernelGGL(k_setop_compact, grid1(nb, 256), dim3(256), 0, c->stream, nb, nr.cnt.get(), new_rank.get(), nr.prefix.get(), nr.start.get(), nr.kind.get(),
+                               cr.prefix.get(), cr.start.get(), cr.cnt.get(), cr.kind.get(), cr.bv.get());
+            hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, cr.start.get() + kept, N);
+            hipLaunchKernelGGL(k_popc_words, grid1(nwords, 256), dim3(256), 0, c->stream, nwords, cr.bv.get(), popc.get());
+            CBLX_HIP(hipGetLastError());
+            if (exclusive_scan<u64>(c, popc.get(), nwords, cr.rank_dir.get()) != kept) throw Error(CBLX_EDEVICE, "set_op: the compacted directory does not match its bitvector (internal error)");
+            cr.a_lo = std::move(nr.a_lo);
+            cr.a_hi = std::move(nr.a_hi);
+            CBLX_HIP(hipStreamSynchronize(c->stream));  // the old tables die here
+            nr = std::move(cr);
+        }
+    }
+    {
+        Buf<u64> total(c->pool, 1);
+        CBLX_HIP(hipMemsetAsync(total.get(), 0, 8, c->stream));
+        hipLaunchKernelGGL(k_sum_u32, dim3((unsigned)std::min<u64>(2048, std::max<u64>(1, ceil_div(nr.nb, 256)))), dim3(256), 0, c->stream, nr.cnt.get(), nr.nb, total.get());
+        nr.count = d2h<u64>(c, total.get());
+    }
+    return true;
+}
+
 // ---- `&mut a OP &mut b` into a new index, all three resident on this device (src/cbl.rs:411-431, 451-471, 491-511, 531-551 -> src/wordset/set_ops.rs) ----
 // The result becomes c->res. `a` and `b` keep their sets; their Vec buckets on the prefixes both hold are sorted in their own arenas (iter_sorted's side
 // effect). Both operands are non-empty (the caller answers the other cases with a clone or an empty index).
@@ -1686,20 +1743,9 @@ template <typename C> Resident set_op_build(cblx_ctx* c, Resident& a, Resident& 
         Resident junk;
         junk.cnt = Buf<u32>(c->pool, nb + 1);
         junk.kind = Buf<u8>(c->pool, nb + 1);
-        for (int side = 0; side < 2; ++side) {
-            Resident& x = side ? b : a;
-            u64* x_lo = x.a_lo.get();
-            HiT* x_hi = WS ? (HiT*)x.a_hi.get() : (HiT*)nullptr;
-            const BDesc* l_lds = sort_lists.get() + (size_t)(2 * side) * nb;
-            const BDesc* l_gen = sort_lists.get() + (size_t)(2 * side + 1) * nb;
-            if (ln[2 * side]) {
-                StageTimer t(c, ST_BMED);
-                hipLaunchKernelGGL((k_bucket_medium<512, WS, HiT>), dim3(ln[2 * side]), dim3(512), 0, c->stream, l_lds, list_n.get() + 2 * side, x_lo, x_hi, P.SB, junk.cnt.get(),
-                                   junk.kind.get(), MergeArgs{});
-                CBLX_HIP(hipGetLastError());
-            }
-            huge_stage<C>(c, l_gen, list_n.get() + 2 * side + 1, ln[2 * side + 1], x_lo, x_hi, junk, MergeArgs{});
-        }
+        for (int side = 0; side < 2; ++side)
+            sort_vec_sides<C>(c, side ? b : a, sort_lists.get() + (size_t)(2 * side) * nb, sort_lists.get() + (size_t)(2 * side + 1) * nb, list_n.get() + 2 * side, ln[2 * side],
+                              ln[2 * side + 1], junk);
         CBLX_HIP(hipStreamSynchronize(c->stream));  // `junk` dies here
     }
     if (ln[4]) {
@@ -1737,45 +1783,135 @@ template <typename C> Resident set_op_build(cblx_ctx* c, Resident& a, Resident& 
         else both(std::integral_constant<u32, SETOP_XOR>());
         CBLX_HIP(hipGetLastError());
     }
-    {
-        // buckets that came out empty leave the directory (never for OR)
-        StageTimer t(c, ST_DIR);
-        Buf<u32> live(c->pool, nb);
-        Buf<u64> new_rank(c->pool, nb);
-        hipLaunchKernelGGL(k_setop_live, grid1(nb, 256), dim3(256), 0, c->stream, nb, nr.cnt.get(), live.get());
-        const u64 kept = exclusive_scan<u64>(c, live.get(), nb, new_rank.get());
-        if (kept == 0) { CBLX_HIP(hipStreamSynchronize(c->stream)); return Resident(); }
-        if (kept != nb) {
-            Resident cr;
-            cr.nb = kept;
-            cr.bv = Buf<u64>(c->pool, nwords);
-            cr.rank_dir = Buf<u64>(c->pool, nwords + 1);
-            cr.prefix = Buf<u32>(c->pool, kept + 1);
-            cr.start = Buf<u64>(c->pool, kept + 1);
-            cr.cnt = Buf<u32>(c->pool, kept + 1);
-            cr.kind = Buf<u8>(c->pool, kept + 1);
-            CBLX_HIP(hipMemsetAsync(cr.bv.get(), 0, nwords * 8, c->stream));
-            hipLaunchKernelGGL(k_setop_compact, grid1(nb, 256), dim3(256), 0, c->stream, nb, nr.cnt.get(), new_rank.get(), nr.prefix.get(), nr.start.get(), nr.kind.get(),
-                               cr.prefix.get(), cr.start.get(), cr.cnt.get(), cr.kind.get(), cr.bv.get());
-            hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, cr.start.get() + kept, N);
-            hipLaunchKernelGGL(k_popc_words, grid1(nwords, 256), dim3(256), 0, c->stream, nwords, cr.bv.get(), popc.get());
-            CBLX_HIP(hipGetLastError());
-            if (exclusive_scan<u64>(c, popc.get(), nwords, cr.rank_dir.get()) != kept) throw Error(CBLX_EDEVICE, "set_op: the compacted directory does not match its bitvector (internal error)");
-            cr.a_lo = std::move(nr.a_lo);
-            cr.a_hi = std::move(nr.a_hi);
-            CBLX_HIP(hipStreamSynchronize(c->stream));  // the old tables die here
-            nr = std::move(cr);
-        }
-    }
-    {
-        Buf<u64> total(c->pool, 1);
-        CBLX_HIP(hipMemsetAsync(total.get(), 0, 8, c->stream));
-        hipLaunchKernelGGL(k_sum_u32, dim3((unsigned)std::min<u64>(2048, std::max<u64>(1, ceil_div(nr.nb, 256)))), dim3(256), 0, c->stream, nr.cnt.get(), nr.nb, total.get());
-        nr.count = d2h<u64>(c, total.get());
-    }
+    if (!set_op_tail(c, nr, popc, nwords, N)) return Resident();
     CBLX_HIP(hipStreamSynchronize(c->stream));  // the lists and tables of this call die here
     return nr;
 }
+// ---- CBL::merge / CBL::intersect of n operands into a new index (src/cbl.rs:106-124 -> src/wordset/set_ops.rs:11-42, 49-75), all resident on this device ----
+// `xs`: 1 .. 64 non-empty operands in the caller's order (an empty one contributes nothing to a merge and empties an intersection: the caller's business).
+// op: SETOP_OR (merge) | SETOP_AND (intersect). Every operand keeps its set; its Vec buckets on the prefixes the reference visits with iter_sorted — merge:
+// two holders or more, intersect: held by all — are sorted in its own arena. The rules per bucket are at k_many_table / k_bucket_setop_many.
+template <typename C> Resident set_op_many_build(cblx_ctx* c, const std::vector<Resident*>& xs, u32 op) {
+    constexpr bool WS = C::WS;
+    const Consts& P = c->P;
+    const u32 n = (u32)xs.size();
+    const u64 nprefix = 1ull << P.PB, nwords = std::max<u64>(1, nprefix / 64);
+    std::vector<ManyOp> h_ops(n);
+    for (u32 i = 0; i < n; ++i) h_ops[i] = ManyOp{xs[i]->view(), xs[i]->a_lo.get(), xs[i]->a_hi.get()};
+    Buf<ManyOp> ops(c->pool, n);
+    h2d(c, ops.get(), h_ops.data(), n);
+    Resident nr;
+    Buf<u32> cap, popc(c->pool, nwords), list_n(c->pool, 3);
+    Buf<u64> hmask;
+    Buf<BDesc> lists;  // [3][nb]: the multi-held buckets by route
+    u64 N = 0;
+    {
+        StageTimer t(c, ST_DIR);
+        nr.bv = Buf<u64>(c->pool, nwords);
+        nr.rank_dir = Buf<u64>(c->pool, nwords + 1);
+        hipLaunchKernelGGL(k_many_bv, grid1(nwords, 256), dim3(256), 0, c->stream, nwords, (const ManyOp*)ops.get(), n, op, nr.bv.get(), popc.get());
+        nr.nb = exclusive_scan<u64>(c, popc.get(), nwords, nr.rank_dir.get());
+        if (nr.nb == 0) { CBLX_HIP(hipStreamSynchronize(c->stream)); return Resident(); }  // (intersect of indexes that share no prefix)
+        const u64 nb = nr.nb;
+        nr.prefix = Buf<u32>(c->pool, nb + 1);
+        nr.start = Buf<u64>(c->pool, nb + 1);
+        nr.cnt = Buf<u32>(c->pool, nb + 1);
+        nr.kind = Buf<u8>(c->pool, nb + 1);
+        cap = Buf<u32>(c->pool, nb + 1);
+        hmask = Buf<u64>(c->pool, nb + 1);
+        lists = Buf<BDesc>(c->pool, 3 * nb);
+        CBLX_HIP(hipMemsetAsync(list_n.get(), 0, 3 * 4, c->stream));
+        hipLaunchKernelGGL(k_many_table, grid1(nprefix, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nprefix, (const u64*)nr.bv.get(), (const u64*)nr.rank_dir.get(),
+                           (const ManyOp*)ops.get(), n, op, nb, nr.prefix.get(), hmask.get(), cap.get(), nr.cnt.get(), nr.kind.get(), lists.get(), list_n.get());
+        N = exclusive_scan<u64>(c, cap.get(), nb, nr.start.get());
+        hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, nr.start.get() + nb, N);
+        CBLX_HIP(hipGetLastError());
+    }
+    const u64 nb = nr.nb;
+    nr.a_lo = Buf<u64>(c->pool, N + 2);
+    if (WS) nr.a_hi = Buf<u64>(c->pool, N + 2);
+    if (op == SETOP_OR) {
+        StageTimer t(c, ST_EXPAND);
+        with_lpb(N, nb, [&](auto lpb) {
+            constexpr int LPB = decltype(lpb)::value;
+            hipLaunchKernelGGL((k_many_gather<WS, LPB>), lpb_grid(nb, LPB), dim3(256), 0, c->stream, nb, (const u64*)nr.start.get(), (const u32*)nr.prefix.get(), (const u64*)hmask.get(),
+                               (const ManyOp*)ops.get(), nr.a_lo.get(), nr.a_hi.get());
+        });
+        CBLX_HIP(hipGetLastError());
+    }
+    const std::vector<u32> ln = d2h_vec<u32>(c, list_n.get(), 3);
+    if (ln[0] || ln[1] || ln[2]) {
+        // the Vec sides, one operand after the other through the same two lists (the launches of one operand are behind it when its counts are read)
+        Resident junk;
+        junk.cnt = Buf<u32>(c->pool, nb + 1);
+        junk.kind = Buf<u8>(c->pool, nb + 1);
+        Buf<BDesc> sort_lists(c->pool, 2 * nb);
+        Buf<u32> sort_n(c->pool, 2);
+        for (u32 i = 0; i < n; ++i) {
+            CBLX_HIP(hipMemsetAsync(sort_n.get(), 0, 2 * 4, c->stream));
+            hipLaunchKernelGGL(k_many_sortplan, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, (const u32*)nr.prefix.get(), (const u64*)hmask.get(), op,
+                               (const ManyOp*)ops.get(), i, sort_lists.get(), sort_n.get());
+            CBLX_HIP(hipGetLastError());
+            const std::vector<u32> sn = d2h_vec<u32>(c, sort_n.get(), 2);
+            sort_vec_sides<C>(c, *xs[i], sort_lists.get(), sort_lists.get() + nb, sort_n.get(), sn[0], sn[1], junk);
+            CBLX_HIP(hipStreamSynchronize(c->stream));  // the lists are rewritten for the next operand
+        }
+    }
+    auto with_op = [&](auto&& f) {
+        if (op == SETOP_OR) f(std::integral_constant<u32, SETOP_OR>()); else f(std::integral_constant<u32, SETOP_AND>());
+    };
+    if (ln[0] || ln[1]) {
+        StageTimer t(c, ST_BBIG);
+        with_op([&](auto opc) {
+            constexpr u32 OP = decltype(opc)::value;
+            if (ln[0])
+                hipLaunchKernelGGL((k_bucket_setop_many<WS, OP, MANY_SMALL, 64>), dim3(ln[0]), dim3(64), 0, c->stream, (const BDesc*)lists.get(), (const u32*)list_n.get(),
+                                   (const u32*)nr.prefix.get(), (const u64*)hmask.get(), (const ManyOp*)ops.get(), (const u64*)nr.start.get(), nr.a_lo.get(), nr.a_hi.get(), P.SB,
+                                   nr.cnt.get());
+            if (ln[1])
+                hipLaunchKernelGGL((k_bucket_setop_many<WS, OP, MANY_LDS, 256>), dim3(ln[1]), dim3(256), 0, c->stream, (const BDesc*)lists.get() + nb, (const u32*)list_n.get() + 1,
+                                   (const u32*)nr.prefix.get(), (const u64*)hmask.get(), (const ManyOp*)ops.get(), (const u64*)nr.start.get(), nr.a_lo.get(), nr.a_hi.get(), P.SB,
+                                   nr.cnt.get());
+        });
+        CBLX_HIP(hipGetLastError());
+    }
+    if (ln[2]) {
+        // the long route: correct at any length, not fast — one k_bucket_setop launch per operand over the long buckets it holds
+        StageTimer t(c, ST_BBIG);
+        const u32 nl = ln[2];
+        const BDesc* ll = lists.get() + 2 * nb;
+        Buf<u32> words(c->pool, nl), acc_cnt(c->pool, nl), t_cs(c->pool, nl), t_co(c->pool, nl), step_n(c->pool, 1);
+        Buf<u64> sc_start(c->pool, nl + 1), t_sstart(c->pool, nl), t_ostart(c->pool, nl), t_run(c->pool, nl);
+        Buf<u8> acc_side(c->pool, nl);
+        Buf<BDesc> step_list(c->pool, nl);
+        hipLaunchKernelGGL(k_many_long_words, grid1(nl, 256), dim3(256), 0, c->stream, ll, nl, words.get());
+        const u64 S = exclusive_scan<u64>(c, words.get(), nl, sc_start.get());
+        Buf<u64> sc_lo(c->pool, 2 * S + 2), sc_hi(c->pool, WS ? 2 * S + 2 : 1);
+        hipLaunchKernelGGL((k_many_long_init<WS>), dim3(nl), dim3(256), 0, c->stream, ll, nl, (const u32*)nr.prefix.get(), (const u64*)hmask.get(), (const ManyOp*)ops.get(),
+                           (const u64*)sc_start.get(), sc_lo.get(), sc_hi.get(), P.SB, acc_cnt.get(), acc_side.get());
+        for (u32 i = 0; i < n; ++i) {
+            CBLX_HIP(hipMemsetAsync(step_n.get(), 0, 4, c->stream));
+            hipLaunchKernelGGL(k_many_long_plan, grid1(nl, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, ll, nl, (const u32*)nr.prefix.get(), (const u64*)hmask.get(),
+                               (const ManyOp*)ops.get(), i, op, (const u64*)sc_start.get(), S, (const u32*)acc_cnt.get(), acc_side.get(), t_cs.get(), t_co.get(), t_sstart.get(),
+                               t_ostart.get(), t_run.get(), step_list.get(), step_n.get());
+            with_op([&](auto opc) {
+                constexpr u32 OP = decltype(opc)::value;
+                hipLaunchKernelGGL((k_bucket_setop<WS, OP>), dim3(nl), dim3(UNI_THREADS), 0, c->stream, (const BDesc*)step_list.get(), (const u32*)step_n.get(), (const u32*)t_cs.get(),
+                                   (const u32*)t_co.get(), (const u64*)t_sstart.get(), (const u64*)t_ostart.get(), (const u64*)sc_lo.get(), (const u64*)sc_hi.get(),
+                                   (const u64*)xs[i]->a_lo.get(), (const u64*)xs[i]->a_hi.get(), (const u64*)t_run.get(), sc_lo.get(), sc_hi.get(), P.SB, acc_cnt.get(), (u8*)nullptr);
+            });
+        }
+        hipLaunchKernelGGL((k_many_long_finish<WS>), dim3(nl), dim3(256), 0, c->stream, ll, nl, (const u64*)sc_start.get(), S, (const u64*)sc_lo.get(), (const u64*)sc_hi.get(),
+                           (const u32*)acc_cnt.get(), (const u8*)acc_side.get(), (const u64*)nr.start.get(), (const u32*)cap.get(), nr.a_lo.get(), nr.a_hi.get(), nr.cnt.get());
+        CBLX_HIP(hipGetLastError());
+        CBLX_HIP(hipStreamSynchronize(c->stream));  // the scratch runs die here
+    }
+    if (!set_op_tail(c, nr, popc, nwords, N)) return Resident();
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // the lists and tables of this call die here
+    return nr;
+}
+template <typename C> void set_op_many_direct(cblx_ctx* c, const std::vector<Resident*>& xs, u32 op) { c->res = set_op_many_build<C>(c, xs, op); }
+
 template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, u32 op) { c->res = set_op_build<C>(c, a, b, op, false); }
 // `a OP= &mut b` for AND / SUB / XOR, a = c->res: built beside a from a and b, then moved into a, as merge_direct does for `|=`
 template <typename C> void set_op_assign_direct(cblx_ctx* c, Resident& b, u32 op) {

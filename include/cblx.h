@@ -28,7 +28,8 @@ extern "C" {
 /* 3: cblx_merge_from, cblx_stage_units, cblx_fine_builds, cblx_comm_groups_fine, cblx_comm_protocol_used, CBLX_PROTO_AUTO (the default of a new
  * communicator: an unchanged 2 - 4 rank caller no longer runs BINS), CBLX_PROTO_REPLICATE; empty PREFIX_BITS > 24 builds take the FINE route. A binding
  * built against this header must refuse a library that reports less.
- * Added under 3 (a new symbol is compatible): cblx_set_op with CBLX_SETOP_OR / AND / SUB / XOR, cblx_get_device, and cblx_set_op_assign. */
+ * Added under 3 (a new symbol is compatible): cblx_set_op with CBLX_SETOP_OR / AND / SUB / XOR, cblx_get_device, cblx_set_op_assign, and cblx_set_op_many with
+ * CBLX_SETOP_MAX_OPERANDS. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -325,6 +326,17 @@ int cblx_set_op(cblx_ctx* dst, cblx_ctx* a, cblx_ctx* b, uint32_t op);
  * CBLX_SETOP_OR is cblx_merge_assign(a, b). Pending inserts of a and b are applied first. CBLX_EINVAL, with both contexts unchanged: a == b, K /
  * PREFIX_BITS differ, a and b differ in `canonical`, op > 3, or the contexts live on different devices. */
 int cblx_set_op_assign(cblx_ctx* a, cblx_ctx* b, uint32_t op);
+/* dst = CBL::merge (op = CBLX_SETOP_OR) or CBL::intersect (CBLX_SETOP_AND) of the n operands srcs[0 .. n) (/root/reference/src/cbl.rs:106-124 ->
+ * src/wordset/set_ops.rs:11-42, 49-75). merge: a bucket exactly one operand holds is cloned as stored (kind and order kept); a bucket two or more hold becomes
+ * a Vec of the ascending union whatever its length, and every holder's Vec bucket on that prefix is sorted ascending; operands that lack the prefix are
+ * untouched. intersect: only prefixes ALL operands hold are visited; there every operand's Vec bucket is sorted ascending and the result is a Vec of the
+ * ascending intersection, dropped when empty — so intersect of one index turns each of its buckets into an ascending Vec, and an empty operand makes the result
+ * empty and leaves every operand as it is. For n = 2 both equal cblx_set_op byte for byte, operands included; a fold of cblx_set_op over more operands gives
+ * the same SET but other operand and result bytes. dst's content is replaced; pending inserts of every operand are applied first.
+ * CBLX_EINVAL, with every context unchanged: n == 0, n > CBLX_SETOP_MAX_OPERANDS, a null entry, dst among srcs, the same context twice, K / PREFIX_BITS /
+ * `canonical` / device differ, or op is CBLX_SETOP_SUB / XOR (the reference has no n-ary form of them). */
+#define CBLX_SETOP_MAX_OPERANDS 64
+int cblx_set_op_many(cblx_ctx* dst, cblx_ctx* const* srcs, uint32_t n, uint32_t op);
 /* The HIP device ordinal the context lives on (cblx_params.device = -1 resolved at creation). */
 int cblx_get_device(const cblx_ctx* ctx, int32_t* out);
 

@@ -403,6 +403,29 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
     }
 }
 
+impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BITS> {
+    fn set_op_many(cbls: Vec<&mut Self>, op: u32) -> Self {
+        assert!(!cbls.is_empty() && cbls.len() <= sys::CBLX_SETOP_MAX_OPERANDS as usize);
+        let canonical = cbls[0].is_canonical();
+        assert!(cbls.iter().all(|c| c.is_canonical() == canonical), "One of the index is canonical while the other isn't");
+        let s = Self::with(canonical);
+        let srcs: Vec<*mut sys::cblx_ctx> = cbls.iter().map(|c| c.ctx).collect();
+        s.check(unsafe { sys::cblx_set_op_many(s.ctx, srcs.as_ptr(), srcs.len() as u32, op) });
+        s
+    }
+
+    /// Union of many sets (`src/cbl.rs:106-114`): a bucket one operand holds is cloned as stored, a bucket several hold becomes an ascending Vec and the
+    /// Vec buckets of those holders end up sorted (`iter_sorted`).
+    pub fn merge(cbls: Vec<&mut Self>) -> Self {
+        Self::set_op_many(cbls, sys::CBLX_SETOP_OR)
+    }
+
+    /// Intersection of many sets (`src/cbl.rs:116-124`): only prefixes all operands hold are visited.
+    pub fn intersect(cbls: Vec<&mut Self>) -> Self {
+        Self::set_op_many(cbls, sys::CBLX_SETOP_AND)
+    }
+}
+
 impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> BitAnd<Self> for &mut CBL<K, T, PREFIX_BITS> {
     type Output = CBL<K, T, PREFIX_BITS>;
     /// Intersection (`src/cbl.rs:451-471`).
