@@ -145,6 +145,12 @@ SIGNATURES = {
     "cblx_query_fastx_file": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_contains_all": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_int)]),
     "cblx_insert_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cblx_remove_words_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "cblx_remove_seq": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64]),
+    "cblx_remove_seqs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "cblx_remove_seqs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "cblx_remove_fastx_file": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64)]),
+    "cblx_remove_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cblx_contains_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cblx_export_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_bucket_sizes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -435,6 +441,33 @@ class CBL:
         self._chk(self._L.cblx_insert_fastx_file(self._h, os.fsencode(path), C.byref(n)))
         return n.value
 
+    # ---- src/cbl.rs:343-354: pending inserts are applied first, the removal runs before the call returns ------------
+    def remove_seq(self, seq: bytes):
+        """Removes all the k-mers of a sequence from the set. One device round trip per call: remove_seqs batches."""
+        self._chk(self._L.cblx_remove_seq(self._h, seq, len(seq)))
+
+    def remove_seqs(self, bases, offsets):
+        """`for seq in seqs: remove_seq(seq)` in one call. numpy uint8 / uint64 (host) arrays."""
+        import numpy as np
+
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self._chk(self._L.cblx_remove_seqs(self._h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1))
+
+    def remove_seqs_device(self, d_bases, d_offsets, n: int):
+        """Same with inputs resident in HBM (torch uint8 / int64 CUDA tensors or raw device addresses)."""
+        self._chk(self._L.cblx_remove_seqs_device(self._h, _ptr(d_bases), _ptr(d_offsets), n))
+
+    def remove_words_device(self, d_lo, d_hi, n: int):
+        """WordSet::remove_batch (src/wordset/mod.rs:218-237) on device-resident words: one call = one batch."""
+        self._chk(self._L.cblx_remove_words_device(self._h, _ptr(d_lo), _ptr(d_hi), n))
+
+    def remove_fastx_file(self, path) -> int:
+        """`for record in parse_fastx_file(path): remove_seq(record.seq())` (examples/cbl.rs:250-265); returns #records."""
+        n = C.c_uint64(0)
+        self._chk(self._L.cblx_remove_fastx_file(self._h, os.fsencode(path), C.byref(n)))
+        return n.value
+
     def count_fastx_records(self, path) -> int:
         n = C.c_uint64(0)
         self._chk(self._L.cblx_stage_fastx_blocks(self._h, os.fsencode(path), 0, 0, 1, None, None, None, C.byref(n)))
@@ -667,6 +700,19 @@ class CBL:
         out = np.zeros(max(len(lo), 1), dtype=np.uint8)
         self._chk(self._L.cblx_contains_kmers(self._h, _ptr(lo), _ptr(hi), len(lo), _ptr(out)))
         return out[: len(lo)].astype(bool)
+
+    def remove_kmers(self, kmers):
+        """n successive `remove` calls; returns their results as a numpy bool array (True = the k-mer was present)."""
+        import numpy as np
+
+        lo, hi = self._split_kmers(kmers)
+        out = np.zeros(max(len(lo), 1), dtype=np.uint8)
+        self._chk(self._L.cblx_remove_kmers(self._h, _ptr(lo), _ptr(hi) if (self.k > 31 or hi.any()) else None, len(lo), _ptr(out)))
+        return out[: len(lo)].astype(bool)
+
+    def remove(self, kmer: int) -> bool:
+        """Removes a packed k-mer; True if it was present (src/cbl.rs:233-235)."""
+        return bool(self.remove_kmers([kmer])[0])
 
     def insert(self, kmer: int) -> bool:
         """Adds a packed k-mer; True if it was absent (src/cbl.rs:226-228)."""

@@ -1,5 +1,5 @@
-"""`python -m cbl_amd <command>` — the build / insert / merge / inter / diff / sym-diff / count / query / list subcommands of the reference CLI
-(/root/reference/examples/cbl.rs:147-167,230-249,270-309,168-229) on the MI355X path, and merge-all / inter-all: the library's `CBL::merge` and
+"""`python -m cbl_amd <command>` — the build / insert / remove / merge / inter / diff / sym-diff / count / query / list subcommands of the reference CLI
+(/root/reference/examples/cbl.rs:147-167,230-269,270-309,168-229) on the MI355X path, and merge-all / inter-all: the library's `CBL::merge` and
 `CBL::intersect` (src/cbl.rs:106-124) over two or more index files, which the reference's CLI does not expose.
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
@@ -25,6 +25,10 @@ def main(argv=None):
     i.add_argument("index")
     i.add_argument("input")
     i.add_argument("-o", "--output")
+    r = sub.add_parser("remove", help="Remove the k-mers of a FASTA/Q file from an index")
+    r.add_argument("index")
+    r.add_argument("input")
+    r.add_argument("-o", "--output")
     m = sub.add_parser("merge", help="Compute the union of two indexes")
     m.add_argument("first_index")
     m.add_argument("second_index")
@@ -60,6 +64,14 @@ def main(argv=None):
         cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
         print(f"Adding the {'canonical ' if cbl.is_canonical() else ''}{a.k}-mers contained in {a.input} to the index", file=sys.stderr)
         cbl.insert_fastx_file(a.input)
+        if a.output:
+            print(f"Writing the index to {a.output}", file=sys.stderr)
+            cbl.save_to_file(a.output)
+    elif a.cmd == "remove":  # examples/cbl.rs:250-269
+        print(f"Reading the index stored in {a.index}", file=sys.stderr)
+        cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
+        print(f"Removing the {'canonical ' if cbl.is_canonical() else ''}{a.k}-mers contained in {a.input} from the index", file=sys.stderr)
+        cbl.remove_fastx_file(a.input)
         if a.output:
             print(f"Writing the index to {a.output}", file=sys.stderr)
             cbl.save_to_file(a.output)

@@ -1197,6 +1197,104 @@ int cblx_insert_kmers(cblx_ctx* c, const uint64_t* lo, const uint64_t* hi, uint6
         collect_events(c);
     });
 }
+// ---- removal: CBL::remove_seq / CBL::remove (src/cbl.rs:233-235, 343-354) and the reader loop of `cbl remove` (examples/cbl.rs:250-265). Pending inserts are
+// applied first; the removal itself runs before the call returns.
+int cblx_remove_words_device(cblx_ctx* c, const uint64_t* d_lo, const void* d_hi, uint64_t n) {
+    return guard(c, [&] {
+        flush(c);
+        if (n == 0) return;
+        if (!d_lo || (c->P.has_hi() && !d_hi)) throw Error(CBLX_EINVAL, "null argument");
+        if (n >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "a single removal batch takes fewer than 2^32-16 words");
+        dispatch(c->P, [&](auto cfg) {
+            typedef decltype(cfg) C;
+            typedef typename C::HiT HiT;
+            Buf<u32> gstart(c->pool, n + 1);
+            CBLX_HIP(hipMemsetAsync(gstart.get(), 0, (n + 1) * 4, c->stream));
+            remove_words<C>(c, d_lo, (const HiT*)d_hi, n, gstart, false, nullptr);
+        });
+        collect_events(c);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+int cblx_remove_seqs_device(cblx_ctx* c, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n) {
+    return guard(c, [&] {
+        if (n && (!d_bases || !d_offsets)) throw Error(CBLX_EINVAL, "null argument");
+        flush(c);
+        remove_device(c, d_bases, d_offsets, n);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+int cblx_remove_seqs(cblx_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n) {
+    return guard(c, [&] {
+        flush(c);
+        if (n == 0) return;
+        if (!bases || !offsets) throw Error(CBLX_EINVAL, "null argument");
+        u64 minlen = ~0ull;
+        bool mono = true;
+        for (u64 i = 0; i < n; ++i) { mono &= offsets[i + 1] >= offsets[i]; minlen = std::min(minlen, offsets[i + 1] - offsets[i]); }
+        if (!mono) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
+        if (minlen < c->P.K) throw Error(CBLX_ESHORT, "Sequence size (" + std::to_string(minlen) + ") is smaller than K (" + std::to_string(c->P.K) + ")");
+        const u64 b0 = offsets[0], nbytes = offsets[n] - b0;
+        Buf<u8> d_b(c->pool, nbytes + 64);
+        Buf<u64> d_o(c->pool, n + 1);
+        std::vector<u64> rel(n + 1);
+        for (u64 i = 0; i <= n; ++i) rel[i] = offsets[i] - b0;
+        xfer(c).h2d_copy(d_b.get(), bases + b0, nbytes);  // pinned lanes: the caller's buffers are pageable
+        xfer(c).h2d_copy(d_o.get(), rel.data(), (n + 1) * 8);
+        xfer(c).sync();
+        remove_device(c, d_b.get(), d_o.get(), n);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+int cblx_remove_seq(cblx_ctx* c, const uint8_t* seq, uint64_t len) {
+    if (!c) return CBLX_EINVAL;
+    if (!seq && len) return guard(c, [&] { throw Error(CBLX_EINVAL, "null sequence"); });
+    const uint64_t offs[2] = {0, len};
+    return cblx_remove_seqs(c, seq ? seq : (const uint8_t*)"", offs, 1);
+}
+int cblx_remove_fastx_file(cblx_ctx* c, const char* path, uint64_t* n_records) {
+    return guard(c, [&] {
+        if (n_records) *n_records = 0;
+        flush(c);  // pending inserts first: the queue changes consumer
+        Ingest& g = c->ing;
+        g.query = g.remove = true;
+        try {
+            read_fastx_into_queue(c, path, n_records);
+            flush(c);
+        } catch (const Error& e) {
+            // a record shorter than K: the records in front of it are removed, as cblx_insert_fastx_file leaves them enqueued (the reference panics at that record)
+            if (e.code == CBLX_ESHORT) { try { flush(c); } catch (...) { ingest_drop(c); } } else ingest_drop(c);
+            g.query = g.remove = false;
+            throw;
+        } catch (...) {
+            ingest_drop(c);
+            g.query = g.remove = false;
+            throw;
+        }
+        g.query = g.remove = false;
+    });
+}
+int cblx_remove_kmers(cblx_ctx* c, const uint64_t* lo, const uint64_t* hi, uint64_t n, uint8_t* was_present) {
+    return guard(c, [&] {
+        flush(c);
+        if (n == 0) return;
+        dispatch(c->P, [&](auto cfg) {
+            typedef decltype(cfg) C;
+            typedef typename C::HiT HiT;
+            Buf<u64> w_lo;
+            Buf<u8> w_hi;
+            words_of_host_kmers<C>(c, lo, hi, n, w_lo, w_hi);
+            Buf<u32> gstart(c->pool, n + 1);
+            Buf<u8> flag;
+            if (was_present) flag = Buf<u8>(c->pool, n + 8);
+            CBLX_HIP(hipMemsetAsync(gstart.get(), 0, (n + 1) * 4, c->stream));
+            remove_words<C>(c, w_lo.get(), (const HiT*)w_hi.get(), n, gstart, true, flag.get());  // every call is a group of its own
+            CBLX_HIP(hipStreamSynchronize(c->stream));
+            if (was_present) xfer(c).d2h_copy(was_present, flag.get(), n);
+        });
+        collect_events(c);
+    });
+}
 int cblx_export_kmers(cblx_ctx* c, uint64_t* lo, uint64_t* hi, uint64_t cap, uint64_t* n) {
     return guard(c, [&] {
         flush(c);

@@ -243,6 +243,8 @@ void flush(cblx_ctx* c) {
     if (streamed) {
         struct Done { cblx_ctx* c; ~Done() { try { ingest_wait(c); } catch (...) {} c->ing.streamed.clear(); } } done{c};
         insert_device_streamed(c, g.d_bases.get(), g.d_off.get(), nseq, g.streamed);
+    } else if (g.query && g.remove) {  // examples/cbl.rs:250-265: remove_seq per record
+        remove_device(c, g.d_bases.get(), g.d_off.get(), nseq);
     } else if (g.query) {  // examples/cbl.rs:205-228: contains_seq per record, tallies only
         u64 tot = 0, pos = 0;
         query_device(c, g.d_bases.get(), g.d_off.get(), nseq, nullptr, 0, &tot, &pos);

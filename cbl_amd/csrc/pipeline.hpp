@@ -3,6 +3,7 @@
 #pragma once
 #include "ctx.hpp"
 #include "kernels_kmer.hpp"
+#include "kernels_remove.hpp"
 
 namespace {
 
@@ -1917,6 +1918,170 @@ template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, 
 template <typename C> void set_op_assign_direct(cblx_ctx* c, Resident& b, u32 op) {
     Resident nr = set_op_build<C>(c, c->res, b, op, true);
     c->res = std::move(nr);
+}
+
+// ---- WordSet::remove_batch (src/wordset/mod.rs:218-237) over n device words ------------------------------------------------
+// `gstart` (n + 1 counters): 1 where a word starts a remove_batch call (a chunk of get_seq_words), 0 elsewhere; k_rm_visit adds the prefix changes, or every
+// word with `every` (n successive CBL::remove calls). d_was: CBL::remove's return value per word (n bytes, or null). The result is built beside the resident
+// index — k_bucket_remove writes what is left of the visited buckets, a scan of the new lengths gives the runs of a compacted arena, k_rm_gather fills it from
+// the replay's output and from the old runs of the other buckets — and moved in at the end, so an error leaves the index as it was.
+template <typename C> void remove_words(cblx_ctx* c, const u64* w_lo, const typename C::HiT* w_hi, u64 n, Buf<u32>& gstart, bool every, u8* d_was) {
+    typedef typename C::HiT HiT;
+    constexpr bool WS = C::WS;
+    const Consts& P = c->P;
+    if (d_was && n) CBLX_HIP(hipMemsetAsync(d_was, 0, n, c->stream));
+    if (n == 0 || c->res.nb == 0) { CBLX_HIP(hipStreamSynchronize(c->stream)); return; }
+    if (n >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "a single removal batch takes fewer than 2^32-16 words");
+    const Resident& s = c->res;
+    const u64 nb = s.nb, nprefix = 1ull << P.PB, nwords = std::max<u64>(1, nprefix / 64);
+    const u64* s_hi = WS ? s.a_hi.get() : (const u64*)nullptr;
+    Buf<u32> wrank(c->pool, n + 1), gbefore(c->pool, n + 1), visited(c->pool, nb + 1), cap(c->pool, nb + 1), mingroup(c->pool, nb + 1);
+    Buf<u64> voff(c->pool, nb + 2);
+    Buf<u32> too_long(c->pool, 1);
+    u64 V = 0;
+    {
+        StageTimer t(c, ST_DIR);
+        CBLX_HIP(hipMemsetAsync(visited.get(), 0, (nb + 1) * 4, c->stream));
+        CBLX_HIP(hipMemsetAsync(mingroup.get(), 0xFF, (nb + 1) * 4, c->stream));
+        CBLX_HIP(hipMemsetAsync(too_long.get(), 0, 4, c->stream));
+        hipLaunchKernelGGL(k_rm_visit<HiT>, grid1(n, 256), dim3(256), 0, c->stream, w_lo, w_hi, n, P.SB, P.PB, s.view(), every ? 1u : 0u, gstart.get(), wrank.get(), visited.get());
+        exclusive_scan<u32>(c, gstart.get(), n, gbefore.get());
+        hipLaunchKernelGGL(k_rm_caps, grid1(nb, 256), dim3(256), 0, c->stream, nb, (const u32*)visited.get(), (const u32*)s.cnt.get(), cap.get(), too_long.get());
+        V = exclusive_scan<u64>(c, cap.get(), nb, voff.get());
+        if (d2h<u32>(c, too_long.get())) throw Error(CBLX_ERANGE, "removal from a bucket of more than 2^31 words is not supported");
+        hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, voff.get() + nb, V);
+        CBLX_HIP(hipGetLastError());
+    }
+    if (V == 0) { CBLX_HIP(hipStreamSynchronize(c->stream)); return; }  // no word of the batch names a prefix of the index
+    u64 H = 64;
+    while (H < 2 * V) H <<= 1;
+    Buf<u64> table(c->pool, H), wslot;
+    Buf<u32> first(c->pool, V + 1), lists(c->pool, 3 * nb), list_n(c->pool, 3);
+    if (d_was) wslot = Buf<u64>(c->pool, n + 1);
+    Resident nr;
+    nr.nb = nb;
+    auto dup = [&](auto& d, const auto& o) {
+        typedef typename std::remove_reference<decltype(*o.get())>::type T;
+        if (!o.get()) return;
+        d = Buf<T>(c->pool, o.n);
+        device_copy(c->stream, d.get(), o.get(), o.n * sizeof(T));
+    };
+    dup(nr.bv, s.bv); dup(nr.rank_dir, s.rank_dir); dup(nr.prefix, s.prefix); dup(nr.cnt, s.cnt); dup(nr.kind, s.kind);  // buckets the batch does not visit keep length and kind
+    nr.start = Buf<u64>(c->pool, nb + 1);
+    Buf<u64> x_lo(c->pool, V + 1), x_hi(c->pool, WS ? V + 1 : 1);  // what the replay leaves of the visited buckets, at their table slots
+    Buf<u8> moved(c->pool, nb + 1);
+    CBLX_HIP(hipMemsetAsync(moved.get(), 0, nb + 1, c->stream));
+    std::vector<u32> ln;
+    {
+        StageTimer t(c, ST_REMOVE);
+        CBLX_HIP(hipMemsetAsync(table.get(), 0xFF, H * 8, c->stream));
+        CBLX_HIP(hipMemsetAsync(first.get(), 0xFF, (V + 1) * 4, c->stream));
+        CBLX_HIP(hipMemsetAsync(list_n.get(), 0, 3 * 4, c->stream));
+        const u64 step = 1ull << 31;
+        for (u64 v0 = 0; v0 < V; v0 += step)
+            hipLaunchKernelGGL(k_rm_build, grid1(std::min(step, V - v0), 256), dim3(256), 0, c->stream, v0, V, nb, (const u64*)voff.get(), (const u32*)s.cnt.get(), (const u64*)s.start.get(),
+                               (const u64*)s.a_lo.get(), s_hi, P.SB, table.get(), H - 1);
+        hipLaunchKernelGGL(k_rm_probe<HiT>, grid1(n, 256), dim3(256), 0, c->stream, w_lo, w_hi, n, P.SB, (const u32*)wrank.get(), (const u32*)gstart.get(), (const u32*)gbefore.get(),
+                           (const u64*)voff.get(), (const u64*)s.start.get(), (const u64*)s.a_lo.get(), s_hi, (const u64*)table.get(), H - 1, first.get(), mingroup.get(), wslot.get());
+        if (d_was) hipLaunchKernelGGL(k_rm_flags, grid1(n, 256), dim3(256), 0, c->stream, n, (const u64*)wslot.get(), (const u32*)first.get(), d_was);
+        hipLaunchKernelGGL(k_rm_classify, grid1(nb, 256), dim3(256), 0, c->stream, nb, (const u32*)cap.get(), lists.get(), list_n.get());
+        CBLX_HIP(hipGetLastError());
+        ln = d2h_vec<u32>(c, list_n.get(), 3);
+        Buf<u64> g_keys;
+        Buf<u32> g_pos, g_elem;
+        if (ln[2]) { g_keys = Buf<u64>(c->pool, V + 1); g_pos = Buf<u32>(c->pool, V + 1); g_elem = Buf<u32>(c->pool, V + 1); }
+        auto go = [&](auto thr, auto lds, int cls) {
+            constexpr int T = decltype(thr)::value, CAPV = decltype(lds)::value;
+            if (!ln[cls]) return;
+            hipLaunchKernelGGL((k_bucket_remove<WS, T, CAPV>), dim3(ln[cls]), dim3(T), 0, c->stream, (const u32*)(lists.get() + (size_t)cls * nb), (const u32*)(list_n.get() + cls),
+                               (const u64*)s.start.get(), (const u32*)s.cnt.get(), (const u8*)s.kind.get(), (const u64*)voff.get(), (const u32*)first.get(), (const u32*)gstart.get(),
+                               (const u32*)gbefore.get(), (const u32*)mingroup.get(), (const u64*)s.a_lo.get(), s_hi, x_lo.get(), x_hi.get(), nr.cnt.get(), nr.kind.get(), moved.get(),
+                               g_keys.get(), g_pos.get(), g_elem.get());
+        };
+        go(std::integral_constant<int, 64>(), std::integral_constant<int, (int)RM_SMALL>(), 0);
+        go(std::integral_constant<int, 256>(), std::integral_constant<int, (int)RM_LDS>(), 1);
+        go(std::integral_constant<int, 256>(), std::integral_constant<int, 0>(), 2);
+        CBLX_HIP(hipGetLastError());
+        CBLX_HIP(hipStreamSynchronize(c->stream));  // the global tables die here
+    }
+    // the compacted arena: runs as long as the buckets are now
+    u64 N = 0;
+    {
+        StageTimer t(c, ST_EXPAND);
+        N = exclusive_scan<u64>(c, nr.cnt.get(), nb, nr.start.get());
+        hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, nr.start.get() + nb, N);
+        nr.a_lo = Buf<u64>(c->pool, N + 2);
+        if (WS) nr.a_hi = Buf<u64>(c->pool, N + 2);
+        with_lpb(N, nb, [&](auto lpb) {
+            constexpr int LPB = decltype(lpb)::value;
+            hipLaunchKernelGGL((k_rm_gather<WS, LPB>), lpb_grid(nb, LPB), dim3(256), 0, c->stream, nb, (const u64*)nr.start.get(), (const u32*)nr.cnt.get(), (const u8*)moved.get(),
+                               (const u64*)voff.get(), (const u64*)s.start.get(), (const u64*)s.a_lo.get(), s_hi, (const u64*)x_lo.get(), (const u64*)x_hi.get(), nr.a_lo.get(),
+                               nr.a_hi.get());
+        });
+        CBLX_HIP(hipGetLastError());
+    }
+    // emptied buckets leave the directory and the bitvector, the k-mers are counted
+    Buf<u32> popc(c->pool, nwords);
+    const bool any = set_op_tail(c, nr, popc, nwords, N);
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // the tables of this call die here
+    c->res = any ? std::move(nr) : Resident();
+}
+
+// CBL::remove_seq (src/cbl.rs:343-354) for every sequence of a device-resident batch: KRN-1 as for a query, one remove_batch per chunk
+void remove_device_one(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64 nseq, const u64* ends) {
+    dispatch(c->P, [&](auto cfg) {
+        typedef decltype(cfg) C;
+        typedef typename C::HiT HiT;
+        ChunkPlan pl;
+        plan_chunks(c, d_bases, d_offsets, nseq, pl, ends);
+        const u64 nk = pl.n_kmers;
+        if (nk == 0 || c->res.nb == 0) return;
+        if (nk >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "one sequence of 2^32-16 k-mers or more is not supported");
+        Buf<u64> w_lo(c->pool, nk + 2);
+        Buf<u8> w_hi(c->pool, (nk + 2) * std::max<size_t>(1, hi_elem_size(c->P)));
+        Buf<u32> gstart(c->pool, nk + 1);
+        CBLX_HIP(hipMemsetAsync(gstart.get(), 0, (nk + 1) * 4, c->stream));
+        encode<C>(c, d_bases, pl, w_lo.get(), (HiT*)w_hi.get(), 0);
+        hipLaunchKernelGGL(k_rm_chunk_marks, grid1(pl.nchunks, 256), dim3(256), 0, c->stream, (const u64*)pl.kmer_off.get(), pl.nchunks, nk, gstart.get());
+        CBLX_HIP(hipGetLastError());
+        remove_words<C>(c, w_lo.get(), (const HiT*)w_hi.get(), nk, gstart, false, nullptr);
+    });
+    collect_events(c);
+}
+// cut into sub-batches at sequence boundaries exactly as insert_device cuts an insert (a sequence boundary is a chunk boundary: same result)
+void remove_device(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64 nseq) {
+    if (nseq == 0) return;
+    check_aligned16(d_bases, "d_bases");
+    const u64 cap = batch_max_bases();
+    const u64 first = d2h<u64>(c, d_offsets), last = d2h<u64>(c, d_offsets + nseq);
+    if (last < first) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
+    if (last - first <= cap) {
+        const u64 ends[2] = {first, last};
+        remove_device_one(c, d_bases, d_offsets, nseq, ends);
+        return;
+    }
+    {   // a sequence shorter than K anywhere in the batch: nothing is removed, as when the batch goes in as one
+        Buf<unsigned long long> ml(c->pool, 1);
+        CBLX_HIP(hipMemsetAsync(ml.get(), 0xFF, 8, c->stream));
+        hipLaunchKernelGGL(k_rm_min_len, grid1(nseq, 256), dim3(256), 0, c->stream, d_offsets, nseq, ml.get());
+        CBLX_HIP(hipGetLastError());
+        const u64 m = d2h<unsigned long long>(c, ml.get());
+        if (m < c->P.K) throw Error(CBLX_ESHORT, "Sequence size (" + std::to_string(m) + ") is smaller than K (" + std::to_string(c->P.K) + ")");
+    }
+    u64 a = 0, oa = first;
+    while (a < nseq) {
+        u64 lo = a + 1, hi = nseq;  // largest b in [a + 1, nseq] with offsets[b] - oa <= cap (a + 1 if even one sequence is longer)
+        if (d2h<u64>(c, d_offsets + hi) - oa <= cap) lo = hi;
+        else {
+            while (hi - lo > 1) {
+                const u64 mid = lo + (hi - lo) / 2;
+                if (d2h<u64>(c, d_offsets + mid) - oa <= cap) lo = mid; else hi = mid;
+            }
+        }
+        remove_device_one(c, d_bases, d_offsets + a, lo - a, nullptr);
+        a = lo;
+        oa = d2h<u64>(c, d_offsets + a);
+    }
 }
 
 }  // namespace

@@ -29,7 +29,7 @@ extern "C" {
  * communicator: an unchanged 2 - 4 rank caller no longer runs BINS), CBLX_PROTO_REPLICATE; empty PREFIX_BITS > 24 builds take the FINE route. A binding
  * built against this header must refuse a library that reports less.
  * Added under 3 (a new symbol is compatible): cblx_set_op with CBLX_SETOP_OR / AND / SUB / XOR, cblx_get_device, cblx_set_op_assign, and cblx_set_op_many with
- * CBLX_SETOP_MAX_OPERANDS. */
+ * CBLX_SETOP_MAX_OPERANDS; cblx_remove_words_device, cblx_remove_seq, cblx_remove_seqs, cblx_remove_seqs_device, cblx_remove_fastx_file and cblx_remove_kmers. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -374,6 +374,29 @@ int cblx_contains_all(cblx_ctx* ctx, const uint8_t* seq, uint64_t len, int* out)
  * above 2K is refused (CBLX_EINVAL) and nothing is inserted. */
 int cblx_insert_kmers(cblx_ctx* ctx, const uint64_t* lo, const uint64_t* hi, uint64_t n, uint8_t* was_absent);
 int cblx_contains_kmers(cblx_ctx* ctx, const uint64_t* lo, const uint64_t* hi, uint64_t n, uint8_t* out);
+/* ---- removal: CBL::remove_seq (src/cbl.rs:343-354), CBL::remove (:233-235) and `cbl remove` (examples/cbl.rs:250-269). The index after the call holds the
+ * bytes the reference's sequential replay leaves: a Vec bucket loses its words by swap_remove in stream order, a Trie bucket by deletion,
+ * and a Trie of at most 1024 words at the end of a GROUP — a maximal run of consecutive words of one remove_batch call with equal prefix — becomes an ascending Vec
+ * there (adapt_container_shrink runs after every group whose prefix is present, hit or no hit). A bucket that comes out empty leaves the index.
+ * Rules: pending inserts are applied first; a removal runs before the call returns, it is not enqueued; a sequence shorter than K is CBLX_ESHORT with the
+ * behaviour of the matching insert entry point (a batch, host or device, whatever its size: nothing is removed — all lengths are checked before the first
+ * sub-batch; a file: the records in front of it are removed); removal from an empty index or with
+ * n == 0 is a no-op that returns 0; bytes that are not ACGT are skipped exactly as insertion skips them; a batch has the insert path's size limit (the sequence forms
+ * are cut into sub-batches at sequence boundaries, one call of cblx_remove_words_device / cblx_remove_kmers takes fewer than 2^32-16 words). cblx_remove_seq called once per
+ * read costs a device round trip and a pass over the index per call: cblx_remove_fastx_file and the batch forms batch for it; there is no per-record queue for removals. */
+/* WordSet::remove_batch (src/wordset/mod.rs:218-237) on already transformed words: ONE call = ONE batch, its groups are the maximal runs of
+ * consecutive words with equal prefix. Device word arrays as for cblx_insert_words_device. */
+int cblx_remove_words_device(cblx_ctx* ctx, const uint64_t* d_lo, const void* d_hi, uint64_t n);
+/* CBL::remove_seq (src/cbl.rs:343-354) for sequence 0, then 1, ...: one remove_batch per chunk of get_seq_words. */
+int cblx_remove_seq(cblx_ctx* ctx, const uint8_t* seq, uint64_t len);
+int cblx_remove_seqs(cblx_ctx* ctx, const uint8_t* bases, const uint64_t* offsets, uint64_t n);
+int cblx_remove_seqs_device(cblx_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n);
+/* the reader loop of `cbl remove` (examples/cbl.rs:250-265), read like cblx_insert_fastx_file */
+int cblx_remove_fastx_file(cblx_ctx* ctx, const char* path, uint64_t* n_records);
+/* n successive CBL::remove calls (src/cbl.rs:233-235 -> src/wordset/mod.rs:122-137; every call a group of its own); was_present[i] (may be
+ * NULL) is the i-th call's return value: 1 iff the k-mer was in the set and not removed earlier in this batch. Packed k-mers, canonical
+ * handling and the refusal of bits above 2K as for cblx_insert_kmers. */
+int cblx_remove_kmers(cblx_ctx* ctx, const uint64_t* lo, const uint64_t* hi, uint64_t n, uint8_t* was_present);
 /* CBL::iter (src/cbl.rs:358-361): every k-mer of the set, packed as above, in the reference's iteration order
  * (prefixes ascending; a Vec bucket in stored order, a Trie bucket ascending), recovered from its word by
  * revert_necklace_pos (src/necklace/mod.rs:29-31). *n = count(); `hi` may be NULL when K <= 31. */

@@ -254,6 +254,15 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         absent.into_iter().map(|b| b != 0).collect()
     }
 
+    /// Removes a k-mer; returns `true` if it was present (`src/cbl.rs:233-235`). One device round trip per call.
+    #[inline]
+    pub fn remove(&mut self, kmer: IntKmer<K, T>) -> bool {
+        let (lo, hi) = kmer.to_int().split();
+        let mut present = 0u8;
+        self.check(unsafe { sys::cblx_remove_kmers(self.ctx, &lo, &hi, 1, &mut present) });
+        present != 0
+    }
+
     fn assert_len(seq: &[u8]) {
         // the reference's assert, before anything is handed over (`src/cbl.rs:294-299,312-317,329-334`)
         assert!(seq.len() >= K, "Sequence size ({}) is smaller than K ({})", seq.len(), K);
@@ -286,6 +295,13 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
     pub fn insert_seq(&mut self, seq: &[u8]) {
         Self::assert_len(seq);
         self.check(unsafe { sys::cblx_insert_seq(self.ctx, seq.as_ptr(), seq.len() as u64) });
+    }
+
+    /// Removes all the k-mers of a sequence (`src/cbl.rs:343-354`). Runs before it returns: pending inserts are applied first.
+    #[inline]
+    pub fn remove_seq(&mut self, seq: &[u8]) {
+        Self::assert_len(seq);
+        self.check(unsafe { sys::cblx_remove_seq(self.ctx, seq.as_ptr(), seq.len() as u64) });
     }
 
     /// The reader loop `for record in reader { cbl.insert_seq(record.seq()) }` (`examples/cbl.rs:154-163`) inside the

@@ -305,6 +305,12 @@ extern "C" {
 
     pub fn cblx_insert_kmers(ctx: *mut cblx_ctx, lo: *const u64, hi: *const u64, n: u64, was_absent: *mut u8) -> c_int;
     pub fn cblx_contains_kmers(ctx: *mut cblx_ctx, lo: *const u64, hi: *const u64, n: u64, out: *mut u8) -> c_int;
+    pub fn cblx_remove_words_device(ctx: *mut cblx_ctx, d_lo: *const u64, d_hi: *const c_void, n: u64) -> c_int;
+    pub fn cblx_remove_seq(ctx: *mut cblx_ctx, seq: *const u8, len: u64) -> c_int;
+    pub fn cblx_remove_seqs(ctx: *mut cblx_ctx, bases: *const u8, offsets: *const u64, n: u64) -> c_int;
+    pub fn cblx_remove_seqs_device(ctx: *mut cblx_ctx, d_bases: *const u8, d_offsets: *const u64, n: u64) -> c_int;
+    pub fn cblx_remove_fastx_file(ctx: *mut cblx_ctx, path: *const c_char, n_records: *mut u64) -> c_int;
+    pub fn cblx_remove_kmers(ctx: *mut cblx_ctx, lo: *const u64, hi: *const u64, n: u64, was_present: *mut u8) -> c_int;
     pub fn cblx_export_kmers(ctx: *mut cblx_ctx, lo: *mut u64, hi: *mut u64, cap: u64, n: *mut u64) -> c_int;
     pub fn cblx_bucket_sizes(ctx: *mut cblx_ctx, prefix: *mut u32, len: *mut u32, kind: *mut u8, cap: u64, n: *mut u64) -> c_int;
 
