@@ -153,6 +153,13 @@ SIGNATURES = {
     "cblx_remove_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cblx_contains_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cblx_export_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_export_kmers_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cblx_export_kmers_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cblx_list_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_list_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_list_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_list_to_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_bucket_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_bucket_sizes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_checksum": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "cblx_checksum_words_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -722,25 +729,103 @@ class CBL:
         """True if the set contains the packed k-mer (src/cbl.rs:219-221)."""
         return bool(self.contains_kmers([kmer])[0])
 
-    def kmers_np(self):
-        """All k-mers of the set in the reference's iteration order as (lo, hi) uint64 arrays (hi is None for K <= 31)."""
+    def kmers_np(self, first: int = 0, n=None):
+        """The k-mers of the set in the reference's iteration order as (lo, hi) uint64 arrays (hi is None for K <= 31): all of them, or
+        with `first` / `n` elements [first, first + n) of that order (clamped at the end; `first` past the end raises). A ranged call
+        takes device and host memory for its n elements only."""
         import numpy as np
 
-        n = self.count()
+        if first == 0 and n is None:
+            n = self.count()
+            lo = np.empty(max(n, 1), dtype=np.uint64)
+            hi = np.empty(max(n, 1), dtype=np.uint64) if self.k > 31 else None
+            got = C.c_uint64(0)
+            self._chk(self._L.cblx_export_kmers(self._h, _ptr(lo), _ptr(hi) if hi is not None else None, n, C.byref(got)))
+            return lo[: got.value], (hi[: got.value] if hi is not None else None)
+        total = self.count()
+        n = max(min(total - first, total if n is None else n), 0)  # (first > count: the library refuses it)
         lo = np.empty(max(n, 1), dtype=np.uint64)
         hi = np.empty(max(n, 1), dtype=np.uint64) if self.k > 31 else None
+        got = self.export_kmers_range(first, n, lo, hi)
+        return lo[:got], (hi[:got] if hi is not None else None)
+
+    def export_kmers_range(self, first: int, n: int, lo, hi=None) -> int:
+        """Elements [first, first + n) of the iteration order into the caller's uint64 numpy arrays (`hi` may be None for K <= 31);
+        returns how many were written: min(n, count - first)."""
         got = C.c_uint64(0)
-        self._chk(self._L.cblx_export_kmers(self._h, _ptr(lo), _ptr(hi) if hi is not None else None, n, C.byref(got)))
-        return lo[: got.value], (hi[: got.value] if hi is not None else None)
+        self._chk(self._L.cblx_export_kmers_range(self._h, first, n, _ptr(lo), _ptr(hi), C.byref(got)))
+        return got.value
 
-    def iter(self):
-        """Iterator over the packed k-mers of the set (src/cbl.rs:358-361)."""
-        lo, hi = self.kmers_np()
-        if hi is None:
-            return iter(int(x) for x in lo)
-        return iter((int(h) << 64) | int(l) for l, h in zip(lo, hi))
+    def export_kmers_range_device(self, first: int, n: int, d_lo, d_hi=None) -> int:
+        """The same into device arrays (torch int64 / uint64 CUDA tensors or raw device addresses)."""
+        got = C.c_uint64(0)
+        self._chk(self._L.cblx_export_kmers_range_device(self._h, first, n, _ptr(d_lo), _ptr(d_hi), C.byref(got)))
+        return got.value
 
-    __iter__ = iter
+    def iter(self, chunk: int = 1 << 22):
+        """Iterator over the packed k-mers of the set (src/cbl.rs:358-361), pulled from the device `chunk` k-mers at a time: the first
+        one is there after one chunk, and no more than a chunk is held at once. The index must not change while the generator is
+        alive (the reference's `iter` borrows the set: the borrow checker enforces there what is a rule here) — an insert, a removal
+        or a set operation in between makes the rest of the sequence meaningless."""
+        if chunk < 1:
+            raise ValueError("iter: chunk must be at least 1")
+        import numpy as np
+
+        first, total = 0, self.count()
+        cap = max(min(chunk, total), 1)
+        lo = np.empty(cap, dtype=np.uint64)
+        hi = np.empty(cap, dtype=np.uint64) if self.k > 31 else None
+        while first < total:
+            got = self.export_kmers_range(first, cap, lo, hi)
+            if got == 0:
+                return
+            if hi is None:
+                yield from lo[:got].tolist()
+            else:
+                for l, h in zip(lo[:got].tolist(), hi[:got].tolist()):
+                    yield (h << 64) | l
+            first += got
+
+    def __iter__(self):
+        return self.iter()
+
+    # ---- `cbl list` (examples/cbl.rs:177-201): one line per k-mer, K bytes of IntKmer::to_nucs + '\n' -------------------------
+    def list_range(self, first: int, n: int, buf, cap=None) -> int:
+        """The lines of elements [first, first + n) of the iteration order into the caller's uint8 numpy array; returns the bytes
+        written. A buffer too small raises CblxError(ERANGE) and is left untouched."""
+        got = C.c_uint64(0)
+        self._chk(self._L.cblx_list_range(self._h, first, n, _ptr(buf), buf.size if cap is None else cap, C.byref(got)))
+        return got.value
+
+    def list_range_device(self, first: int, n: int, d_buf, cap: int) -> int:
+        """The same into device memory (a 16-byte aligned torch uint8 CUDA tensor or raw device address of `cap` bytes)."""
+        got = C.c_uint64(0)
+        self._chk(self._L.cblx_list_range_device(self._h, first, n, _ptr(d_buf), cap, C.byref(got)))
+        return got.value
+
+    def list_np(self, first: int = 0, n=None):
+        """Elements [first, first + n) of the iteration order as text: a uint8 array of shape (written, K + 1), row = the k-mer's
+        bases (b"ACTG"[code], first base first) and '\\n'."""
+        import numpy as np
+
+        total = self.count()
+        n = max(min(total - first, total if n is None else n), 0)
+        buf = np.empty(max(n, 1) * (self.k + 1), dtype=np.uint8)
+        got = self.list_range(first, n, buf)
+        return buf[:got].reshape(-1, self.k + 1)
+
+    def list_to_file(self, path, chunk: int = 0) -> int:
+        """Writes every k-mer as a line to `path` (created / truncated), streamed from the device `chunk` k-mers at a time (0 = the
+        library's default); returns the number of k-mers."""
+        n = C.c_uint64(0)
+        self._chk(self._L.cblx_list_to_file(self._h, os.fsencode(path), chunk, C.byref(n)))
+        return n.value
+
+    def list_to_fd(self, fd: int, chunk: int = 0) -> int:
+        """The same to an open file descriptor (flush any Python-level buffer over it first)."""
+        n = C.c_uint64(0)
+        self._chk(self._L.cblx_list_to_fd(self._h, fd, chunk, C.byref(n)))
+        return n.value
 
     # ---- bucket statistics (src/cbl.rs:364-386) ---------------------------------------------------------------------
     def bucket_table_np(self):
@@ -776,6 +861,28 @@ class CBL:
         """bucket length -> share of the k-mers held by buckets of that length (src/cbl.rs:382-385)."""
         total = float(max(self.count(), 1))
         return {size: size * n / total for size, n in self.buckets_size_count().items()}
+
+    def bucket_nodes_np(self):
+        """Node count of every non-empty bucket, ascending prefixes, as a uint64 array (pairs with bucket_table_np)."""
+        import numpy as np
+
+        nb = self.num_buckets()
+        nodes = np.empty(max(nb, 1), dtype=np.uint64)
+        got = C.c_uint64(0)
+        self._chk(self._L.cblx_bucket_nodes(self._h, _ptr(nodes), nb, C.byref(got)))
+        return nodes[: got.value]
+
+    def buckets_nodes(self):
+        """(prefix, node count) pairs, ascending prefixes (src/cbl.rs:386-390): a Vec bucket counts its words, a Trie bucket its nodes."""
+        p, _, _ = self.bucket_table_np()
+        return list(zip(p.tolist(), self.bucket_nodes_np().tolist()))
+
+    def buckets_node_count(self) -> dict:
+        """node count -> number of buckets with that many nodes, sorted by node count (src/cbl.rs:392-396)."""
+        import numpy as np
+
+        v, c = np.unique(self.bucket_nodes_np(), return_counts=True)
+        return dict(zip(v.tolist(), c.tolist()))
 
     # ---- src/cbl.rs:127-160 ---------------------------------------------------------------------------------
     def serialize(self) -> bytes:

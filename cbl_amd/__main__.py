@@ -1,5 +1,5 @@
-"""`python -m cbl_amd <command>` — the build / insert / remove / merge / inter / diff / sym-diff / count / query / list subcommands of the reference CLI
-(/root/reference/examples/cbl.rs:147-167,230-269,270-309,168-229) on the MI355X path, and merge-all / inter-all: the library's `CBL::merge` and
+"""`python -m cbl_amd <command>` — the build / insert / remove / merge / inter / diff / sym-diff / count / query / list / repartition subcommands of the
+reference CLI (/root/reference/examples/cbl.rs:147-167,230-269,270-309,168-229,310-366) on the MI355X path, and merge-all / inter-all: the library's `CBL::merge` and
 `CBL::intersect` (src/cbl.rs:106-124) over two or more index files, which the reference's CLI does not expose.
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
@@ -9,6 +9,55 @@ import argparse
 import sys
 
 from . import CBL
+
+
+def _f1(x):
+    """Rust's `{:.1}` of an f64 (a quotient by zero prints as NaN / inf there)."""
+    if x != x:
+        return "NaN"
+    return ("inf" if x > 0 else "-inf") if x in (float("inf"), float("-inf")) else f"{x:.1f}"
+
+
+def _div(a, b):
+    a, b = int(a), int(b)
+    return a / b if b else (float("nan") if a == 0 else float("inf"))
+
+
+def repartition_report(prefix_bits, prefix, length, nodes):
+    """The lines `cbl repartition` prints to stderr (examples/cbl.rs:313-365, same order and formatting) and the machine-readable stdout line
+    `prefix_load n_buckets n_items max_prefix max_size vec_count vec_nodes trie_count trie_nodes total_nodes`, from the bucket table (numpy arrays,
+    ascending prefixes). As in the reference a bucket counts as a "vec" when its NODE count is <= 1024, and the total adds the bucket count to the
+    node counts. An empty index gives the load line and zeros (the reference panics on it)."""
+    import numpy as np
+
+    nb = len(prefix)
+    load = nb / float(1 << prefix_bits)
+    lines = [f"{_f1(load * 100.0)}% of the available prefixes are used"]
+    if nb == 0:
+        return lines, f"{load} 0 0 0 0 0 0 0 0 0"
+    sizes, counts = np.unique(np.asarray(length, dtype=np.int64), return_counts=True)
+    sizes, counts = sizes.tolist(), counts.tolist()
+    total_buckets, total_items = sum(counts), sum(s * c for s, c in zip(sizes, counts))
+    lines.append(f"The average bucket size is {_f1(_div(total_items, total_buckets))} items")
+    bucket_count = item_count = 0
+    for size, count in zip(sizes, counts):
+        bucket_count += count
+        item_count += size * count
+        if count > total_buckets // 100 // 2 or size * count > total_items // 100 // 2 or bucket_count == total_buckets:
+            lines.append(f"{_f1(_div(item_count * 100, total_items))}% of items are in a bucket of size \u2264 {size} ({_f1(_div(bucket_count * 100, total_buckets))}% of buckets)")
+    ln = np.asarray(length, dtype=np.int64)
+    at = nb - 1 - int(np.argmax(ln[::-1]))  # Iterator::max_by_key keeps the last of equal maxima
+    max_prefix, max_size = int(prefix[at]), int(ln[at])
+    lines.append(f"The biggest bucket (of size {max_size}) corresponds to prefix {max_prefix}")
+    nd = np.asarray(nodes, dtype=np.uint64)
+    small = nd <= 1024
+    vec_count, trie_count = int(small.sum()), int((~small).sum())
+    vec_nodes, trie_nodes = sum(nd[small].tolist()), sum(nd[~small].tolist())
+    lines.append(f"{vec_count} vecs, average node count = {_f1(_div(vec_nodes, vec_count))}")
+    lines.append(f"{trie_count} tries, average node count = {_f1(_div(trie_nodes, trie_count))}")
+    total = total_buckets + vec_nodes + trie_nodes
+    lines.append(f"{total} nodes in total")
+    return lines, f"{load} {total_buckets} {total_items} {max_prefix} {max_size} {vec_count} {vec_nodes} {trie_count} {trie_nodes} {total}"
 
 
 def main(argv=None):
@@ -50,6 +99,9 @@ def main(argv=None):
     ls = sub.add_parser("list", help="List the k-mers contained in an index")
     ls.add_argument("index")
     ls.add_argument("-o", "--output")
+    rp = sub.add_parser("repartition", help="Show statistics about the buckets of an index: sizes, node counts. An empty index prints the prefix load "
+                                            "and zeros (the reference panics on an empty index)")
+    rp.add_argument("index")
     a = ap.parse_args(argv)
 
     if a.cmd == "build":
@@ -108,27 +160,22 @@ def main(argv=None):
         print(f"# queries: {total}", file=sys.stderr)
         print(f"# positive queries: {positive} ({positive * 100 / total if total else float('nan'):.2f}%)", file=sys.stderr)
         print(total, positive)
-    elif a.cmd == "list":  # examples/cbl.rs:177-203: one k-mer per line, IntKmer::to_nucs (first base most significant)
-        import numpy as np
-
+    elif a.cmd == "list":  # examples/cbl.rs:177-203: one k-mer per line, IntKmer::to_nucs (first base most significant), streamed from the device
         cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
         print(f"Listing {'canonical ' if cbl.is_canonical() else ''}{a.k}-mers contained in {a.index}", file=sys.stderr)
-        lo, hi = cbl.kmers_np()
-        nuc = np.frombuffer(b"ACTG", dtype=np.uint8)  # src/kmer.rs:26-27
-        out = open(a.output, "wb") if a.output else sys.stdout.buffer
-        for c0 in range(0, len(lo), 1 << 20):
-            l = lo[c0 : c0 + (1 << 20)]
-            h = hi[c0 : c0 + (1 << 20)] if hi is not None else None
-            lines = np.empty((len(l), a.k + 1), dtype=np.uint8)
-            lines[:, a.k] = ord("\n")
-            for j in range(a.k):  # base j sits 2 * (k - 1 - j) bits up
-                sh = 2 * (a.k - 1 - j)
-                code = (l >> np.uint64(sh)) if sh < 64 else (h >> np.uint64(sh - 64))
-                lines[:, j] = nuc[(code & np.uint64(3)).astype(np.intp)]
-            out.write(lines.tobytes())
         if a.output:
-            out.close()
-
+            cbl.list_to_file(a.output)
+        else:
+            sys.stdout.flush()
+            cbl.list_to_fd(sys.stdout.fileno())
+    elif a.cmd == "repartition":  # examples/cbl.rs:310-366
+        cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
+        prefix, length, _ = cbl.bucket_table_np()
+        lines, summary = repartition_report(a.prefix_bits, prefix, length, cbl.bucket_nodes_np())
+        sys.stderr.flush()
+        sys.stderr.buffer.write(("\n".join(lines) + "\n").encode("utf-8"))
+        sys.stderr.buffer.flush()
+        print(summary)
 
 if __name__ == "__main__":
     main()

@@ -6,6 +6,7 @@
 // HBM: bitvector words, popcount-scan rank directory, bucket table indexed by rank, one suffix arena.
 // There is no CPU fallback: every data-path step below is a kernel launch.
 #include "comm.hpp"
+#include "kernels_list.hpp"
 
 namespace {
 
@@ -158,6 +159,124 @@ Resident clone_resident(cblx_ctx* dst, const cblx_ctx* src) {
     dup(copy.cnt, o.cnt); dup(copy.kind, o.kind); dup(copy.a_lo, o.a_lo); dup(copy.a_hi, o.a_hi);
     CBLX_HIP(hipStreamSynchronize(dst->stream));
     return copy;
+}
+
+// ---- reading the index out (kernels_list.hpp) --------------------------------------------------------------------------
+// res_off[nb + 1]: where every bucket begins in the iteration order, and the total behind the last one
+u64 iteration_offsets(cblx_ctx* c, Buf<u64>& res_off) {
+    const Resident& r = c->res;
+    res_off = Buf<u64>(c->pool, r.nb + 1);
+    const u64 tot = exclusive_scan<u64>(c, r.cnt.get(), r.nb, res_off.get());
+    hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, res_off.get() + r.nb, tot);
+    CBLX_HIP(hipGetLastError());
+    return tot;
+}
+// elements [first, first + n) of the iteration order (n != 0, inside the index) to device arrays, from their index 0; asynchronous on the ctx's stream.
+// d_text != null: lines (16-byte aligned); else packed k-mers, d_hi may be null.
+void export_range_launch(cblx_ctx* c, const u64* res_off, u64 first, u64 n, u64* d_lo, u64* d_hi, u8* d_text) {
+    const Resident& r = c->res;
+    const u64 LINE = c->P.K + 1, STEP = 1ull << 31;  // one launch addresses fewer than 2^32 work items; a multiple of LIST_THREADS keeps every text launch 16-byte aligned
+    const bool ws = c->P.wide_suffix();
+    for (u64 o = 0; o < n; o += STEP) {
+        const u64 m = std::min<u64>(STEP, n - o);
+        const dim3 grid = grid1(m, LIST_THREADS);
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, grid, dim3(LIST_THREADS), 0, c->stream, first + o, m, r.nb, res_off, r.prefix.get(), r.start.get(), r.a_lo.get(),
+                               ws ? r.a_hi.get() : (const u64*)nullptr, c->P, d_text ? (u64*)nullptr : d_lo + o, (d_text || !d_hi) ? (u64*)nullptr : d_hi + o,
+                               d_text ? d_text + o * LINE : (u8*)nullptr);
+        };
+        if (d_text) { if (ws) go(k_export_range<true, true>); else go(k_export_range<true, false>); }
+        else { if (ws) go(k_export_range<false, true>); else go(k_export_range<false, false>); }
+    }
+    CBLX_HIP(hipGetLastError());
+}
+// the checks the range calls share: *m = min(n, count - first)
+void range_clamp(cblx_ctx* c, u64 first, u64 n, u64* m) {
+    flush(c);
+    if (first > c->res.count) throw Error(CBLX_EINVAL, "first = " + std::to_string(first) + " is past the end: the index holds " + std::to_string(c->res.count) + " k-mers");
+    *m = std::min<u64>(n, c->res.count - first);
+}
+
+// `cbl list`: the lines of the whole index to a file descriptor, chunk by chunk. Two device buffers and two pinned ones: while the device emits
+// chunk i, chunk i - 1 crosses to its pinned buffer and a writer thread hands chunk i - 2 to write(), in order.
+static const u64 LIST_CHUNK_DEFAULT = 1ull << 21;
+void list_to_fd(cblx_ctx* c, int fd, u64 chunk, u64* n_kmers) {
+    flush(c);
+    const Resident& r = c->res;
+    if (n_kmers) *n_kmers = r.count;
+    if (r.count == 0) return;
+    if (chunk == 0) chunk = LIST_CHUNK_DEFAULT;
+    chunk = std::min<u64>(chunk, r.count);
+    const u64 LINE = c->P.K + 1, cbytes = chunk * LINE, nch = ceil_div(r.count, chunk);
+    Buf<u64> res_off;
+    iteration_offsets(c, res_off);
+    Buf<u8> dev[2] = {Buf<u8>(c->pool, cbytes), Buf<u8>(c->pool, nch > 1 ? cbytes : 1)};
+    struct Pinned {
+        u8* p[2] = {nullptr, nullptr};
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        ~Pinned() { for (int i = 0; i < 2; ++i) { if (p[i]) (void)hipHostFree(p[i]); if (ev[i]) (void)hipEventDestroy(ev[i]); } }
+    } pin;
+    for (int i = 0; i < (nch > 1 ? 2 : 1); ++i) CBLX_HIP(hipHostMalloc((void**)&pin.p[i], cbytes, hipHostMallocDefault));
+    for (int i = 0; i < 2; ++i) CBLX_HIP(hipEventCreateWithFlags(&pin.ev[i], hipEventDisableTiming));
+    struct Drain {  // on any way out no emitter is still writing into a buffer that goes back to the pool
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{c->stream};
+    // the writer: chunks [0, handed) may be written, `written` are done; it stops at the first error
+    struct Writer {
+        std::mutex mu;
+        std::condition_variable cv;
+        u64 handed = 0, written = 0;
+        bool quit = false;
+        int err = 0;  // errno of a failed write, EIO for one that wrote nothing
+        std::thread th;
+        ~Writer() { { std::lock_guard<std::mutex> g(mu); quit = true; } cv.notify_all(); if (th.joinable()) th.join(); }
+    } wr;
+    auto chunk_len = [&](u64 i) { return std::min<u64>(chunk, r.count - i * chunk) * LINE; };
+    wr.th = std::thread([&] {
+        for (u64 i = 0;; ++i) {
+            {
+                std::unique_lock<std::mutex> g(wr.mu);
+                wr.cv.wait(g, [&] { return wr.quit || wr.handed > i; });
+                if (wr.handed <= i) return;
+            }
+            const u8* src = pin.p[i & 1];
+            u64 left = chunk_len(i);
+            int err = 0;
+            while (left) {
+                const ssize_t k = ::write(fd, src, left);
+                if (k < 0 && errno == EINTR) continue;
+                if (k <= 0) { err = k < 0 ? errno : EIO; break; }
+                src += k; left -= (u64)k;
+            }
+            std::lock_guard<std::mutex> g(wr.mu);
+            if (err) { wr.err = err; wr.cv.notify_all(); return; }
+            wr.written = i + 1;
+            wr.cv.notify_all();
+        }
+    });
+    auto fail_if_bad = [&] { if (wr.err) throw Error(CBLX_EINVAL, std::string("Failed to write the list: ") + std::strerror(wr.err)); };
+    for (u64 i = 0; i <= nch; ++i) {
+        if (i < nch) {  // dev[i & 1] is free: chunk i - 2 was downloaded in the previous round
+            export_range_launch(c, res_off.get(), i * chunk, std::min<u64>(chunk, r.count - i * chunk), nullptr, nullptr, dev[i & 1].get());
+            CBLX_HIP(hipEventRecord(pin.ev[i & 1], c->stream));
+        }
+        if (i >= 1) {
+            const u64 j = i - 1;
+            CBLX_HIP(hipEventSynchronize(pin.ev[j & 1]));
+            {
+                std::unique_lock<std::mutex> g(wr.mu);  // the pinned buffer of chunk j still holds chunk j - 2 until that is written
+                wr.cv.wait(g, [&] { return wr.err || wr.written + 2 > j; });
+                fail_if_bad();
+            }
+            xfer(c).d2h_copy(pin.p[j & 1], dev[j & 1].get(), chunk_len(j));
+            { std::lock_guard<std::mutex> g(wr.mu); wr.handed = j + 1; }
+            wr.cv.notify_all();
+        }
+    }
+    std::unique_lock<std::mutex> g(wr.mu);
+    wr.cv.wait(g, [&] { return wr.err || wr.written == nch; });
+    fail_if_bad();
 }
 }  // namespace
 
@@ -1313,6 +1432,114 @@ int cblx_export_kmers(cblx_ctx* c, uint64_t* lo, uint64_t* hi, uint64_t cap, uin
         CBLX_HIP(hipStreamSynchronize(c->stream));
         xfer(c).d2h_copy(lo, d_lo.get(), tot * 8);
         if (hi) xfer(c).d2h_copy(hi, d_hi.get(), tot * 8);
+    });
+}
+int cblx_export_kmers_range_device(cblx_ctx* c, uint64_t first, uint64_t n, uint64_t* d_lo, uint64_t* d_hi, uint64_t* written) {
+    return guard(c, [&] {
+        u64 m;
+        range_clamp(c, first, n, &m);
+        if (written) *written = m;
+        if (m == 0) return;
+        if (!d_lo || (c->P.wide_kmer() && !d_hi)) throw Error(CBLX_EINVAL, c->P.wide_kmer() ? "null argument (K >= 33 needs a hi array)" : "null argument");
+        Buf<u64> res_off;
+        iteration_offsets(c, res_off);
+        export_range_launch(c, res_off.get(), first, m, d_lo, d_hi, nullptr);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+int cblx_export_kmers_range(cblx_ctx* c, uint64_t first, uint64_t n, uint64_t* lo, uint64_t* hi, uint64_t* written) {
+    return guard(c, [&] {
+        u64 m;
+        range_clamp(c, first, n, &m);
+        if (written) *written = m;
+        if (m == 0) return;
+        if (!lo || (c->P.wide_kmer() && !hi)) throw Error(CBLX_EINVAL, c->P.wide_kmer() ? "null argument (K >= 33 needs a hi array)" : "null argument");
+        Buf<u64> res_off, d_lo(c->pool, m), d_hi(c->pool, hi ? m : 1);
+        iteration_offsets(c, res_off);
+        export_range_launch(c, res_off.get(), first, m, d_lo.get(), hi ? d_hi.get() : (u64*)nullptr, nullptr);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+        xfer(c).d2h_copy(lo, d_lo.get(), m * 8);
+        if (hi) xfer(c).d2h_copy(hi, d_hi.get(), m * 8);
+    });
+}
+int cblx_list_range_device(cblx_ctx* c, uint64_t first, uint64_t n, uint8_t* d_buf, uint64_t cap, uint64_t* written_bytes) {
+    return guard(c, [&] {
+        u64 m;
+        range_clamp(c, first, n, &m);
+        const u64 need = m * (c->P.K + 1);
+        if (written_bytes) *written_bytes = need;
+        if (m == 0) return;
+        if (need > cap) throw Error(CBLX_ERANGE, "buffer too small: need " + std::to_string(need) + " bytes");
+        if (!d_buf) throw Error(CBLX_EINVAL, "null argument");
+        check_aligned16(d_buf, "d_buf");
+        Buf<u64> res_off;
+        iteration_offsets(c, res_off);
+        export_range_launch(c, res_off.get(), first, m, nullptr, nullptr, d_buf);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+int cblx_list_range(cblx_ctx* c, uint64_t first, uint64_t n, uint8_t* buf, uint64_t cap, uint64_t* written_bytes) {
+    return guard(c, [&] {
+        u64 m;
+        range_clamp(c, first, n, &m);
+        const u64 need = m * (c->P.K + 1);
+        if (written_bytes) *written_bytes = need;
+        if (m == 0) return;
+        if (need > cap) throw Error(CBLX_ERANGE, "buffer too small: need " + std::to_string(need) + " bytes");
+        if (!buf) throw Error(CBLX_EINVAL, "null argument");
+        Buf<u64> res_off;
+        Buf<u8> d_buf(c->pool, need);
+        iteration_offsets(c, res_off);
+        export_range_launch(c, res_off.get(), first, m, nullptr, nullptr, d_buf.get());
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+        xfer(c).d2h_copy(buf, d_buf.get(), need);
+    });
+}
+int cblx_list_to_fd(cblx_ctx* c, int fd, uint64_t chunk_kmers, uint64_t* n_kmers) {
+    return guard(c, [&] {
+        if (fd < 0) throw Error(CBLX_EINVAL, "bad file descriptor");
+        list_to_fd(c, fd, chunk_kmers, n_kmers);
+    });
+}
+int cblx_list_to_file(cblx_ctx* c, const char* path, uint64_t chunk_kmers, uint64_t* n_kmers) {
+    return guard(c, [&] {
+        if (!path) throw Error(CBLX_EINVAL, "null argument");
+        const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) throw Error(CBLX_EINVAL, std::string("Failed to open ") + path);
+        try { list_to_fd(c, fd, chunk_kmers, n_kmers); } catch (...) { (void)::close(fd); throw; }
+        if (::close(fd) != 0) throw Error(CBLX_EINVAL, std::string("Failed to write the list to ") + path);
+    });
+}
+int cblx_bucket_nodes(cblx_ctx* c, uint64_t* nodes, uint64_t cap, uint64_t* n) {
+    return guard(c, [&] {
+        flush(c);
+        const Resident& r = c->res;
+        if (n) *n = r.nb;
+        if (r.nb == 0) return;
+        if (r.nb > cap) throw Error(CBLX_ERANGE, "output capacity too small: the index holds " + std::to_string(r.nb) + " buckets");
+        if (!nodes) throw Error(CBLX_EINVAL, "null argument");
+        const u32 long_cap = (u32)std::min<u64>(r.nb, r.count / NODES_WAVE_MAX + 1);  // Tries of more than NODES_WAVE_MAX words
+        Buf<u64> d_nodes(c->pool, r.nb);
+        Buf<u32> long_list(c->pool, long_cap), long_n(c->pool, 1);
+        CBLX_HIP(hipMemsetAsync(long_n.get(), 0, 4, c->stream));
+        const bool ws = c->P.wide_suffix();
+        const u64* a_hi = ws ? r.a_hi.get() : (const u64*)nullptr;
+        for (u64 r0 = 0; r0 < r.nb; r0 += 1ull << 25) {  // one wave per bucket, fewer than 2^32 work items per launch
+            const dim3 grid = grid1(std::min<u64>(1ull << 25, r.nb - r0) * 64, 256);
+            if (ws) hipLaunchKernelGGL(k_bucket_nodes<true>, grid, dim3(256), 0, c->stream, r0, r.nb, r.start.get(), r.cnt.get(), r.kind.get(), r.a_lo.get(), a_hi, c->P.SB, c->P.BYTES,
+                                       d_nodes.get(), long_list.get(), long_n.get(), long_cap);
+            else hipLaunchKernelGGL(k_bucket_nodes<false>, grid, dim3(256), 0, c->stream, r0, r.nb, r.start.get(), r.cnt.get(), r.kind.get(), r.a_lo.get(), a_hi, c->P.SB, c->P.BYTES,
+                                    d_nodes.get(), long_list.get(), long_n.get(), long_cap);
+        }
+        if (r.count > NODES_WAVE_MAX) {  // else no bucket is long
+            if (ws) hipLaunchKernelGGL(k_bucket_nodes_long<true>, dim3(long_cap), dim3(NODES_LONG_THREADS), 0, c->stream, long_list.get(), long_n.get(), r.start.get(), r.cnt.get(),
+                                       r.a_lo.get(), a_hi, c->P.SB, c->P.BYTES, d_nodes.get());
+            else hipLaunchKernelGGL(k_bucket_nodes_long<false>, dim3(long_cap), dim3(NODES_LONG_THREADS), 0, c->stream, long_list.get(), long_n.get(), r.start.get(), r.cnt.get(),
+                                    r.a_lo.get(), a_hi, c->P.SB, c->P.BYTES, d_nodes.get());
+        }
+        CBLX_HIP(hipGetLastError());
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+        xfer(c).d2h_copy(nodes, d_nodes.get(), r.nb * 8);
     });
 }
 int cblx_bucket_sizes(cblx_ctx* c, uint32_t* prefix, uint32_t* len, uint8_t* kind, uint64_t cap, uint64_t* n) {

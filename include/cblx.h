@@ -29,7 +29,8 @@ extern "C" {
  * communicator: an unchanged 2 - 4 rank caller no longer runs BINS), CBLX_PROTO_REPLICATE; empty PREFIX_BITS > 24 builds take the FINE route. A binding
  * built against this header must refuse a library that reports less.
  * Added under 3 (a new symbol is compatible): cblx_set_op with CBLX_SETOP_OR / AND / SUB / XOR, cblx_get_device, cblx_set_op_assign, and cblx_set_op_many with
- * CBLX_SETOP_MAX_OPERANDS; cblx_remove_words_device, cblx_remove_seq, cblx_remove_seqs, cblx_remove_seqs_device, cblx_remove_fastx_file and cblx_remove_kmers. */
+ * CBLX_SETOP_MAX_OPERANDS; cblx_remove_words_device, cblx_remove_seq, cblx_remove_seqs, cblx_remove_seqs_device, cblx_remove_fastx_file and cblx_remove_kmers;
+ * cblx_export_kmers_range, cblx_export_kmers_range_device, cblx_list_range, cblx_list_range_device, cblx_list_to_fd, cblx_list_to_file and cblx_bucket_nodes. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -401,6 +402,28 @@ int cblx_remove_kmers(cblx_ctx* ctx, const uint64_t* lo, const uint64_t* hi, uin
  * (prefixes ascending; a Vec bucket in stored order, a Trie bucket ascending), recovered from its word by
  * revert_necklace_pos (src/necklace/mod.rs:29-31). *n = count(); `hi` may be NULL when K <= 31. */
 int cblx_export_kmers(cblx_ctx* ctx, uint64_t* lo, uint64_t* hi, uint64_t cap, uint64_t* n);
+/* ---- reading the index out in pieces. Element e of the ITERATION ORDER is the e-th k-mer CBL::iter yields (order as for cblx_export_kmers). The range
+ * calls take elements [first, first + n): first > count() is CBLX_EINVAL, a range that runs past the end is clamped, first == count() or n == 0 writes
+ * nothing and returns 0. Device workspace is O(n) plus one uint64_t per bucket, not O(count()). Pending inserts are applied first. The index must not
+ * change between the calls that walk it: positions are positions in the order of the moment. */
+/* CBL::iter, elements [first, first + n) of the iteration order; *written = min(n, count - first). Host / device outputs. `hi` may be NULL when
+ * K <= 31, is CBLX_EINVAL when K >= 33. */
+int cblx_export_kmers_range(cblx_ctx* ctx, uint64_t first, uint64_t n, uint64_t* lo, uint64_t* hi, uint64_t* written);
+int cblx_export_kmers_range_device(cblx_ctx* ctx, uint64_t first, uint64_t n, uint64_t* d_lo, uint64_t* d_hi, uint64_t* written);
+/* The same elements as text: K bytes of IntKmer::to_nucs (b"ACTG"[code], first base first: src/kmer.rs:26-27) + '\n' each (examples/cbl.rs:190-193). cap in
+ * bytes; *written_bytes = (K + 1) * min(n, count - first). When cap is smaller than that the call returns CBLX_ERANGE, *written_bytes is the need and
+ * nothing is written. */
+int cblx_list_range(cblx_ctx* ctx, uint64_t first, uint64_t n, uint8_t* buf, uint64_t cap, uint64_t* written_bytes);
+int cblx_list_range_device(cblx_ctx* ctx, uint64_t first, uint64_t n, uint8_t* d_buf /* 16-byte aligned */, uint64_t cap, uint64_t* written_bytes);
+/* `cbl list` (examples/cbl.rs:177-201): every k-mer as a line, streamed to a file descriptor in order. chunk_kmers = k-mers per device chunk (0 = default:
+ * 2^21, 64 MiB of text at K = 31). While the device emits chunk i, chunk i - 1 crosses to pinned memory and chunk i - 2 is handed to write(): two device and
+ * two pinned buffers of one chunk each, whatever the size of the index. A short or failed write is CBLX_EINVAL with the errno text; what was written
+ * before it stays written. *n_kmers = count(). */
+int cblx_list_to_fd(cblx_ctx* ctx, int fd, uint64_t chunk_kmers, uint64_t* n_kmers);
+int cblx_list_to_file(cblx_ctx* ctx, const char* path, uint64_t chunk_kmers, uint64_t* n_kmers);   /* create / truncate, then the above */
+/* CBL::buckets_nodes (src/cbl.rs:386-390): per non-empty prefix ascending, TrieVec::count_nodes (src/trievec/mod.rs:37-42) — a Vec's length, a Trie's
+ * nodes (src/trie.rs:90-102: the root and one node per distinct proper byte prefix of its suffixes). Pairs with cblx_bucket_sizes. */
+int cblx_bucket_nodes(cblx_ctx* ctx, uint64_t* nodes, uint64_t cap, uint64_t* n);
 /* Bucket table only (CBL::buckets_sizes src/cbl.rs:370-373 and the statistics built on it): per non-empty prefix in
  * ascending order its value, the bucket's length and kind (0 = Vec, 1 = Trie). Any of the arrays may be NULL. */
 int cblx_bucket_sizes(cblx_ctx* ctx, uint32_t* prefix, uint32_t* len, uint8_t* kind, uint64_t cap, uint64_t* n);

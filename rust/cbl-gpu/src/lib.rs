@@ -370,6 +370,26 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         let total = self.count() as f64;
         self.buckets_size_count().into_iter().map(|(size, n)| (size, (size * n) as f64 / total)).collect()
     }
+
+    /// The prefixes of the set with the node counts of their buckets (`src/cbl.rs:386-390`): a Vec bucket counts its words, a Trie
+    /// bucket its nodes (`TrieVec::count_nodes`), computed on the device.
+    pub fn buckets_nodes(&self) -> impl Iterator<Item = (usize, usize)> + '_ {
+        let (prefix, _) = self.bucket_table();
+        let mut nodes = vec![0u64; prefix.len()];
+        let mut got = 0u64;
+        self.check(unsafe { sys::cblx_bucket_nodes(self.ctx, nodes.as_mut_ptr(), nodes.len() as u64, &mut got) });
+        nodes.truncate(got as usize);
+        prefix.into_iter().zip(nodes).map(|(p, n)| (p as usize, n as usize))
+    }
+
+    /// Number of buckets for each node count (`src/cbl.rs:392-396`).
+    pub fn buckets_node_count(&self) -> BTreeMap<usize, usize> {
+        let mut m = BTreeMap::new();
+        for (_, nodes) in self.buckets_nodes() {
+            *m.entry(nodes).or_insert(0usize) += 1;
+        }
+        m
+    }
 }
 
 impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> Default for CBL<K, T, PREFIX_BITS> {
