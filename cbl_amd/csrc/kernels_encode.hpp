@@ -489,11 +489,16 @@ __global__ __launch_bounds__(ENC_THREADS) void k_encode(BaseView B, u64 total_ba
             }
         };
         if (uniform) {
+            // Chunk ci, position j in it, first base cs and first k-mer koff of the chunk are carried from trip to trip, their products taken
+            // once: a trip moves on by ENC_THREADS = dci * nk0 + dj k-mers, that is dci chunks and dj positions, and one chunk more where j
+            // wraps (dj < nk0: at most once). (A walk `while (j >= nk0)` ran 256 / nk0 times per k-mer, and every lane as often as the slowest.)
+            const u32 dci = ENC_THREADS / nk0, dj = ENC_THREADS - dci * nk0, dcs = dci * len0, dkoff = dci * nk0;
             u32 ci = tid / nk0, j = tid - ci * nk0;
+            u32 cs = cs0 + ci * len0, koff = ci * nk0;
             for (u32 q = tid; q < Q; q += ENC_THREADS) {
-                body(q, ci, cs0 + ci * len0, j, ci * nk0);
-                j += ENC_THREADS;
-                while (j >= nk0) { j -= nk0; ++ci; }
+                body(q, ci, cs, j, koff);
+                j += dj; ci += dci; cs += dcs; koff += dkoff;
+                if (j >= nk0) { j -= nk0; ++ci; cs += len0; koff += nk0; }
             }
         } else {
             u32 ci = tid < Q ? find_chunk(tid) : 0u;

@@ -1,5 +1,5 @@
 // dev: issue cost of the 64-bit integer VALU instructions the necklace code leans on (v_lshlrev_b64, v_cmp_*_u64) against
-// 32-bit ones (v_alignbit_b32, v_lshlrev_b32, v_and_b32) on gfx950. Every wave runs N iterations of 8 independent chains;
+// 32-bit ones (v_alignbit_b32, v_lshlrev_b32, v_and_b32), the three-input logic operations and the integer multiplies on gfx950. Every wave runs N iterations of 8 independent chains;
 // the table prints cycles per wave-instruction at full occupancy (8 waves per SIMD).
 // Build + run on the GPU box: hipcc --offload-arch=gfx950 -O3 -o tools/dev_valu_rate.bin tools/dev_valu_rate.cpp && tools/dev_valu_rate.bin
 #include <hip/hip_runtime.h>
@@ -25,6 +25,11 @@ template <int MODE> __global__ __launch_bounds__(256) void k(uint64_t* out, uint
             if (MODE == 7) { asm volatile("v_lshl_add_u64 %0, %0, 2, %1" : "+v"(a[j]) : "v"(a[(j + 1) % CH])); }
             if (MODE == 8) { asm volatile("v_ffbh_u32 %0, %1" : "=v"(b[j]) : "v"(c[j])); }
             if (MODE == 9) { asm volatile("v_bfe_u32 %0, %1, 3, 8" : "=v"(b[j]) : "v"(c[j])); }
+            if (MODE == 10) { asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0xa8" : "+v"(b[j]) : "v"(c[j]), "v"(c[(j + 1) % CH])); }
+            if (MODE == 11) { asm volatile("v_mul_lo_u32 %0, %0, %1" : "+v"(b[j]) : "v"(c[j])); }
+            if (MODE == 12) { asm volatile("v_or_b32 %0, %0, %1\n v_and_b32 %0, %0, %2" : "+v"(b[j]) : "v"(c[j]), "v"(c[(j + 1) % CH])); }
+            if (MODE == 13) { asm volatile("v_and_or_b32 %0, %0, %1, %2" : "+v"(b[j]) : "v"(c[j]), "v"(c[(j + 1) % CH])); }
+            if (MODE == 14) { asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(a[j]) : "v"(b[j]), "v"(c[j]) : "vcc"); }
         }
     }
     uint64_t s = 0;
@@ -57,5 +62,6 @@ template <int MODE> int run(const char* name, int per_iter) {
 int main() {
     run<0>("v_lshlrev_b64", 1); run<1>("v_lshrrev_b64", 1); run<2>("v_alignbit_b32", 1); run<3>("v_lshlrev_b32", 1); run<4>("v_and_b32", 1);
     run<5>("v_cmp_lt_u64 + v_cndmask_b32", 2); run<6>("v_cmp_lt_u32 + v_cndmask_b32", 2); run<7>("v_lshl_add_u64", 1); run<8>("v_ffbh_u32", 1); run<9>("v_bfe_u32", 1);
+    run<10>("v_bitop3_b32", 1); run<11>("v_mul_lo_u32", 1); run<12>("v_or_b32 + v_and_b32", 2); run<13>("v_and_or_b32", 1); run<14>("v_mad_u64_u32", 1);
     return 0;
 }
