@@ -283,13 +283,37 @@ template <typename OutT> u64 exclusive_scan(cblx_ctx* c, const u32* in, u64 n, O
 }
 
 // column prefixes + column totals of counts[tile][256] (see k_colscan_*); nt_dev (device) overrides nt_upper when set
-void colscan(cblx_ctx* c, const u32* counts, const u32* nt_dev, u32 nt_upper, u32* colpre, u32* coltot, Buf<u32>& scratch) {
-    const u32 nchunks = (u32)std::max<u64>(1, ceil_div(nt_upper, COLSCAN_ROWS));
+// (rows: rows of the matrix per chunk = per workgroup of the reduce and apply kernels)
+void colscan(cblx_ctx* c, const u32* counts, const u32* nt_dev, u32 nt_upper, u32* colpre, u32* coltot, Buf<u32>& scratch, u32 rows = COLSCAN_ROWS) {
+    const u32 nchunks = (u32)std::max<u64>(1, ceil_div(nt_upper, rows));
     if (scratch.n < (size_t)nchunks * 256) scratch = Buf<u32>(c->pool, (size_t)nchunks * 256);
-    hipLaunchKernelGGL(k_colscan_reduce, dim3(nchunks), dim3(256), 0, c->stream, counts, nt_dev, nt_upper, scratch.get());
+    hipLaunchKernelGGL(k_colscan_reduce, dim3(nchunks), dim3(256), 0, c->stream, counts, nt_dev, nt_upper, scratch.get(), rows);
     hipLaunchKernelGGL(k_colscan_spine, dim3(1), dim3(256), 0, c->stream, scratch.get(), nchunks, coltot);
-    hipLaunchKernelGGL(k_colscan_apply, dim3(nchunks), dim3(256), 0, c->stream, counts, nt_dev, nt_upper, scratch.get(), colpre);
+    hipLaunchKernelGGL(k_colscan_apply, dim3(nchunks), dim3(256), 0, c->stream, counts, nt_dev, nt_upper, scratch.get(), colpre, rows);
 }
+
+// The two-level form of the same (colprefix.hpp): the buffers of one partition, sized for an upper bound of the tile count. A producer
+// (k_radix_hist_bytes, k_colscan_sup) fills `local` and `sup`; scan() runs the flat column scan over the 16 x smaller `sup` and leaves
+// sup_pre + coltot; view() is what the scatter, k_seg_adjust and k_dir_gather read through.
+struct SupPrefix {
+    Buf<u16> local;
+    Buf<u32> sup, sup_pre, nst_dev, scratch;
+    void reserve(cblx_ctx* c, u32 nt_upper) {
+        const size_t nst = std::max<size_t>(1, sup_count(nt_upper));
+        if (local.n >= nst * SUP_TILES * 256) return;
+        local = Buf<u16>(c->pool, nst * SUP_TILES * 256);
+        sup = Buf<u32>(c->pool, nst * 256);
+        sup_pre = Buf<u32>(c->pool, nst * 256);
+        if (!nst_dev.get()) nst_dev = Buf<u32>(c->pool, 1);
+    }
+    // nst_on_device: the producer wrote the number of super-tiles to nst_dev (tile count known on the device only)
+    // (chunks of SUP_SCAN_ROWS rows: at the flat scan's 1024 the 18 K super-tiles of 1.2 G records would be walked by 18 workgroups)
+    static constexpr u32 SUP_SCAN_ROWS = 128;
+    void scan(cblx_ctx* c, bool nst_on_device, u32 nt_upper, u32* coltot) {
+        colscan(c, sup.get(), nst_on_device ? nst_dev.get() : nullptr, sup_count(nt_upper), sup_pre.get(), coltot, scratch, SUP_SCAN_ROWS);
+    }
+    ColPre view() const { return ColPre(local.get(), sup_pre.get()); }
+};
 
 // ---- template configuration ------------------------------------------------------------------------------
 template <bool WIDE_, typename HiT_, bool WS_> struct Cfg {

@@ -13,6 +13,7 @@
 #pragma once
 #include <type_traits>
 
+#include "colprefix.hpp"
 #include "cuts.hpp"
 #include "kernels_encode.hpp"
 
@@ -200,6 +201,7 @@ __device__ __forceinline__ void tile_rank_packed(u32 (&dp)[ITEMS], u32* s_wcnt, 
 static const int RDX_THREADS = 512;
 static const int RDX_ITEMS = 8;
 static const int RDX_TILE = RDX_THREADS * RDX_ITEMS;  // 4096 records per workgroup
+static_assert((u32)RDX_TILE == SUP_TILE_RECORDS, "colprefix.hpp sizes its 16-bit local prefixes for this tile");
 
 // digit of a record: a bit field of the word (LSD passes) ...
 struct DigitBits {
@@ -333,6 +335,19 @@ __device__ __forceinline__ bool tile_get(const TileView& tv, u32 b, u32& tile, u
     }
     return true;
 }
+// the same for a TILE index (no workgroup map): where tile `tile` < ntiles starts and what it holds
+__device__ __forceinline__ void tile_at(const TileView& tv, u32 tile, u64& tbase, u32& n_tile) {
+    if (tv.start64) {
+        tbase = tv.start64[tile];
+        n_tile = tv.count[tile];
+    } else if (tv.start) {
+        tbase = tv.start[tile];
+        n_tile = tv.count[tile];
+    } else {
+        tbase = (u64)tile * RDX_TILE;
+        n_tile = (u32)((tv.n - tbase) < (u64)RDX_TILE ? (tv.n - tbase) : (u64)RDX_TILE);
+    }
+}
 
 // per-tile digit histogram -> counts[tile * 256 + digit] (tile-major: one coalesced 1 KiB row per workgroup).
 // Counting needs no ranks: per-wave private LDS histograms fed by non-returning ds_add (the ballot matching of
@@ -373,65 +388,100 @@ __global__ __launch_bounds__(RDX_THREADS) void k_radix_hist(const u64* __restric
     }
 }
 
-// The same histogram from the DIGIT SIDE CHANNEL the previous pass's scatter left behind (dig[i] = this pass's digit
-// of record i): 1 byte per record is read instead of the whole record. A thread takes one aligned 8-byte word of the
-// tile's byte range (RDX_THREADS * 8 = RDX_TILE bytes, plus one word for an unaligned start).
-static const int HISTB_WAVES = 4;  // tiles per workgroup of k_radix_hist_bytes
-__global__ __launch_bounds__(64 * HISTB_WAVES) void k_radix_hist_bytes(const u8* __restrict__ dig, TileView tv, u32* __restrict__ counts) {
-    // one WAVE per tile (no workgroup barrier): a lane takes every 64th aligned 8-byte word of the tile's byte range.
-    // Two private counter sets per wave (even / odd lanes) halve the same-address serialisation of the LDS atomics
-    // (four sets measured the same).
-    __shared__ u32 s_cnt[HISTB_WAVES * 512];
-    const u32 w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    u32* my = s_cnt + w * 512;
+// Tile histograms from the DIGIT SIDE CHANNEL the previous pass's scatter left behind (dig[i] = this pass's digit of record i: 1 byte
+// per record is read instead of the whole record), delivered as two-level column prefixes (colprefix.hpp): one workgroup per
+// SUPER-TILE, one WAVE per tile (no barrier while counting): a lane takes every 64th aligned 8-byte word of the tile's byte range. Two
+// private counter sets per wave (even / odd lanes) halve the same-address serialisation of the LDS atomics (four sets measured the
+// same). The 16 count rows never leave LDS: thread d scans column d over them, the exclusive prefixes go out as the 16 u16 `local`
+// rows (512 B each, contiguous), the column sums as the super-tile's `sup` row. The grid is sized for the upper bound of the tile
+// count; nst_dev (may be null) receives the number of super-tiles for the scan of `sup`.
+__global__ __launch_bounds__(64 * SUP_TILES) void k_radix_hist_bytes(const u8* __restrict__ dig, TileView tv, u16* __restrict__ local, u32* __restrict__ sup,
+                                                                     u32* __restrict__ nst_dev) {
+    constexpr u32 WS = 512;  // per wave: two counter sets (even / odd lanes)
+    __shared__ u32 s_cnt[SUP_TILES * WS];
+    const u32 tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    u32* my = s_cnt + w * WS;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) my[k * 64 + lane] = 0;
-    u32 tile, n_tile, seg;
-    u64 tbase;
-    // tile_get maps a WORKGROUP index to a tile (XCD-aware); here the unit is the wave
-    if (!tile_get(tv, blockIdx.x * HISTB_WAVES + w, tile, tbase, n_tile, seg)) return;
-    __builtin_amdgcn_wave_barrier();
-    u32* mine = my + (lane & 1u) * 256;
-    const u64 w0 = tbase >> 3, wend = (tbase + n_tile + 7) >> 3;  // aligned words covering [tbase, tbase + n_tile)
-    const u64* __restrict__ words = reinterpret_cast<const u64*>(dig);
-    // a tile spans at most RDX_TILE / 8 + 1 aligned words = 8 full rounds of the wave + one word: all loads are issued
-    // before the first counter update (one load -> 8 LDS atomics -> next load left the wave latency-bound)
-    constexpr int ROUNDS = RDX_TILE / 512 + 1;
-    u64 v[ROUNDS];
+    for (u32 k = 0; k < WS / 64; ++k) my[k * 64 + lane] = 0;
+    const u32 nt = tv.ntiles_dev ? *tv.ntiles_dev : tv.ntiles;
+    const u32 st = blockIdx.x;
+    if (st == 0 && tid == 0 && nst_dev) *nst_dev = sup_count(nt);
+    const u32 rows = sup_rows(st, nt);  // workgroup-uniform
+    if (rows == 0) return;
+    const u32 tile = st * SUP_TILES + w;
+    if (w < rows) {
+        u64 tbase;
+        u32 n_tile;
+        tile_at(tv, tile, tbase, n_tile);
+        __builtin_amdgcn_wave_barrier();
+        u32* mine = my + (lane & 1u) * 256;
+        const u64 w0 = tbase >> 3, wend = (tbase + n_tile + 7) >> 3;  // aligned words covering [tbase, tbase + n_tile)
+        const u64* __restrict__ words = reinterpret_cast<const u64*>(dig);
+        // at most RDX_TILE / 8 + 1 aligned words = 8 full rounds of the wave + one word; all loads before the first counter update
+        constexpr int ROUNDS = RDX_TILE / 512 + 1;
+        u64 v[ROUNDS];
 #pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        const u64 wi = w0 + lane + (u64)r * 64;
-        v[r] = wi < wend ? words[wi] : 0ull;
-    }
+        for (int r = 0; r < ROUNDS; ++r) {
+            const u64 wi = w0 + lane + (u64)r * 64;
+            v[r] = wi < wend ? words[wi] : 0ull;
+        }
 #pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        const u64 wi = w0 + lane + (u64)r * 64;
-        if (wi < wend) {
-            const u64 b0 = wi << 3;
-            if (b0 >= tbase && b0 + 8 <= tbase + n_tile) {  // whole word inside the tile (all but the first and last)
+        for (int r = 0; r < ROUNDS; ++r) {
+            const u64 wi = w0 + lane + (u64)r * 64;
+            if (wi < wend) {
+                const u64 b0 = wi << 3;
+                if (b0 >= tbase && b0 + 8 <= tbase + n_tile) {  // whole word inside the tile (all but the first and last)
 #pragma unroll
-                for (int k = 0; k < 8; ++k) atomicAdd(&mine[(u32)(v[r] >> (8 * k)) & 255u], 1u);
-            } else {
+                    for (int k = 0; k < 8; ++k) atomicAdd(&mine[(u32)(v[r] >> (8 * k)) & 255u], 1u);
+                } else {
 #pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const u64 pos = b0 + k;
-                    if (pos >= tbase && pos < tbase + n_tile) atomicAdd(&mine[(u32)(v[r] >> (8 * k)) & 255u], 1u);
+                    for (int k = 0; k < 8; ++k) {
+                        const u64 pos = b0 + k;
+                        if (pos >= tbase && pos < tbase + n_tile) atomicAdd(&mine[(u32)(v[r] >> (8 * k)) & 255u], 1u);
+                    }
                 }
             }
         }
     }
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
+    __syncthreads();
+    if (tid < 256) {  // column tid over the rows (a missing row of a ragged super-tile counted nothing); the prefixes replace the counts
+        const u32 tot = sup_scan_column(SUP_TILES, [&](u32 r) { return s_cnt[r * WS + tid] + s_cnt[r * WS + 256 + tid]; },
+                                        [&](u32 r, u16 p) { s_cnt[r * WS + tid] = p; });
+        sup[(u64)st * 256 + tid] = tot;
+    }
+    __syncthreads();
+    u32* __restrict__ out = reinterpret_cast<u32*>(local + (u64)st * SUP_TILES * 256);  // row r = 128 dwords of two prefixes
+    for (u32 i = tid; i < rows * 128; i += 64 * SUP_TILES) {
+        const u32 r = i >> 7, c = (i & 127u) * 2;
+        out[i] = s_cnt[r * WS + c] | (s_cnt[r * WS + c + 1] << 16);
+    }
+}
+// The same two levels from a count matrix that exists already (pass A: KRN-1 accumulated it): one workgroup per super-tile reads its
+// 16 rows once; a thread owns two neighbouring columns (8-byte loads, one packed dword of `local` per row).
+__global__ __launch_bounds__(128) void k_colscan_sup(const u32* __restrict__ counts, u32 ntiles, u16* __restrict__ local, u32* __restrict__ sup) {
+    const u32 st = blockIdx.x, t = threadIdx.x;
+    const u32 rows = sup_rows(st, ntiles);
+    if (rows == 0) return;
+    const uint2* __restrict__ in = reinterpret_cast<const uint2*>(counts + (u64)st * SUP_TILES * 256) + t;
+    uint2 v[SUP_TILES];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) counts[(u64)tile * 256 + k * 64 + lane] = my[k * 64 + lane] + my[256 + k * 64 + lane];
+    for (u32 r = 0; r < SUP_TILES; ++r) v[r] = r < rows ? in[(u64)r * 128] : uint2{0u, 0u};
+    u32* __restrict__ out = reinterpret_cast<u32*>(local + (u64)st * SUP_TILES * 256) + t;
+    u32 p0[SUP_TILES], p1[SUP_TILES];
+    const u32 t0 = sup_scan_column(SUP_TILES, [&](u32 r) { return v[r].x; }, [&](u32 r, u16 p) { p0[r] = p; });
+    const u32 t1 = sup_scan_column(SUP_TILES, [&](u32 r) { return v[r].y; }, [&](u32 r, u16 p) { p1[r] = p; });
+#pragma unroll
+    for (u32 r = 0; r < SUP_TILES; ++r)
+        if (r < rows) out[(u64)r * 128] = p0[r] | (p1[r] << 16);
+    reinterpret_cast<uint2*>(sup + (u64)st * 256)[t] = uint2{t0, t1};
 }
 
-// scatter. colpre[tile * 256 + d] = records with digit d in earlier tiles (pure column prefix); adj[seg * 256 + d] turns it
+// scatter. colpre[tile * 256 + d] = records with digit d in earlier tiles (pure column prefix: flat or two-level, colprefix.hpp); adj[seg * 256 + d] turns it
 // into a global position (k_seg_adjust). OutHiT = NoHi drops the hi part on the way out (first pass of 65..72-bit words:
 // the bits it held are implied by the segment from then on).
 template <typename HiT, typename OutHiT, typename DigitFn, bool REDIR = false>
 __global__ __launch_bounds__(RDX_THREADS, (HiTraits<HiT>::has && HiTraits<OutHiT>::has) ? 4 : 8) void k_radix_scatter(const u64* __restrict__ lo, const HiT* __restrict__ hi, TileView tv,
-                                                               DigitFn dfn, const u32* __restrict__ colpre,
+                                                               DigitFn dfn, const ColPre colpre,
                                                                const u32* __restrict__ adj, u64* __restrict__ out_lo,
                                                                OutHiT* __restrict__ out_hi, DigitBits next_dfn = DigitBits{0, 0},
                                                                u8* __restrict__ out_next = nullptr, u32* __restrict__ start_dense = nullptr,
@@ -494,8 +544,9 @@ __global__ __launch_bounds__(RDX_THREADS, (HiTraits<HiT>::has && HiTraits<OutHiT
     if (tid < 256) {
         // seg_base: adj is relative to the segment's own start and may be "negative" (the column prefix counts the digit in
         // the tiles of EARLIER segments too): 32-bit modular arithmetic, sign-extended (a segment is shorter than 2^31)
-        if (seg_base) s_gbase[tid] = seg_base[seg] + (u64)(long long)(int)(adj[(u64)seg * 256 + tid] + colpre[(u64)tile * 256 + tid] - s_dbase[tid]);
-        else s_gbase[tid] = (u64)adj[(u64)seg * 256 + tid] + colpre[(u64)tile * 256 + tid] - s_dbase[tid];
+        const u32 a = adj[(u64)seg * 256 + tid], cp = colpre_at(colpre, tile, tid);  // all loads issued before the first is waited for
+        if (seg_base) s_gbase[tid] = seg_base[seg] + (u64)(long long)(int)(a + cp - s_dbase[tid]);
+        else s_gbase[tid] = (u64)a + cp - s_dbase[tid];
     }
     __syncthreads();  // every wave is done with the rank counters before records are staged over them
     u32 g_first = 0;
@@ -582,14 +633,16 @@ __global__ void k_dir_resolve(const u32* __restrict__ ntiles_dev, u32 amb_stride
 // ------------------------------------------------------------------------------------------------
 // Column prefixes of the tile-major count matrix C[tile][256]: P[tile][d] = sum_{t' < tile} C[t'][d], and the column
 // totals. Every access is a coalesced 1 KiB row (thread d owns column d); rows are cut into chunks of COLSCAN_ROWS for
-// parallelism. k_seg_adjust then supplies, per segment, what must be added to P to get a global position.
+// parallelism (`rows` per chunk: COLSCAN_ROWS for the full-size matrices; the 16 x smaller matrix of super-tile sums takes shorter
+// chunks, or a handful of workgroups would walk it row by row). k_seg_adjust then supplies, per segment, what must be added to P to
+// get a global position.
 static const u32 COLSCAN_ROWS = 1024;
 __device__ __forceinline__ u32 dev_ntiles(const u32* ntiles_dev, u32 ntiles) { return ntiles_dev ? *ntiles_dev : ntiles; }
 __global__ __launch_bounds__(256) void k_colscan_reduce(const u32* __restrict__ counts, const u32* ntiles_dev, u32 ntiles,
-                                                        u32* __restrict__ chunk_sums) {
+                                                        u32* __restrict__ chunk_sums, u32 rows = COLSCAN_ROWS) {
     const u32 nt = dev_ntiles(ntiles_dev, ntiles);
-    const u32 d = threadIdx.x, r0 = blockIdx.x * COLSCAN_ROWS;
-    const u32 r1 = r0 + COLSCAN_ROWS < nt ? r0 + COLSCAN_ROWS : nt;
+    const u32 d = threadIdx.x, r0 = blockIdx.x * rows;
+    const u32 r1 = r0 + rows < nt ? r0 + rows : nt;
     u32 s = 0;
 #pragma unroll 8
     for (u32 r = r0; r < r1; ++r) s += counts[(u64)r * 256 + d];
@@ -607,10 +660,10 @@ __global__ __launch_bounds__(256) void k_colscan_spine(u32* __restrict__ chunk_s
     coltot[d] = run;
 }
 __global__ __launch_bounds__(256) void k_colscan_apply(const u32* __restrict__ counts, const u32* ntiles_dev, u32 ntiles,
-                                                       const u32* __restrict__ chunk_sums, u32* __restrict__ colpre) {
+                                                       const u32* __restrict__ chunk_sums, u32* __restrict__ colpre, u32 rows = COLSCAN_ROWS) {
     const u32 nt = dev_ntiles(ntiles_dev, ntiles);
-    const u32 d = threadIdx.x, r0 = blockIdx.x * COLSCAN_ROWS;
-    const u32 r1 = r0 + COLSCAN_ROWS < nt ? r0 + COLSCAN_ROWS : nt;
+    const u32 d = threadIdx.x, r0 = blockIdx.x * rows;
+    const u32 r1 = r0 + rows < nt ? r0 + rows : nt;
     u32 run = chunk_sums[(u64)blockIdx.x * 256 + d];
 #pragma unroll 8
     for (u32 r = r0; r < r1; ++r) {
@@ -622,7 +675,7 @@ __global__ __launch_bounds__(256) void k_colscan_apply(const u32* __restrict__ c
 // One workgroup per segment s (tiles [first[s], first[s+1]), records from seg_start[s]):
 //   adj[s][d] = seg_start[s] + (records of the segment with a smaller digit) - P[first[s]][d]
 // so that adj[s][d] + P[tile][d] is where tile's first record with digit d goes. A plain pass is the case of one segment.
-__global__ __launch_bounds__(256) void k_seg_adjust(const u32* __restrict__ colpre, const u32* __restrict__ coltot,
+__global__ __launch_bounds__(256) void k_seg_adjust(const ColPre colpre, const u32* __restrict__ coltot,
                                                     const u32* __restrict__ seg_first /* nseg+1, null: {0, ntiles} */,
                                                     const u32* __restrict__ seg_start /* nseg, null: {0} */, const u32* ntiles_dev,
                                                     u32 ntiles, u32 nseg, u32* __restrict__ adj, u32* __restrict__ grp_start = nullptr) {
@@ -630,8 +683,8 @@ __global__ __launch_bounds__(256) void k_seg_adjust(const u32* __restrict__ colp
     const u32 nt = dev_ntiles(ntiles_dev, ntiles);
     const u32 s = blockIdx.x, d = threadIdx.x;
     const u32 f0 = seg_first ? seg_first[s] : 0u, f1 = seg_first ? seg_first[s + 1] : nt;
-    const u32 p0 = f0 < nt ? colpre[(u64)f0 * 256 + d] : coltot[d];
-    const u32 p1 = f1 < nt ? colpre[(u64)f1 * 256 + d] : coltot[d];
+    const u32 p0 = f0 < nt ? colpre_at(colpre, f0, d) : coltot[d];
+    const u32 p1 = f1 < nt ? colpre_at(colpre, f1, d) : coltot[d];
     const u32 ex = block_exclusive_scan<256, u32>(p1 - p0, sm, nullptr);
     adj[(u64)s * 256 + d] = (seg_start ? seg_start[s] : 0u) + ex - p0;
     // where digit d of segment s starts after this pass: the (segment, digit) GROUPS the next pass may cut its tiles at
@@ -722,7 +775,7 @@ __global__ void k_tile_table_grp(u32 G, u32 low_bits, const u32* __restrict__ gr
 // column prefixes: the bucket starts where the group's first tile puts its digit-d records and holds what the group's
 // tiles count for d. One workgroup per group, one thread per digit value.
 __global__ __launch_bounds__(256) void k_dir_gather(u32 low_bits, u32 last_bits, const u32* __restrict__ grp_first, const u32* __restrict__ seg_start,
-                                                    const u32* __restrict__ ntiles_dev, const u32* __restrict__ colpre, const u32* __restrict__ coltot,
+                                                    const u32* __restrict__ ntiles_dev, const ColPre colpre, const u32* __restrict__ coltot,
                                                     const u32* __restrict__ adj, u32* __restrict__ start_dense, u32 w_lo = 0, u32 w_hi = 0xFFFFFFFFu,
                                                     const u32* __restrict__ seg_prefix = nullptr /* FINE bins: first prefix of the segment's block */) {
     // [w_lo, w_hi): the prefixes this launch owns (a receiver's group works on its window of the prefix space: start_dense is that
@@ -740,8 +793,8 @@ __global__ __launch_bounds__(256) void k_dir_gather(u32 low_bits, u32 last_bits,
         return;
     }
     const u32 f0 = grp_first[g], f1 = grp_first[g + 1];
-    const u32 p0 = f0 < nt ? colpre[(u64)f0 * 256 + d] : coltot[d];
-    const u32 p1 = f1 < nt ? colpre[(u64)f1 * 256 + d] : coltot[d];
+    const u32 p0 = f0 < nt ? colpre_at(colpre, f0, d) : coltot[d];
+    const u32 p1 = f1 < nt ? colpre_at(colpre, f1, d) : coltot[d];
     if (p1 > p0) start_dense[prefix] = adj[s * 256 + d] + p0;
     else if (!seg_prefix) start_dense[prefix] = 0xFFFFFFFFu;
 }

@@ -138,8 +138,12 @@ template <typename C> void partition_and_directory(cblx_ctx* c, Records& rec, u6
         const bool grp_tiles = tbl_dir && low_bits > 0;  // low_bits = 0: the groups are the segments (existing tile table)
         const u32 G = nseg << low_bits, nt_maxC = grp_tiles ? ntiles + G + 256 : nt_max;
         const bool haveA = countsA.get() != nullptr;
-        Buf<u32> counts = haveA ? std::move(countsA) : Buf<u32>(c->pool, (size_t)256 * nt_max);
-        Buf<u32> colpre(c->pool, (size_t)256 * nt_maxC), scratch, coltot(c->pool, 256),
+        Buf<u32> counts = haveA ? std::move(countsA) : (pin ? Buf<u32>() : Buf<u32>(c->pool, (size_t)256 * nt_max));  // pass A's tile histogram
+        // column prefixes: two levels (colprefix.hpp) in pass A and in every LSD pass fed by the digit side channel; an LSD pass that
+        // has to count from the records (pieces that came without their digits) keeps the flat matrix, allocated when it is needed
+        SupPrefix sp;
+        sp.reserve(c, std::max(nt_max, nt_maxC));
+        Buf<u32> colpre, scratch, coltot(c->pool, 256),
             adj(c->pool, 256 * 256), seg_first(c->pool, 257), nt_dev(c->pool, 1), t_start(c->pool, nt_max), t_count(c->pool, nt_max);
         Buf<u16> t_seg(c->pool, nt_max);
         Buf<u32> grp_start, grp_first, seg_firstC, nt_devC, t_startC, t_countC;
@@ -191,8 +195,9 @@ template <typename C> void partition_and_directory(cblx_ctx* c, Records& rec, u6
             if (!haveA) { StageTimer t(c, ST_HIST);
               hipLaunchKernelGGL((k_radix_hist<HiT, DigitBits>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, lo, hi, tv, dfn, counts.get()); }
             { StageTimer t(c, ST_SCAN);
-              colscan(c, counts.get(), nullptr, ntiles, colpre.get(), coltot.get(), scratch);
-              hipLaunchKernelGGL(k_seg_adjust, dim3(1), dim3(256), 0, c->stream, colpre.get(), coltot.get(), (const u32*)nullptr, (const u32*)nullptr,
+              hipLaunchKernelGGL(k_colscan_sup, dim3(std::max(1u, sup_count(ntiles))), dim3(128), 0, c->stream, (const u32*)counts.get(), ntiles, sp.local.get(), sp.sup.get());
+              sp.scan(c, false, ntiles, coltot.get());
+              hipLaunchKernelGGL(k_seg_adjust, dim3(1), dim3(256), 0, c->stream, sp.view(), coltot.get(), (const u32*)nullptr, (const u32*)nullptr,
                                  (const u32*)nullptr, ntiles, 1u, adj.get(), (u32*)nullptr);
               hipLaunchKernelGGL(k_seg_table, dim3(1), dim3(256), 0, c->stream, coltot.get(), seg_start.get(), seg_first.get(), nt_dev.get());
               hipLaunchKernelGGL(k_tile_table, grid1(nt_max, 256), dim3(256), 0, c->stream, seg_start.get(), seg_first.get(), nt_dev.get(), t_start.get(),
@@ -200,15 +205,15 @@ template <typename C> void partition_and_directory(cblx_ctx* c, Records& rec, u6
             { StageTimer t(c, ST_SCATTER);
               c->stages[ST_SCATTER].units += N;  // (records through a partition pass: cblx_stage_units — the passes a record takes vary with the route)
               if constexpr (DROP_HI)
-                  hipLaunchKernelGGL((k_radix_scatter<HiT, NoHi, DigitBits>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, lo, hi, tv, dfn, colpre.get(),
+                  hipLaunchKernelGGL((k_radix_scatter<HiT, NoHi, DigitBits>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, lo, hi, tv, dfn, sp.view(),
                                      adj.get(), lo2, (NoHi*)nullptr, nd, ndp);
               else
-                  hipLaunchKernelGGL((k_radix_scatter<HiT, HiT, DigitBits>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, lo, hi, tv, dfn, colpre.get(),
+                  hipLaunchKernelGGL((k_radix_scatter<HiT, HiT, DigitBits>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, lo, hi, tv, dfn, sp.view(),
                                      adj.get(), lo2, hi2, nd, ndp); }
             have_dig = ndp != nullptr;
             advance();
         }
-        if (counts.n < (size_t)256 * nt_maxC) counts = Buf<u32>(c->pool, (size_t)256 * nt_maxC);
+        counts.reset();  // pass A's count matrix: the LSD passes count in LDS
         const TileView tvL{t_start.get(), t_count.get(), t_seg.get(), nt_dev.get(), nt_max, N};
         const TileView tvC{t_startC.get(), t_countC.get(), t_segC.get(), nt_devC.get(), nt_maxC, N};
         for (u32 pass = 0; pass < npassL; ++pass) {
@@ -224,14 +229,18 @@ template <typename C> void partition_and_directory(cblx_ctx* c, Records& rec, u6
                 H* hout = (H*)hi2;
                 const DigitBits nd = next_digit(pass + 1);
                 u8* ndp = nd.nbits && dig_wr ? dig_wr : nullptr;
+                const bool two_level = have_dig;
+                if (!two_level && colpre.n < (size_t)256 * ntm) { counts = Buf<u32>(c->pool, (size_t)256 * ntm); colpre = Buf<u32>(c->pool, (size_t)256 * ntm); }
+                const ColPre cp = two_level ? sp.view() : ColPre(colpre.get());
                 { StageTimer t(c, ST_HIST);
-                  if (have_dig)
-                      hipLaunchKernelGGL(k_radix_hist_bytes, dim3((xcd_grid(ntm) + HISTB_WAVES - 1) / HISTB_WAVES + 8), dim3(64 * HISTB_WAVES), 0, c->stream, dig_rd, tv, counts.get());
+                  if (two_level)
+                      hipLaunchKernelGGL(k_radix_hist_bytes, dim3(std::max(1u, sup_count(ntm))), dim3(64 * SUP_TILES), 0, c->stream, dig_rd, tv, sp.local.get(), sp.sup.get(), sp.nst_dev.get());
                   else
                       hipLaunchKernelGGL((k_radix_hist<H, DigitBits>), dim3(xcd_grid(ntm)), dim3(RDX_THREADS), 0, c->stream, lo, hin, tv, dfn, counts.get()); }
                 { StageTimer t(c, ST_SCAN);
-                  colscan(c, counts.get(), ntd, ntm, colpre.get(), coltot.get(), scratch);
-                  hipLaunchKernelGGL(k_seg_adjust, dim3(nseg), dim3(256), 0, c->stream, colpre.get(), coltot.get(), sf, seg_start.get(), ntd, ntm, nseg, adj.get(),
+                  if (two_level) sp.scan(c, true, ntm, coltot.get());
+                  else colscan(c, counts.get(), ntd, ntm, colpre.get(), coltot.get(), scratch);
+                  hipLaunchKernelGGL(k_seg_adjust, dim3(nseg), dim3(256), 0, c->stream, cp, coltot.get(), sf, seg_start.get(), ntd, ntm, nseg, adj.get(),
                                      (grp_tiles && pass + 2 == npassL) ? grp_start.get() : (u32*)nullptr);
                   if (grp_tiles && pass + 2 == npassL) {  // the next pass is the last one: cut its tiles at the groups this pass creates
                       hipLaunchKernelGGL(k_grp_table, dim3(1), dim3(1024), 0, c->stream, G, low_bits, grp_start.get(), seg_start.get(), (u32)N, grp_first.get(), seg_firstC.get(),
@@ -249,7 +258,7 @@ template <typename C> void partition_and_directory(cblx_ctx* c, Records& rec, u6
                 }
                 { StageTimer t(c, ST_SCATTER);
                   c->stages[ST_SCATTER].units += N;
-                  hipLaunchKernelGGL((k_radix_scatter<H, H, DigitBits>), dim3(xcd_grid(ntm)), dim3(RDX_THREADS), 0, c->stream, lo, hin, tv, dfn, colpre.get(),
+                  hipLaunchKernelGGL((k_radix_scatter<H, H, DigitBits>), dim3(xcd_grid(ntm)), dim3(RDX_THREADS), 0, c->stream, lo, hin, tv, dfn, cp,
                                      adj.get(), lo2, hout, nd, ndp, fused_dir ? sd : (u32*)nullptr, SBs, RB, low_bits, amb.get(), amb_stride,
                                      OwnWindow{0, 0, nullptr, nullptr, nullptr}, (const u64*)nullptr, segp); }
                 if (fused_dir) {
@@ -273,7 +282,7 @@ template <typename C> void partition_and_directory(cblx_ctx* c, Records& rec, u6
                     // FINE bins: the segments' blocks need not cover the window (the last group's reaches up to 2^PREFIX_BITS, its bins do not)
                     if (fine) CBLX_HIP(hipMemsetAsync(start_dense.get(), 0xFF, nsuper * 4, c->stream));
                     hipLaunchKernelGGL(k_dir_gather, dim3(G), dim3(256), 0, c->stream, low_bits, last_bits, grp_tiles ? grp_first.get() : seg_first.get(), seg_start.get(), ntd,
-                                       colpre.get(), coltot.get(), adj.get(), sd, sw_lo, win ? (u32)std::min<u64>(sw_hi, 0xFFFFFFFFull) : 0xFFFFFFFFu, segp);
+                                       cp, coltot.get(), adj.get(), sd, sw_lo, win ? (u32)std::min<u64>(sw_hi, 0xFFFFFFFFull) : 0xFFFFFFFFu, segp);
                     if (grp_tiles)  // cold segments kept plain tiles: their boundaries come from their (few) records, now in lo2
                         hipLaunchKernelGGL(k_boundaries_cold<H>, dim3(nseg, 32), dim3(256), 0, c->stream, (const u64*)lo2, (const H*)hout, SBs, RB, seg_start.get(), sd, segp);
                     have_dense = true;
