@@ -15,7 +15,7 @@
 #include <cstdio>
 
 #include "fastx_parse.hpp"
-#include "pipeline.hpp"
+#include "setops.hpp"
 
 namespace {
 

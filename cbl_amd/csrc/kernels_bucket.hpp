@@ -225,10 +225,14 @@ struct MergeArgs {
     const u64* s_lo = nullptr; const u64* s_hi = nullptr; const u64* sstart = nullptr;
 };
 
-__global__ void k_bv_or(u64 nwords, const u64* __restrict__ a, const u64* __restrict__ b, u64* __restrict__ out, u32* __restrict__ popc) {
+// The set operations (= CBLX_SETOP_* of include/cblx.h) and the candidate prefixes of their result, word by word of the two bitvectors: AND needs both
+// sides, SUB needs a's (what only b holds yields nothing), OR / XOR either. OR is also the directory of `self |= other` and of a batch merged into a
+// resident index.
+static const u32 SETOP_OR = 0, SETOP_AND = 1, SETOP_SUB = 2, SETOP_XOR = 3;
+__global__ void k_setop_bv(u64 nwords, const u64* __restrict__ a, const u64* __restrict__ b, u32 op, u64* __restrict__ out, u32* __restrict__ popc) {
     const u64 w = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= nwords) return;
-    const u64 v = a[w] | b[w];
+    const u64 v = op == SETOP_AND ? (a[w] & b[w]) : op == SETOP_SUB ? a[w] : (a[w] | b[w]);
     out[w] = v;
     popc[w] = (u32)__builtin_popcountll(v);
 }
@@ -335,919 +339,6 @@ __global__ __launch_bounds__(CLASSIFY_THREADS) void k_classify_merge(u64 nb, u32
         __syncthreads();
         if (threadIdx.x <= CLS_N && s_cw[threadIdx.x]) atomicAdd(&cls_words[threadIdx.x], s_cw[threadIdx.x]);
     }
-}
-
-// ---- Trie |= Trie: the union of two ASCENDING lists is a merge, not a sort (/root/reference/src/trievec/set_ops.rs:43-71 merges two
-// sorted iterators with two pointers; src/trievec/mod.rs:118-136 inserts what self lacks) ------------------------------------------------
-// One workgroup per bucket, any length. Rounds of UNI_TILE outputs: the next <= UNI_TILE words of either list are staged in LDS
-// (coalesced loads from the two indexes' own arenas — the merged run is written, never read), every thread finds the co-rank of the
-// END of its UNI_ITEMS consecutive outputs by a binary search on the round's diagonal (merge path; ties take self's copy first) and gets
-// its start from its neighbour, loads n + n candidates into registers and merges them with a fixed network — min(a[k], b[n-1-k]) leaves
-// the n smallest as a bitonic sequence, log2 n compare-exchange stages sort it — so no lane follows data-dependent control flow. The
-// outputs go back to LDS (one padding word per 8: a lane's 64-byte row would otherwise hit the banks of its neighbours'), are
-// compared with their predecessor there (equal = other's copy of a word self holds: dropped) and leave compacted in order. The
-// co-rank of the round's last output says how far either list was consumed. HBM traffic: every word read once (the staging areas are
-// rings since round 5: a round refills only the slots it consumed — see the kernel), the union written once.
-// Workgroup shape, measured on cfg 5's share (`bench.py --config merge`, stage bucket_big) / at the 8-GPU depth of cfg 5 (`tools/emulate_rank.py --merge`:
-// 752 M + 752 M words in buckets of 10 635 each): 256 threads x 8 outputs 3.18 / 9.4 ms, 128 x 8 3.09, 256 x 4 2.14 / 6.3, **128 x 4 2.07 / 6.2**, 256 x 2 2.53 — half the registers
-// (a[], b[], o[]), half the merge network and a shorter search per round buy more than the extra rounds cost; padding one word per 4 instead of 8: 2.33 / 6.7.
-static const int UNI_THREADS = 128, UNI_ITEMS = 4, UNI_TILE = UNI_THREADS * UNI_ITEMS;
-__device__ __forceinline__ u32 uni_pad(u32 i) { return i + (i >> 3); }
-// An element of a union: the suffix alone — one u64, or (hi, lo) for suffixes wider than 64 bits (round 5: those took the sorting
-// classes whatever their kinds; the rings hold their two halves in two arrays of the same shape).
-template <bool WS> struct UniE;
-template <> struct UniE<false> { u64 lo; };
-template <> struct UniE<true> { u64 lo, hi; };
-template <bool WS> __device__ __forceinline__ bool uni_lt(const UniE<WS>& a, const UniE<WS>& b) {
-    if constexpr (WS) return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo);
-    else return a.lo < b.lo;
-}
-template <bool WS> __device__ __forceinline__ bool uni_eq(const UniE<WS>& a, const UniE<WS>& b) {
-    if constexpr (WS) return a.lo == b.lo && a.hi == b.hi;
-    else return a.lo == b.lo;
-}
-template <bool WS> __device__ __forceinline__ UniE<WS> uni_inf() {
-    UniE<WS> e;
-    e.lo = ~0ull;
-    if constexpr (WS) e.hi = ~0ull;
-    return e;
-}
-// (selects word by word: a select between two structs sends the arrays they sit in to scratch memory — 224 bytes per lane and 1.4 TB/s
-//  as first written)
-template <bool WS> __device__ __forceinline__ UniE<WS> uni_sel(bool take_a, const UniE<WS>& a, const UniE<WS>& b) {
-    UniE<WS> e;
-    e.lo = take_a ? a.lo : b.lo;
-    if constexpr (WS) e.hi = take_a ? a.hi : b.hi;
-    return e;
-}
-template <bool WS> __device__ __forceinline__ void uni_cmpx(UniE<WS>& a, UniE<WS>& b) {
-    const bool sw = uni_lt<WS>(b, a);
-    const UniE<WS> lo = uni_sel<WS>(sw, b, a), hi = uni_sel<WS>(sw, a, b);
-    a = lo;
-    b = hi;
-}
-template <bool WS>
-__global__ __launch_bounds__(UNI_THREADS) void k_bucket_union(const BDesc* __restrict__ list, const u32* __restrict__ list_n, const u32* __restrict__ m_cs,
-                                                              const u64* __restrict__ m_sstart, const u64* __restrict__ m_ostart, const u64* __restrict__ s_lo,
-                                                              const u64* __restrict__ s_hi, const u64* __restrict__ o_lo, const u64* __restrict__ o_hi,
-                                                              u64* __restrict__ out_lo, u64* __restrict__ out_hi, u32 SB, u32* __restrict__ out_count,
-                                                              u8* __restrict__ out_kind) {
-    typedef UniE<WS> E;
-    constexpr int NW = UNI_THREADS / 64;
-    constexpr u32 T = UNI_TILE;
-    static_assert((T & (T - 1)) == 0, "the staging rings index by g mod T");
-    constexpr u32 SLOTS = T * 2 + (T * 2) / 8 + 8;
-    __shared__ u64 s_in[SLOTS];  // A's ring at logical [0, T), B's at [T, 2T); the round's outputs in the slots it consumed
-    __shared__ u64 s_inh[WS ? SLOTS : 1];  // (wide suffixes: the high halves, same slots)
-    __shared__ u32 s_split[NW + 1];
-    __shared__ u32 s_wtot[NW + 1];
-    if (blockIdx.x >= *list_n) return;
-    const BDesc dsc = list[blockIdx.x];
-    const u32 r = dsc.r, c = dsc.c & BDESC_LEN_MASK, cs = m_cs[r], co = c - cs;
-    const u64 a_self = m_sstart[r], a_oth = m_ostart[r];
-    const u64* __restrict__ A = s_lo + a_self;
-    const u64* __restrict__ B = o_lo + a_oth;
-    const u64* __restrict__ Ah = WS ? s_hi + a_self : nullptr;
-    const u64* __restrict__ Bh = WS ? o_hi + a_oth : nullptr;
-    u64* __restrict__ dst = out_lo + dsc.start;
-    u64* __restrict__ dsth = WS ? out_hi + dsc.start : nullptr;
-    // narrow: suffix = lo & mask; wide: (hi & mask(SB - 64), lo)
-    const u64 mask = WS ? ((1ull << (SB - 64)) - 1ull) : (SB >= 64 ? ~0ull : ((1ull << SB) - 1ull));
-    const u32 tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    auto get = [&](u32 slot) { E e; e.lo = s_in[slot]; if constexpr (WS) e.hi = s_inh[slot]; return e; };
-    auto put = [&](u32 slot, const E& e) { s_in[slot] = e.lo; if constexpr (WS) s_inh[slot] = e.hi; };
-    // The two staging areas are RINGS of T slots (round 5): word g of a list lives in slot g mod T of its ring, a round consumes nout
-    // words — iend from A, the rest from B — and only those nout slots are refilled in front of the next round; the round's outputs pass
-    // through exactly the slots it freed. As first written every round staged the next T words of BOTH lists again and consumed T in
-    // all: every word crossed the L2 twice, and with 16 workgroups per CU holding 8 KB each the second read missed — 6.3 GB fetched for
-    // 4.0 GB of lists by the TCC counters (profiles/r05_merge_hbm_traffic.md).
-    u32 ia = 0, ib = 0, written = 0;
-    u32 ha = 0, hb = 0;  // words of A from ia / of B from ib already in the rings
-    E carry = uni_inf<WS>();
-    bool have_carry = false;
-    auto ra = [&](u32 g) { return uni_pad(g & (T - 1)); };
-    auto rb = [&](u32 g) { return uni_pad(T + (g & (T - 1))); };
-    while (ia < cs || ib < co) {
-        const u32 na = cs - ia < T ? cs - ia : T, nb = co - ib < T ? co - ib : T, nout = na + nb < T ? na + nb : T;
-        for (u32 g = ia + ha + tid; g < ia + na; g += UNI_THREADS) {
-            if constexpr (WS) { s_in[ra(g)] = A[g]; s_inh[ra(g)] = Ah[g] & mask; }
-            else s_in[ra(g)] = A[g] & mask;
-        }
-        for (u32 g = ib + hb + tid; g < ib + nb; g += UNI_THREADS) {
-            if constexpr (WS) { s_in[rb(g)] = B[g]; s_inh[rb(g)] = Bh[g] & mask; }
-            else s_in[rb(g)] = B[g] & mask;
-        }
-        __syncthreads();
-        // co-rank of the end of this thread's outputs: how many of the first d1 outputs come from A
-        const u32 d0 = tid * UNI_ITEMS < nout ? tid * UNI_ITEMS : nout, d1 = (tid + 1) * UNI_ITEMS < nout ? (tid + 1) * UNI_ITEMS : nout;
-        u32 lo = d1 > nb ? d1 - nb : 0u, hi = d1 < na ? d1 : na;
-        while (lo < hi) {
-            const u32 mid = (lo + hi) >> 1;
-            if (!uni_lt<WS>(get(rb(ib + d1 - 1 - mid)), get(ra(ia + mid)))) lo = mid + 1; else hi = mid;  // A[mid] <= B[d1 - 1 - mid]: ties take self's copy first
-        }
-        const u32 i1 = lo;
-        if (lane == 63) s_split[w + 1] = i1;
-        if (tid == 0) s_split[0] = 0;
-        __syncthreads();
-        u32 i0 = __shfl_up(i1, 1, 64);
-        if (lane == 0) i0 = s_split[w];
-        const u32 iend = s_split[NW];  // co-rank of nout (the last thread's end)
-        const u32 j0 = d0 - i0;
-        E a[UNI_ITEMS], b[UNI_ITEMS];
-#pragma unroll
-        for (int k = 0; k < UNI_ITEMS; ++k) {
-            const u32 x = i0 + k, y = j0 + k;
-            a[k] = uni_sel<WS>(x < na, get(ra(ia + (x < na ? x : 0u))), uni_inf<WS>());
-            b[k] = uni_sel<WS>(y < nb, get(rb(ib + (y < nb ? y : 0u))), uni_inf<WS>());
-        }
-        E o[UNI_ITEMS];
-#pragma unroll
-        for (int k = 0; k < UNI_ITEMS; ++k) o[k] = uni_sel<WS>(uni_lt<WS>(a[k], b[UNI_ITEMS - 1 - k]), a[k], b[UNI_ITEMS - 1 - k]);
-#pragma unroll
-        for (int st = UNI_ITEMS / 2; st >= 1; st >>= 1)
-#pragma unroll
-            for (int k = 0; k < UNI_ITEMS; ++k)
-                if ((k & st) == 0) uni_cmpx<WS>(o[k], o[k + st]);
-        __syncthreads();  // every read of the chunks is done: the outputs take the place of what the round consumed
-        // output q of the round sits in the q-th freed slot: A's ring first (iend of them), then B's
-        auto oslot = [&](u32 q) { return q < iend ? ra(ia + q) : rb(ib + (q - iend)); };
-#pragma unroll
-        for (int k = 0; k < UNI_ITEMS; ++k) {
-            const u32 q = tid * UNI_ITEMS + k;
-            if (q < nout) put(oslot(q), o[k]);  // (nothing past nout: those slots hold words of the next round)
-        }
-        __syncthreads();
-        // ordered compaction of the outputs that differ from their predecessor (wave-contiguous slices keep the order)
-        E v[UNI_ITEMS];
-        bool head[UNI_ITEMS];
-        u32 wh = 0;
-#pragma unroll
-        for (int j = 0; j < UNI_ITEMS; ++j) {
-            const u32 p = w * (64 * UNI_ITEMS) + j * 64 + lane;
-            const bool live = p < nout;
-            v[j] = get(oslot(live ? p : 0u));
-            const E u = get(oslot((live && p) ? p - 1 : 0u));
-            head[j] = live && (p ? !uni_eq<WS>(v[j], u) : (!have_carry || !uni_eq<WS>(v[j], carry)));
-            wh += (u32)__builtin_popcountll(__ballot(head[j]));
-        }
-        const E last = get(oslot(nout - 1));
-        if (lane == 0) s_wtot[w] = wh;
-        __syncthreads();
-        u32 run = 0, tot = 0;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) { const u32 t = s_wtot[ww]; if ((u32)ww < w) run += t; tot += t; }
-#pragma unroll
-        for (int j = 0; j < UNI_ITEMS; ++j) {
-            const u64 bal = __ballot(head[j]);
-            if (head[j]) {
-                dst[written + run + mbcnt(bal)] = v[j].lo;
-                if constexpr (WS) dsth[written + run + mbcnt(bal)] = v[j].hi;
-            }
-            run += (u32)__builtin_popcountll(bal);
-        }
-        carry = last;
-        have_carry = true;
-        written += tot;
-        ha = na - iend;
-        hb = nb - (nout - iend);
-        ia += iend;
-        ib += nout - iend;
-        __syncthreads();  // the next round refills the freed slots and rewrites the split table
-    }
-    if (tid == 0) { out_count[r] = written; out_kind[r] = KIND_TRIE; }
-}
-
-// ---- `&mut a OP &mut b` into a new index (cblx_set_op; /root/reference/src/wordset/set_ops.rs:78-121, 159-190, 241-279, 319-364 walk the
-// two prefix bitvectors, src/trievec/set_ops.rs:5-41, 73-99, 131-161, 189-224 the buckets): a bucket only one side holds is cloned as
-// stored, a bucket both hold becomes TrieOrVec::Vec(sorted OP of the two sorted iterators) — always a Vec, ascending, dropped when empty;
-// iter_sorted leaves the Vec buckets of either operand sorted on the prefixes both hold. --------------------------------------------------
-static const u32 SETOP_OR = 0, SETOP_AND = 1, SETOP_SUB = 2, SETOP_XOR = 3;  // = CBLX_SETOP_* of include/cblx.h
-// candidate prefixes of the result: AND needs both sides, SUB needs a's (what only b holds yields nothing), OR / XOR either
-__global__ void k_setop_bv(u64 nwords, const u64* __restrict__ a, const u64* __restrict__ b, u32 op, u64* __restrict__ out, u32* __restrict__ popc) {
-    const u64 w = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= nwords) return;
-    const u64 v = op == SETOP_AND ? (a[w] & b[w]) : op == SETOP_SUB ? a[w] : (a[w] | b[w]);
-    out[w] = v;
-    popc[w] = (u32)__builtin_popcountll(v);
-}
-// One thread per candidate prefix, after k_merge_table (cap = cs + co on entry): the run capacity becomes the op's upper bound, a one-sided bucket
-// gets its final count and kind (it is cloned as stored), a both-sided one joins the `both` list, and each of its Vec sides of two words or more
-// joins the list of the sorting class of its length ([side][0]: one workgroup's LDS radix sort, [side][1]: the general kernel) with the run in the
-// OPERAND's arena as its descriptor — sorted in place there, which is the side effect the reference has.
-static const u32 SETOP_SORT_LDS = 512 * MED_ITEMS;  // k_bucket_medium<512>'s capacity
-__global__ __launch_bounds__(CLASSIFY_THREADS) void k_setop_plan(u64 nb, u32 op, u32* __restrict__ cap, const u32* __restrict__ m_cs, u32* __restrict__ m_co,
-                                                                  const u64* __restrict__ m_sstart, const u64* __restrict__ m_ostart, const u8* __restrict__ m_skind,
-                                                                  const u8* __restrict__ m_okind, u32* __restrict__ out_count, u8* __restrict__ out_kind,
-                                                                  BDesc* __restrict__ sort_lists /* [2 sides][2 classes][nb] */, BDesc* __restrict__ both_list,
-                                                                  u32* __restrict__ list_n /* [4] sort lists, [1] both */) {
-    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    int cls_a = -1, cls_b = -1, cls_both = -1;
-    u32 cs = 0, co = 0;
-    if (r < nb) {
-        cs = m_cs[r];
-        co = cap[r] - cs;
-        m_co[r] = co;
-        if (cs != 0 && co != 0) {
-            cap[r] = op == SETOP_AND ? (cs < co ? cs : co) : op == SETOP_SUB ? cs : cs + co;
-            out_count[r] = 0;  // (written by k_bucket_setop)
-            out_kind[r] = KIND_VEC;
-            cls_both = 0;
-            if (m_skind[r] == KIND_VEC && cs > 1) cls_a = cs <= SETOP_SORT_LDS ? 0 : 1;
-            if (m_okind[r] == KIND_VEC && co > 1) cls_b = co <= SETOP_SORT_LDS ? 0 : 1;
-        } else {  // one-sided (never for AND, never b's side for SUB: such prefixes are no candidates)
-            cap[r] = cs + co;
-            out_count[r] = cs + co;
-            out_kind[r] = cs ? m_skind[r] : m_okind[r];
-        }
-    }
-    const u32 slot_a = block_append<CLASSIFY_THREADS, 2>(cls_a, list_n);
-    if (cls_a >= 0) sort_lists[(u64)cls_a * nb + slot_a] = BDesc{m_sstart[r], cs | BDESC_TRIE, (u32)r};  // (TRIE: the kernel leaves the run sorted)
-    __syncthreads();  // block_append's tables are reused
-    const u32 slot_b = block_append<CLASSIFY_THREADS, 2>(cls_b, list_n + 2);
-    if (cls_b >= 0) sort_lists[(u64)(2 + cls_b) * nb + slot_b] = BDesc{m_ostart[r], co | BDESC_TRIE, (u32)r};
-    const u32 slot = block_append<CLASSIFY_THREADS, 1>(cls_both, list_n + 4);
-    if (cls_both >= 0) both_list[slot] = BDesc{0, 0, (u32)r};
-}
-// LPB lanes per candidate: a one-sided bucket is copied into its run as stored
-template <bool WS, int LPB>
-__global__ __launch_bounds__(256) void k_setop_gather(u64 nb, const u64* __restrict__ start, const u32* __restrict__ m_cs, const u32* __restrict__ m_co,
-                                                      const u64* __restrict__ m_sstart, const u64* __restrict__ m_ostart, const u64* __restrict__ s_lo,
-                                                      const u64* __restrict__ s_hi, const u64* __restrict__ o_lo, const u64* __restrict__ o_hi,
-                                                      u64* __restrict__ out_lo, u64* __restrict__ out_hi) {
-    const u64 r = ((u64)blockIdx.x * 256 + threadIdx.x) / LPB;
-    if (r >= nb) return;
-    const u32 lane = threadIdx.x & (LPB - 1);
-    const u32 cs = m_cs[r], co = m_co[r];
-    if (cs != 0 && co != 0) return;
-    const u64 d0 = start[r], src = cs ? m_sstart[r] : m_ostart[r];
-    const u64* __restrict__ lo = cs ? s_lo : o_lo;
-    const u64* __restrict__ hi = cs ? s_hi : o_hi;
-    for (u32 j = lane; j < cs + co; j += LPB) {
-        out_lo[d0 + j] = lo[src + j];
-        if constexpr (WS) out_hi[d0 + j] = hi[src + j];
-    }
-}
-// Both-sided buckets: k_bucket_union's rounds (two staging rings, co-rank on the round's diagonal, register merge network, ordered compaction by
-// ballot) with another keep-predicate. Both lists are duplicate-free, so a value occurs once or twice in the merged sequence, a's copy first:
-//   OR keeps what differs from its predecessor, AND what equals it (the second of a pair), XOR what differs from both neighbours, SUB what
-//   differs from both neighbours and came from a.
-// ORIGIN (SUB): the merge network loses it. No tag bit is used — a bit above the suffix is free below 64 bits and in the high half of a wide
-// suffix, but not at SUFFIX_BITS = 64, and a tagged all-ones suffix would have to be kept apart from the network's padding value. Instead the
-// thread that merged an output knows how many of its outputs came from a (the difference of its two co-ranks) and still holds exactly those
-// candidates in registers: an output that equals none of them came from b. (One that equals one of them is a's copy or b's copy of a PAIR, which SUB
-// drops on its neighbours alone, so the answer is exact wherever it is used.) The same code serves every suffix width; the flags travel to the
-// compaction through one LDS word per thread.
-// ROUND EDGES: a's copy of a pair may be the last output of a round and b's copy the first of the next. The last output of every round is therefore
-// HELD BACK — its value, whether it equals its predecessor and where it came from stay in registers — and is decided as the first element of the
-// next round, when its successor is known; after the last round it has no successor. A round thus emits [held-back value, outputs 0 .. nout-2].
-template <bool WS, u32 OP>
-__global__ __launch_bounds__(UNI_THREADS) void k_bucket_setop(const BDesc* __restrict__ list, const u32* __restrict__ list_n, const u32* __restrict__ m_cs,
-                                                              const u32* __restrict__ m_co, const u64* __restrict__ m_sstart, const u64* __restrict__ m_ostart,
-                                                              const u64* __restrict__ s_lo, const u64* __restrict__ s_hi, const u64* __restrict__ o_lo,
-                                                              const u64* __restrict__ o_hi, const u64* __restrict__ run_start, u64* __restrict__ out_lo,
-                                                              u64* __restrict__ out_hi, u32 SB, u32* __restrict__ out_count, u8* __restrict__ out_kind) {
-    typedef UniE<WS> E;
-    constexpr int NW = UNI_THREADS / 64;
-    constexpr u32 T = UNI_TILE;
-    static_assert((T & (T - 1)) == 0, "the staging rings index by g mod T");
-    static_assert(UNI_ITEMS <= 32, "one origin bit per output in a 32-bit word");
-    constexpr u32 SLOTS = T * 2 + (T * 2) / 8 + 8;
-    __shared__ u64 s_in[SLOTS];
-    __shared__ u64 s_inh[WS ? SLOTS : 1];
-    __shared__ u32 s_org[OP == SETOP_SUB ? UNI_THREADS : 1];  // bit k of word t: output t * UNI_ITEMS + k of the round came from a
-    __shared__ u32 s_split[NW + 1];
-    __shared__ u32 s_wtot[NW + 1];
-    if (blockIdx.x >= *list_n) return;
-    const u32 r = list[blockIdx.x].r, cs = m_cs[r], co = m_co[r];
-    const u64 a_self = m_sstart[r], a_oth = m_ostart[r], d_run = run_start[r];
-    const u64* __restrict__ A = s_lo + a_self;
-    const u64* __restrict__ B = o_lo + a_oth;
-    const u64* __restrict__ Ah = WS ? s_hi + a_self : nullptr;
-    const u64* __restrict__ Bh = WS ? o_hi + a_oth : nullptr;
-    u64* __restrict__ dst = out_lo + d_run;
-    u64* __restrict__ dsth = WS ? out_hi + d_run : nullptr;
-    const u64 mask = WS ? ((1ull << (SB - 64)) - 1ull) : (SB >= 64 ? ~0ull : ((1ull << SB) - 1ull));
-    const u32 tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    auto get = [&](u32 slot) { E e; e.lo = s_in[slot]; if constexpr (WS) e.hi = s_inh[slot]; return e; };
-    auto put = [&](u32 slot, const E& e) { s_in[slot] = e.lo; if constexpr (WS) s_inh[slot] = e.hi; };
-    auto keep_rule = [](bool eqp, bool eqn, bool from_a) {
-        return OP == SETOP_OR ? !eqp : OP == SETOP_AND ? eqp : OP == SETOP_XOR ? (!eqp && !eqn) : (from_a && !eqp && !eqn);
-    };
-    u32 ia = 0, ib = 0, written = 0;
-    u32 ha = 0, hb = 0;
-    E carry = uni_inf<WS>();  // the held-back output
-    bool have_carry = false, carry_eqp = false, carry_a = false;
-    auto ra = [&](u32 g) { return uni_pad(g & (T - 1)); };
-    auto rb = [&](u32 g) { return uni_pad(T + (g & (T - 1))); };
-    while (ia < cs || ib < co) {
-        const u32 na = cs - ia < T ? cs - ia : T, nb = co - ib < T ? co - ib : T, nout = na + nb < T ? na + nb : T;
-        for (u32 g = ia + ha + tid; g < ia + na; g += UNI_THREADS) {
-            if constexpr (WS) { s_in[ra(g)] = A[g]; s_inh[ra(g)] = Ah[g] & mask; }
-            else s_in[ra(g)] = A[g] & mask;
-        }
-        for (u32 g = ib + hb + tid; g < ib + nb; g += UNI_THREADS) {
-            if constexpr (WS) { s_in[rb(g)] = B[g]; s_inh[rb(g)] = Bh[g] & mask; }
-            else s_in[rb(g)] = B[g] & mask;
-        }
-        __syncthreads();
-        const u32 d0 = tid * UNI_ITEMS < nout ? tid * UNI_ITEMS : nout, d1 = (tid + 1) * UNI_ITEMS < nout ? (tid + 1) * UNI_ITEMS : nout;
-        u32 lo = d1 > nb ? d1 - nb : 0u, hi = d1 < na ? d1 : na;
-        while (lo < hi) {
-            const u32 mid = (lo + hi) >> 1;
-            if (!uni_lt<WS>(get(rb(ib + d1 - 1 - mid)), get(ra(ia + mid)))) lo = mid + 1; else hi = mid;  // ties take a's copy first
-        }
-        const u32 i1 = lo;
-        if (lane == 63) s_split[w + 1] = i1;
-        if (tid == 0) s_split[0] = 0;
-        __syncthreads();
-        u32 i0 = __shfl_up(i1, 1, 64);
-        if (lane == 0) i0 = s_split[w];
-        const u32 iend = s_split[NW];
-        const u32 j0 = d0 - i0;
-        E a[UNI_ITEMS], b[UNI_ITEMS];
-#pragma unroll
-        for (int k = 0; k < UNI_ITEMS; ++k) {
-            const u32 x = i0 + k, y = j0 + k;
-            a[k] = uni_sel<WS>(x < na, get(ra(ia + (x < na ? x : 0u))), uni_inf<WS>());
-            b[k] = uni_sel<WS>(y < nb, get(rb(ib + (y < nb ? y : 0u))), uni_inf<WS>());
-        }
-        E o[UNI_ITEMS];
-#pragma unroll
-        for (int k = 0; k < UNI_ITEMS; ++k) o[k] = uni_sel<WS>(uni_lt<WS>(a[k], b[UNI_ITEMS - 1 - k]), a[k], b[UNI_ITEMS - 1 - k]);
-#pragma unroll
-        for (int st = UNI_ITEMS / 2; st >= 1; st >>= 1)
-#pragma unroll
-            for (int k = 0; k < UNI_ITEMS; ++k)
-                if ((k & st) == 0) uni_cmpx<WS>(o[k], o[k + st]);
-        u32 org = 0;
-        if constexpr (OP == SETOP_SUB) {
-            const u32 from_a = i1 - i0;  // a[0 .. from_a) are the thread's outputs that came from a
-#pragma unroll
-            for (int k = 0; k < UNI_ITEMS; ++k) {
-                bool fa = false;
-#pragma unroll
-                for (int j = 0; j < UNI_ITEMS; ++j) fa = fa || ((u32)j < from_a && uni_eq<WS>(o[k], a[j]));
-                org |= fa ? 1u << k : 0u;
-            }
-        }
-        __syncthreads();  // every read of the chunks is done: the outputs take the place of what the round consumed
-        auto oslot = [&](u32 q) { return q < iend ? ra(ia + q) : rb(ib + (q - iend)); };
-#pragma unroll
-        for (int k = 0; k < UNI_ITEMS; ++k) {
-            const u32 q = tid * UNI_ITEMS + k;
-            if (q < nout) put(oslot(q), o[k]);
-        }
-        if constexpr (OP == SETOP_SUB) s_org[tid] = org;
-        __syncthreads();
-        auto org_of = [&](u32 q) { return OP == SETOP_SUB ? ((s_org[q / UNI_ITEMS] >> (q % UNI_ITEMS)) & 1u) != 0 : false; };
-        // emit slot e of the round holds output e - 1 (slot 0: the value held back); its successor is output e
-        E v[UNI_ITEMS];
-        bool keep[UNI_ITEMS];
-        u32 wh = 0;
-#pragma unroll
-        for (int j = 0; j < UNI_ITEMS; ++j) {
-            const u32 e = w * (64 * UNI_ITEMS) + j * 64 + lane;
-            const bool in = e < nout;
-            const E succ = get(oslot(in ? e : 0u));
-            const E x1 = get(oslot(in && e >= 1 ? e - 1 : 0u)), x2 = get(oslot(in && e >= 2 ? e - 2 : 0u));
-            v[j] = uni_sel<WS>(e >= 1, x1, carry);
-            const E pred = uni_sel<WS>(e >= 2, x2, carry);
-            const bool eqp = e == 0 ? carry_eqp : ((e >= 2 || have_carry) && uni_eq<WS>(v[j], pred));
-            const bool from_a = e == 0 ? carry_a : org_of(in && e >= 1 ? e - 1 : 0u);
-            keep[j] = in && (e >= 1 || have_carry) && keep_rule(eqp, uni_eq<WS>(v[j], succ), from_a);
-            wh += (u32)__builtin_popcountll(__ballot(keep[j]));
-        }
-        // the round's last output is held back
-        const E last = get(oslot(nout - 1));
-        const E before = uni_sel<WS>(nout >= 2, get(oslot(nout >= 2 ? nout - 2 : 0u)), carry);
-        const bool last_eqp = (nout >= 2 || have_carry) && uni_eq<WS>(last, before);
-        const bool last_a = org_of(nout - 1);
-        if (lane == 0) s_wtot[w] = wh;
-        __syncthreads();
-        u32 run = 0, tot = 0;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) { const u32 t = s_wtot[ww]; if ((u32)ww < w) run += t; tot += t; }
-#pragma unroll
-        for (int j = 0; j < UNI_ITEMS; ++j) {
-            const u64 bal = __ballot(keep[j]);
-            if (keep[j]) {
-                dst[written + run + mbcnt(bal)] = v[j].lo;
-                if constexpr (WS) dsth[written + run + mbcnt(bal)] = v[j].hi;
-            }
-            run += (u32)__builtin_popcountll(bal);
-        }
-        carry = last;
-        carry_eqp = last_eqp;
-        carry_a = last_a;
-        have_carry = true;
-        written += tot;
-        ha = na - iend;
-        hb = nb - (nout - iend);
-        ia += iend;
-        ib += nout - iend;
-        __syncthreads();  // the next round refills the freed slots and rewrites the split table
-    }
-    if (tid == 0) {
-        if (have_carry && keep_rule(carry_eqp, false, carry_a)) {  // the last value of the merged sequence has no successor
-            dst[written] = carry.lo;
-            if constexpr (WS) dsth[written] = carry.hi;
-            ++written;
-        }
-        out_count[r] = written;
-        if (out_kind) out_kind[r] = KIND_VEC;  // (null: the bucket keeps the kind the plan gave it)
-    }
-}
-// the candidates that keep at least one word stay in the directory
-__global__ void k_setop_live(u64 nb, const u32* __restrict__ cnt, u32* __restrict__ live) {
-    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < nb) live[r] = cnt[r] != 0 ? 1u : 0u;
-}
-// ... and move to their new rank (ascending prefixes stay ascending); their bits make up the result's bitvector (zeroed by the caller)
-__global__ void k_setop_compact(u64 nb, const u32* __restrict__ cnt, const u64* __restrict__ new_rank, const u32* __restrict__ prefix, const u64* __restrict__ start,
-                                const u8* __restrict__ kind, u32* __restrict__ o_prefix, u64* __restrict__ o_start, u32* __restrict__ o_cnt, u8* __restrict__ o_kind,
-                                u64* __restrict__ bv) {
-    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= nb || cnt[r] == 0) return;
-    const u64 n = new_rank[r];
-    const u32 p = prefix[r];
-    o_prefix[n] = p;
-    o_start[n] = start[r];
-    o_cnt[n] = cnt[r];
-    o_kind[n] = kind[r];
-    atomicOr((unsigned long long*)&bv[p >> 6], 1ull << (p & 63));
-}
-
-// ---- CBL::merge / CBL::intersect of n operands (cblx_set_op_many; /root/reference/src/cbl.rs:106-124 -> src/wordset/set_ops.rs:11-42, 49-75) ----------
-// Per distinct prefix the reference gets the operands that hold it. merge: one holder -> cloned as stored; two or more -> every holder's Vec is sorted
-// (iter_sorted) and the result is Vec(ascending union), whatever its length. intersect: only prefixes ALL operands hold; every holder's Vec is sorted, the
-// result is Vec(ascending intersection), dropped when empty — also for n = 1, which turns every bucket into an ascending Vec.
-// A candidate bucket carries a 64-bit holder mask (hence at most 64 operands); nothing of size [buckets][operands] exists: a holder's rank in its own
-// directory is rank_dir[word] + popc(bits below), recomputed where its run is needed.
-static const u32 MANY_MAX = 64;  // = CBLX_SETOP_MAX_OPERANDS
-// words of all holders of a bucket that k_bucket_setop_many stages in LDS: up to MANY_SMALL one wave and 2 KB (4 KB wide), up to MANY_LDS four waves and
-// 24 KB (40 KB wide: 6 / 4 workgroups per CU); longer buckets are folded pairwise by k_bucket_setop (tests/test_gpu_setops_many.py mirrors both)
-static const u32 MANY_SMALL = 256, MANY_LDS = 2048;
-struct ManyOp { DirView d; const u64* lo; const u64* hi; };  // one operand: its directory and its arena
-
-__global__ void k_many_bv(u64 nwords, const ManyOp* __restrict__ ops, u32 n, u32 op, u64* __restrict__ out, u32* __restrict__ popc) {
-    const u64 w = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= nwords) return;
-    u64 v = ops[0].d.bv[w];
-    for (u32 i = 1; i < n; ++i) { const u64 x = ops[i].d.bv[w]; v = op == SETOP_AND ? (v & x) : (v | x); }
-    out[w] = v;
-    popc[w] = (u32)__builtin_popcountll(v);
-}
-// One thread per prefix slot of the candidate bitvector: holder mask, run capacity (merge: sum of the holders' counts, intersect: the smallest) and the
-// bucket's fate — a merge bucket with one holder gets its final count and kind (k_many_gather clones it), every other one joins the list of its route:
-// [0] up to MANY_SMALL words of all holders, [1] up to MANY_LDS, [2] longer. BDesc.c = words of all holders.
-__global__ __launch_bounds__(CLASSIFY_THREADS) void k_many_table(u64 nprefix, const u64* __restrict__ bv, const u64* __restrict__ rank_dir, const ManyOp* __restrict__ ops, u32 n,
-                                                                  u32 op, u64 nb, u32* __restrict__ bucket_prefix, u64* __restrict__ hmask, u32* __restrict__ cap,
-                                                                  u32* __restrict__ out_count, u8* __restrict__ out_kind, BDesc* __restrict__ lists /* [3][nb] */,
-                                                                  u32* __restrict__ list_n) {
-    const u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    int cls = -1;
-    u64 r = 0;
-    u32 sum = 0;
-    if (p < nprefix) {
-        const u64 w = bv[p >> 6];
-        if ((w >> (p & 63)) & 1ull) {
-            r = rank_dir[p >> 6] + (u64)__builtin_popcountll(w & ((1ull << (p & 63)) - 1ull));
-            u64 mask = 0;
-            u32 mn = 0xFFFFFFFFu;
-            u8 k0 = KIND_VEC;
-            for (u32 i = 0; i < n; ++i) {
-                u64 rank;
-                if (!dir_lookup(ops[i].d, (u32)p, rank)) continue;
-                const u32 c = ops[i].d.count[rank];
-                if (!mask) k0 = ops[i].d.kind[rank];
-                mask |= 1ull << i;
-                sum += c;
-                mn = c < mn ? c : mn;
-            }
-            bucket_prefix[r] = (u32)p;
-            hmask[r] = mask;
-            if (op == SETOP_OR && (mask & (mask - 1ull)) == 0) {
-                cap[r] = sum;
-                out_count[r] = sum;
-                out_kind[r] = k0;
-            } else {
-                cap[r] = op == SETOP_AND ? mn : sum;
-                out_count[r] = 0;  // (written by the bucket's kernel)
-                out_kind[r] = KIND_VEC;
-                cls = sum <= MANY_SMALL ? 0 : sum <= MANY_LDS ? 1 : 2;
-            }
-        }
-    }
-    const u32 slot = block_append<CLASSIFY_THREADS, 3>(cls, list_n);
-    if (cls >= 0) lists[(u64)cls * nb + slot] = BDesc{0, sum, (u32)r};
-}
-// LPB lanes per candidate (merge): a bucket one operand holds is copied into its run as stored — k_setop_gather's n-ary twin
-template <bool WS, int LPB>
-__global__ __launch_bounds__(256) void k_many_gather(u64 nb, const u64* __restrict__ start, const u32* __restrict__ bucket_prefix, const u64* __restrict__ hmask,
-                                                     const ManyOp* __restrict__ ops, u64* __restrict__ out_lo, u64* __restrict__ out_hi) {
-    const u64 r = ((u64)blockIdx.x * 256 + threadIdx.x) / LPB;
-    if (r >= nb) return;
-    const u32 lane = threadIdx.x & (LPB - 1);
-    const u64 mask = hmask[r];
-    if (mask & (mask - 1ull)) return;
-    const ManyOp o = ops[__builtin_ctzll(mask)];
-    u64 rank;
-    if (!dir_lookup(o.d, bucket_prefix[r], rank)) return;
-    const u64 d0 = start[r], src = o.d.start[rank];
-    const u32 c = o.d.count[rank];
-    for (u32 j = lane; j < c; j += LPB) {
-        out_lo[d0 + j] = o.lo[src + j];
-        if constexpr (WS) out_hi[d0 + j] = o.hi[src + j];
-    }
-}
-// One thread per candidate, once per operand: the operand's Vec bucket of two words or more on a prefix the reference visits with iter_sorted (merge: two
-// holders or more; intersect: every candidate) joins the list of its sorting class, with the run in the OPERAND's arena as descriptor (as k_setop_plan)
-__global__ __launch_bounds__(CLASSIFY_THREADS) void k_many_sortplan(u64 nb, const u32* __restrict__ bucket_prefix, const u64* __restrict__ hmask, u32 op,
-                                                                     const ManyOp* __restrict__ ops, u32 i, BDesc* __restrict__ sort_lists /* [2][nb] */,
-                                                                     u32* __restrict__ list_n) {
-    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    int cls = -1;
-    u64 st = 0;
-    u32 c = 0;
-    if (r < nb) {
-        const u64 mask = hmask[r];
-        u64 rank;
-        if (((mask >> i) & 1ull) && (op == SETOP_AND || (mask & (mask - 1ull)) != 0) && dir_lookup(ops[i].d, bucket_prefix[r], rank)) {
-            c = ops[i].d.count[rank];
-            st = ops[i].d.start[rank];
-            if (ops[i].d.kind[rank] == KIND_VEC && c > 1) cls = c <= SETOP_SORT_LDS ? 0 : 1;
-        }
-    }
-    const u32 slot = block_append<CLASSIFY_THREADS, 2>(cls, list_n);
-    if (cls >= 0) sort_lists[(u64)cls * nb + slot] = BDesc{st, c | BDESC_TRIE, (u32)r};  // (TRIE: the kernel leaves the run sorted)
-}
-// One workgroup per bucket of up to CAP words over all its m holders, whose runs are ascending and duplicate-free by now. The runs are staged back to back
-// in LDS (lane t of the first wave looks up operand t; a wave scan of the counts gives the offsets).
-//   OR: every element finds its position in the merged multiset by one binary search per other run — runs of lower index count their elements <= it, runs of
-//       higher index those < it, so the lowest holder's copy of a value comes first — and the searches in the lower runs also say whether one of them holds
-//       the value: then this copy is not kept. (element index, kept) goes to the merged position; an ordered compaction by ballot / mbcnt / wave totals writes
-//       the kept ones out. No tag bit in the suffix and no padding value: SUFFIX_BITS = 64 has no free bit and all-ones is a legal suffix.
-//   AND: the elements of the shortest holder (the lowest one on ties) are searched in every other run and kept when all hold them; same compaction.
-template <bool WS, u32 OP, u32 CAP, int THREADS>
-__global__ __launch_bounds__(THREADS) void k_bucket_setop_many(const BDesc* __restrict__ list, const u32* __restrict__ list_n, const u32* __restrict__ bucket_prefix,
-                                                               const u64* __restrict__ hmask, const ManyOp* __restrict__ ops, const u64* __restrict__ run_start,
-                                                               u64* __restrict__ out_lo, u64* __restrict__ out_hi, u32 SB, u32* __restrict__ out_count) {
-    typedef UniE<WS> E;
-    static_assert(OP == SETOP_OR || OP == SETOP_AND, "the reference has no n-ary SUB / XOR");
-    static_assert(THREADS % 64 == 0, "whole waves");
-    constexpr int NW = THREADS / 64;
-    __shared__ u64 s_lo[CAP];
-    __shared__ u64 s_hi[WS ? CAP : 1];
-    __shared__ u32 s_perm[OP == SETOP_OR ? CAP : 1];  // merged position -> element | kept << 31
-    __shared__ u64 s_src[MANY_MAX];                    // holder k: first arena slot of its run,
-    __shared__ u32 s_opi[MANY_MAX];                    // its operand,
-    __shared__ u32 s_off[MANY_MAX + 1];                // and where its run starts in s_lo; [m] = words of all holders
-    __shared__ u32 s_wtot[NW];
-    if (blockIdx.x >= *list_n) return;
-    const u32 r = list[blockIdx.x].r;
-    const u64 holders = hmask[r];
-    const u32 p = bucket_prefix[r], m = (u32)__builtin_popcountll(holders);
-    const u64 mask = WS ? ((1ull << (SB - 64)) - 1ull) : (SB >= 64 ? ~0ull : ((1ull << SB) - 1ull));
-    const u32 tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    if (tid < 64) {
-        const bool holds = ((holders >> tid) & 1ull) != 0;
-        u32 c = 0;
-        u64 st = 0, rank;
-        if (holds && dir_lookup(ops[tid].d, p, rank)) { c = ops[tid].d.count[rank]; st = ops[tid].d.start[rank]; }
-        u32 inc = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const u32 t = __shfl_up(inc, d, 64); if ((int)lane >= d) inc += t; }
-        if (holds) {
-            const u32 k = (u32)__builtin_popcountll(holders & ((1ull << tid) - 1ull));
-            s_off[k] = inc - c;
-            s_src[k] = st;
-            s_opi[k] = tid;
-        }
-        if (tid == 63) s_off[m] = inc;
-    }
-    __syncthreads();
-    const u32 total = s_off[m] < CAP ? s_off[m] : CAP;  // (the list's class says total <= CAP)
-    auto run_of = [&](u32 e) { u32 k = 0; while (k + 1 < m && s_off[k + 1] <= e) ++k; return k; };
-    auto get = [&](u32 i) { E e; e.lo = s_lo[i]; if constexpr (WS) e.hi = s_hi[i]; return e; };
-    for (u32 e = tid; e < total; e += THREADS) {
-        const u32 k = run_of(e);
-        const ManyOp& o = ops[s_opi[k]];
-        const u64 g = s_src[k] + (e - s_off[k]);
-        if constexpr (WS) { s_lo[e] = o.lo[g]; s_hi[e] = o.hi[g] & mask; }
-        else s_lo[e] = o.lo[g] & mask;
-        if constexpr (OP == SETOP_OR) s_perm[e] = 0;
-    }
-    __syncthreads();
-    u64* __restrict__ dst = out_lo + run_start[r];
-    u64* __restrict__ dsth = WS ? out_hi + run_start[r] : nullptr;
-    // first index in [a, b) whose element is not below v (UPPER: is above v)
-    auto bound = [&](u32 a, u32 b, const E& v, bool upper) {
-        while (a < b) {
-            const u32 mid = (a + b) >> 1;
-            const E x = get(mid);
-            if (upper ? !uni_lt<WS>(v, x) : uni_lt<WS>(x, v)) a = mid + 1; else b = mid;
-        }
-        return a;
-    };
-    u32 ks = 0, len = total;
-    if constexpr (OP == SETOP_OR) {
-        for (u32 e = tid; e < total; e += THREADS) {
-            const u32 k = run_of(e);
-            const E v = get(e);
-            u32 pos = e - s_off[k];
-            bool dup = false;
-            for (u32 kk = 0; kk < m; ++kk) {
-                if (kk == k) continue;
-                const u32 a = s_off[kk], at = bound(a, s_off[kk + 1] < total ? s_off[kk + 1] : total, v, kk < k);
-                pos += at - a;
-                if (kk < k && at > a && uni_eq<WS>(get(at - 1), v)) dup = true;
-            }
-            if (pos < total) s_perm[pos] = e | (dup ? 0u : 0x80000000u);
-        }
-        __syncthreads();
-    } else {
-        len = s_off[1] - s_off[0];
-        for (u32 k = 1; k < m; ++k) { const u32 c = s_off[k + 1] - s_off[k]; if (c < len) { len = c; ks = k; } }
-        if (s_off[ks] + len > total) len = 0;
-    }
-    u32 written = 0;
-    for (u32 base = 0; base < len; base += THREADS) {
-        const u32 q = base + tid;
-        bool keep = q < len;
-        u32 src = 0;
-        if constexpr (OP == SETOP_OR) {
-            const u32 pe = keep ? s_perm[q] : 0u;
-            keep = (pe >> 31) != 0;
-            src = pe & 0x7FFFFFFFu;
-        } else if (keep) {
-            src = s_off[ks] + q;
-            const E v = get(src);
-            for (u32 kk = 0; kk < m && keep; ++kk) {
-                if (kk == ks) continue;
-                const u32 b = s_off[kk + 1] < total ? s_off[kk + 1] : total, at = bound(s_off[kk], b, v, false);
-                keep = at < b && uni_eq<WS>(get(at), v);
-            }
-        }
-        const u64 bal = __ballot(keep);
-        if (lane == 0) s_wtot[w] = (u32)__builtin_popcountll(bal);
-        __syncthreads();
-        u32 run = 0, tot = 0;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) { const u32 t = s_wtot[ww]; if ((u32)ww < w) run += t; tot += t; }
-        if (keep) {
-            dst[written + run + mbcnt(bal)] = s_lo[src];
-            if constexpr (WS) dsth[written + run + mbcnt(bal)] = s_hi[src];
-        }
-        written += tot;
-        __syncthreads();  // s_wtot is rewritten
-    }
-    if (tid == 0) out_count[r] = written;
-}
-// ---- the long route: a bucket whose holders have more than MANY_LDS words is folded holder by holder with k_bucket_setop over two scratch runs of
-// sum-of-counts words each (X at sc_start[q], Y at S + sc_start[q]; q = the bucket's place in the long list). acc_side[q] says which one holds the
-// accumulator: a step whose operand does not hold the bucket leaves it where it is.
-// the accumulator starts as the lowest holder's run (ascending by now), suffix bits only
-template <bool WS>
-__global__ __launch_bounds__(256) void k_many_long_init(const BDesc* __restrict__ list, u32 nlong, const u32* __restrict__ bucket_prefix, const u64* __restrict__ hmask,
-                                                        const ManyOp* __restrict__ ops, const u64* __restrict__ sc_start, u64* __restrict__ sc_lo, u64* __restrict__ sc_hi,
-                                                        u32 SB, u32* __restrict__ acc_cnt, u8* __restrict__ acc_side) {
-    const u32 q = blockIdx.x;
-    if (q >= nlong) return;
-    const u32 r = list[q].r;
-    const ManyOp o = ops[__builtin_ctzll(hmask[r])];
-    u64 rank;
-    if (!dir_lookup(o.d, bucket_prefix[r], rank)) return;
-    const u64 mask = WS ? ((1ull << (SB - 64)) - 1ull) : (SB >= 64 ? ~0ull : ((1ull << SB) - 1ull));
-    const u64 src = o.d.start[rank], d0 = sc_start[q];
-    const u32 c = o.d.count[rank];
-    for (u32 j = threadIdx.x; j < c; j += 256) {
-        if constexpr (WS) { sc_lo[d0 + j] = o.lo[src + j]; sc_hi[d0 + j] = o.hi[src + j] & mask; }
-        else sc_lo[d0 + j] = o.lo[src + j] & mask;
-    }
-    if (threadIdx.x == 0) { acc_cnt[q] = c; acc_side[q] = 0; }
-}
-__global__ void k_many_long_words(const BDesc* __restrict__ list, u32 nlong, u32* __restrict__ words) {
-    const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < nlong) words[q] = list[q].c;
-}
-// step i of the fold: the long buckets operand i holds (beyond their first holder, and unless an intersection is empty already) get k_bucket_setop's
-// tables — a = the accumulator, b = operand i's run, output = the other scratch run — and change sides
-__global__ __launch_bounds__(CLASSIFY_THREADS) void k_many_long_plan(const BDesc* __restrict__ list, u32 nlong, const u32* __restrict__ bucket_prefix,
-                                                                      const u64* __restrict__ hmask, const ManyOp* __restrict__ ops, u32 i, u32 op,
-                                                                      const u64* __restrict__ sc_start, u64 S, const u32* __restrict__ acc_cnt, u8* __restrict__ acc_side,
-                                                                      u32* __restrict__ t_cs, u32* __restrict__ t_co, u64* __restrict__ t_sstart, u64* __restrict__ t_ostart,
-                                                                      u64* __restrict__ t_run, BDesc* __restrict__ step_list, u32* __restrict__ step_n) {
-    const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
-    int cls = -1;
-    if (q < nlong) {
-        const u32 r = list[q].r;
-        const u64 mask = hmask[r];
-        u64 rank;
-        if (((mask >> i) & 1ull) && (u32)__builtin_ctzll(mask) != i && !(op == SETOP_AND && acc_cnt[q] == 0) && dir_lookup(ops[i].d, bucket_prefix[r], rank)) {
-            const u8 side = acc_side[q];
-            t_cs[q] = acc_cnt[q];
-            t_co[q] = ops[i].d.count[rank];
-            t_sstart[q] = sc_start[q] + (side ? S : 0ull);
-            t_ostart[q] = ops[i].d.start[rank];
-            t_run[q] = sc_start[q] + (side ? 0ull : S);
-            acc_side[q] = side ^ 1;
-            cls = 0;
-        }
-    }
-    const u32 slot = block_append<CLASSIFY_THREADS, 1>(cls, step_n);
-    if (cls >= 0) step_list[slot] = BDesc{0, 0, q};
-}
-// the accumulator becomes the result bucket
-template <bool WS>
-__global__ __launch_bounds__(256) void k_many_long_finish(const BDesc* __restrict__ list, u32 nlong, const u64* __restrict__ sc_start, u64 S, const u64* __restrict__ sc_lo,
-                                                          const u64* __restrict__ sc_hi, const u32* __restrict__ acc_cnt, const u8* __restrict__ acc_side,
-                                                          const u64* __restrict__ run_start, const u32* __restrict__ cap, u64* __restrict__ out_lo, u64* __restrict__ out_hi,
-                                                          u32* __restrict__ out_count) {
-    const u32 q = blockIdx.x;
-    if (q >= nlong) return;
-    const u32 r = list[q].r;
-    const u32 c = acc_cnt[q] < cap[r] ? acc_cnt[q] : cap[r];  // (an intersection is no longer than its shortest holder, a union than all of them)
-    const u64 src = sc_start[q] + (acc_side[q] ? S : 0ull), d0 = run_start[r];
-    for (u32 j = threadIdx.x; j < c; j += 256) {
-        out_lo[d0 + j] = sc_lo[src + j];
-        if constexpr (WS) out_hi[d0 + j] = sc_hi[src + j];
-    }
-    if (threadIdx.x == 0) out_count[r] = c;
-}
-
-// ---- `a &= &mut b`, `a -= &mut b`, `a ^= &mut b` (cblx_set_op_assign; src/wordset/set_ops.rs:192-239, 281-317, 366-410 walk the prefixes,
-// src/trievec/set_ops.rs:101-129, 163-187, 226-257 the buckets). A bucket both hold keeps a's KIND. A Trie is the ascending result (Trie::remove
-// prunes empty nodes, so the trie is a function of its set): k_bucket_setop's output. A Vec is sorted by iter_sorted, takes the ascending words
-// only b holds at its end (`^=`: insert_sorted_iter) and loses its deletions through remove_sorted_iter: swap_remove on ascending indices in
-// reverse (src/trievec/mod.rs:146-168). With v the Vec remove_sorted_iter scans, n = len(v), D the deleted indices (all inside sorted a),
-// m = |D|, L = n - m and dl(p) the number of deleted indices below p, the result r of length L is
-//     r[i] = v[i]                       for i < L outside D
-//     r[h] = v[s], s = next*(L + dl(h)) for a hole h < L in D, with next(p) = p outside D and L + dl(p) inside D, followed to its fixed point
-// (L + dl(p) = n - |{d in D: d >= p}|: where the last word stood when index p was removed). Chains live in [L, n) and can be as long as m, so
-// they are settled by pointer doubling (next = next o next until nothing moves), never walked by one lane.
-// One thread per candidate prefix, as k_setop_plan: a both-sided bucket keeps a's kind and joins the list of its kernel — [0] a's side a Trie
-// (k_bucket_setop), [1] a's side a Vec of up to SA_LDS words (tables in LDS), [2] a longer Vec (tables in `scratch`, 3 cs + 1 words from
-// BDesc.start on; the sum of those goes to scratch_n).
-static const int SA_THREADS = 256;
-static const u32 SA_LDS = 1024;
-__global__ __launch_bounds__(CLASSIFY_THREADS) void k_setop_assign_plan(u64 nb, u32 op, u32* __restrict__ cap, const u32* __restrict__ m_cs, u32* __restrict__ m_co,
-                                                                         const u64* __restrict__ m_sstart, const u64* __restrict__ m_ostart, const u8* __restrict__ m_skind,
-                                                                         const u8* __restrict__ m_okind, u32* __restrict__ out_count, u8* __restrict__ out_kind,
-                                                                         BDesc* __restrict__ sort_lists /* [2 sides][2 classes][nb] */,
-                                                                         BDesc* __restrict__ both_lists /* [3][nb] */, u32* __restrict__ list_n /* [4] sort lists, [3] both */,
-                                                                         unsigned long long* __restrict__ scratch_n) {
-    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    int cls_a = -1, cls_b = -1, cls_both = -1;
-    u32 cs = 0, co = 0;
-    u64 off = 0;
-    if (r < nb) {
-        cs = m_cs[r];
-        co = cap[r] - cs;
-        m_co[r] = co;
-        if (cs != 0 && co != 0) {
-            cap[r] = op == SETOP_AND ? (cs < co ? cs : co) : op == SETOP_SUB ? cs : cs + co;
-            out_count[r] = 0;  // (written by the bucket's kernel)
-            out_kind[r] = m_skind[r];
-            cls_both = m_skind[r] == KIND_TRIE ? 0 : cs <= SA_LDS ? 1 : 2;
-            if (cls_both == 2) off = atomicAdd(scratch_n, 3ull * cs + 1ull);  // (long Vecs are rare: one atomic each)
-            if (m_skind[r] == KIND_VEC && cs > 1) cls_a = cs <= SETOP_SORT_LDS ? 0 : 1;
-            if (m_okind[r] == KIND_VEC && co > 1) cls_b = co <= SETOP_SORT_LDS ? 0 : 1;
-        } else {  // one-sided (never for AND, never b's side for SUB: such prefixes are no candidates): cloned as stored
-            cap[r] = cs + co;
-            out_count[r] = cs + co;
-            out_kind[r] = cs ? m_skind[r] : m_okind[r];
-        }
-    }
-    const u32 slot_a = block_append<CLASSIFY_THREADS, 2>(cls_a, list_n);
-    if (cls_a >= 0) sort_lists[(u64)cls_a * nb + slot_a] = BDesc{m_sstart[r], cs | BDESC_TRIE, (u32)r};  // (TRIE: the kernel leaves the run sorted)
-    __syncthreads();  // block_append's tables are reused
-    const u32 slot_b = block_append<CLASSIFY_THREADS, 2>(cls_b, list_n + 2);
-    if (cls_b >= 0) sort_lists[(u64)(2 + cls_b) * nb + slot_b] = BDesc{m_ostart[r], co | BDESC_TRIE, (u32)r};
-    const u32 slot = block_append<CLASSIFY_THREADS, 3>(cls_both, list_n + 4);
-    if (cls_both >= 0) both_lists[(u64)cls_both * nb + slot] = BDesc{off, 0, (u32)r};
-}
-template <bool WS> __device__ __forceinline__ UniE<WS> sa_load(const u64* __restrict__ lo, const u64* __restrict__ hi, u32 i, u64 mask) {
-    UniE<WS> e;
-    if constexpr (WS) { e.lo = lo[i]; e.hi = hi[i] & mask; }
-    else e.lo = lo[i] & mask;
-    return e;
-}
-// is x one of the n ascending words of (lo, hi)?
-template <bool WS> __device__ __forceinline__ bool sa_member(const u64* __restrict__ lo, const u64* __restrict__ hi, u32 n, u64 mask, const UniE<WS>& x) {
-    u32 l = 0, h = n;
-    while (l < h) {
-        const u32 mid = l + ((h - l) >> 1);
-        if (uni_lt<WS>(sa_load<WS>(lo, hi, mid, mask), x)) l = mid + 1; else h = mid;
-    }
-    return l < n && uni_eq<WS>(sa_load<WS>(lo, hi, l, mask), x);
-}
-// One workgroup per both-sided bucket whose a side is a Vec; both runs are ascending in their arenas (a's was sorted there, as b's if it is a Vec).
-//   1. every word of a is looked up in b by binary search — its index in sorted a is the index remove_sorted_iter finds, so no merge has to carry
-//      it: deleted = absent (AND) / present (SUB, XOR); an ordered count of the flags gives dl[0 .. cs], dl[cs] = m;
-//   2. XOR: the words of b that a lacks, in order, go to dst[cs ..) — the places insert_sorted_iter pushes them to;
-//   3. next[] over the tail [L, cs) of sorted a (beyond cs nothing is deleted: a fixed point), doubled until no entry moves;
-//   4. dst[i], i < min(L, cs): a[i] if it stays, else v[next*(L + dl(i))], read from a below cs and from the pushed words (dst itself, at or
-//      beyond cs, where step 4 writes nothing) above.
-// BIG: dl and the two copies of next[] sit in global memory instead of LDS; the steps are the same.
-template <bool WS, u32 OP, bool BIG>
-__global__ __launch_bounds__(SA_THREADS) void k_bucket_setop_assign(const BDesc* __restrict__ list, const u32* __restrict__ list_n, const u32* __restrict__ m_cs,
-                                                                    const u32* __restrict__ m_co, const u64* __restrict__ m_sstart, const u64* __restrict__ m_ostart,
-                                                                    const u64* __restrict__ s_lo, const u64* __restrict__ s_hi, const u64* __restrict__ o_lo,
-                                                                    const u64* __restrict__ o_hi, const u64* __restrict__ run_start, u64* out_lo, u64* out_hi, u32 SB,
-                                                                    u32* __restrict__ out_count, u8* __restrict__ out_kind, u32* scratch) {
-    typedef UniE<WS> E;
-    static_assert(OP == SETOP_AND || OP == SETOP_SUB || OP == SETOP_XOR, "`|=` is cblx_merge_assign");
-    constexpr int NW = SA_THREADS / 64;
-    __shared__ u32 s_dl[BIG ? 1 : SA_LDS + 1];
-    __shared__ u32 s_nx[BIG ? 1 : 2 * SA_LDS];
-    __shared__ u32 s_wtot[NW];
-    if (blockIdx.x >= *list_n) return;
-    const BDesc dsc = list[blockIdx.x];
-    const u32 r = dsc.r, cs = m_cs[r], co = m_co[r];
-    const u64 a_self = m_sstart[r], a_oth = m_ostart[r], d_run = run_start[r];
-    const u64* __restrict__ A = s_lo + a_self;
-    const u64* __restrict__ B = o_lo + a_oth;
-    const u64* __restrict__ Ah = WS ? s_hi + a_self : nullptr;
-    const u64* __restrict__ Bh = WS ? o_hi + a_oth : nullptr;
-    u64* dst = out_lo + d_run;
-    u64* dsth = WS ? out_hi + d_run : nullptr;
-    const u64 mask = WS ? ((1ull << (SB - 64)) - 1ull) : (SB >= 64 ? ~0ull : ((1ull << SB) - 1ull));
-    const u32 tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    u32 *dl, *nx0, *nx1;
-    if constexpr (BIG) { dl = scratch + dsc.start; nx0 = dl + cs + 1; nx1 = nx0 + cs; }
-    else { dl = s_dl; nx0 = s_nx; nx1 = s_nx + SA_LDS; }
-    // flags of the workgroup's threads in thread order: -> how many are set in front of this thread; returns how many are set in all
-    auto count_before = [&](bool f, u32& before) {
-        const u64 bal = __ballot(f);
-        if (lane == 0) s_wtot[w] = (u32)__builtin_popcountll(bal);
-        __syncthreads();
-        u32 run = 0, tot = 0;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) { const u32 t = s_wtot[ww]; if ((u32)ww < w) run += t; tot += t; }
-        before = run + mbcnt(bal);
-        __syncthreads();  // s_wtot is rewritten by the next call
-        return tot;
-    };
-    u32 m = 0;
-    for (u32 base = 0; base < cs; base += SA_THREADS) {
-        const u32 i = base + tid;
-        bool del = false;
-        if (i < cs) del = sa_member<WS>(B, Bh, co, mask, sa_load<WS>(A, Ah, i, mask)) != (OP == SETOP_AND);
-        u32 before;
-        const u32 tot = count_before(del, before);
-        if (i < cs) dl[i] = m + before;
-        m += tot;
-    }
-    if (tid == 0) dl[cs] = m;
-    u32 ins = 0;
-    if constexpr (OP == SETOP_XOR) {
-        for (u32 base = 0; base < co; base += SA_THREADS) {
-            const u32 j = base + tid;
-            E y = uni_inf<WS>();
-            bool push = false;
-            if (j < co) { y = sa_load<WS>(B, Bh, j, mask); push = !sa_member<WS>(A, Ah, cs, mask, y); }
-            u32 before;
-            const u32 tot = count_before(push, before);
-            if (push) {
-                dst[cs + ins + before] = y.lo;
-                if constexpr (WS) dsth[cs + ins + before] = y.hi;
-            }
-            ins += tot;
-        }
-    }
-    const u32 L = cs + ins - m, low = L < cs ? L : cs;
-    __syncthreads();
-    u32* cur = nx0;
-    if (L < cs) {
-        const u32 T = cs - L;
-        for (u32 q = tid; q < T; q += SA_THREADS) {
-            const u32 p = L + q, d0 = dl[p];
-            nx0[q] = dl[p + 1] != d0 ? L + d0 : p;
-        }
-        __syncthreads();
-        u32* nxt = nx1;
-        for (;;) {
-            bool moved = false;
-            for (u32 q = tid; q < T; q += SA_THREADS) {
-                const u32 v = cur[q], v2 = v < cs ? cur[v - L] : v;
-                nxt[q] = v2;
-                moved = moved || v2 != v;
-            }
-            u32* const t = cur; cur = nxt; nxt = t;
-            if (!__syncthreads_or(moved)) break;
-        }
-    }
-    for (u32 i = tid; i < low; i += SA_THREADS) {
-        const u32 d0 = dl[i];
-        u32 s = i;
-        if (dl[i + 1] != d0) { s = L + d0; if (s < cs) s = cur[s - L]; }
-        E e;
-        if (s < cs) e = sa_load<WS>(A, Ah, s, mask);
-        else { e.lo = dst[s]; if constexpr (WS) e.hi = dsth[s]; }
-        dst[i] = e.lo;
-        if constexpr (WS) dsth[i] = e.hi;
-    }
-    if (tid == 0) { out_count[r] = L; out_kind[r] = KIND_VEC; }
 }
 
 // ---- suffix access --------------------------------------------------------------------------------------

@@ -25,16 +25,16 @@ from oracle.pyref import PyCBL
 
 import setops_model as sm
 
-VEC, TRIE = 0, 1           # kernels_bucket.hpp:25 KIND_VEC / KIND_TRIE
+VEC, TRIE = 0, 1           # kernels_bucket.hpp: KIND_VEC / KIND_TRIE
 THRESHOLD = 1024           # common.hpp:30 VEC_THRESHOLD
-SMALL_MAX = 32             # kernels_bucket.hpp:137 SMALL_MAX: all-pairs in a slice of a wave up to here
-MED_ITEMS = 8              # kernels_bucket.hpp:138 MED_ITEMS: slots per lane of the counting-sort classes
-BIG_MAX = 1 << 18          # kernels_bucket.hpp:131 BIG_MAX: longest run of the split path
-BIG_SUB = 1024             # kernels_bucket.hpp:131 BIG_SUB: words per sub-range big_bits aims at
-LDS_MAX = 4096             # pipeline.hpp:611 k_classify's lds_max, the same for every suffix width
-PK_BITS = 12               # kernels_bucket.hpp:1705 PK_BITS: a packed element is suffix + 12-bit position in 64 bits
-MSD_MAX_BITS = 128         # kernels_bucket.hpp:1720 msd_takes: wide suffixes up to SB + 12 <= 128 take the counting sort, wider ones the radix kernel
-DIRECT_UPTO = 512 * MED_ITEMS  # pipeline.hpp:1477 direct_upto: both-sided buckets `|=` reads in place
+SMALL_MAX = 32             # kernels_bucket.hpp: SMALL_MAX, all-pairs in a slice of a wave up to here
+MED_ITEMS = 8              # kernels_bucket.hpp: MED_ITEMS, slots per lane of the counting-sort classes
+BIG_MAX = 1 << 18          # kernels_bucket.hpp: BIG_MAX, longest run of the split path
+BIG_SUB = 1024             # kernels_bucket.hpp: BIG_SUB, words per sub-range big_bits aims at
+LDS_MAX = 4096             # pipeline.hpp: bucket_stage, k_classify's lds_max, the same for every suffix width
+PK_BITS = 12               # kernels_bucket.hpp: PK_BITS, a packed element is suffix + 12-bit position in 64 bits
+MSD_MAX_BITS = 128         # kernels_bucket.hpp: msd_takes, wide suffixes up to SB + 12 <= 128 take the counting sort, wider ones the radix kernel
+DIRECT_UPTO = 512 * MED_ITEMS  # setops.hpp: merge_direct, direct_upto, both-sided buckets `|=` reads in place
 
 BUILD_CLASSES = ("CLS_S16", "CLS_S32", "CLS_M16", "CLS_M32", "CLS_M64", "CLS_M128", "CLS_M256", "CLS_M512", "CLS_BIG", "CLS_HUGE")
 MERGE_CLASSES = ("CLS_UNION", "CLS_M16", "CLS_M64", "CLS_M128", "CLS_M256", "CLS_M512", "CLS_BIG", "CLS_M1024", "CLS_HUGE")
@@ -42,7 +42,7 @@ MSD_CLASSES = ("CLS_M16", "CLS_M32", "CLS_M64", "CLS_M128", "CLS_M256", "CLS_M51
 
 
 def classify_build(rc, rkind, c, lds_max=LDS_MAX):
-    """k_classify (kernels_bucket.hpp:191-205): resident count, resident kind, run length -> class, "untouched" or "single"."""
+    """k_classify (kernels_bucket.hpp): resident count, resident kind, run length -> class, "untouched" or "single"."""
     if rc != 0 and c == rc:
         return "untouched"                                   # :191
     if c == 1 and rc == 0:
@@ -65,7 +65,7 @@ def classify_build(rc, rkind, c, lds_max=LDS_MAX):
 
 
 def classify_merge(cs, co, ks, ko, wide, union_path=True):
-    """k_classify_merge (kernels_bucket.hpp:311-321); med_max_threads is 512 for wide suffixes, 1024 otherwise (pipeline.hpp:1493)."""
+    """k_classify_merge (kernels_bucket.hpp); med_max_threads is 512 for wide suffixes, 1024 otherwise (setops.hpp: merge_direct)."""
     c = cs + co
     if co == 0:
         return "self_only"                                   # :311
@@ -91,7 +91,7 @@ def classify_merge(cs, co, ks, ko, wide, union_path=True):
 
 
 def big_bits(c):
-    """kernels_bucket.hpp:132-136: a big run is cut into 2^bits sub-ranges; the count changes at 8193, 16385, ..."""
+    """kernels_bucket.hpp: big_bits. A big run is cut into 2^bits sub-ranges; the count changes at 8193, 16385, ..."""
     b = 1
     while b < 8 and ((c - 1) >> b) >= BIG_SUB:
         b += 1
@@ -111,9 +111,9 @@ def props(name):
     k, pb = CONFIGS[name]
     sb = pyref.params(k, pb)["SB"]
     wide = sb > 64                                           # common.hpp:26 wide_suffix
-    return dict(k=k, pb=pb, sb=sb, wide=wide, packed=not wide and sb + PK_BITS <= 64,  # pipeline.hpp:735
+    return dict(k=k, pb=pb, sb=sb, wide=wide, packed=not wide and sb + PK_BITS <= 64,  # pipeline.hpp: bucket_stage, `stage`
                 msd=not wide or sb + 12 <= MSD_MAX_BITS,     # msd_takes
-                prepass=not wide and sb < 64)                # pipeline.hpp:751-752
+                prepass=not wide and sb < 64)                # pipeline.hpp: bucket_stage, the pre-pass of the long runs
 
 
 # ---- the model -------------------------------------------------------------------------------------------------------------------------------
@@ -482,9 +482,9 @@ def merge_classes(shape, union_path):
 
 
 def merge_units(shape, union_path, direct, result):
-    """The words cblx_stage_units reports for one `|=` (pipeline.hpp:1590-1608), from the restated classification; `result`: the merged model."""
+    """The words cblx_stage_units reports for one `|=` (setops.hpp: merge_direct, `prof`), from the restated classification; `result`: the merged model."""
     wide = shape.sb > 64
-    direct = direct and (not wide or shape.sb + 12 <= MSD_MAX_BITS)  # pipeline.hpp:1476
+    direct = direct and (not wide or shape.sb + 12 <= MSD_MAX_BITS)  # setops.hpp: merge_direct, `direct`
     un = {"merge_gather": 0, "bucket_medium": 0, "bucket_huge": 0, "bucket_big": 0}
     for p in set(shape.a) | set(shape.b):
         cs, co = len(shape.a.get(p, (0, ()))[1]), len(shape.b.get(p, (0, ()))[1])

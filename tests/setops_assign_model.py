@@ -176,7 +176,7 @@ def swap_remove_closed_form(v, D):
 
 
 def fixup_by_doubling(v, D, cs):
-    """What k_bucket_setop_assign computes (cbl_amd/csrc/kernels_bucket.hpp): v = sorted a (cs words) ++ pushed words, D inside [0, cs).
+    """What k_bucket_setop_assign computes (cbl_amd/csrc/kernels_setops.hpp): v = sorted a (cs words) ++ pushed words, D inside [0, cs).
     dl[p] = deleted indices below p (dl[cs] = m); next[] over the tail [L, cs) — beyond cs nothing is deleted — doubled until nothing moves;
     r[i] = v[i] or v[next*(L + dl[i])]. -> (r, rounds of doubling)"""
     n, m = len(v), len(D)

@@ -8,12 +8,12 @@ intersect. Per visited prefix:
     `TrieVec::new().insert_sorted_iter(union)`, src/trievec/mod.rs:118-131 — a Vec, ascending, whatever its length;
   * intersect: `iter_sorted` on every operand; the result is Vec(ascending intersection), dropped when empty. Nothing else in any operand changes.
 `merge` / `intersect` return a new PyCBL and mutate their operands the way the reference does; `PyCBL.serialize()` gives the expected bytes of all.
-The second half restates the short route of k_bucket_setop_many (cbl_amd/csrc/kernels_bucket.hpp) thread by thread."""
+The second half restates the short route of k_bucket_setop_many (cbl_amd/csrc/kernels_setops.hpp) thread by thread."""
 from bisect import bisect_left, bisect_right
 
 from oracle.pyref import PyCBL
 
-MANY_SMALL, MANY_LDS = 256, 2048  # kernels_bucket.hpp: words of all holders one wave / one workgroup stages in LDS; longer buckets are folded
+MANY_SMALL, MANY_LDS = 256, 2048  # kernels_setops.hpp: words of all holders one wave / one workgroup stages in LDS; longer buckets are folded
 MAX_OPERANDS = 64  # include/cblx.h CBLX_SETOP_MAX_OPERANDS
 
 

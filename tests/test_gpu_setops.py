@@ -19,8 +19,8 @@ from oracle.pyref import PyCBL, params  # noqa: E402
 import query_shapes as qs  # noqa: E402  (tests/)
 import setops_model as sm  # noqa: E402  (tests/)
 
-T = 512  # kernels_bucket.hpp UNI_TILE = UNI_THREADS * UNI_ITEMS = 128 * 4: outputs of one round of k_bucket_setop
-SORT_LDS = 4096  # kernels_bucket.hpp SETOP_SORT_LDS: the longest Vec side one workgroup sorts in LDS; longer ones take the general kernel
+T = 512  # kernels_setops.hpp UNI_TILE = UNI_THREADS * UNI_ITEMS = 128 * 4: outputs of one round of k_bucket_setop
+SORT_LDS = 4096  # kernels_setops.hpp SETOP_SORT_LDS: the longest Vec side one workgroup sorts in LDS; longer ones take the general kernel
 
 
 def _need_gpu():

@@ -23,9 +23,9 @@ import setops_assign_model as am  # noqa: E402  (tests/)
 import setops_model as sm  # noqa: E402  (tests/)
 
 ROOT = Path(__file__).resolve().parent.parent
-T = 512  # kernels_bucket.hpp UNI_TILE: outputs of one round of k_bucket_setop (a's side a Trie)
-SORT_LDS = 4096  # kernels_bucket.hpp SETOP_SORT_LDS: the longest Vec side one workgroup sorts in LDS
-SA_LDS = 1024  # kernels_bucket.hpp SA_LDS: the longest Vec whose fix-up tables sit in LDS
+T = 512  # kernels_setops.hpp UNI_TILE: outputs of one round of k_bucket_setop (a's side a Trie)
+SORT_LDS = 4096  # kernels_setops.hpp SETOP_SORT_LDS: the longest Vec side one workgroup sorts in LDS
+SA_LDS = 1024  # kernels_setops.hpp SA_LDS: the longest Vec whose fix-up tables sit in LDS
 LENGTHS = (1, 2, 3, 63, 64, 65, T - 1, T, T + 1, 2 * T + 1, 1024, 1025, 4096, 4097, 5000)
 CONFIGS = [(31, 24), (59, 28)]  # SUFFIX_BITS 43 (one word) and 97 (two words)
 assert SA_LDS in LENGTHS and SA_LDS + 1 in LENGTHS and SORT_LDS in LENGTHS and SORT_LDS + 1 in LENGTHS

@@ -26,8 +26,8 @@ import setops_model as sm  # noqa: E402  (tests/)
 
 ROOT = Path(__file__).resolve().parent.parent
 OPS = ("or", "and")
-MANY_SMALL, MANY_LDS = mm.MANY_SMALL, mm.MANY_LDS  # kernels_bucket.hpp (tests/test_setops_many_model.py compares the values)
-SORT_LDS = 4096  # kernels_bucket.hpp SETOP_SORT_LDS
+MANY_SMALL, MANY_LDS = mm.MANY_SMALL, mm.MANY_LDS  # kernels_setops.hpp (tests/test_setops_many_model.py compares the values)
+SORT_LDS = 4096  # kernels_setops.hpp SETOP_SORT_LDS
 
 
 def _need_gpu():

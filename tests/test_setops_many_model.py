@@ -1,7 +1,7 @@
 """CPU checks of the n-ary set operations CBL.merge / CBL.intersect (cblx_set_op_many):
 (a) tests/setops_many_model.py — the expected bytes of every GPU test — as sets, against tests/setops_model.py at n = 2, and where it differs from a
     FOLD of the binary operation (the reason the n-ary form is no fold);
-(b) the short route of `k_bucket_setop_many` (cbl_amd/csrc/kernels_bucket.hpp) restated thread by thread: the merged position by binary searches with the
+(b) the short route of `k_bucket_setop_many` (cbl_amd/csrc/kernels_setops.hpp) restated thread by thread: the merged position by binary searches with the
     `<=` / `<` tie rule, the kept flags, the ordered compaction; the search over the shortest run for intersect;
 (c) the ABI: header, ctypes signatures, the Rust crates, and the thresholds the GPU tests mirror."""
 import itertools
@@ -205,7 +205,7 @@ def test_python_refuses_before_the_call():
 
 
 def test_thresholds_the_gpu_tests_mirror():
-    src = (ROOT / "cbl_amd" / "csrc" / "kernels_bucket.hpp").read_text()
+    src = (ROOT / "cbl_amd" / "csrc" / "kernels_setops.hpp").read_text()
     m = re.search(r"static const u32 MANY_SMALL = (\d+), MANY_LDS = (\d+);", src)
     assert m and (int(m.group(1)), int(m.group(2))) == (mm.MANY_SMALL, mm.MANY_LDS)
     assert re.search(r"static const u32 MANY_MAX = 64;", src)

@@ -1,6 +1,6 @@
 """CPU checks of the set operations `a | b`, `a & b`, `a - b`, `a ^ b` (cblx_set_op):
 (a) tests/setops_model.py — the expected bytes of every GPU test — against the C++ oracle where the two overlap;
-(b) `k_bucket_setop`'s rounds (cbl_amd/csrc/kernels_bucket.hpp) restated thread by thread, as tests/test_union_rounds_model.py does for the union: the
+(b) `k_bucket_setop`'s rounds (cbl_amd/csrc/kernels_setops.hpp) restated thread by thread, as tests/test_union_rounds_model.py does for the union: the
     two staging rings, the co-rank on the round's diagonal, the merge network, the origin of an output recovered from the candidates the thread
     still holds, the round's last output HELD BACK until its successor is known, the ordered compaction;
 (c) the ABI: header, ctypes signatures and the Rust sys crate name the new function and its four constants."""
@@ -18,7 +18,7 @@ from oracle.pyref import PyCBL
 
 ROOT = Path(__file__).resolve().parent.parent
 INF = (1 << 64) - 1
-UNI_THREADS, UNI_ITEMS = 128, 4  # kernels_bucket.hpp UNI_THREADS / UNI_ITEMS: the kernel's tile is their product
+UNI_THREADS, UNI_ITEMS = 128, 4  # kernels_setops.hpp UNI_THREADS / UNI_ITEMS: the kernel's tile is their product
 
 
 # ---------------------------------------------------------------- (a) the model against the oracle

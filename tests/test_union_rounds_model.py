@@ -1,4 +1,4 @@
-"""A model of `k_bucket_union`'s rounds (cbl_amd/csrc/kernels_bucket.hpp; Trie |= Trie, /root/reference/src/trievec/set_ops.rs:43-71 merges two
+"""A model of `k_bucket_union`'s rounds (cbl_amd/csrc/kernels_setops.hpp; Trie |= Trie, /root/reference/src/trievec/set_ops.rs:43-71 merges two
 ascending iterators with two pointers and drops other's copy of a word self holds): the index arithmetic of the kernel restated thread by thread in
 Python — the two staging RINGS of T slots (word g of a list in slot g mod T, only the slots a round consumed are refilled, the round's outputs pass
 through exactly those slots), the co-rank of every thread's last output by binary search on the round's diagonal (ties take self's copy first), the
