@@ -143,6 +143,14 @@ SIGNATURES = {
     "cblx_contains_seqs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                             C.POINTER(C.c_uint64)]),
     "cblx_query_fastx_file": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_contains_seqs_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64)]),
+    "cblx_contains_seqs_counts_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.c_uint64)]),
+    "cblx_contains_seqs_flags_counts_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_query_fastx_file_counts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_uint64)]),
     "cblx_contains_all": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_int)]),
     "cblx_insert_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cblx_remove_words_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
@@ -674,6 +682,60 @@ class CBL:
         nrec, tot, pos = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         self._chk(self._L.cblx_query_fastx_file(self._h, os.fsencode(path), C.byref(nrec), C.byref(tot), C.byref(pos)))
         return nrec.value, tot.value, pos.value
+
+    # ---- per-sequence tallies: (k-mers queried, k-mers found) of every sequence; the flags never leave the device ------------------
+    def contains_seqs_counts(self, bases, offsets):
+        """contains_seq for a batch, reduced per sequence on the device: (total uint32[n], positive uint32[n]) — the k-mers of every
+        sequence queried and found (include/cblx.h cblx_contains_seqs_counts)."""
+        import numpy as np
+
+        n = max(len(offsets) - 1, 0)
+        total, positive = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        tot, pos = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_contains_seqs_counts(self._h, _ptr(bases), _ptr(offsets), n, _ptr(total), _ptr(positive), C.byref(tot), C.byref(pos)))
+        return total, positive
+
+    def contains_seqs_counts_device(self, d_bases, d_offsets, n: int, d_total=None, d_positive=None, d_flags=None):
+        """Device-resident batch; returns the two tensors (n uint32 each, int32 storage: torch has no arithmetic on uint32), allocated on
+        d_bases' device when not given. d_flags (uint8 tensor) also receives the flags, as contains_seqs_device's d_out does."""
+        import torch
+
+        if d_total is None:
+            d_total = torch.empty(n, dtype=torch.int32, device=d_bases.device)
+        if d_positive is None:
+            d_positive = torch.empty(n, dtype=torch.int32, device=d_bases.device)
+        tot, pos = C.c_uint64(0), C.c_uint64(0)
+        if d_flags is None:
+            self._chk(self._L.cblx_contains_seqs_counts_device(self._h, _ptr(d_bases), _ptr(d_offsets), n, _ptr(d_total), _ptr(d_positive), C.byref(tot), C.byref(pos)))
+        else:
+            self._chk(self._L.cblx_contains_seqs_flags_counts_device(self._h, _ptr(d_bases), _ptr(d_offsets), n, _ptr(d_flags), d_flags.numel(), _ptr(d_total),
+                                                                     _ptr(d_positive), C.byref(tot), C.byref(pos)))
+        return d_total, d_positive
+
+    def query_fastx_file_counts(self, path):
+        """`cbl query` per record: (total uint32[records], positive uint32[records]) of a FASTA/FASTQ(.gz) file, record i = the i-th
+        record of the file. The arrays are sized with count_fastx_records; the index is not modified."""
+        import numpy as np
+
+        cap = self.count_fastx_records(path)
+        total, positive = np.empty(cap, dtype=np.uint32), np.empty(cap, dtype=np.uint32)
+        nrec, tot, pos = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_query_fastx_file_counts(self._h, os.fsencode(path), _ptr(total), _ptr(positive), cap, C.byref(nrec), C.byref(tot), C.byref(pos)))
+        return total[: nrec.value], positive[: nrec.value]
+
+    @staticmethod
+    def matching(total, positive, min_fraction: float = 0.5, min_hits: int = 0):
+        """The screening rule on per-sequence counts (host, numpy): positive >= max(min_hits, ceil(min_fraction * total)) and
+        total > 0 — a sequence without a k-mer never matches."""
+        import numpy as np
+
+        total, positive = np.asarray(total, dtype=np.int64), np.asarray(positive, dtype=np.int64)
+        need = np.maximum(np.ceil(min_fraction * total).astype(np.int64), int(min_hits))
+        return (total > 0) & (positive >= need)
+
+    def matching_seqs(self, bases, offsets, min_fraction: float = 0.5, min_hits: int = 0):
+        """Which sequences of the batch match the index: the boolean mask `matching` of contains_seqs_counts."""
+        return self.matching(*self.contains_seqs_counts(bases, offsets), min_fraction=min_fraction, min_hits=min_hits)
 
     def contains_all(self, seq: bytes) -> bool:
         """True if the set contains all the k-mers of a sequence (src/cbl.rs:293-307)."""

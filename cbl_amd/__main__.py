@@ -96,6 +96,8 @@ def main(argv=None):
     q = sub.add_parser("query", help="Query an index for every k-mer contained in a FASTA/Q file")
     q.add_argument("index")
     q.add_argument("input")
+    q.add_argument("--per-record", metavar="OUT", help="also write one line per record to OUT ('-': stdout): its 0-based position in the file, the k-mers "
+                   "queried and the k-mers found, tab-separated")
     ls = sub.add_parser("list", help="List the k-mers contained in an index")
     ls.add_argument("index")
     ls.add_argument("-o", "--output")
@@ -156,7 +158,17 @@ def main(argv=None):
     elif a.cmd == "query":  # examples/cbl.rs:205-228
         cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
         print(f"Querying the {'canonical ' if cbl.is_canonical() else ''}{a.k}-mers contained in {a.input}", file=sys.stderr)
-        _, total, positive = cbl.query_fastx_file(a.input)
+        if a.per_record is None:
+            _, total, positive = cbl.query_fastx_file(a.input)
+        else:  # the parser keeps no record names: a record is known by its position in the file
+            rec_total, rec_positive = cbl.query_fastx_file_counts(a.input)
+            total, positive = int(rec_total.sum(dtype="uint64")), int(rec_positive.sum(dtype="uint64"))
+            out = sys.stdout if a.per_record == "-" else open(a.per_record, "w")
+            try:
+                out.write("".join(f"{i}\t{t}\t{p}\n" for i, (t, p) in enumerate(zip(rec_total.tolist(), rec_positive.tolist()))))
+            finally:
+                if out is not sys.stdout:
+                    out.close()
         print(f"# queries: {total}", file=sys.stderr)
         print(f"# positive queries: {positive} ({positive * 100 / total if total else float('nan'):.2f}%)", file=sys.stderr)
         print(total, positive)

@@ -407,26 +407,37 @@ int cblx_flush(cblx_ctx* c) { return guard(c, [&] { flush(c); }); }
 int cblx_insert_fastx_file(cblx_ctx* c, const char* path, uint64_t* n_records) {
     return guard(c, [&] { read_fastx_into_queue(c, path, n_records); });
 }
+// the `cbl query` reader loop; rec_total / rec_positive (host, `cap` entries each, either may be null) take the per-record tallies
+static void query_fastx(cblx_ctx* c, const char* path, u32* rec_total, u32* rec_positive, u64 cap, uint64_t* n_records, uint64_t* total, uint64_t* positive) {
+    if (total) *total = 0;
+    if (positive) *positive = 0;
+    flush(c);  // pending inserts first: the queue changes consumer
+    Ingest& g = c->ing;
+    struct Restore { Ingest& g; ~Restore() { g.query = false; g.q_rec_total = g.q_rec_positive = nullptr; g.q_rec_cap = g.q_rec_base = 0; g.q_rec_over = false; } } restore{g};
+    g.query = true;
+    g.q_total = g.q_positive = 0;
+    g.q_rec_total = rec_total;
+    g.q_rec_positive = rec_positive;
+    g.q_rec_cap = cap;
+    g.q_rec_base = 0;
+    g.q_rec_over = false;
+    try {
+        read_fastx_into_queue(c, path, n_records);
+        flush(c);
+    } catch (...) {
+        ingest_drop(c);
+        throw;
+    }
+    if (total) *total = g.q_total;
+    if (positive) *positive = g.q_positive;
+    if (g.q_rec_over) throw Error(CBLX_ERANGE, "output capacity too small: the file holds " + std::to_string(g.q_rec_base) + " records");
+}
 int cblx_query_fastx_file(cblx_ctx* c, const char* path, uint64_t* n_records, uint64_t* total, uint64_t* positive) {
-    return guard(c, [&] {
-        if (total) *total = 0;
-        if (positive) *positive = 0;
-        flush(c);  // pending inserts first: the queue changes consumer
-        Ingest& g = c->ing;
-        g.query = true;
-        g.q_total = g.q_positive = 0;
-        try {
-            read_fastx_into_queue(c, path, n_records);
-            flush(c);
-        } catch (...) {
-            ingest_drop(c);
-            g.query = false;
-            throw;
-        }
-        g.query = false;
-        if (total) *total = g.q_total;
-        if (positive) *positive = g.q_positive;
-    });
+    return guard(c, [&] { query_fastx(c, path, nullptr, nullptr, 0, n_records, total, positive); });
+}
+int cblx_query_fastx_file_counts(cblx_ctx* c, const char* path, uint32_t* rec_total, uint32_t* rec_positive, uint64_t cap, uint64_t* n_records, uint64_t* total,
+                                 uint64_t* positive) {
+    return guard(c, [&] { query_fastx(c, path, rec_total, rec_positive, cap, n_records, total, positive); });
 }
 
 int cblx_stage_fastx_blocks(cblx_ctx* c, const char* path, uint64_t block, uint32_t rank, uint32_t world, const uint8_t** d_bases,
@@ -1240,6 +1251,50 @@ int cblx_contains_seqs_device(cblx_ctx* c, const uint8_t* d_bases, const uint64_
         query_device(c, d_bases, d_offsets, n, d_out, cap, n_out, positive);
         CBLX_HIP(hipStreamSynchronize(c->stream));
     });
+}
+int cblx_contains_seqs_counts(cblx_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n, uint32_t* seq_total, uint32_t* seq_positive, uint64_t* n_out,
+                              uint64_t* positive) {
+    return guard(c, [&] {
+        if (n_out) *n_out = 0;
+        if (positive) *positive = 0;
+        flush(c);
+        if (n == 0) return;
+        if (!bases || !offsets) throw Error(CBLX_EINVAL, "null argument");
+        u64 minlen = ~0ull;
+        bool mono = true;
+        for (u64 i = 0; i < n; ++i) { mono &= offsets[i + 1] >= offsets[i]; minlen = std::min(minlen, offsets[i + 1] - offsets[i]); }
+        if (!mono) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
+        if (minlen < c->P.K) throw Error(CBLX_ESHORT, "Sequence size (" + std::to_string(minlen) + ") is smaller than K (" + std::to_string(c->P.K) + ")");
+        const u64 b0 = offsets[0], nb = offsets[n] - b0;
+        Buf<u8> d_b(c->pool, nb + 64);
+        Buf<u64> d_o(c->pool, n + 1);
+        Buf<u32> d_tot(c->pool, seq_total ? n : 1), d_pos(c->pool, seq_positive ? n : 1);
+        std::vector<u64> rel(n + 1);
+        for (u64 i = 0; i <= n; ++i) rel[i] = offsets[i] - b0;
+        xfer(c).h2d_copy(d_b.get(), bases + b0, nb);  // pinned lanes: the caller's buffers are pageable
+        xfer(c).h2d_copy(d_o.get(), rel.data(), (n + 1) * 8);
+        xfer(c).sync();
+        query_device(c, d_b.get(), d_o.get(), n, nullptr, 0, n_out, positive, seq_total ? d_tot.get() : nullptr, seq_positive ? d_pos.get() : nullptr);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+        if (seq_total) xfer(c).d2h_copy(seq_total, d_tot.get(), n * 4);  // 8 bytes per sequence come back, not a byte per k-mer
+        if (seq_positive) xfer(c).d2h_copy(seq_positive, d_pos.get(), n * 4);
+    });
+}
+int cblx_contains_seqs_flags_counts_device(cblx_ctx* c, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n, uint8_t* d_out, uint64_t cap,
+                                           uint32_t* d_seq_total, uint32_t* d_seq_positive, uint64_t* n_out, uint64_t* positive) {
+    return guard(c, [&] {
+        if (n_out) *n_out = 0;
+        if (positive) *positive = 0;
+        flush(c);
+        if (n == 0) return;
+        if (!d_bases || !d_offsets) throw Error(CBLX_EINVAL, "null argument");
+        query_device(c, d_bases, d_offsets, n, d_out, cap, n_out, positive, d_seq_total, d_seq_positive);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+int cblx_contains_seqs_counts_device(cblx_ctx* c, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n, uint32_t* d_seq_total, uint32_t* d_seq_positive,
+                                     uint64_t* n_out, uint64_t* positive) {
+    return cblx_contains_seqs_flags_counts_device(c, d_bases, d_offsets, n, nullptr, 0, d_seq_total, d_seq_positive, n_out, positive);
 }
 int cblx_contains_all(cblx_ctx* c, const uint8_t* seq, uint64_t len, int* out) {
     return guard(c, [&] {

@@ -162,6 +162,12 @@ struct Ingest {
     bool query = false;
     bool remove = false;  // with `query`: the queue feeds remove_device instead (cblx_remove_fastx_file)
     u64 q_total = 0, q_positive = 0;
+    // with `query` alone (cblx_query_fastx_file_counts): host arrays of q_rec_cap entries that take the per-record tallies of every flush at
+    // q_rec_base, the records queried so far; q_rec_over: the file holds more records than that (nothing more is written)
+    u32* q_rec_total = nullptr;
+    u32* q_rec_positive = nullptr;
+    u64 q_rec_cap = 0, q_rec_base = 0;
+    bool q_rec_over = false;
 };
 
 // a fully partitioned batch of words waiting to be exported (multi-GPU build, sender side)

@@ -247,7 +247,19 @@ void flush(cblx_ctx* c) {
         remove_device(c, g.d_bases.get(), g.d_off.get(), nseq);
     } else if (g.query) {  // examples/cbl.rs:205-228: contains_seq per record, tallies only
         u64 tot = 0, pos = 0;
-        query_device(c, g.d_bases.get(), g.d_off.get(), nseq, nullptr, 0, &tot, &pos);
+        const bool per_rec = (g.q_rec_total || g.q_rec_positive) && !g.q_rec_over;
+        if (per_rec && g.q_rec_base + nseq > g.q_rec_cap) g.q_rec_over = true;  // the caller learns the record count and comes back
+        if (per_rec && !g.q_rec_over) {  // this flush's pairs go to their place behind those of the flushes before it
+            Buf<u32> d_tot(c->pool, g.q_rec_total ? nseq : 1), d_pos(c->pool, g.q_rec_positive ? nseq : 1);
+            query_device(c, g.d_bases.get(), g.d_off.get(), nseq, nullptr, 0, &tot, &pos, g.q_rec_total ? d_tot.get() : nullptr,
+                         g.q_rec_positive ? d_pos.get() : nullptr);
+            CBLX_HIP(hipStreamSynchronize(c->stream));
+            if (g.q_rec_total) xfer(c).d2h_copy(g.q_rec_total + g.q_rec_base, d_tot.get(), nseq * 4);
+            if (g.q_rec_positive) xfer(c).d2h_copy(g.q_rec_positive + g.q_rec_base, d_pos.get(), nseq * 4);
+        } else {
+            query_device(c, g.d_bases.get(), g.d_off.get(), nseq, nullptr, 0, &tot, &pos);
+        }
+        g.q_rec_base += nseq;
         g.q_total += tot;
         g.q_positive += pos;
     } else {

@@ -187,6 +187,82 @@ __global__ __launch_bounds__(JOIN_THREADS) void k_query_join(u64 nbq, u64 b0, co
     if (tid == 0) per_run[b] = s_tab[0];
 }
 
+// ---- per-sequence tallies (cblx_contains_seqs_counts*): k-mers queried and k-mers found of EVERY sequence of a batch, from the
+// batch's flag bytes without bringing them to the host. The flags lie sequence after sequence, each in get_seq_words order, and
+// kmer_off[c] is the first flag of chunk c, so the flags of sequence s are [kmer_off[seq_chunk[s]], kmer_off[seq_chunk[s + 1]]).
+// Two levels: the flag bytes of every chunk are summed once (1 byte read per k-mer, 4 bytes written per chunk), then every
+// sequence sums its chunks (4 bytes per chunk, 8 per sequence written). No tally goes through an atomic: every output has one
+// writer and the sums are integers, so the result does not depend on the schedule. -------------------------------------------
+// chunk_pos[c] = sum of the flag bytes of chunk c; one wave per chunk (at most CHUNK_KMERS = 2048 flags = two 16-byte loads per
+// lane). kmer_off[c] is not aligned in general: the at most 15 bytes in front of and behind the 16-byte aligned run are read
+// bytewise by the upper lanes, which a read's chunk (120 flags: eight aligned runs at most) leaves idle anyway.
+__global__ __launch_bounds__(256) void k_chunk_tally(const u8* __restrict__ flags, const u64* __restrict__ kmer_off /* nchunks + 1 */, u64 c0, u64 nchunks,
+                                                     u32* __restrict__ chunk_pos) {
+    const u64 c = c0 + (((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const u32 lane = threadIdx.x & 63;
+    if (c >= nchunks) return;
+    const u64 a = kmer_off[c];
+    const u32 n = (u32)(kmer_off[c + 1] - a);
+    const u8* p = flags + a;
+    const u32 mis = (16u - (u32)((uintptr_t)p & 15u)) & 15u;
+    const u32 head = mis < n ? mis : n;
+    const u32 nvec = (n - head) >> 4, tail0 = head + (nvec << 4);
+    const uint4* v = reinterpret_cast<const uint4*>(p + head);
+    u32 s = 0;
+    for (u32 i = lane; i < nvec; i += 64) {
+        const uint4 w = v[i];
+        s = __builtin_amdgcn_sad_u8(w.x, 0u, s);  // s += the four bytes of the word
+        s = __builtin_amdgcn_sad_u8(w.y, 0u, s);
+        s = __builtin_amdgcn_sad_u8(w.z, 0u, s);
+        s = __builtin_amdgcn_sad_u8(w.w, 0u, s);
+    }
+    if (lane >= 32 && lane - 32 < head) s += p[lane - 32];
+    if (lane >= 48 && tail0 + (lane - 48) < n) s += p[tail0 + (lane - 48)];
+    s = wave_reduce_sum(s);
+    if (lane == 0) chunk_pos[c] = s;
+}
+// seq_total[s] = k-mers of sequence s, seq_pos[s] = the sum of chunk_pos over its chunks (either may be null). A read has one
+// chunk, a chromosome tens of thousands: a sequence of up to SEQ_TALLY_LANE_MAX chunks takes one lane (reads: a coalesced
+// gather), a longer one is left to a workgroup (k_seq_tally_long) through a list, as k_bucket_nodes leaves its long Tries.
+// The list's counter is the only atomic: it decides where a long sequence waits, never what is written for it.
+static const u32 SEQ_TALLY_LANE_MAX = 8, SEQ_TALLY_LONG_THREADS = 256;
+__global__ __launch_bounds__(256) void k_seq_tally(const u64* __restrict__ seq_chunk /* nseq + 1 */, const u64* __restrict__ kmer_off, const u32* __restrict__ chunk_pos,
+                                                   u64 nseq, u32* __restrict__ seq_total, u32* __restrict__ seq_pos, u32* __restrict__ long_list,
+                                                   u32* __restrict__ long_n, u32 long_cap) {
+    const u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nseq) return;
+    const u64 a = seq_chunk[s], b = seq_chunk[s + 1];
+    if (seq_total) seq_total[s] = (u32)(kmer_off[b] - kmer_off[a]);
+    if (!seq_pos) return;
+    if (b - a > SEQ_TALLY_LANE_MAX) {
+        const u32 at = atomicAdd(long_n, 1u);  // one per long sequence
+        if (at < long_cap) long_list[at] = (u32)s;
+        return;
+    }
+    u32 p = 0;
+    for (u64 j = a; j < b; ++j) p += chunk_pos[j];
+    seq_pos[s] = p;
+}
+__global__ __launch_bounds__(SEQ_TALLY_LONG_THREADS) void k_seq_tally_long(const u32* __restrict__ long_list, const u32* __restrict__ long_n,
+                                                                           const u64* __restrict__ seq_chunk, const u32* __restrict__ chunk_pos,
+                                                                           u32* __restrict__ seq_pos) {
+    constexpr u32 NW = SEQ_TALLY_LONG_THREADS / 64;
+    __shared__ u32 s_sum[NW];
+    if (blockIdx.x >= *long_n) return;
+    const u32 s = long_list[blockIdx.x], tid = threadIdx.x;
+    const u64 a = seq_chunk[s], b = seq_chunk[s + 1];
+    u32 p = 0;
+    for (u64 j = a + tid; j < b; j += SEQ_TALLY_LONG_THREADS) p += chunk_pos[j];
+    p = wave_reduce_sum(p);
+    if ((tid & 63u) == 0) s_sum[tid >> 6] = p;
+    __syncthreads();
+    if (tid == 0) {
+        u32 t = 0;
+        for (u32 i = 0; i < NW; ++i) t += s_sum[i];
+        seq_pos[s] = t;
+    }
+}
+
 // CBL::iter: element e of the index in iteration order (prefixes ascending, bucket order as stored: a Vec in
 // first-occurrence order, a Trie ascending — src/wordset/mod.rs:298-309, src/trievec/mod.rs:198-206) -> word ->
 // recover_kmer (src/cbl.rs:208-214, revert_necklace_pos src/necklace/mod.rs:29-31).

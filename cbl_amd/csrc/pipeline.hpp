@@ -948,6 +948,10 @@ struct ChunkPlan {
     Buf<u32> chunk_len, tile_first;
     Buf<u8> dirty;
     Buf<u32> dirty_list;  // the dirty chunks, any order (ndirty of them)
+    // sequence -> chunk map: sequence s owns the chunks [seq_chunk[s], seq_chunk[s + 1]) (nseq + 1 entries). Kept only when the caller sets
+    // keep_seq_chunk before the plan (the per-sequence query tallies); everyone else lets it die with the plan's temporaries.
+    bool keep_seq_chunk = false;
+    Buf<u64> seq_chunk;
 };
 // what a SLICE of a plan needs (sequences [seq_a, seq_b) of the planned ones): its chunks, k-mers and tiles
 struct PlanSlice { u64 c_lo = 0, c_hi = 0, k_lo = 0, k_hi = 0, t_lo = 0, t_hi = 0; };
@@ -1031,6 +1035,7 @@ void plan_chunks(cblx_ctx* c, BaseView& d_bases, const u64* d_offsets, u64 nseq,
         }
     }
     CBLX_HIP(hipStreamSynchronize(c->stream));  // temporaries (nch, err, chunk_base, chunk_nk, ndirty) die here
+    if (pl.keep_seq_chunk) pl.seq_chunk = std::move(chunk_base);
 }
 void plan_chunks(cblx_ctx* c, const u8*& d_bases, const u64* d_offsets, u64 nseq, ChunkPlan& pl, const u64* ends = nullptr) {
     BaseView B = ascii_view(d_bases);
@@ -1219,41 +1224,71 @@ template <typename C> u64 query_join(cblx_ctx* c, const u8* d_bases /* as left b
 }
 // words whose hi part leaves 32 bits for the query's ordinal, and whose suffix fits 64 bits: flags can come from the join
 inline bool query_flags_by_join(const Consts& P) { return !P.wide_suffix() && P.WB <= 96; }
+// Per-sequence tallies from the flags of a planned batch (kernels_kmer.hpp): seq_total[s] / seq_pos[s] for every sequence of the plan
+// (pl.seq_chunk kept). The flags stay on the device.
+void seq_tallies(cblx_ctx* c, const ChunkPlan& pl, u64 nseq, const u8* d_flags, u32* d_seq_total, u32* d_seq_pos) {
+    Buf<u32> chunk_pos(c->pool, pl.nchunks + 1);
+    const u32 long_cap = (u32)std::min<u64>(nseq, pl.nchunks / (SEQ_TALLY_LANE_MAX + 1) + 1);  // sequences of more than SEQ_TALLY_LANE_MAX chunks
+    Buf<u32> long_list(c->pool, long_cap), long_n(c->pool, 1);
+    CBLX_HIP(hipMemsetAsync(long_n.get(), 0, 4, c->stream));
+    if (d_seq_pos)
+        for (u64 c0 = 0; c0 < pl.nchunks; c0 += 1ull << 25)  // one wave per chunk, fewer than 2^32 work items per launch
+            hipLaunchKernelGGL(k_chunk_tally, grid1(std::min<u64>(1ull << 25, pl.nchunks - c0) * 64, 256), dim3(256), 0, c->stream, d_flags, (const u64*)pl.kmer_off.get(), c0,
+                               pl.nchunks, chunk_pos.get());
+    hipLaunchKernelGGL(k_seq_tally, grid1(nseq, 256), dim3(256), 0, c->stream, (const u64*)pl.seq_chunk.get(), (const u64*)pl.kmer_off.get(), (const u32*)chunk_pos.get(), nseq,
+                       d_seq_total, d_seq_pos, long_list.get(), long_n.get(), long_cap);
+    if (d_seq_pos && pl.nchunks > SEQ_TALLY_LANE_MAX)  // else no sequence is long
+        hipLaunchKernelGGL(k_seq_tally_long, dim3(long_cap), dim3(SEQ_TALLY_LONG_THREADS), 0, c->stream, (const u32*)long_list.get(), (const u32*)long_n.get(),
+                           (const u64*)pl.seq_chunk.get(), (const u32*)chunk_pos.get(), d_seq_pos);
+    CBLX_HIP(hipGetLastError());
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // chunk_pos and the list die here
+}
 // CBL::contains_seq over a batch of device-resident sequences: KRN-1, then one membership flag per k-mer (sequence after
 // sequence, each in get_seq_words order) into d_out[cap] when given; *total / *positive count the flags.
-void query_device(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64 nseq, u8* d_out, u64 cap, u64* total, u64* positive) {
+// d_seq_total / d_seq_pos (device, nseq entries each, either may be null): k-mers queried and k-mers found of every sequence. They are
+// tallied on the device from the flags, which then go to scratch unless d_out takes them: by the join with ordinals where
+// query_flags_by_join holds and the batch is big enough, by k_contains otherwise — the routes of a query with d_out.
+void query_device(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64 nseq, u8* d_out, u64 cap, u64* total, u64* positive, u32* d_seq_total = nullptr,
+                  u32* d_seq_pos = nullptr) {
     if (total) *total = 0;
     if (positive) *positive = 0;
     if (nseq == 0) return;
     check_aligned16(d_bases, "d_bases");
+    const bool per_seq = d_seq_total || d_seq_pos;
     dispatch(c->P, [&](auto cfg) {
         typedef decltype(cfg) C;
         typedef typename C::HiT HiT;
         ChunkPlan pl;
+        pl.keep_seq_chunk = per_seq;
         plan_chunks(c, d_bases, d_offsets, nseq, pl);
         const u64 nk = pl.n_kmers;
         if (total) *total = nk;
-        if (nk == 0) return;
-        if (nk >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "too many k-mers in one query batch");
-        if (nk >= query_join_min() && (!d_out || query_flags_by_join(c->P))) {  // big batch: join instead of one bucket read per query
-            if (d_out && nk > cap) throw Error(CBLX_ERANGE, "output capacity too small: " + std::to_string(nk) + " k-mers");
-            const u64 p = query_join<C>(c, d_bases, pl, d_out);
-            if (positive) *positive = p;
+        if (nk == 0) {  // (not with nseq > 0 today: every chunk holds at least its first k-mer)
+            if (d_seq_total) CBLX_HIP(hipMemsetAsync(d_seq_total, 0, nseq * 4, c->stream));
+            if (d_seq_pos) CBLX_HIP(hipMemsetAsync(d_seq_pos, 0, nseq * 4, c->stream));
             return;
         }
+        if (nk >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "too many k-mers in one query batch");
         if (d_out && nk > cap) throw Error(CBLX_ERANGE, "output capacity too small: " + std::to_string(nk) + " k-mers");
-        Buf<u64> w_lo(c->pool, nk + 2);
-        Buf<u8> w_hi(c->pool, (nk + 2) * std::max<size_t>(1, hi_elem_size(c->P)));
         Buf<u8> flags;
-        if (!d_out) { flags = Buf<u8>(c->pool, nk + 8); d_out = flags.get(); }
-        Buf<u32> zeros(c->pool, 1);
-        CBLX_HIP(hipMemsetAsync(zeros.get(), 0, 4, c->stream));
-        encode<C>(c, d_bases, pl, w_lo.get(), (HiT*)w_hi.get(), 0);
-        contains_words<C>(c, w_lo.get(), (const HiT*)w_hi.get(), nk, d_out);
-        hipLaunchKernelGGL(k_count_zero_u8, dim3((unsigned)std::min<u64>(4096, ceil_div(nk, 256))), dim3(256), 0, c->stream, (const u8*)d_out, nk, zeros.get());
-        CBLX_HIP(hipGetLastError());
-        const u64 z = d2h<u32>(c, zeros.get());  // also: the temporaries may go back to the pool
-        if (positive) *positive = nk - z;
+        if (d_seq_pos && !d_out) { flags = Buf<u8>(c->pool, nk + 16); d_out = flags.get(); }
+        if (nk >= query_join_min() && (!d_out || query_flags_by_join(c->P))) {  // big batch: join instead of one bucket read per query
+            const u64 p = query_join<C>(c, d_bases, pl, d_out);
+            if (positive) *positive = p;
+        } else {
+            Buf<u64> w_lo(c->pool, nk + 2);
+            Buf<u8> w_hi(c->pool, (nk + 2) * std::max<size_t>(1, hi_elem_size(c->P)));
+            if (!d_out) { flags = Buf<u8>(c->pool, nk + 8); d_out = flags.get(); }
+            Buf<u32> zeros(c->pool, 1);
+            CBLX_HIP(hipMemsetAsync(zeros.get(), 0, 4, c->stream));
+            encode<C>(c, d_bases, pl, w_lo.get(), (HiT*)w_hi.get(), 0);
+            contains_words<C>(c, w_lo.get(), (const HiT*)w_hi.get(), nk, d_out);
+            hipLaunchKernelGGL(k_count_zero_u8, dim3((unsigned)std::min<u64>(4096, ceil_div(nk, 256))), dim3(256), 0, c->stream, (const u8*)d_out, nk, zeros.get());
+            CBLX_HIP(hipGetLastError());
+            const u64 z = d2h<u32>(c, zeros.get());  // also: the temporaries may go back to the pool
+            if (positive) *positive = nk - z;
+        }
+        if (per_seq) seq_tallies(c, pl, nseq, d_out, d_seq_total, d_seq_pos);
     });
     collect_events(c);
 }

@@ -30,7 +30,8 @@ extern "C" {
  * built against this header must refuse a library that reports less.
  * Added under 3 (a new symbol is compatible): cblx_set_op with CBLX_SETOP_OR / AND / SUB / XOR, cblx_get_device, cblx_set_op_assign, and cblx_set_op_many with
  * CBLX_SETOP_MAX_OPERANDS; cblx_remove_words_device, cblx_remove_seq, cblx_remove_seqs, cblx_remove_seqs_device, cblx_remove_fastx_file and cblx_remove_kmers;
- * cblx_export_kmers_range, cblx_export_kmers_range_device, cblx_list_range, cblx_list_range_device, cblx_list_to_fd, cblx_list_to_file and cblx_bucket_nodes. */
+ * cblx_export_kmers_range, cblx_export_kmers_range_device, cblx_list_range, cblx_list_range_device, cblx_list_to_fd, cblx_list_to_file and cblx_bucket_nodes;
+ * cblx_contains_seqs_counts, cblx_contains_seqs_counts_device, cblx_contains_seqs_flags_counts_device and cblx_query_fastx_file_counts. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -362,6 +363,26 @@ int cblx_contains_seqs_device(cblx_ctx* ctx, const uint8_t* d_bases, const uint6
 /* `cbl query <index> <fastx>` (examples/cbl.rs:205-228): contains_seq for every record of a FASTA/FASTQ(.gz) file, read like
  * cblx_insert_fastx_file; *total = k-mers queried, *positive = those found. The index is not modified. */
 int cblx_query_fastx_file(cblx_ctx* ctx, const char* path, uint64_t* n_records, uint64_t* total, uint64_t* positive);
+/* ---- per-sequence tallies: which of my reads match the index? CBL::contains_seq (src/cbl.rs:311-324) for every sequence of a batch, reduced where the
+ * flags are made to the pair the loop of `cbl query` (examples/cbl.rs:205-228) keeps per file: seq_total[i] = k-mers of sequence i queried (the length of its
+ * contains_seq result: what get_seq_words yields, bytes that are not ACGT skipped), seq_positive[i] = those found. n entries each, either array may be NULL,
+ * every entry is written. The flags are produced and summed on the device and never cross to the host: 8 bytes per sequence come back instead of a byte per
+ * k-mer. *n_out / *positive are the tallies of the whole batch as cblx_contains_seqs returns them: the sums of the two arrays. Contract of the batch query:
+ * a sequence shorter than K is CBLX_ESHORT and nothing is queried or written, n == 0 is a no-op, the index is not modified, one call takes fewer than
+ * 2^32 - 16 k-mers. _device: device pointers for bases, offsets (as for cblx_contains_seqs_device) and the two arrays.
+ * _flags_counts_device: the same call that also leaves the flags in d_out[cap] (device), as cblx_contains_seqs_device does. */
+int cblx_contains_seqs_counts(cblx_ctx* ctx, const uint8_t* bases, const uint64_t* offsets, uint64_t n, uint32_t* seq_total, uint32_t* seq_positive,
+                              uint64_t* n_out, uint64_t* positive);
+int cblx_contains_seqs_counts_device(cblx_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n, uint32_t* d_seq_total,
+                                     uint32_t* d_seq_positive, uint64_t* n_out, uint64_t* positive);
+int cblx_contains_seqs_flags_counts_device(cblx_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n, uint8_t* d_out, uint64_t cap,
+                                           uint32_t* d_seq_total, uint32_t* d_seq_positive, uint64_t* n_out, uint64_t* positive);
+/* cblx_query_fastx_file (`cbl query`, examples/cbl.rs:205-228) that keeps the pair of every record: rec_total[i] / rec_positive[i] (host, cap entries each,
+ * either may be NULL) for record i of the file, 0-based, in file order. A file of more than cap records is CBLX_ERANGE with *n_records = its record count
+ * (cblx_stage_fastx_blocks with block = 0 counts in advance); the arrays then hold only the records of the flushes that fitted. With both arrays NULL it is
+ * cblx_query_fastx_file. */
+int cblx_query_fastx_file_counts(cblx_ctx* ctx, const char* path, uint32_t* rec_total, uint32_t* rec_positive, uint64_t cap, uint64_t* n_records,
+                                 uint64_t* total, uint64_t* positive);
 /* CBL::contains_all (src/cbl.rs:293-307): *out = 1 iff every k-mer of the sequence is in the set. */
 int cblx_contains_all(cblx_ctx* ctx, const uint8_t* seq, uint64_t len, int* out);
 

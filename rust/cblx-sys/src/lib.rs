@@ -301,6 +301,48 @@ extern "C" {
         positive: *mut u64,
     ) -> c_int;
     pub fn cblx_query_fastx_file(ctx: *mut cblx_ctx, path: *const c_char, n_records: *mut u64, total: *mut u64, positive: *mut u64) -> c_int;
+    pub fn cblx_contains_seqs_counts(
+        ctx: *mut cblx_ctx,
+        bases: *const u8,
+        offsets: *const u64,
+        n: u64,
+        seq_total: *mut u32,
+        seq_positive: *mut u32,
+        n_out: *mut u64,
+        positive: *mut u64,
+    ) -> c_int;
+    pub fn cblx_contains_seqs_counts_device(
+        ctx: *mut cblx_ctx,
+        d_bases: *const u8,
+        d_offsets: *const u64,
+        n: u64,
+        d_seq_total: *mut u32,
+        d_seq_positive: *mut u32,
+        n_out: *mut u64,
+        positive: *mut u64,
+    ) -> c_int;
+    pub fn cblx_contains_seqs_flags_counts_device(
+        ctx: *mut cblx_ctx,
+        d_bases: *const u8,
+        d_offsets: *const u64,
+        n: u64,
+        d_out: *mut u8,
+        cap: u64,
+        d_seq_total: *mut u32,
+        d_seq_positive: *mut u32,
+        n_out: *mut u64,
+        positive: *mut u64,
+    ) -> c_int;
+    pub fn cblx_query_fastx_file_counts(
+        ctx: *mut cblx_ctx,
+        path: *const c_char,
+        rec_total: *mut u32,
+        rec_positive: *mut u32,
+        cap: u64,
+        n_records: *mut u64,
+        total: *mut u64,
+        positive: *mut u64,
+    ) -> c_int;
     pub fn cblx_contains_all(ctx: *mut cblx_ctx, seq: *const u8, len: u64, out: *mut c_int) -> c_int;
 
     pub fn cblx_insert_kmers(ctx: *mut cblx_ctx, lo: *const u64, hi: *const u64, n: u64, was_absent: *mut u8) -> c_int;
