@@ -349,6 +349,50 @@ __device__ __forceinline__ void tile_at(const TileView& tv, u32 tile, u64& tbase
     }
 }
 
+// The hi BYTES of a tile's records (65..72-bit words), in the tile kernels' record-to-lane map: khi[j] = hi_t[w * 512 + j * 64 + lane].
+// Read as that, they are eight 64-byte requests per wave next to the eight 512-byte ones of `lo`: twice the vector loads of a pass
+// without a hi part for an eighth more bytes. A wave whose 512 records lie wholly inside the tile and whose bytes start on an 8-byte
+// boundary fetches them as ONE u64 per lane instead (tile_hi_fetch, issued in front of the lo loads so that it is the first to
+// land), writes the 512 bytes to its own slice of `s_raw` (LDS [RDX_TILE] bytes, 8-byte aligned) and reads its eight bytes back
+// from there (tile_hi_take). The slice belongs to the wave alone, and a wave's LDS operations complete in order: the fences keep the
+// compiler from moving the reads over the write, and no workgroup barrier (which would drain the lo loads) stands between them.
+// Every other wave — a ragged tile's last ones, a caller's misaligned array — reads bytes as before; tail slots re-read slot 0.
+// No byte outside [hi_t, hi_t + n_tile) is read either way. The condition is wave-uniform.
+// (The wave number goes through readfirstlane so that the compiler knows the condition and the slice to be uniform: a scalar branch
+// whose arms keep their own wait counts, the fetch waited for with the lo loads still in flight. The LDS slice is addressed as LDS
+// explicitly: left generic, the compiler merges the last byte read of the two arms into one flat load of either pointer.)
+typedef __attribute__((address_space(3))) u8 lds_u8;
+typedef __attribute__((address_space(3))) u64 lds_u64;
+__device__ __forceinline__ u32 tile_wave_base() { return (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * (64 * RDX_ITEMS); }
+__device__ __forceinline__ bool tile_hi_wide(const u8* hi_t, u32 n_tile) {
+    const u32 wb = tile_wave_base();
+    return wb + 64 * RDX_ITEMS <= n_tile && (reinterpret_cast<uintptr_t>(hi_t + wb) & 7u) == 0;
+}
+// NT: streaming loads (the scatter, see there)
+template <bool NT> __device__ __forceinline__ u64 tile_hi_fetch(const u8* hi_t) {
+    const u64* p = reinterpret_cast<const u64*>(hi_t + tile_wave_base()) + (threadIdx.x & 63);
+    return NT ? __builtin_nontemporal_load(p) : *p;
+}
+__device__ __forceinline__ void tile_hi_spread(u64 raw, u8* s_raw, u32 (&khi)[RDX_ITEMS]) {
+    const u32 lane = threadIdx.x & 63;
+    lds_u8* mine = (lds_u8*)(s_raw + tile_wave_base());
+    ((lds_u64*)mine)[lane] = raw;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int j = 0; j < RDX_ITEMS; ++j) khi[j] = mine[j * 64 + lane];
+}
+template <bool NT> __device__ __forceinline__ void tile_hi_bytes(const u8* hi_t, u32 n_tile, u32 (&khi)[RDX_ITEMS]) {
+    const u32 wb = tile_wave_base(), lane = threadIdx.x & 63;
+#pragma unroll
+    for (int j = 0; j < RDX_ITEMS; ++j) {
+        const u32 e = wb + j * 64 + lane;
+        const u8* p = &hi_t[e < n_tile ? e : 0u];
+        khi[j] = NT ? __builtin_nontemporal_load(p) : *p;
+    }
+}
+
 // per-tile digit histogram -> counts[tile * 256 + digit] (tile-major: one coalesced 1 KiB row per workgroup).
 // Counting needs no ranks: per-wave private LDS histograms fed by non-returning ds_add (the ballot matching of
 // tile_rank costs ~50 VALU per record and made this kernel VALU-bound).
@@ -356,6 +400,10 @@ template <typename HiT, typename DigitFn>
 __global__ __launch_bounds__(RDX_THREADS) void k_radix_hist(const u64* __restrict__ lo, const HiT* __restrict__ hi, TileView tv,
                                                             DigitFn dfn, u32* __restrict__ counts) {
     __shared__ u32 s_wcnt[(RDX_THREADS / 64) * 256];
+    // one-byte hi parts come through LDS (tile_hi_fetch): 4 KB next to the 8 KB of counters, 12 KB per workgroup — the four workgroups
+    // a CU's wave slots hold take 48 of its 160 KB, as little a limit as the 32 KB before
+    constexpr bool HI_BYTES = std::is_same<HiT, u8>::value;
+    __shared__ __attribute__((aligned(8))) u8 s_raw[HI_BYTES ? RDX_TILE : 1];
     const u32 tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     for (u32 i = tid; i < (RDX_THREADS / 64) * 256; i += RDX_THREADS) s_wcnt[i] = 0;
     __syncthreads();
@@ -367,12 +415,30 @@ __global__ __launch_bounds__(RDX_THREADS) void k_radix_hist(const u64* __restric
     typename std::conditional<std::is_same<HiT, u64>::value, u64, u32>::type khi[RDX_ITEMS];
     const u64* __restrict__ lo_t = lo + tbase;
     const HiT* __restrict__ hi_t = HiTraits<HiT>::has ? hi + tbase : hi;
+    if constexpr (HI_BYTES) {
+        auto load_lo = [&]() {
 #pragma unroll
-    for (int j = 0; j < RDX_ITEMS; ++j) {
-        const u32 e = w * (64 * RDX_ITEMS) + j * 64 + lane;
-        const u32 eo = e < n_tile ? e : 0u;
-        klo[j] = lo_t[eo];
-        khi[j] = ld_hi<HiT>(hi_t, eo);
+            for (int j = 0; j < RDX_ITEMS; ++j) {
+                const u32 e = w * (64 * RDX_ITEMS) + j * 64 + lane;
+                klo[j] = lo_t[e < n_tile ? e : 0u];
+            }
+        };
+        if (tile_hi_wide(hi_t, n_tile)) {  // one arm per form, each with the lo loads inside: the wide arm waits for its fetch alone
+            const u64 raw = tile_hi_fetch<false>(hi_t);
+            load_lo();
+            tile_hi_spread(raw, s_raw, khi);
+        } else {
+            load_lo();
+            tile_hi_bytes<false>(hi_t, n_tile, khi);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < RDX_ITEMS; ++j) {
+            const u32 e = w * (64 * RDX_ITEMS) + j * 64 + lane;
+            const u32 eo = e < n_tile ? e : 0u;
+            klo[j] = lo_t[eo];
+            khi[j] = ld_hi<HiT>(hi_t, eo);
+        }
     }
 #pragma unroll
     for (int j = 0; j < RDX_ITEMS; ++j) {
@@ -493,8 +559,13 @@ __global__ __launch_bounds__(RDX_THREADS, (HiTraits<HiT>::has && HiTraits<OutHiT
     constexpr bool TABLE = DigitUsesTable<DigitFn>::value;  // the digit comes from a table staged in LDS (dead once the records are staged)
     constexpr bool KEEP_DIG = !STAGE_HI || TABLE;
     __shared__ u64 s_lo[RDX_TILE];
-    __shared__ typename std::conditional<STAGE_HI, HiT, u8>::type s_hi[STAGE_HI ? RDX_TILE : 1];
-    __shared__ u8 s_dig[KEEP_DIG ? RDX_TILE : 1];  // digit of the staged record when it cannot be recomputed from lo alone
+    __shared__ __attribute__((aligned(8))) typename std::conditional<STAGE_HI, HiT, u8>::type s_hi[STAGE_HI ? RDX_TILE : 1];
+    __shared__ __attribute__((aligned(8))) u8 s_dig[KEEP_DIG ? RDX_TILE : 1];  // digit of the staged record when it cannot be recomputed from lo alone
+    // one-byte hi parts are fetched as 8-byte words and handed to their lanes through LDS (tile_hi_fetch). The raw bytes lie in
+    // whichever byte staging array this instantiation has: both are first written behind the barrier that follows the ranking, and
+    // the raw bytes are in registers before the ranking starts
+    constexpr bool HI_BYTES = std::is_same<HiT, u8>::value;
+    u8* const s_raw = KEEP_DIG ? reinterpret_cast<u8*>(s_dig) : reinterpret_cast<u8*>(s_hi);
     // the ranking counters live in the staging area (they are dead before the first record is staged): 39 KB of LDS per
     // workgroup instead of 47 KB = four resident workgroups per CU instead of three
     static_assert((RDX_THREADS / 64) * 256 * 4 <= RDX_TILE * 8, "rank counters must fit the staging area");
@@ -512,17 +583,39 @@ __global__ __launch_bounds__(RDX_THREADS, (HiTraits<HiT>::has && HiTraits<OutHiT
     u32 digit[RDX_ITEMS];
     const u64* __restrict__ lo_t = lo + tbase;
     const HiT* __restrict__ hi_t = HiTraits<HiT>::has ? hi + tbase : hi;
+    // streaming reads (uniform tile base + 32-bit lane offset): the records are used once, and what they would evict
+    // from the L2 are the partial lines of the output waiting for their neighbours (-1.5 .. -2.6 % per launch; the
+    // same hint on the STORES doubles the time: they are what must stay)
+    if constexpr (HI_BYTES) {
+        auto load_lo = [&]() {
 #pragma unroll
-    for (int j = 0; j < RDX_ITEMS; ++j) {
-        const u32 e = w * (64 * RDX_ITEMS) + j * 64 + lane;
-        const bool valid = e < n_tile;
-        const u32 eo = valid ? e : 0u;  // tail slots re-read slot 0 and are never written back
-        // streaming read (uniform tile base + 32-bit lane offset): the records are used once, and what they would evict
-        // from the L2 are the partial lines of the output waiting for their neighbours (-1.5 .. -2.6 % per launch; the
-        // same hint on the STORES doubles the time: they are what must stay)
-        klo[j] = __builtin_nontemporal_load(&lo_t[eo]);
-        if constexpr (HiTraits<HiT>::has) khi[j] = __builtin_nontemporal_load(&hi_t[eo]); else khi[j] = 0;
-        if constexpr (!TABLE) digit[j] = valid ? dfn(klo[j], (u64)khi[j]) : 255u;
+            for (int j = 0; j < RDX_ITEMS; ++j) {
+                const u32 e = w * (64 * RDX_ITEMS) + j * 64 + lane;
+                klo[j] = __builtin_nontemporal_load(&lo_t[e < n_tile ? e : 0u]);  // tail slots re-read slot 0 and are never written back
+            }
+        };
+        if (tile_hi_wide(hi_t, n_tile)) {  // one arm per form, each with the lo loads inside: the wide arm waits for its fetch alone
+            const u64 raw = tile_hi_fetch<true>(hi_t);
+            load_lo();
+            tile_hi_spread(raw, s_raw, khi);
+        } else {
+            load_lo();
+            tile_hi_bytes<true>(hi_t, n_tile, khi);
+        }
+        if constexpr (!TABLE) {
+#pragma unroll
+            for (int j = 0; j < RDX_ITEMS; ++j) digit[j] = w * (64 * RDX_ITEMS) + j * 64 + lane < n_tile ? dfn(klo[j], (u64)khi[j]) : 255u;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < RDX_ITEMS; ++j) {
+            const u32 e = w * (64 * RDX_ITEMS) + j * 64 + lane;
+            const bool valid = e < n_tile;
+            const u32 eo = valid ? e : 0u;  // tail slots re-read slot 0 and are never written back
+            klo[j] = __builtin_nontemporal_load(&lo_t[eo]);
+            if constexpr (HiTraits<HiT>::has) khi[j] = __builtin_nontemporal_load(&hi_t[eo]); else khi[j] = 0;
+            if constexpr (!TABLE) digit[j] = valid ? dfn(klo[j], (u64)khi[j]) : 255u;
+        }
     }
     if constexpr (TABLE) {
         // the bin table goes into LDS behind the rank counters (the first 8 KB of the staging area) — its loads are issued behind the
