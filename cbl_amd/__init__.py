@@ -118,6 +118,7 @@ SIGNATURES = {
     "cblx_comm_groups_fine": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "cblx_comm_protocol_used": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "cblx_fine_builds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cblx_uniform_plans": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "cblx_sharded_insert_seqs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
                                                   C.POINTER(C.c_int)]),
     "cblx_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -1137,6 +1138,12 @@ class CBL:
         """Batches built through the FINE-bins route (PREFIX_BITS > 24, empty index, CBLX_FINE_MIN k-mers or more)."""
         v = C.c_uint64(0)
         self._chk(self._L.cblx_fine_builds(self._h, C.byref(v)))
+        return v.value
+
+    def uniform_plans(self) -> int:
+        """Insert batches whose chunk plan was arithmetic (reads of one length, no invalid byte): no chunk table was built."""
+        v = C.c_uint64(0)
+        self._chk(self._L.cblx_uniform_plans(self._h, C.byref(v)))
         return v.value
 
     def trim(self):

@@ -311,6 +311,7 @@ void cblx_destroy(cblx_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& e : ctx->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto& e : ctx->ev_free) (void)hipEventDestroy(e);
+    if (ctx->mbox) (void)hipHostFree(ctx->mbox);
     ctx->res = Resident();
     ingest_destroy(ctx);
     (void)hipStreamDestroy(ctx->stream);
@@ -1685,6 +1686,7 @@ int cblx_stage_units(cblx_ctx* c, uint64_t* units, uint32_t cap, uint32_t* n) {
 }
 int cblx_kmers_inserted(cblx_ctx* c, uint64_t* out) { if (!c || !out) return CBLX_EINVAL; *out = c->kmers_inserted; return CBLX_OK; }
 int cblx_fine_builds(cblx_ctx* c, uint64_t* out) { if (!c || !out) return CBLX_EINVAL; *out = c->fine_builds; return CBLX_OK; }
+int cblx_uniform_plans(cblx_ctx* c, uint64_t* out) { if (!c || !out) return CBLX_EINVAL; *out = c->uniform_plans; return CBLX_OK; }
 int cblx_trim(cblx_ctx* c) {
     return guard(c, [&] {
         if (c->ing.nseq == 0) { ingest_wait(c); c->ing.d_bases.reset(); c->ing.d_off.reset(); }

@@ -193,6 +193,10 @@ struct cblx_ctx {
     std::string err;
     u64 kmers_inserted = 0;
     u64 fine_builds = 0;       // batches that took the FINE-bins build (PREFIX_BITS > 24 on an empty index: comm.hpp insert_device_fine)
+    u64 uniform_plans = 0;     // batches whose chunk plan was arithmetic (uniform_plan.hpp): no chunk table was built
+    static constexpr size_t MBOX_HALF = 2048;
+    u8* mbox = nullptr;        // pinned destination of the small device -> host reads (mailbox() below), 2 * MBOX_HALF bytes
+    bool mbox_tried = false;
     Stage stages[ST_N];
     struct Ev { int st; hipEvent_t a, b; };
     std::vector<Ev> evs;
@@ -236,20 +240,61 @@ inline dim3 grid1(u64 n, u32 threads) {
     return dim3((unsigned)blocks);
 }
 
+// Small device -> host reads land in a pinned MAILBOX of the context (allocated once): a copy into pageable memory goes through the
+// runtime's staging buffer and blocks the host for several times as long. The lower half takes the queued reads of a ReadGroup, the
+// upper half the single reads of d2h / d2h_vec, so that a single read between a group's queueing and its wait leaves the group alone.
+// CBLX_PINNED_READBACK=0 (read when the context first reads back): pageable destinations, as before.
+inline u8* mailbox(cblx_ctx* c) {
+    if (!c->mbox_tried) {
+        c->mbox_tried = true;
+        const char* e = std::getenv("CBLX_PINNED_READBACK");
+        if (!(e && e[0] == '0')) {
+            void* p = nullptr;
+            if (hipHostMalloc(&p, 2 * cblx_ctx::MBOX_HALF, hipHostMallocDefault) == hipSuccess) c->mbox = (u8*)p;
+            else (void)hipGetLastError();  // no pinned memory to be had: pageable reads still work
+        }
+    }
+    return c->mbox;
+}
 template <typename T> T d2h(cblx_ctx* c, const T* dptr) {
     T v;
-    CBLX_HIP(hipMemcpyAsync(&v, dptr, sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    u8* m = sizeof(T) <= cblx_ctx::MBOX_HALF ? mailbox(c) : nullptr;
+    if (m) m += cblx_ctx::MBOX_HALF;
+    CBLX_HIP(hipMemcpyAsync(m ? (void*)m : (void*)&v, dptr, sizeof(T), hipMemcpyDeviceToHost, c->stream));
     CBLX_HIP(hipStreamSynchronize(c->stream));
+    if (m) memcpy(&v, m, sizeof(T));
     return v;
 }
 template <typename T> std::vector<T> d2h_vec(cblx_ctx* c, const T* dptr, size_t n) {
     std::vector<T> v(n);
     if (n) {
-        CBLX_HIP(hipMemcpyAsync(v.data(), dptr, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+        u8* m = n * sizeof(T) <= cblx_ctx::MBOX_HALF ? mailbox(c) : nullptr;
+        if (m) m += cblx_ctx::MBOX_HALF;
+        CBLX_HIP(hipMemcpyAsync(m ? (void*)m : (void*)v.data(), dptr, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
         CBLX_HIP(hipStreamSynchronize(c->stream));
+        if (m) memcpy(v.data(), m, n * sizeof(T));
     }
     return v;
 }
+// Reads that belong to ONE decision: queued one after the other, waited for once.
+struct ReadGroup {
+    cblx_ctx* c;
+    u8* dst;
+    size_t fill = 0;
+    std::vector<u8> pageable;  // without a mailbox
+    explicit ReadGroup(cblx_ctx* ctx) : c(ctx), dst(mailbox(ctx)) {
+        if (!dst) { pageable.resize(cblx_ctx::MBOX_HALF); dst = pageable.data(); }
+    }
+    template <typename T> size_t add(const T* dptr, size_t n = 1) {  // returns the handle get() takes
+        const size_t at = (fill + 7) & ~(size_t)7;
+        if (at + n * sizeof(T) > cblx_ctx::MBOX_HALF) throw Error(CBLX_EDEVICE, "read group larger than the mailbox (internal error)");
+        CBLX_HIP(hipMemcpyAsync(dst + at, dptr, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+        fill = at + n * sizeof(T);
+        return at;
+    }
+    void wait() { CBLX_HIP(hipStreamSynchronize(c->stream)); }
+    template <typename T> T get(size_t at, size_t i = 0) const { T v; memcpy(&v, dst + at + i * sizeof(T), sizeof(T)); return v; }
+};
 template <typename T> void h2d(cblx_ctx* c, T* dptr, const T* h, size_t n) {
     if (n) CBLX_HIP(hipMemcpyAsync(dptr, h, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
 }

@@ -14,6 +14,7 @@
 #pragma once
 #include "common.hpp"
 #include "necklace.hpp"
+#include "uniform_plan.hpp"
 
 namespace cblx {
 
@@ -246,6 +247,31 @@ __global__ void k_scan_invalid(BaseView B, u64 total, const u64* __restrict__ ch
         }
     }
 }
+// Probe of the arithmetic plan (uniform_plan.hpp), run before any table exists: flags[0] = some sequence is not L bases long,
+// flags[1] = some byte of [s0, total) is invalid (the bytes between the aligned start and offsets[0] belong to nobody: the table
+// path's mark_dirty finds no chunk for them). One thread per sequence and per group of 16 bases, whichever are more.
+__global__ __launch_bounds__(256) void k_uniform_probe(BaseView B, u64 total, u32 s0, const u64* __restrict__ offsets, u64 nseq, u64 L, u32* __restrict__ flags) {
+    const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < nseq && offsets[g + 1] - offsets[g] != L) flags[0] = 1u;  // benign race: every writer stores 1
+    const u64 b0 = g * 16;
+    if (b0 >= total) return;
+    if (B.ascii) {
+        const u8* __restrict__ bases = B.ascii;
+        if (b0 >= s0 && b0 + 16 <= total) {
+            const uint4 v = *reinterpret_cast<const uint4*>(bases + b0);
+            const u32 m = valid_mask4(v.x) & valid_mask4(v.y) & valid_mask4(v.z) & valid_mask4(v.w);
+            if (m != 0x80808080u) flags[1] = 1u;
+            return;
+        }
+        for (u64 b = b0 > s0 ? b0 : (u64)s0; b < b0 + 16 && b < total; ++b)
+            if (!nuc_valid(bases[b])) flags[1] = 1u;
+    } else {
+        const u32 n = total - b0 < 16 ? (u32)(total - b0) : 16u;
+        u32 bad = ~(u32)B.valid[g] & ((1u << n) - 1u);
+        if (b0 < s0) bad &= ~((1u << s0) - 1u);  // (s0 < 16: group 0 only)
+        if (bad) flags[1] = 1u;
+    }
+}
 // The dirty chunks as a list (any order), so that the kernels below put a whole wave on every one of them: one THREAD per
 // dirty chunk walking its 150 .. 2100 bytes alone, among 63 idle lanes, cost 2 ms per 82 000 dirty chunks (1 % of the reads
 // with an N) and 130 ms when every read had one.
@@ -356,7 +382,8 @@ __global__ __launch_bounds__(ENC_THREADS) void k_encode(BaseView B, u64 total_ba
                                                         const u8* __restrict__ dirty /* may be null */,
                                                         const u32* __restrict__ tile_first, Consts P,
                                                         u64* __restrict__ out_lo, HiT* __restrict__ out_hi, u64 out_base,
-                                                        EncHist eh, u32 c_lo = 0, u32 c_hi = 0xFFFFFFFFu /* only the chunks in [c_lo, c_hi): a slice of a plan */) {
+                                                        EncHist eh, u32 c_lo = 0, u32 c_hi = 0xFFFFFFFFu /* only the chunks in [c_lo, c_hi): a slice of a plan */,
+                                                        UniformPlan up = UniformPlan() /* set: the tables are null, their entries arithmetic (uniform_plan.hpp) */) {
     typedef typename KmerT<WIDE>::type T;
     __shared__ u32 s_hist[ENC_HIST_WINDOWS * 256];
     __shared__ u32 s_codes[ENC_CODE_WORDS];
@@ -368,19 +395,44 @@ __global__ __launch_bounds__(ENC_THREADS) void k_encode(BaseView B, u64 total_ba
     extern __shared__ u32 s_cut[];              // the cut table of the fused histogram's bins (launched with its size only when there is one)
 
     const u32 tid = threadIdx.x;
-    u32 c0 = tile_first[blockIdx.x], c1 = tile_first[blockIdx.x + 1];
-    c0 = c0 > c_lo ? c0 : c_lo;  // (a tile on the edge of the slice holds chunks of its neighbour: theirs to encode)
-    c1 = c1 < c_hi ? c1 : c_hi;
+    // chunk range of the tile, first / last base and first k-mer: from the tables or by arithmetic. ONE branch, so that the table arm's
+    // dependent loads are issued together as before (an arm per value puts a wait between them)
+    u32 c0, c1;
+    u64 B0 = 0, B1 = 0, kbase = 0;
+    if (up.uniform) {
+        // (the 64-bit divisions run on the vector unit; without the readfirstlane the chunk range, and every loop bound and stride that
+        // follows from it, would stay in vector registers where the table arm has them in scalar ones)
+        c0 = (u32)__builtin_amdgcn_readfirstlane((int)uniform_tile_first(up, blockIdx.x, ENC_TILE_BYTES));
+        c1 = (u32)__builtin_amdgcn_readfirstlane((int)uniform_tile_first(up, (u64)blockIdx.x + 1, ENC_TILE_BYTES));
+        c0 = c0 > c_lo ? c0 : c_lo;
+        c1 = c1 < c_hi ? c1 : c_hi;
+        B0 = uniform_chunk_start(up, c0);
+        B1 = uniform_chunk_start(up, c1);
+        kbase = uniform_kmer_off(up, c0);
+    } else {
+        c0 = tile_first[blockIdx.x];
+        c1 = tile_first[blockIdx.x + 1];
+        c0 = c0 > c_lo ? c0 : c_lo;  // (a tile on the edge of the slice holds chunks of its neighbour: theirs to encode)
+        c1 = c1 < c_hi ? c1 : c_hi;
+        if (c0 < c1) {
+            B0 = chunk_start[c0];
+            B1 = chunk_start[c1 - 1] + chunk_len[c1 - 1];
+            kbase = kmer_off[c0];
+        }
+    }
     if (c0 >= c1) return;
     const u32 nc = c1 - c0;  // <= ENC_MAX_CHUNKS by construction (chunk length >= K >= 5)
-    const u64 B0 = chunk_start[c0];
-    const u64 B1 = chunk_start[c1 - 1] + chunk_len[c1 - 1];
     const u64 A0 = B0 & ~(u64)15;
-    const u64 kbase = kmer_off[c0];
 
-    for (u32 i = tid; i <= nc; i += ENC_THREADS) s_koff[i] = (u32)(kmer_off[c0 + i] - kbase);
-    for (u32 i = tid; i < nc; i += ENC_THREADS) {
-        s_cstart[i] = (u32)(chunk_start[c0 + i] - A0) | ((dirty && dirty[c0 + i]) ? 0x80000000u : 0u);
+    if (up.uniform) {  // the same LDS copies, by arithmetic: everything below reads them as it reads loaded ones
+        const u32 rel0 = (u32)(B0 - A0);
+        for (u32 i = tid; i <= nc; i += ENC_THREADS) s_koff[i] = i * up.nk0;
+        for (u32 i = tid; i < nc; i += ENC_THREADS) s_cstart[i] = rel0 + i * up.L;
+    } else {
+        for (u32 i = tid; i <= nc; i += ENC_THREADS) s_koff[i] = (u32)(kmer_off[c0 + i] - kbase);
+        for (u32 i = tid; i < nc; i += ENC_THREADS) {
+            s_cstart[i] = (u32)(chunk_start[c0 + i] - A0) | ((dirty && dirty[c0 + i]) ? 0x80000000u : 0u);
+        }
     }
     const u64 win0 = (out_base + kbase) / ENC_HIST_WINDOW;  // first window this tile's outputs fall into
     if (eh.counts)

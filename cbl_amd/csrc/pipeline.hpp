@@ -952,7 +952,15 @@ struct ChunkPlan {
     // keep_seq_chunk before the plan (the per-sequence query tallies); everyone else lets it die with the plan's temporaries.
     bool keep_seq_chunk = false;
     Buf<u64> seq_chunk;
+    // Arithmetic plan (uniform_plan.hpp). A caller that reads the plan through encode() alone sets allow_uniform before the plan; plan_chunks
+    // then probes the batch first and, for reads of one length without an invalid byte, sets `uni` and allocates no table at all.
+    bool allow_uniform = false;
+    UniformPlan uni;
 };
+inline bool uniform_plan_enabled() {  // read per call: tests switch it
+    const char* e = std::getenv("CBLX_UNIFORM_PLAN");
+    return !(e && e[0] == '0');
+}
 // what a SLICE of a plan needs (sequences [seq_a, seq_b) of the planned ones): its chunks, k-mers and tiles
 struct PlanSlice { u64 c_lo = 0, c_hi = 0, k_lo = 0, k_hi = 0, t_lo = 0, t_hi = 0; };
 __global__ void k_plan_marks(const u64* __restrict__ chunk_base, const u64* __restrict__ marks, u32 n, u64 nchunks, const u64* __restrict__ chunk_start, const u64* __restrict__ kmer_off,
@@ -974,12 +982,39 @@ void plan_chunks(cblx_ctx* c, BaseView& d_bases, const u64* d_offsets, u64 nseq,
     const Consts& P = c->P;
     // offsets may start anywhere in the buffer (a slice of a larger batch): work relative to the 16-byte aligned
     // position below offsets[0] so that the tile grid and the validity scan cover only this slice
-    const u64 first = ends ? ends[0] : d2h<u64>(c, d_offsets);
+    u64 first, last;
+    if (ends) { first = ends[0]; last = ends[1]; }
+    else {  // one wait for the two
+        ReadGroup rg(c);
+        const size_t h_first = rg.add(d_offsets), h_last = rg.add(d_offsets + nseq);
+        rg.wait();
+        first = rg.get<u64>(h_first); last = rg.get<u64>(h_last);
+    }
     pl.bias = first & ~(u64)15;
-    const u64 last = ends ? ends[1] : d2h<u64>(c, d_offsets + nseq);
     if (last < first) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
     pl.total_bases = last - pl.bias;
     d_bases.advance16(pl.bias);
+    bool probed_clean = false;  // the probe ran and found every byte of the batch valid
+    if (pl.allow_uniform && !pl.keep_seq_chunk && !seq_marks && nseq && uniform_plan_enabled()) {
+        const u64 span = last - first, L = span / nseq;
+        if (span % nseq == 0 && uniform_plan_shape(nseq, L, P.K, CHUNK_KMERS)) {  // (else some length differs, or the tables are needed: no probe)
+            Buf<u32> flags(c->pool, 2);
+            CBLX_HIP(hipMemsetAsync(flags.get(), 0, 8, c->stream));
+            const u32 s0 = (u32)(first - pl.bias);
+            hipLaunchKernelGGL(k_uniform_probe, grid1(std::max<u64>(nseq, ceil_div(pl.total_bases, 16)), 256), dim3(256), 0, c->stream, d_bases, pl.total_bases, s0, d_offsets, nseq, L,
+                               flags.get());
+            CBLX_HIP(hipGetLastError());
+            const std::vector<u32> f = d2h_vec<u32>(c, flags.get(), 2);  // steers the work: tables or none
+            if (!f[0] && !f[1]) {
+                pl.uni.uniform = 1; pl.uni.L = (u32)L; pl.uni.nk0 = (u32)(L - P.K + 1); pl.uni.s0 = s0; pl.uni.n = nseq;
+                pl.nchunks = nseq;
+                pl.n_kmers = nseq * pl.uni.nk0;
+                ++c->uniform_plans;
+                return;
+            }
+            probed_clean = !f[1];
+        }
+    }
     Buf<u32> nch(c->pool, nseq + 1);
     Buf<u64> err(c->pool, 2), chunk_base(c->pool, nseq + 1);
     CBLX_HIP(hipMemsetAsync(err.get(), 0, 16, c->stream));
@@ -998,9 +1033,11 @@ void plan_chunks(cblx_ctx* c, BaseView& d_bases, const u64* d_offsets, u64 nseq,
                        pl.chunk_start.get(), pl.chunk_len.get(), chunk_nk.get());
     CBLX_HIP(hipMemsetAsync(pl.dirty.get(), 0, pl.nchunks + 8, c->stream));
     CBLX_HIP(hipMemsetAsync(ndirty.get(), 0, 4, c->stream));
-    hipLaunchKernelGGL(k_scan_invalid, grid1(ceil_div(pl.total_bases, 16), 256), dim3(256), 0, c->stream, d_bases, pl.total_bases,
-                       pl.chunk_start.get(), pl.chunk_len.get(), pl.nchunks, pl.dirty.get(), ndirty.get());
-    pl.ndirty = d2h<u32>(c, ndirty.get());  // a flag so far
+    if (!probed_clean) {  // (the probe's scan covered the same bytes: nothing is dirty)
+        hipLaunchKernelGGL(k_scan_invalid, grid1(ceil_div(pl.total_bases, 16), 256), dim3(256), 0, c->stream, d_bases, pl.total_bases,
+                           pl.chunk_start.get(), pl.chunk_len.get(), pl.nchunks, pl.dirty.get(), ndirty.get());
+        pl.ndirty = d2h<u32>(c, ndirty.get());  // a flag so far
+    }
     if (pl.ndirty) {
         pl.dirty_list = Buf<u32>(c->pool, pl.nchunks + 1);
         CBLX_HIP(hipMemsetAsync(ndirty.get(), 0, 4, c->stream));
@@ -1048,6 +1085,7 @@ template <typename C> void encode(cblx_ctx* c, const BaseView& d_bases, const Ch
     typedef typename C::HiT HiT;
     StageTimer t(c, ST_ENCODE);
     if (sl) {
+        if (pl.uni.uniform) throw Error(CBLX_EDEVICE, "a slice of an arithmetic chunk plan (internal error)");
         if (sl->c_hi <= sl->c_lo) return;
         const u64 nt = sl->t_hi - sl->t_lo, ob = out_base - sl->k_lo;  // (modulo 2^64: the kernels add a chunk's k-mer offset back)
         hipLaunchKernelGGL((k_encode<C::WIDE, HiT>), dim3((unsigned)nt), dim3(ENC_THREADS), (eh.counts && eh.cut_tab) ? 8192 : 0, c->stream, d_bases, pl.total_bases, pl.chunk_start.get(),
@@ -1062,7 +1100,8 @@ template <typename C> void encode(cblx_ctx* c, const BaseView& d_bases, const Ch
     const u64 ntiles = ceil_div(pl.total_bases, ENC_TILE_BYTES);
     if (ntiles)  // (dynamic LDS: the cut table of the fused histogram's bins, when there is one — 8 KB more per workgroup cost the kernel nothing, measured)
         hipLaunchKernelGGL((k_encode<C::WIDE, HiT>), dim3((unsigned)ntiles), dim3(ENC_THREADS), (eh.counts && eh.cut_tab) ? 8192 : 0, c->stream, d_bases, pl.total_bases, pl.chunk_start.get(),
-                           pl.chunk_len.get(), pl.kmer_off.get(), pl.ndirty ? pl.dirty.get() : (const u8*)nullptr, pl.tile_first.get(), c->P, out_lo, out_hi, out_base, eh);
+                           pl.chunk_len.get(), pl.kmer_off.get(), pl.ndirty ? pl.dirty.get() : (const u8*)nullptr, pl.tile_first.get(), c->P, out_lo, out_hi, out_base, eh, 0u, 0xFFFFFFFFu,
+                           pl.uni);
     if (pl.ndirty)
         hipLaunchKernelGGL((k_encode_dirty_wave<C::WIDE, HiT>), dim3((pl.ndirty + 3) / 4), dim3(256), 0, c->stream, d_bases, pl.chunk_start.get(), pl.chunk_len.get(),
                            pl.kmer_off.get(), pl.dirty_list.get(), pl.ndirty, c->P, out_lo, out_hi, out_base, eh);
@@ -1093,7 +1132,10 @@ void insert_device(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64 nse
     if (nseq == 0) return;
     check_aligned16(d_bases, "d_bases");
     const u64 cap = batch_max_bases();
-    const u64 first = d2h<u64>(c, d_offsets), last = d2h<u64>(c, d_offsets + nseq);
+    ReadGroup rg(c);  // first + last: one wait
+    const size_t h_first = rg.add(d_offsets), h_last = rg.add(d_offsets + nseq);
+    rg.wait();
+    const u64 first = rg.get<u64>(h_first), last = rg.get<u64>(h_last);
     if (last < first) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
     if (last - first <= cap) {
         const u64 ends[2] = {first, last};
@@ -1120,6 +1162,7 @@ void insert_device_one(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64
     dispatch(c->P, [&](auto cfg) {
         typedef decltype(cfg) C;
         ChunkPlan pl;
+        pl.allow_uniform = true;  // the plan is read by encode() alone
         plan_chunks(c, d_bases, d_offsets, nseq, pl, ends);
         if (pl.n_kmers == 0) return;
         if (pl.n_kmers >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "one sequence of 2^32-16 k-mers or more is not supported");

@@ -480,6 +480,10 @@ int cblx_kmers_inserted(cblx_ctx* ctx, uint64_t* out);
  * 2^22 —, CBLX_FINE_BINS != 0): the first partition pass runs on 253 intervals of the prefix space — aligned blocks of 2^16 prefixes
  * where the necklace prefixes are dense — so that most words need two more passes instead of three. Same index either way. */
 int cblx_fine_builds(cblx_ctx* ctx, uint64_t* out);
+/* Insert batches of this ctx whose chunk plan was ARITHMETIC: every sequence of the batch had the same length L with K <= L <= K + 2047 and
+ * no byte outside ACGTacgt, so KRN-1 took chunk and tile positions from (offsets[0], L, K) and no chunk table was built. Any other batch
+ * builds the tables; CBLX_UNIFORM_PLAN=0 (read per call) makes every batch do so. Same index either way. */
+int cblx_uniform_plans(cblx_ctx* ctx, uint64_t* out);
 /* Release cached device workspace (kept between flushes to avoid hipMalloc in the hot path). */
 int cblx_trim(cblx_ctx* ctx);
 /* Back to the state of CBL::new(): drops the resident index and anything enqueued, keeps the cached workspace. */
