@@ -6,6 +6,7 @@
 // HBM: bitvector words, popcount-scan rank directory, bucket table indexed by rank, one suffix arena.
 // There is no CPU fallback: every data-path step below is a kernel launch.
 #include "comm.hpp"
+#include "host_input.hpp"
 #include "kernels_list.hpp"
 
 namespace {
@@ -93,7 +94,7 @@ void read_fastx_into_queue(cblx_ctx* c, const char* path, uint64_t* n_records, c
         if (!path) throw Error(CBLX_EINVAL, "null argument");
         if (!filt) {   // large plain files: parallel readers; anything they do not take is read sequentially below
             u64 npar = 0;
-            if (fastx_parallel_planes(c, path, &npar)) { if (n_records) *n_records = npar; return; }  // (comm.hpp) bit planes, the insert behind the parse
+            if (fastx_parallel_planes(c, path, &npar)) { if (n_records) *n_records = npar; return; }  // (host_input.hpp) bit planes, the insert behind the parse
             if (fastx_parallel(c, path, &npar)) { if (n_records) *n_records = npar; return; }
         }
         auto mine = [&](u64 i) { return !filt || filt->mine(i); };
@@ -390,7 +391,7 @@ int cblx_insert_seqs(cblx_ctx* c, const uint8_t* bases, const uint64_t* offsets,
             scan(i0, i1, 4u, mono, ml);
             if (!mono || ml < c->P.K) { validate(); throw Error(CBLX_EINVAL, "offsets must be non-decreasing"); }
         };
-        // a big batch into an empty queue crosses PCIe as bit planes and is inserted right behind the transfer (comm.hpp)
+        // a big batch into an empty queue crosses PCIe as bit planes and is inserted right behind the transfer (host_input.hpp)
         if (ingest_seqs_planes(c, bases, offsets, n, check_slice)) return;
         ingest_seqs(c, bases, offsets, n, validate);
     });
@@ -538,29 +539,15 @@ int cblx_seq_words_partitioned_device(cblx_ctx* c, const uint8_t* d_bases, const
             if (nw > cap) throw Error(CBLX_ERANGE, "output capacity too small");
             if (nw == 0) return;
             if (nw >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "too many words in one partition call");
-            const size_t hs = hi_elem_size(c->P);
-            Buf<u64> t_lo(c->pool, nw + 2);
-            Buf<u8> t_hi(c->pool, hs ? (nw + 2) * hs : 8);
-            const u32 ntiles = (u32)ceil_div(nw, RDX_TILE);
-            Buf<u32> cnt(c->pool, (size_t)256 * (ntiles + 2)), colpre(c->pool, (size_t)256 * ntiles), scratch, coltot(c->pool, 256), adj(c->pool, 256);
-            CBLX_HIP(hipMemsetAsync(cnt.get(), 0, (size_t)256 * (ntiles + 2) * 4, c->stream));
             DigitDest fn;
             fn.SB = c->P.SB; fn.PB = c->P.PB; fn.nd = nd;
             EncHist eh{};
-            eh.counts = cnt.get();
             eh.nd = nd; eh.SB = c->P.SB; eh.PB = c->P.PB;
             for (u32 i = 0; i < MAX_DEST - 1; ++i) { fn.bounds[i] = i + 1 < nd ? bounds[i] : 0xFFFFFFFFu; eh.bounds[i] = fn.bounds[i]; }
-            encode<C>(c, d_bases, pl, t_lo.get(), (H*)t_hi.get(), 0, eh);
-            const TileView tv{nullptr, nullptr, nullptr, nullptr, ntiles, nw};
-            { StageTimer t(c, ST_SCAN);
-              colscan(c, cnt.get(), nullptr, ntiles, colpre.get(), coltot.get(), scratch);
-              hipLaunchKernelGGL(k_seg_adjust, dim3(1), dim3(256), 0, c->stream, colpre.get(), coltot.get(), (const u32*)nullptr, (const u32*)nullptr,
-                                 (const u32*)nullptr, ntiles, 1u, adj.get()); }
-            { StageTimer t(c, ST_SCATTER);
-              hipLaunchKernelGGL((k_radix_scatter<H, H, DigitDest>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, t_lo.get(), (const H*)t_hi.get(), tv, fn,
-                                 colpre.get(), adj.get(), d_out_lo, (H*)d_out_hi); }
-            CBLX_HIP(hipGetLastError());
-            std::vector<u32> tot = d2h_vec<u32>(c, coltot.get(), 256);
+            FirstPass wk;
+            first_pass_count<C>(c, wk, ascii_view(d_bases), pl, nw, eh);
+            first_pass_scatter<H, H, DigitDest>(c, wk, wk.t_lo.get(), (const H*)wk.t_hi.get(), fn, d_out_lo, (H*)d_out_hi);
+            std::vector<u32> tot = d2h_vec<u32>(c, wk.coltot.get(), 256);
             for (u32 d = 0; d < nd; ++d) counts[d] = tot[d];
         });
         collect_events(c);
@@ -581,28 +568,24 @@ int cblx_partition_words_device(cblx_ctx* c, const uint64_t* d_lo, const void* d
         fn.SB = c->P.SB; fn.PB = c->P.PB; fn.nd = nd;
         for (u32 i = 0; i < MAX_DEST - 1; ++i) fn.bounds[i] = i + 1 < nd ? bounds[i] : 0xFFFFFFFFu;
         for (u32 i = 1; i + 1 < nd; ++i) if (bounds[i] < bounds[i - 1]) throw Error(CBLX_EINVAL, "bounds must be ascending");
-        const u32 ntiles = (u32)ceil_div(n, RDX_TILE);
-        Buf<u32> cnt(c->pool, (size_t)256 * ntiles), colpre(c->pool, (size_t)256 * ntiles), scratch, coltot(c->pool, 256), adj(c->pool, 256);
-        const TileView tv{nullptr, nullptr, nullptr, nullptr, ntiles, n};
+        FirstPass wk;  // (the words are the caller's: the histogram is a pass of its own, the rest is the first pass's)
+        wk.n = n;
+        wk.ntiles = (u32)ceil_div(n, RDX_TILE);
+        wk.counts = Buf<u32>(c->pool, (size_t)256 * wk.ntiles); wk.colpre = Buf<u32>(c->pool, (size_t)256 * wk.ntiles);
+        wk.coltot = Buf<u32>(c->pool, 256); wk.adj = Buf<u32>(c->pool, 256);
+        const TileView tv{nullptr, nullptr, nullptr, nullptr, wk.ntiles, n};
         dispatch(c->P, [&](auto cfg) {
             typedef typename decltype(cfg)::HiT H;
             const H* hi = (const H*)d_hi;
-            H* ohi = (H*)d_out_hi;
             { StageTimer t(c, ST_HIST);
-              hipLaunchKernelGGL((k_radix_hist<H, DigitDest>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, d_lo, hi, tv, fn, cnt.get()); }
-            { StageTimer t(c, ST_SCAN);
-              colscan(c, cnt.get(), nullptr, ntiles, colpre.get(), coltot.get(), scratch);
-              hipLaunchKernelGGL(k_seg_adjust, dim3(1), dim3(256), 0, c->stream, colpre.get(), coltot.get(), (const u32*)nullptr, (const u32*)nullptr,
-                                 (const u32*)nullptr, ntiles, 1u, adj.get()); }
-            { StageTimer t(c, ST_SCATTER);
-              hipLaunchKernelGGL((k_radix_scatter<H, H, DigitDest>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, d_lo, hi, tv, fn, colpre.get(),
-                                 adj.get(), d_out_lo, ohi); }
-            CBLX_HIP(hipGetLastError());
+              hipLaunchKernelGGL((k_radix_hist<H, DigitDest>), dim3(xcd_grid(wk.ntiles)), dim3(RDX_THREADS), 0, c->stream, d_lo, hi, tv, fn, wk.counts.get()); }
+            first_pass_prefixes(c, wk);
+            first_pass_scatter<H, H, DigitDest>(c, wk, d_lo, hi, fn, d_out_lo, (H*)d_out_hi);
         });
         // run length of every destination = its column total
         std::vector<u64> starts(nd + 1, n);
         {
-            std::vector<u32> tot = d2h_vec<u32>(c, coltot.get(), 256);
+            std::vector<u32> tot = d2h_vec<u32>(c, wk.coltot.get(), 256);
             u64 run = 0;
             for (u32 d = 0; d < nd; ++d) { starts[d] = run; run += tot[d]; }
         }

@@ -1,15 +1,17 @@
 // comm.hpp — the multi-GPU build behind the C ABI: a communicator (RCCL over xGMI, loaded at run time, or host callbacks
-// supplied by the embedding program) and the sharded insert that runs on it. Included by cblx.cpp only.
+// supplied by the embedding program) and the sharded insert that runs on it. Included by cblx.cpp only (through host_input.hpp, which holds
+// the PCIe ingest that feeds the one-rank routes). The first partition pass of a piece is pipeline.hpp's (first_pass_count / first_pass_scatter),
+// the layout arithmetic between bin totals, headers, send ranges and piece tables is wire_layout.hpp's (host-only, unit-tested with g++).
 //
 // No reference counterpart (the reference is one process); the path is BASELINE.json's north_star: buckets are
 // independent by prefix, so the 2^PREFIX_BITS space is cut into `world` contiguous ranges (quantiles of a sampled, all-reduced
 // prefix histogram) and what the k-mers turn into crosses the links once. Three protocols, same result (byte-identical to the
 // one-process build in the job's stream order, slice-major / rank-minor):
-//   "bins", grouped receiver (default on an empty index; sharded_insert_grouped): the senders run KRN-1 + the FIRST partition pass on
+//   "bins", grouped receiver (default on an empty index; sharded_insert_grouped = the phases of GroupedInsert): the senders run KRN-1 + the FIRST partition pass on
 //     bins that refine that pass's digit by the destination rank and by G groups per rank; 8-byte records + a digit byte cross the
 //     links group-major, and the receiver runs the remaining passes, its window of the directory and the bucket kernels of group g
 //     while groups g+1.. are still on the wire;
-//   "bins", plain receiver (sharded_insert_bins: non-empty index, degenerate bounds, one rank, the sliced one-GPU host input): the
+//   "bins", plain receiver (sharded_insert_bins = BinsInsert: non-empty index, degenerate bounds, one rank, the sliced one-GPU host input): the
 //     same records slice-major, everything behind the first pass once the last record has landed;
 //   "sorted" (sharded_insert_sorted): the sender partitions completely and ships prefixes, counts and packed suffixes; the receiver
 //     merges the batches run by run — a third fewer bytes on the wire, one more pass over the words (2 - 4 GPUs, PREFIX_BITS <= 8).
@@ -25,6 +27,7 @@
 #include <functional>
 
 #include "shard.hpp"
+#include "wire_layout.hpp"
 
 namespace {
 
@@ -227,7 +230,6 @@ struct CallbackTransport : Transport {
         }
     }
 };
-
 
 // ---- rehearsal of ONE rank of a W-GPU job on one GPU (dev / bench: tools/emulate_wire.py; cblx_comm_init_sim) ----------------------
 // No multi-GPU node was available while this was built, so the schedule of the sharded insert — what the receiver's kernels hide of
@@ -449,11 +451,18 @@ void choose_bounds_from_slice(cblx_ctx* c, Transport& T, const u8* d_bases, cons
     if (hist_out) *hist_out = std::move(hist);
 }
 
+// ---- what the protocols share -------------------------------------------------------------------------------------------------------
+// an error between two slices must not hand the buffers of an exchange that is still running back to the pool (armed once `t` is set)
+struct Drain { Transport* t; ~Drain() { if (t) try { t->wait(); } catch (...) {} } };
+inline void check_slice_cuts(const u64* cuts, u32 nslices, u64 n) {
+    for (u32 s = 0; s < nslices; ++s) if (cuts[s + 1] < cuts[s] || cuts[s + 1] > n) throw Error(CBLX_EINVAL, "slice cuts must be ascending and at most n");
+}
+static const u64 ROUND_LIMIT = 0xFFFFFFF0ull - 2 * RDX_TILE;  // one round = one batch of the pipeline (32-bit positions)
+
 // ---- protocol "sorted": the sender partitions completely; prefixes, counts and packed suffixes on the wire; the receiver
 // merges the batches run by run (fewest bytes per word: the choice when the links are the bound, world <= 4) ----------------
 template <typename C>
 void sharded_insert_sorted(cblx_ctx* c, Transport& T, const u8* d_bases, const u64* d_offsets, u64 n, const u64* cuts, u32 nslices, u32* bounds, int* bounds_valid) {
-    typedef typename C::HiT HiT;
     const Consts& P = c->P;
     const u32 W = T.world, B = P.BYTES;
     struct Slice {
@@ -462,11 +471,10 @@ void sharded_insert_sorted(cblx_ctx* c, Transport& T, const u8* d_bases, const u
         std::vector<u64> rb, rw;   // received buckets / words per source rank
     };
     std::vector<Slice> sl(nslices);
-    // an error between two slices must not hand the buffers of an exchange that is still running back to the pool
-    struct Drain { Transport& t; ~Drain() { try { t.wait(); } catch (...) {} } } drain{T};
+    Drain drain{&T};
     for (u32 s = 0; s < nslices; ++s) {
         const u64 a = cuts[s], b = cuts[s + 1];
-        if (b < a || b > n) throw Error(CBLX_EINVAL, "slice cuts must be ascending and at most n");
+        check_slice_cuts(cuts + s, 1, n);
         if (!*bounds_valid) {
             choose_bounds_from_slice<C>(c, T, d_bases, d_offsets + a, b - a, bounds);
             *bounds_valid = 1;
@@ -519,68 +527,84 @@ void sharded_insert_sorted(cblx_ctx* c, Transport& T, const u8* d_bases, const u
 // segment, as on one GPU) plus the 1-byte digit side channel of the next pass. The receiver keeps the arena as the input of
 // the remaining passes: a piece table (slice, source, segment) -> tile table of the first LSD pass (k_piece_tables), after
 // which the one-GPU pipeline continues unchanged. No pass is added to the one-GPU path and no record is copied: per rank the
-// job costs what the direct build costs plus the slices' fixed costs.
-struct BinMap {
-    u32 v_of[256], d_of[256];  // bin -> segment, destination (0xFFFFFFFF: no such bin)
-    bool ok = true;
-};
-inline BinMap make_bin_map(const Consts& P, const u32* bounds, u32 W) {
-    BinMap M;
-    for (u32 i = 0; i < 256; ++i) M.v_of[i] = M.d_of[i] = 0xFFFFFFFFu;
-    const u32 RB = P.PB - 8;
-    auto dest = [&](u64 p) { u32 d = 0; for (u32 i = 0; i + 1 < W; ++i) d += bounds[i] <= p ? 1u : 0u; return d; };
-    for (u32 i = 0; i + 1 < W; ++i) if ((u64)bounds[i] > (255ull << RB)) M.ok = false;  // the all-ones segment must belong to one rank
-    for (u32 v = 0; v < 128; ++v)
-        for (u32 d = dest((u64)v << RB); d <= dest((((u64)v + 1) << RB) - 1); ++d) { M.v_of[v + d] = v; M.d_of[v + d] = d; }
-    M.v_of[255] = 255; M.d_of[255] = W - 1;
-    return M;
-}
-inline bool bins_protocol_fits(const Consts& P, const u32* bounds, u32 W) { return P.PB >= 9 && make_bin_map(P, bounds, W).ok; }
+// job costs what the direct build costs plus the slices' fixed costs. (The bin map and the layout arithmetic: wire_layout.hpp.)
+inline bool bins_protocol_fits(const Consts& P, const u32* bounds, u32 W) { return P.PB >= 9 && make_bin_map(P.PB, bounds, W).ok; }
 
-// `before_slice` (optional): called before slice s is touched — where a caller whose slices are still arriving (a batch on its way
-// over PCIe, flush()) makes the ctx's stream wait for slice s; before_slice(~0u) precedes the first read of the offsets.
-template <typename C, typename Hook>
-void sharded_insert_bins(cblx_ctx* c, Transport& T, const BaseView& d_bases, const u64* d_offsets, u64 n, const u64* cuts, u32 nslices, const u32* bounds, Hook&& before_slice) {
-    typedef typename C::HiT HiT;
-    constexpr bool DROP_HI = std::is_same<HiT, u8>::value;
-    typedef typename std::conditional<DROP_HI, NoHi, HiT>::type OutH;  // record layout behind pass A
-    constexpr size_t OHS = HiTraits<OutH>::has ? sizeof(u64) : 0;       // bytes of the hi part on the wire (u64 or none)
-    const Consts& P = c->P;
-    const u32 W = T.world, me = T.rank, RB = P.PB - 8;
-    const BinMap M = make_bin_map(P, bounds, W);
-    const LsdPlan LP = lsd_plan(P, false);  // (the receiver runs LSD passes only: pipeline.hpp)
-    const DigitBits nextd{P.SB + LP.sh[0], LP.wid[0]};
-    DigitBin fn;
-    fn.SB = P.SB; fn.PB = P.PB; fn.RB = RB; fn.nd = W;
-    EncHist eh0{};
-    eh0.nd = W; eh0.SB = P.SB; eh0.PB = P.PB; eh0.binRB = RB;
-    for (u32 i = 0; i < MAX_DEST - 1; ++i) { fn.bounds[i] = i + 1 < W ? bounds[i] : 0xFFFFFFFFu; eh0.bounds[i] = fn.bounds[i]; }
-
-    // receive arena: the slices land back to back; capacity from the job's k-mer count (an upper bound: bases - (K - 1) per
-    // sequence), the rank's share of it with slack for uneven ranges; it grows when a slice does not fit
-    for (u32 s = 0; s < nslices; ++s) if (cuts[s + 1] < cuts[s] || cuts[s + 1] > n) throw Error(CBLX_EINVAL, "slice cuts must be ascending and at most n");
-    const u64 n0 = cuts[0], n1 = cuts[nslices];
-    u64 mine = 0;
-    before_slice(~0u);
-    if (n1 > n0) {
-        const u64 first = d2h<u64>(c, d_offsets + n0), last = d2h<u64>(c, d_offsets + n1);
-        if (last < first) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
-        const u64 sub = (n1 - n0) * (u64)(P.K - 1);
-        mine = last - first > sub ? last - first - sub : 0;
+// The receive log (arena) of the "bins" protocols: the slices land back to back — 8-byte records, the hi parts of words that keep
+// one behind pass A, and the digit byte of the receiver's first LSD pass (`wire_dig`; off the wire: one block, the receiver's first
+// histogram reads the records). Capacity from the job's k-mer count (an upper bound), the rank's share of it with slack for uneven
+// ranges; it grows when a slice does not fit.
+struct RecvLog {
+    cblx_ctx* c;
+    Transport& T;
+    size_t ohs;            // bytes of the hi part of a record (u64 or none)
+    bool wire_dig = true;  // digits on the wire
+    Buf<u64> lo;
+    Buf<u8> hi, dig;
+    u64 cap = 0, filled = 0;
+    void alloc_into(u64 ncap, Buf<u64>& l, Buf<u8>& h, Buf<u8>& dg) const {
+        l = Buf<u64>(c->pool, ncap + 2);
+        h = Buf<u8>(c->pool, ohs ? (ncap + 2) * ohs : 8);
+        dg = Buf<u8>(c->pool, wire_dig ? ncap + 64 : 64);
     }
-    u64 job = mine;
-    T.all_reduce_sum_u64(&job, 1);
-    const u64 LIMIT = 0xFFFFFFF0ull - 2 * RDX_TILE;  // one round = one batch of the pipeline (32-bit positions)
+    void alloc() { alloc_into(cap, lo, hi, dig); }
+    void grow(u64 need) {  // (grouped receiver: only own pieces and the first group's early shares are in the log)
+        T.wait();
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+        const u64 ncap = std::min<u64>(ROUND_LIMIT, need + need / 4 + 4096);
+        Buf<u64> l;
+        Buf<u8> h, dg;
+        alloc_into(ncap, l, h, dg);
+        if (filled) {
+            CBLX_HIP(hipMemcpyAsync(l.get(), lo.get(), filled * 8, hipMemcpyDeviceToDevice, c->stream));
+            if (ohs) CBLX_HIP(hipMemcpyAsync(h.get(), hi.get(), filled * ohs, hipMemcpyDeviceToDevice, c->stream));
+            if (wire_dig) CBLX_HIP(hipMemcpyAsync(dg.get(), dig.get(), filled, hipMemcpyDeviceToDevice, c->stream));
+            CBLX_HIP(hipStreamSynchronize(c->stream));
+        }
+        lo = std::move(l); hi = std::move(h); dig = std::move(dg);
+        cap = ncap;
+    }
+    void room(u64 need) {  // the log holds `need` records from here on
+        if (!lo.get()) alloc();
+        if (need > cap) grow(need);
+    }
+    void reset() { lo.reset(); hi.reset(); dig.reset(); }
+    // where the first pass writes the sender's own records: the end of the log
+    OwnWindow own_window(const OwnShare& own) const {
+        return OwnWindow{own.a, own.a + own.n, lo.get() + filled, ohs ? (void*)(hi.get() + filled * ohs) : nullptr, wire_dig ? dig.get() + filled : (u8*)nullptr};
+    }
+};
+
+// One rank: the bin totals of a first pass that stay on the device until the passes of the round are queued (no host round trip between
+// KRN-1 and the pass), then become the piece's row of the piece table. `what`: "slice" or "piece" (the text of the count check).
+struct DeferredTotals { size_t piece; u64 n; Buf<u32> coltot; };
+template <typename Map> void fold_deferred(cblx_ctx* c, const Map& M, std::vector<DeferredTotals>& v, const char* what, std::vector<u32>& pcnt) {
+    for (DeferredTotals& d : v) {
+        const std::vector<u32> t = d2h_vec<u32>(c, d.coltot.get(), 256);
+        std::vector<u64> row(WIRE_HDR, 0);
+        wire_header(M, t.data(), 1, 0, d.n, what, row.data());
+        for (u32 cl = 0; cl < 256; ++cl) pcnt[d.piece * 256 + cl] += (u32)row[1 + cl];
+    }
+    v.clear();
+}
+
+// One call of sharded_insert_bins (below): the slices one by one, the round's end.
+template <typename C>
+struct BinsInsert {
+    typedef typename C::HiT HiT;
+    static constexpr bool DROP_HI = std::is_same<HiT, u8>::value;
+    typedef typename std::conditional<DROP_HI, NoHi, HiT>::type OutH;  // record layout behind pass A
+    static constexpr size_t OHS = HiTraits<OutH>::has ? sizeof(u64) : 0;  // bytes of the hi part on the wire (u64 or none)
+    cblx_ctx* c;
+    Transport& T;
+    const u32 W, me;
+    const BinMap M;
+    DigitBin fn;
+    EncHist eh0{};
+    DigitBits nextd;
     const bool trace = std::getenv("CBLX_TRACE_SHARDED") != nullptr;
-    u64 cap = W == 1 ? mine : std::min<u64>(job, job / W + job / (4 * W) + (1u << 20));
-    cap = std::min<u64>(std::max<u64>(cap, 1024), LIMIT);
-    Buf<u64> a_lo;
-    Buf<u8> a_hi, a_dig;
-    auto alloc_arena = [&](u64 ncap, Buf<u64>& lo, Buf<u8>& hi, Buf<u8>& dg) {
-        lo = Buf<u64>(c->pool, ncap + 2);
-        hi = Buf<u8>(c->pool, OHS ? (ncap + 2) * OHS : 8);
-        dg = Buf<u8>(c->pool, ncap + 64);
-    };
+    u64 mine, job;
+    RecvLog log;
     // send buffers of the exchanges in flight. A slice's buffers go back to the pool as soon as its exchange has completed (an event
     // behind it on the transport's stream, polled at the start of every later slice): what stays allocated is bounded by the slices the
     // wire is behind, not by the job (a whole call's send buffers — (W-1)/W of the rank's words, 9 bytes each — next to the receive
@@ -588,7 +612,28 @@ void sharded_insert_bins(cblx_ctx* c, Transport& T, const BaseView& d_bases, con
     struct Sent { Buf<u64> lo; Buf<u8> hi, dig; hipEvent_t done = nullptr; };
     std::vector<Sent> sent;
     struct SentEvents { std::vector<Sent>& v; ~SentEvents() { for (Sent& x : v) if (x.done) (void)hipEventDestroy(x.done); } } sent_events{sent};
-    auto reap_sent = [&]() {
+    std::vector<u32> pcnt, pbase;      // piece table of the round: [piece][256] counts, arena position of every piece
+    FirstPass prev_work;  // workspace of the previous slice
+    // one rank (a batch arriving over PCIe, insert_device_sliced): everything is the rank's own, nothing has to be agreed per slice —
+    // the bin counts of a slice stay on the device until the round ends, and the slices run without a host round trip between
+    // KRN-1 and pass A
+    std::vector<DeferredTotals> deferred;
+    Drain drain{nullptr};
+
+    // `mine_`: an upper bound of this rank's k-mers — the job's count (all-reduced) gives the capacity of the log
+    BinsInsert(cblx_ctx* ctx, Transport& t, const u32* bounds, u64 mine_) : c(ctx), T(t), W(t.world), me(t.rank), M(make_bin_map(ctx->P.PB, bounds, t.world)), mine(mine_), job(mine_), log{ctx, t, OHS} {
+        const Consts& P = c->P;
+        const LsdPlan LP = lsd_plan(P, false);  // (the receiver runs LSD passes only: pipeline.hpp)
+        nextd = DigitBits{P.SB + LP.sh[0], LP.wid[0]};
+        fn.SB = P.SB; fn.PB = P.PB; fn.RB = P.PB - 8; fn.nd = W;
+        eh0.nd = W; eh0.SB = P.SB; eh0.PB = P.PB; eh0.binRB = P.PB - 8;
+        for (u32 i = 0; i < MAX_DEST - 1; ++i) { fn.bounds[i] = i + 1 < W ? bounds[i] : 0xFFFFFFFFu; eh0.bounds[i] = fn.bounds[i]; }
+        T.all_reduce_sum_u64(&job, 1);
+        const u64 cap = W == 1 ? mine : std::min<u64>(job, job / W + job / (4 * W) + (1u << 20));
+        log.cap = std::min<u64>(std::max<u64>(cap, 1024), ROUND_LIMIT);
+        drain.t = &T;
+    }
+    void reap_sent() {
         for (size_t i = 0; i < sent.size();) {
             if (sent[i].done && hipEventQuery(sent[i].done) == hipSuccess) {
                 (void)hipEventDestroy(sent[i].done);
@@ -596,176 +641,85 @@ void sharded_insert_bins(cblx_ctx* c, Transport& T, const BaseView& d_bases, con
                 sent.pop_back();
             } else { (void)hipGetLastError(); ++i; }
         }
-    };
-    std::vector<u32> pcnt, pbase;      // piece table of the round: [piece][256] counts, arena position of every piece
-    // one rank (a batch arriving over PCIe, insert_device_sliced): everything is the rank's own, nothing has to be agreed per slice —
-    // the bin counts of a slice stay on the device until the round ends, and the slices run without a host round trip between
-    // KRN-1 and pass A
-    struct Deferred { size_t piece; u64 n; Buf<u32> coltot; };
-    struct Work { ChunkPlan pl; Buf<u64> t_lo; Buf<u8> t_hi; Buf<u32> counts, colpre, scratch, adj; };  // workspace of one slice
-    Work prev_work;
-    std::vector<Deferred> deferred;
-    u64 filled = 0;
-    struct Drain { Transport& t; ~Drain() { try { t.wait(); } catch (...) {} } } drain{T};
-    auto grow = [&](u64 need) {
-        T.wait();
-        CBLX_HIP(hipStreamSynchronize(c->stream));
-        const u64 ncap = std::min<u64>(LIMIT, need + need / 4 + 4096);
-        Buf<u64> lo;
-        Buf<u8> hi, dg;
-        alloc_arena(ncap, lo, hi, dg);
-        if (filled) {
-            CBLX_HIP(hipMemcpyAsync(lo.get(), a_lo.get(), filled * 8, hipMemcpyDeviceToDevice, c->stream));
-            if (OHS) CBLX_HIP(hipMemcpyAsync(hi.get(), a_hi.get(), filled * OHS, hipMemcpyDeviceToDevice, c->stream));
-            CBLX_HIP(hipMemcpyAsync(dg.get(), a_dig.get(), filled, hipMemcpyDeviceToDevice, c->stream));
-            CBLX_HIP(hipStreamSynchronize(c->stream));
-        }
-        a_lo = std::move(lo); a_hi = std::move(hi); a_dig = std::move(dg);
-        cap = ncap;
-    };
+    }
     // what has been received so far goes through the rest of the pipeline (end of the call, or the arena would pass 2^32 records)
-    auto finish_round = [&]() {
+    void finish_round() {
         T.wait();
         CBLX_HIP(hipStreamSynchronize(c->stream));
         for (Sent& x : sent) if (x.done) { (void)hipEventDestroy(x.done); x.done = nullptr; }
         sent.clear();
-        if (trace) fprintf(stderr, "[cblx bins] rank %u round ends: filled=%llu pieces=%zu\n", me, (unsigned long long)filled, pbase.size());
-        for (Deferred& d : deferred) {
-            const std::vector<u32> t = d2h_vec<u32>(c, d.coltot.get(), 256);
-            u64 sum = 0;
-            for (u32 bin = 0; bin < 256; ++bin) {
-                if (!t[bin]) continue;
-                if (M.v_of[bin] == 0xFFFFFFFFu) throw Error(CBLX_EDEVICE, "sharded build: a word fell into a bin no prefix maps to (internal error)");
-                pcnt[d.piece * 256 + M.v_of[bin]] += t[bin];
-                sum += t[bin];
-            }
-            if (sum != d.n) throw Error(CBLX_EDEVICE, "sharded build: the bin histogram counts " + std::to_string(sum) + " words, the slice has " + std::to_string(d.n) + " (internal error)");
-        }
-        deferred.clear();
-        if (filled) {
+        if (trace) fprintf(stderr, "[cblx bins] rank %u round ends: filled=%llu pieces=%zu\n", me, (unsigned long long)log.filled, pbase.size());
+        fold_deferred(c, M, deferred, "slice", pcnt);
+        if (log.filled) {
             Records rec;
-            rec.lo = std::move(a_lo);
-            rec.hi = std::move(a_hi);
-            rec.lo2 = Buf<u64>(c->pool, filled + 2);
-            rec.hi2 = Buf<u8>(c->pool, OHS ? (filled + 2) * OHS : 8);
+            rec.lo = std::move(log.lo); rec.hi = std::move(log.hi);
+            rec.lo2 = Buf<u64>(c->pool, log.filled + 2); rec.hi2 = Buf<u8>(c->pool, OHS ? (log.filled + 2) * OHS : 8);
             PieceInput pin;
-            pin.np = (u32)pbase.size();
-            pin.cnt = pcnt.data();
-            pin.pbase = pbase.data();
-            pin.dig = &a_dig;
-            pipeline<C>(c, rec, filled, Buf<u32>(), &pin);
-            c->kmers_inserted += filled;
+            pin.np = (u32)pbase.size(); pin.cnt = pcnt.data(); pin.pbase = pbase.data(); pin.dig = &log.dig;
+            pipeline<C>(c, rec, log.filled, Buf<u32>(), &pin);
+            c->kmers_inserted += log.filled;
         }
-        a_lo.reset(); a_hi.reset(); a_dig.reset();
+        log.reset();
         pcnt.clear(); pbase.clear();
-        filled = 0;
-    };
-    for (u32 s = 0; s < nslices; ++s) {
-        const u64 a = cuts[s], b = cuts[s + 1];
-        before_slice(s);
+        log.filled = 0;
+    }
+    // slice s = `nseq` sequences from d_off: KRN-1 + pass A on bins, the count exchange, the own piece into the log, the rest onto the wire
+    void slice(u32 s, const BaseView& d_bases, const u64* d_off, u64 nseq) {
         reap_sent();
         // -- KRN-1 with the bin histogram fused in, column prefixes of pass A
         ChunkPlan pl;
         BaseView pb = d_bases;
         u64 N = 0;
-        if (b > a) { plan_chunks(c, pb, d_offsets + a, b - a, pl); N = pl.n_kmers; }  // (ends with a stream synchronisation)
+        if (nseq) { plan_chunks(c, pb, d_off, nseq, pl); N = pl.n_kmers; }  // (ends with a stream synchronisation)
         else CBLX_HIP(hipStreamSynchronize(c->stream));
-        prev_work = Work();  // the previous slice's kernels are done: its workspace goes back to the pool
+        prev_work = FirstPass();  // the previous slice's kernels are done: its workspace goes back to the pool
         if (N >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "one slice takes fewer than 2^32-16 words (use more slices)");
-        const u32 ntiles = (u32)ceil_div(N, RDX_TILE);
-        Work wk;
-        Buf<u64>& t_lo = wk.t_lo;
-        Buf<u8>& t_hi = wk.t_hi;
-        Buf<u32>&counts = wk.counts, &colpre = wk.colpre, &scratch = wk.scratch, &adj = wk.adj;
-        Buf<u32> coltot(c->pool, 256);
-        adj = Buf<u32>(c->pool, 256);
+        FirstPass wk;
         wk.pl = std::move(pl);
-        const ChunkPlan& plr = wk.pl;
         std::vector<u32> tot(256, 0u);
         if (N) {
-            const size_t hs = hi_elem_size(P);
-            t_lo = Buf<u64>(c->pool, N + 2);
-            t_hi = Buf<u8>(c->pool, hs ? (N + 2) * hs : 8);
-            counts = Buf<u32>(c->pool, (size_t)256 * (ntiles + 2));
-            colpre = Buf<u32>(c->pool, (size_t)256 * ntiles);
-            CBLX_HIP(hipMemsetAsync(counts.get(), 0, (size_t)256 * (ntiles + 2) * 4, c->stream));
-            EncHist eh = eh0;
-            eh.counts = counts.get();
-            encode<C>(c, pb, plr, t_lo.get(), (HiT*)t_hi.get(), 0, eh);
-            { StageTimer t(c, ST_SCAN);
-              colscan(c, counts.get(), nullptr, ntiles, colpre.get(), coltot.get(), scratch);
-              hipLaunchKernelGGL(k_seg_adjust, dim3(1), dim3(256), 0, c->stream, colpre.get(), coltot.get(), (const u32*)nullptr, (const u32*)nullptr,
-                                 (const u32*)nullptr, ntiles, 1u, adj.get()); }
-            CBLX_HIP(hipGetLastError());
-            if (W > 1) tot = d2h_vec<u32>(c, coltot.get(), 256);
+            first_pass_count<C>(c, wk, pb, wk.pl, N, eh0);
+            if (W > 1) tot = d2h_vec<u32>(c, wk.coltot.get(), 256);
         }
         // -- what goes where: per destination the word count and the count of every segment (header of the exchange)
-        const size_t HDR = 257;
+        const size_t HDR = WIRE_HDR;
         std::vector<u64> send((size_t)W * HDR, 0), recv((size_t)W * HDR, 0);
-        if (W == 1) { send[0] = N; recv[0] = N; }  // (the segment counts follow at the end of the round: `deferred`)
-        else
-        for (u32 bin = 0; bin < 256; ++bin) {
-            if (!tot[bin]) continue;
-            if (M.v_of[bin] == 0xFFFFFFFFu) throw Error(CBLX_EDEVICE, "sharded build: a word fell into a bin no prefix maps to (internal error)");
-            send[(size_t)M.d_of[bin] * HDR] += tot[bin];
-            send[(size_t)M.d_of[bin] * HDR + 1 + M.v_of[bin]] += tot[bin];
-        }
-        {
-            u64 sum = 0;
-            for (u32 d = 0; d < W; ++d) sum += send[(size_t)d * HDR];
-            if (sum != N) throw Error(CBLX_EDEVICE, "sharded build: the bin histogram counts " + std::to_string(sum) + " words, the slice has " + std::to_string(N) + " (internal error)");
-        }
+        OwnShare own;
+        if (W == 1) { send[0] = N; recv[0] = N; own.n = N; }  // (the segment counts follow at the end of the round: `deferred`)
+        else own = wire_header(M, tot.data(), W, me, N, "slice", send.data());
         if (W > 1) T.all_to_all_u64(send.data(), recv.data(), HDR);
-        u64 own_a = 0, incoming = 0;
-        for (u32 d = 0; d < me; ++d) own_a += send[(size_t)d * HDR];
-        const u64 own = send[(size_t)me * HDR], own_b = own_a + own;
-        if (recv[(size_t)me * HDR] != own) throw Error(CBLX_EDEVICE, "sharded build: the count exchange returned another own count (transport error)");
+        u64 incoming = 0;
+        if (recv[(size_t)me * HDR] != own.n) throw Error(CBLX_EDEVICE, "sharded build: the count exchange returned another own count (transport error)");
         for (u32 r = 0; r < W; ++r) incoming += recv[(size_t)r * HDR];
-        if (incoming >= LIMIT) throw Error(CBLX_ERANGE, "one slice of the job sends this rank 2^32 words or more (use more slices)");
-        if (trace) fprintf(stderr, "[cblx bins] rank %u slice %u: N=%llu own=%llu incoming=%llu filled=%llu cap=%llu mine=%llu job=%llu\n", me, s, (unsigned long long)N, (unsigned long long)own,
-                           (unsigned long long)incoming, (unsigned long long)filled, (unsigned long long)cap, (unsigned long long)mine, (unsigned long long)job);
-        if (filled + incoming > LIMIT) finish_round();
-        if (!a_lo.get()) alloc_arena(cap, a_lo, a_hi, a_dig);
-        if (filled + incoming > cap) grow(filled + incoming);
-        // -- arena layout of the slice: the own piece first (pass A writes it there), then the other sources in rank order;
-        //    the piece table keeps the logical order (slice-major, source-minor)
+        if (incoming >= ROUND_LIMIT) throw Error(CBLX_ERANGE, "one slice of the job sends this rank 2^32 words or more (use more slices)");
+        if (trace) fprintf(stderr, "[cblx bins] rank %u slice %u: N=%llu own=%llu incoming=%llu filled=%llu cap=%llu mine=%llu job=%llu\n", me, s, (unsigned long long)N, (unsigned long long)own.n,
+                           (unsigned long long)incoming, (unsigned long long)log.filled, (unsigned long long)log.cap, (unsigned long long)mine, (unsigned long long)job);
+        if (log.filled + incoming > ROUND_LIMIT) finish_round();
+        log.room(log.filled + incoming);
+        const u64 filled = log.filled;
+        // -- arena layout of the slice: the own piece first (pass A writes it there), then the other sources in rank order
         std::vector<u64> so(W + 1, 0), ro(W + 1, 0);  // record positions in the send buffer / behind the own piece
         for (u32 d = 0; d < W; ++d) {
             so[d + 1] = so[d] + (d == me ? 0 : send[(size_t)d * HDR]);
             ro[d + 1] = ro[d] + (d == me ? 0 : recv[(size_t)d * HDR]);
         }
-        for (u32 r = 0; r < W; ++r) {
-            pbase.push_back((u32)(r == me ? filled : filled + own + ro[r]));
-            for (u32 v = 0; v < 256; ++v) pcnt.push_back((u32)recv[(size_t)r * HDR + 1 + v]);
-        }
-        if (W == 1 && N) deferred.push_back(Deferred{pbase.size() - 1, N, std::move(coltot)});
+        push_pieces(recv.data(), W, me, filled, own.n, pbase, pcnt);
+        if (W == 1 && N) deferred.push_back(DeferredTotals{pbase.size() - 1, N, std::move(wk.coltot)});
         Sent S;
-        const u64 nsend = N - own;
-        S.lo = Buf<u64>(c->pool, nsend + 2);
-        S.hi = Buf<u8>(c->pool, OHS ? (nsend + 2) * OHS : 8);
-        S.dig = Buf<u8>(c->pool, nsend + 64);
-        if (N) {
-            const TileView tv{nullptr, nullptr, nullptr, nullptr, ntiles, N};
-            const OwnWindow ow{own_a, own_b, a_lo.get() + filled, OHS ? (void*)(a_hi.get() + filled * OHS) : nullptr, a_dig.get() + filled};
-            StageTimer t(c, ST_SCATTER);
-            c->stages[ST_SCATTER].units += N;
-            hipLaunchKernelGGL((k_radix_scatter<HiT, OutH, DigitBin, true>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, (const u64*)t_lo.get(), (const HiT*)t_hi.get(), tv, fn,
-                               (const u32*)colpre.get(), (const u32*)adj.get(), S.lo.get(), (OutH*)S.hi.get(), nextd, S.dig.get(), (u32*)nullptr, 0u, 0u, 0u, (u32*)nullptr, 0u, ow);
-            CBLX_HIP(hipGetLastError());
-        }
+        log.alloc_into(N - own.n, S.lo, S.hi, S.dig);  // (a send buffer is laid out as the log is)
+        if (N) first_pass_scatter<HiT, OutH, DigitBin, true>(c, wk, wk.t_lo.get(), (const HiT*)wk.t_hi.get(), fn, S.lo.get(), (OutH*)S.hi.get(), true, nextd, S.dig.get(), log.own_window(own));
         // -- the exchange (on the transport's stream, behind pass A): records, hi parts, digits
-        u8* dst_lo = (u8*)(a_lo.get() + filled + own);
         std::vector<u64> sob(W + 1), rob(W + 1);
         auto xchg = [&](const u8* src, u8* dst, size_t es) {
             for (u32 d = 0; d <= W; ++d) { sob[d] = so[d] * es; rob[d] = ro[d] * es; }
             T.exchange(src, sob.data(), dst, rob.data(), c->stream);
         };
         if (W > 1) {
-            xchg((const u8*)S.lo.get(), dst_lo, 8);
-            if (OHS) xchg(S.hi.get(), a_hi.get() + (filled + own) * OHS, OHS);
-            xchg(S.dig.get(), a_dig.get() + filled + own, 1);
+            xchg((const u8*)S.lo.get(), (u8*)(log.lo.get() + filled + own.n), 8);
+            if (OHS) xchg(S.hi.get(), log.hi.get() + (filled + own.n) * OHS, OHS);
+            xchg(S.dig.get(), log.dig.get() + filled + own.n, 1);
         }
-        filled += incoming;
+        log.filled += incoming;
         if (W > 1) {
             CBLX_HIP(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
             T.record(S.done, c->stream);
@@ -775,7 +729,19 @@ void sharded_insert_bins(cblx_ctx* c, Transport& T, const BaseView& d_bases, con
         // stream: the host queues the next slice's first kernels while this slice's pass A is still running
         prev_work = std::move(wk);
     }
-    finish_round();
+};
+// `before_slice` (optional): called before slice s is touched — where a caller whose slices are still arriving (a batch on its way
+// over PCIe, flush()) makes the ctx's stream wait for slice s; before_slice(~0u) precedes the first read of the offsets.
+template <typename C, typename Hook>
+void sharded_insert_bins(cblx_ctx* c, Transport& T, const BaseView& d_bases, const u64* d_offsets, u64 n, const u64* cuts, u32 nslices, const u32* bounds, Hook&& before_slice) {
+    check_slice_cuts(cuts, nslices, n);
+    before_slice(~0u);
+    BinsInsert<C> J(c, T, bounds, kmers_upper_bound(c, d_offsets, cuts[0], cuts[nslices]));
+    for (u32 s = 0; s < nslices; ++s) {
+        before_slice(s);
+        J.slice(s, d_bases, d_offsets + cuts[s], cuts[s + 1] - cuts[s]);
+    }
+    J.finish_round();
     CBLX_HIP(hipStreamSynchronize(c->stream));
 }
 
@@ -838,195 +804,245 @@ struct Replica {
     bool per_slice = false;
     std::function<void(u32)> ready;
 };
+// One call of the grouped insert, phase by phase (sharded_insert_grouped below runs them in order).
 // `single`: ONE rank whose "groups" are the part of the prefix space the FINE bins cover in blocks of 2^16 prefixes and the rest (insert_device_fine):
 // no wire, the same sender and receiver steps
 // `rep`: no records cross the wire — piece (slice, source) is what THIS rank's first pass keeps of the source's reads (its own prefix range), the
 // receiver steps are the same
 template <typename C>
-bool sharded_insert_grouped(cblx_ctx* c, cblx_comm* cm, const u8* d_bases, const u64* d_offsets, u64 n, const u64* cuts, u32 nslices, const u32* bounds, bool single = false,
-                            const Replica* rep = nullptr) {
+struct GroupedInsert {
     typedef typename C::HiT HiT;
-    constexpr bool WS = C::WS;
-    constexpr bool DROP_HI = std::is_same<HiT, u8>::value;
+    static constexpr bool WS = C::WS;
+    static constexpr bool DROP_HI = std::is_same<HiT, u8>::value;
     typedef typename std::conditional<DROP_HI, NoHi, HiT>::type OutH;
-    constexpr size_t OHS = HiTraits<OutH>::has ? sizeof(u64) : 0;
+    static constexpr size_t OHS = HiTraits<OutH>::has ? sizeof(u64) : 0;
+    static constexpr size_t HDR = WIRE_HDR;
+    // -- the call (the job is an aggregate: these ten are given, the rest follows from them)
+    cblx_ctx* c; cblx_comm* cm; const u8* d_bases; const u64* d_offsets; u64 n; const u64* cuts; u32 nslices; const u32* bounds; bool single; const Replica* rep;
     Transport& T = *cm->t;
     const Consts& P = c->P;
-    const u32 W = T.world, me = T.rank, RB = P.PB - 8;
-    const u32 G = recv_groups_wanted(cm);
-    cm->groups_used = 0;
-    cm->groups_fine = 0;
-    if ((W < 2 && !single) || W > MAX_DEST || G < 2 || P.PB < 9 || nslices == 0) return false;
-    for (u32 s = 0; s < nslices; ++s) if (cuts[s + 1] < cuts[s] || cuts[s + 1] > n) throw Error(CBLX_EINVAL, "slice cuts must be ascending and at most n");
-    // -- the group cuts that go with these bounds (chosen once per set of bounds: a sampled histogram of the first slice, all-reduced)
-    const std::vector<u32> bvec(bounds, bounds + (W - 1));
-    if (!single && cm->g_bounds != bvec) {
-        std::vector<u64> hist = sampled_prefix_hist<C>(c, T, d_bases, d_offsets + cuts[0], cuts[1] - cuts[0]);
-        weigh_tail_for_fine_bins(hist, P.PB, W, G, std::min(SPLIT_HIST_BITS, P.PB));
-        cm->g_cuts = choose_group_cuts(hist, bounds, W, G, P.PB);
-        cm->g_bounds = bvec;
-    }
-    // PREFIX_BITS > 24: FINE bins (cuts.hpp) — the first pass also cuts the narrow groups into aligned blocks of 2^16 prefixes, so their
-    // receiver sorts 16 bits in two LSD passes instead of 20 in three (CBLX_FINE_BINS=0: the bins of the top 8 prefix bits, as below 25)
+    const u32 W = T.world, me = T.rank, RB = P.PB - 8, G = recv_groups_wanted(cm);
+    // -- what resolve() settles
     FinePlan FM;
-    {
-        const char* fe = std::getenv("CBLX_FINE_BINS");
+    CutPlan LM;
+    bool fine = false, wire_dig = false;
+    const bool trace = std::getenv("CBLX_TRACE_SHARDED") != nullptr;
+    u64 mine = 0, job = 0;
+    DigitBits nextd{0, 0};
+    Buf<u32> d_tab;  // CutCell[CUT_KEYS], or u32[FINE_CELLS]: staged in LDS by the kernels that look bins up
+    DigitCut fn{};
+    EncHist eh0{};
+    u32 my_lo = 0, my_cells = 0, NG = 0, Gmax = 0;
+    std::vector<u32> gc0;  // cells (= my bins) of every one of my groups
+    // -- the senders' side
+    RecvLog log{c, T, OHS};
+    struct Sent { Buf<u64> lo; Buf<u8> hi, dig; std::vector<u32> tot; OwnShare own; };
+    std::vector<Sent> sent;
+    std::vector<u32> pcnt, pbase;  // [piece][256] records per CELL of mine, log position of every piece; piece = slice * W + source
+    std::vector<std::vector<u64>> recvh;  // headers: what every source sends me, per slice
+    Drain drain{nullptr};
+    EventOwner gev;  // gev.e[k] fires when group k of every rank has landed
+    FirstPass prev_work;
+    // ONE chunk plan for the call, the slices are ranges of it (a plan per slice cost the send phase 0.4 ms of host round trips each)
+    ChunkPlan PL;
+    BaseView pb = ascii_view(d_bases);
+    std::vector<PlanSlice> psl;
+    // -- the receiver's side
+    Resident fin;
+    Buf<u64> fin_hi_keep;  // 16-byte records through the passes: a target for the hi parts even when the arena keeps none
+    u64* fin_hi = nullptr;
+    std::vector<u64> gN, gbase;  // words of every group of mine, their slots in the final arena
+    std::vector<Resident> parts;
+
+    const CutPlan& plan() const { return fine ? static_cast<const CutPlan&>(FM) : LM; }
+
+    // FINE plan or cut plan, the job's size and the switches agreed between the ranks; false: the call is not for this route
+    bool resolve() {
+        cm->groups_used = cm->groups_fine = 0;
+        if ((W < 2 && !single) || W > MAX_DEST || G < 2 || P.PB < 9 || nslices == 0) return false;
+        check_slice_cuts(cuts, nslices, n);
+        // -- the group cuts that go with these bounds (chosen once per set of bounds: a sampled histogram of the first slice, all-reduced)
+        const std::vector<u32> bvec(bounds, bounds + (W - 1));
+        if (!single && cm->g_bounds != bvec) {
+            std::vector<u64> hist = sampled_prefix_hist<C>(c, T, d_bases, d_offsets + cuts[0], cuts[1] - cuts[0]);
+            weigh_tail_for_fine_bins(hist, P.PB, W, G, std::min(SPLIT_HIST_BITS, P.PB));
+            cm->g_cuts = choose_group_cuts(hist, bounds, W, G, P.PB);
+            cm->g_bounds = bvec;
+        }
+        // PREFIX_BITS > 24: FINE bins (cuts.hpp) — the first pass also cuts the narrow groups into aligned blocks of 2^16 prefixes, so their
+        // receiver sorts 16 bits in two LSD passes instead of 20 in three (CBLX_FINE_BINS=0: the bins of the top 8 prefix bits, as below 25)
         // every bin must imply the prefix bits a record does not carry behind the first pass: 65..72-bit words travel as their low 64 bits
         const u32 lmax = DROP_HI ? std::min(24u, 64u - P.SB) : 24u;
-        if (P.PB > 24 && !(fe && fe[0] == '0')) FM = make_fine_plan(P.PB, lmax, bounds, W, cm->g_cuts, single);
-    }
-    const bool fine = FM.ok;
-    if (single && !fine) return false;
-    const CutPlan LM = fine ? CutPlan() : make_cut_plan(P.PB, bounds, W, cm->g_cuts);
-    const CutPlan& M = fine ? static_cast<const CutPlan&>(FM) : LM;
-    // -- the job: k-mers per rank (upper bound), whether any rank holds an index already
-    const u64 n0 = cuts[0], n1 = cuts[nslices];
-    u64 mine = 0;
-    if (rep && rep->ready) rep->ready(~0u);
-    if (n1 > n0) {
-        const u64 first = d2h<u64>(c, d_offsets + n0), last = d2h<u64>(c, d_offsets + n1);
-        if (last < first) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
-        const u64 sub = (n1 - n0) * (u64)(P.K - 1);
-        mine = last - first > sub ? last - first - sub : 0;
-    }
-    const u64 LIMIT = 0xFFFFFFF0ull - 2 * RDX_TILE;
-    // (every term of the decision below is replicated: a rank that alone holds 2^32 k-mers says so through the sum)
-    // The digit side channel of the receiver's first LSD pass (1 byte per word) stays OFF the wire by default (round 5): at 8 GPUs and 55 GB/s per
-    // link the step is bound by the wire from the first group on (DESIGN_HISTORY.md §5.8), the byte is a ninth of it, and the receiver's first histogram
-    // reads the records instead (8 bytes per word where it read 1: about the millisecond the senders' byte stores cost). CBLX_WIRE_DIGITS=1 sends
-    // it as rounds 3 - 4 did; one rank (no wire) always keeps it.
-    const char* wd_env = std::getenv("CBLX_WIRE_DIGITS");
-    const bool wire_dig = single || rep != nullptr || (wd_env && wd_env[0] == '1');
-    // What crosses the wire follows from switches every rank reads in its OWN environment (CBLX_FINE_BINS, CBLX_WIRE_DIGITS, CBLX_FINE_TAIL_WEIGHT,
-    // CBLX_RECV_GROUPS): they are job-wide. A rank started with other values would wait for items its peers never send, or bin records by another
-    // table — so the resolved choices ride in the all-reduce below (sum and sum of squares: equal on every rank iff W x sum(v^2) = sum(v)^2).
-    const u64 choice = (fine ? 1ull : 0ull) | (wire_dig ? 2ull : 0ull) | ((u64)G << 2) | (std::min<u64>(fine_tail_weight_pct(), 0xFFFFull) << 8);
-    u64 agree[5] = {mine, c->res.count != 0 ? 1ull : 0ull, mine >= LIMIT ? 1ull : 0ull, choice, choice * choice};
-    T.all_reduce_sum_u64(agree, 5);
-    if (agree[4] * W != agree[3] * agree[3])
-        throw Error(CBLX_EINVAL, "sharded build: the ranks resolved CBLX_FINE_BINS / CBLX_WIRE_DIGITS / CBLX_FINE_TAIL_WEIGHT / CBLX_RECV_GROUPS differently (they are job-wide: set them in every rank's environment)");
-    const u64 job = agree[0];
-    if (!M.ok || agree[1] != 0 || agree[2] != 0 || job / W + job / (2 * W) + (1u << 20) >= LIMIT) return false;
-    if (single && mine < fine_min_words()) return false;  // (a small batch: the groups' fixed costs outweigh the pass saved)
-    const bool trace = std::getenv("CBLX_TRACE_SHARDED") != nullptr;
-    const LsdPlan LP = fine ? lsd_plan_bits(FINE_LEVEL) : lsd_plan(P, false);  // (the receiver runs LSD passes only: pipeline.hpp; FINE bins: the first digit is the same for 16 and 24 sorted bits)
-    const DigitBits nextd = wire_dig ? DigitBits{P.SB + LP.sh[0], LP.wid[0]} : DigitBits{0, 0};
-    Buf<u32> d_tab(c->pool, DigitCut::LDS_WORDS);  // CutCell[CUT_KEYS], or u32[FINE_CELLS]: staged in LDS by the kernels that look bins up
-    if (fine) h2d(c, d_tab.get(), FM.tab32.data(), FM.tab32.size());
-    else h2d(c, d_tab.get(), reinterpret_cast<const u32*>(M.tab.data()), M.tab.size() * 2);
-    DigitCut fn{P.SB, P.PB, RB, d_tab.get(), fine ? FM.ksh : 0xFFFFFFFFu};
-    EncHist eh0{};
-    eh0.nd = W; eh0.SB = P.SB; eh0.PB = P.PB; eh0.binRB = RB; eh0.cut_tab = d_tab.get(); eh0.cut_ksh = fn.ksh;
-    if (single && fine) {
-        // one rank: the plan is regular — multiples of 2^16 up to the one group cut, multiples of 2^lmax above — and the bin is arithmetic
-        // (checked against the plan's table, cell by cell; the table route stays for anything else)
-        const u32 x = cm->g_cuts[0], lm = DROP_HI ? std::min(24u, 64u - P.SB) : 24u;
-        bool regular = (x & 0xFFFFu) == 0;
-        for (u32 k = 0; regular && k < FINE_CELLS; ++k) {
-            const u32 p = k << FM.ksh, b = ((p < x ? p : x) >> 16) + (p >= x ? (p >> lm) - (x >> lm) : 0u);
-            regular = (FM.tab32[k] >> 8) == FINE_NO_CUT && (FM.tab32[k] & 255u) == b;
+        if (P.PB > 24 && fine_bins_enabled()) FM = make_fine_plan(P.PB, lmax, bounds, W, cm->g_cuts, single);
+        fine = FM.ok;
+        if (single && !fine) return false;
+        if (!fine) LM = make_cut_plan(P.PB, bounds, W, cm->g_cuts);
+        const CutPlan& M = plan();
+        // -- the job: k-mers per rank (upper bound), whether any rank holds an index already
+        if (rep && rep->ready) rep->ready(~0u);
+        mine = kmers_upper_bound(c, d_offsets, cuts[0], cuts[nslices]);
+        // (every term of the decision below is replicated: a rank that alone holds 2^32 k-mers says so through the sum)
+        // The digit side channel of the receiver's first LSD pass (1 byte per word) stays OFF the wire by default (round 5): at 8 GPUs and 55 GB/s per
+        // link the step is bound by the wire from the first group on (DESIGN_HISTORY.md §5.8), the byte is a ninth of it, and the receiver's first histogram
+        // reads the records instead (8 bytes per word where it read 1: about the millisecond the senders' byte stores cost). CBLX_WIRE_DIGITS=1 sends
+        // it as rounds 3 - 4 did; one rank (no wire) always keeps it.
+        const char* wd_env = std::getenv("CBLX_WIRE_DIGITS");
+        wire_dig = single || rep != nullptr || (wd_env && wd_env[0] == '1');
+        // What crosses the wire follows from switches every rank reads in its OWN environment (CBLX_FINE_BINS, CBLX_WIRE_DIGITS, CBLX_FINE_TAIL_WEIGHT,
+        // CBLX_RECV_GROUPS): they are job-wide. A rank started with other values would wait for items its peers never send, or bin records by another
+        // table — so the resolved choices ride in the all-reduce below (sum and sum of squares: equal on every rank iff W x sum(v^2) = sum(v)^2).
+        const u64 choice = (fine ? 1ull : 0ull) | (wire_dig ? 2ull : 0ull) | ((u64)G << 2) | (std::min<u64>(fine_tail_weight_pct(), 0xFFFFull) << 8);
+        u64 agree[5] = {mine, c->res.count != 0 ? 1ull : 0ull, mine >= ROUND_LIMIT ? 1ull : 0ull, choice, choice * choice};
+        T.all_reduce_sum_u64(agree, 5);
+        if (agree[4] * W != agree[3] * agree[3])
+            throw Error(CBLX_EINVAL, "sharded build: the ranks resolved CBLX_FINE_BINS / CBLX_WIRE_DIGITS / CBLX_FINE_TAIL_WEIGHT / CBLX_RECV_GROUPS differently (they are job-wide: set them in every rank's environment)");
+        job = agree[0];
+        if (!M.ok || agree[1] != 0 || agree[2] != 0 || job / W + job / (2 * W) + (1u << 20) >= ROUND_LIMIT) return false;
+        if (single && mine < fine_min_words()) return false;  // (a small batch: the groups' fixed costs outweigh the pass saved)
+        const LsdPlan LP = fine ? lsd_plan_bits(FINE_LEVEL) : lsd_plan(P, false);  // (the receiver runs LSD passes only: pipeline.hpp; FINE bins: the first digit is the same for 16 and 24 sorted bits)
+        nextd = wire_dig ? DigitBits{P.SB + LP.sh[0], LP.wid[0]} : DigitBits{0, 0};
+        d_tab = Buf<u32>(c->pool, DigitCut::LDS_WORDS);
+        if (fine) h2d(c, d_tab.get(), FM.tab32.data(), FM.tab32.size());
+        else h2d(c, d_tab.get(), reinterpret_cast<const u32*>(M.tab.data()), M.tab.size() * 2);
+        fn = DigitCut{P.SB, P.PB, RB, d_tab.get(), fine ? FM.ksh : 0xFFFFFFFFu};
+        eh0.nd = W; eh0.SB = P.SB; eh0.PB = P.PB; eh0.binRB = RB; eh0.cut_tab = d_tab.get(); eh0.cut_ksh = fn.ksh;
+        if (single && fine) {
+            // one rank: the plan is regular — multiples of 2^16 up to the one group cut, multiples of 2^lmax above — and the bin is arithmetic
+            // (checked against the plan's table, cell by cell; the table route stays for anything else)
+            const u32 x = cm->g_cuts[0];
+            bool regular = (x & 0xFFFFu) == 0;
+            for (u32 k = 0; regular && k < FINE_CELLS; ++k) {
+                const u32 p = k << FM.ksh, b = ((p < x ? p : x) >> 16) + (p >= x ? (p >> lmax) - (x >> lmax) : 0u);
+                regular = (FM.tab32[k] >> 8) == FINE_NO_CUT && (FM.tab32[k] & 255u) == b;
+            }
+            if (regular) { fn.reg_x = x; fn.reg_lmax = lmax; fn.tab = nullptr; eh0.reg_x = x; eh0.reg_lmax = lmax; eh0.cut_tab = nullptr; }
         }
-        if (regular) { fn.reg_x = x; fn.reg_lmax = lm; fn.tab = nullptr; eh0.reg_x = x; eh0.reg_lmax = lm; eh0.cut_tab = nullptr; }
+        my_lo = M.bin_lo[me]; my_cells = M.bin_lo[me + 1] - M.bin_lo[me]; NG = M.ngroups[me];
+        gc0 = group_cells(M, me);
+        for (u32 d = 0; d < W; ++d) Gmax = std::max(Gmax, M.ngroups[d]);
+        log.wire_dig = wire_dig;
+        log.cap = std::min<u64>(std::max<u64>(std::min<u64>(job, job / W + job / (4 * W) + (1u << 20)), 1024), ROUND_LIMIT);
+        sent.resize(nslices); recvh.resize(nslices); psl.resize(nslices);
+        gev.e.assign(Gmax, nullptr);
+        drain.t = &T;
+        return true;
     }
-    const u32 my_lo = M.bin_lo[me], my_cells = M.bin_lo[me + 1] - M.bin_lo[me], NG = M.ngroups[me];
-    // cells (= my bins) of every one of my groups
-    // (a cut that falls exactly on a segment boundary leaves one bin number unused: such a cell holds nothing and belongs nowhere)
-    std::vector<u32> gc0(NG + 1, my_cells);
-    for (u32 cl = my_cells; cl-- > 0;) if (M.iv_of[my_lo + cl] != 0xFFFFFFFFu) gc0[M.grp_of[M.iv_of[my_lo + cl]]] = cl;
-    for (int g = (int)NG - 1; g >= 0; --g) if (gc0[g] > gc0[g + 1]) gc0[g] = gc0[g + 1];
-    u32 Gmax = 0;
-    for (u32 d = 0; d < W; ++d) Gmax = std::max(Gmax, M.ngroups[d]);
 
-    // -- senders: KRN-1 + pass A of every slice; the own records go straight into the log, the rest waits in the slice's send buffer
-    u64 cap = std::min<u64>(std::max<u64>(std::min<u64>(job, job / W + job / (4 * W) + (1u << 20)), 1024), LIMIT);
-    Buf<u64> a_lo;
-    Buf<u8> a_hi, a_dig;
-    auto alloc_log = [&](u64 ncap, Buf<u64>& lo, Buf<u8>& hi, Buf<u8>& dg) {
-        lo = Buf<u64>(c->pool, ncap + 2);
-        hi = Buf<u8>(c->pool, OHS ? (ncap + 2) * OHS : 8);
-        dg = Buf<u8>(c->pool, wire_dig ? ncap + 64 : 64);
-    };
-    struct Sent { Buf<u64> lo; Buf<u8> hi, dig; std::vector<u32> tot; u64 own_a = 0, own = 0; };
-    std::vector<Sent> sent(nslices);
-    std::vector<u32> pcnt, pbase;  // [piece][256] records per CELL of mine, log position of every piece; piece = slice * W + source
-    const size_t HDR = 257;
-    std::vector<std::vector<u64>> recvh(nslices);  // headers: what every source sends me, per slice
-    u64 filled = 0;
-    struct Drain { Transport& t; ~Drain() { try { t.wait(); } catch (...) {} } } drain{T};
-    auto grow = [&](u64 need) {  // (only own pieces and the first group's early shares are in the log)
-        T.wait();
-        CBLX_HIP(hipStreamSynchronize(c->stream));
-        const u64 ncap = std::min<u64>(LIMIT, need + need / 4 + 4096);
-        Buf<u64> lo;
-        Buf<u8> hi, dg;
-        alloc_log(ncap, lo, hi, dg);
-        if (filled) {
-            CBLX_HIP(hipMemcpyAsync(lo.get(), a_lo.get(), filled * 8, hipMemcpyDeviceToDevice, c->stream));
-            if (OHS) CBLX_HIP(hipMemcpyAsync(hi.get(), a_hi.get(), filled * OHS, hipMemcpyDeviceToDevice, c->stream));
-            if (wire_dig) CBLX_HIP(hipMemcpyAsync(dg.get(), a_dig.get(), filled, hipMemcpyDeviceToDevice, c->stream));
-            CBLX_HIP(hipStreamSynchronize(c->stream));
-        }
-        a_lo = std::move(lo); a_hi = std::move(hi); a_dig = std::move(dg);
-        cap = ncap;
-    };
-    std::vector<hipEvent_t> gev(Gmax, nullptr);
-    struct Events { std::vector<hipEvent_t>& v; ~Events() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); } } events{gev};
-    // record range [first, first + len) of bins [b0, b1) in a slice's send buffer (the own window is not in it)
-    auto send_range = [&](const Sent& S, u32 b0, u32 b1, u64& first, u64& len) {
-        u64 before = 0, inside = 0;
-        for (u32 bin = 0; bin < b1; ++bin) (bin < b0 ? before : inside) += S.tot[bin];
-        first = before >= S.own_a + S.own ? before - S.own : before;  // ranges of other ranks lie wholly before or behind the own window
-        len = inside;
-    };
     // the items of (group k, slice s): this rank's records for every other rank's group k, and where the other ranks' records for
     // this rank's group k land in the log (every rank issues the same items in the same order, empty ones included: a callback
     // transport's exchange is a collective)
-    auto add_items = [&](u32 k, u32 s, std::vector<Transport::Item>& items) {
+    void add_items(u32 k, u32 s, std::vector<Transport::Item>& items) {
+        const CutPlan& M = plan();
         Sent& S = sent[s];
         std::vector<u64> so(W, 0), sl(W, 0), rof(W, 0), rl(W, 0);
         for (u32 d = 0; d < W; ++d) {
             if (d == me || k >= M.ngroups[d]) continue;
-            u32 b0 = 256, b1 = 0;  // bins of (rank d, group k)
-            for (u32 bin = M.bin_lo[d]; bin < M.bin_lo[d + 1]; ++bin)
-                if (M.iv_of[bin] != 0xFFFFFFFFu && M.grp_of[M.iv_of[bin]] == k) { b0 = std::min(b0, bin); b1 = std::max(b1, bin + 1); }
+            u32 b0, b1;  // bins of (rank d, group k)
+            group_bins(M, d, k, b0, b1);
             if (b0 >= b1) continue;
-            send_range(S, b0, b1, so[d], sl[d]);
+            send_range(S.tot.data(), S.own, b0, b1, so[d], sl[d]);
         }
         if (k < NG)
             for (u32 r = 0; r < W; ++r) {
                 if (r == me) continue;
-                const u32* pc = pcnt.data() + ((size_t)s * W + r) * 256;
-                u64 before = 0, inside = 0;
-                for (u32 cl = 0; cl < gc0[k + 1]; ++cl) (cl < gc0[k] ? before : inside) += pc[cl];
+                u64 before;
+                count_range(pcnt.data() + ((size_t)s * W + r) * 256, gc0[k], gc0[k + 1], before, rl[r]);
                 rof[r] = (u64)pbase[(size_t)s * W + r] + before;
-                rl[r] = inside;
             }
         auto item = [&](const u8* src, u8* dst, size_t es) {
             Transport::Item it{src, dst, so, sl, rof, rl};
             for (u32 r = 0; r < W; ++r) { it.s_off[r] *= es; it.s_len[r] *= es; it.r_off[r] *= es; it.r_len[r] *= es; }
             items.push_back(std::move(it));
         };
-        item((const u8*)S.lo.get(), (u8*)a_lo.get(), 8);
-        if (OHS) item(S.hi.get(), a_hi.get(), OHS);
-        if (wire_dig) item(S.dig.get(), a_dig.get(), 1);
-    };
-    struct Work { ChunkPlan pl; Buf<u64> t_lo; Buf<u8> t_hi; Buf<u32> counts, colpre, scratch, adj, coltot; };
-    Work prev_work;
-    // ONE chunk plan for the call, the slices are ranges of it (a plan per slice cost the send phase 0.4 ms of host round trips each)
-    ChunkPlan PL;
-    BaseView pb = ascii_view(d_bases);
-    std::vector<PlanSlice> psl(nslices);
-    if (rep) {
-        // -- "replicate": KRN-1 + the first pass over EVERY rank's reads, piece by piece; the pass keeps the records of this rank's prefix range (they
-        //    go straight into the log) and drops the others. The own pieces first: the peers' planes are still crossing the links meanwhile.
+        item((const u8*)S.lo.get(), (u8*)log.lo.get(), 8);
+        if (OHS) item(S.hi.get(), log.hi.get(), OHS);
+        if (wire_dig) item(S.dig.get(), log.dig.get(), 1);
+    }
+
+    // -- senders, records on the wire: KRN-1 + pass A of every slice; the own records go straight into the log, the rest waits in the
+    //    slice's send buffer. Group 0 of every slice but the last leaves under the next slice's kernels; then the wire, group-major.
+    void send_wire() {
+        const u64 n0 = cuts[0], n1 = cuts[nslices];
+        if (n1 > n0) {
+            std::vector<u64> marks(nslices + 1);
+            for (u32 s = 0; s <= nslices; ++s) marks[s] = cuts[s] - n0;
+            plan_chunks(c, pb, d_offsets + n0, n1 - n0, PL, nullptr, &marks, &psl);
+        }
+        for (u32 s = 0; s < nslices; ++s) {
+            wire_slice(s);
+            if (s + 1 < nslices) {  // the first group's share of this slice crosses the links under the next slice's kernels
+                std::vector<Transport::Item> items;
+                add_items(0, s, items);
+                T.exchange_items(items, c->stream);
+            }
+        }
+        // -- the wire, group-major: exchange k carries group k of EVERY rank (ranks with fewer groups send nothing in the later ones)
+        for (u32 k = 0; k < Gmax; ++k) {
+            std::vector<Transport::Item> items;
+            // (group 0 of every slice but the last left right behind that slice's pass A, under the next slice's kernels)
+            for (u32 s = (k == 0 ? nslices - 1 : 0u); s < nslices; ++s) add_items(k, s, items);
+            T.exchange_items(items, c->stream);
+            CBLX_HIP(hipEventCreateWithFlags(&gev.e[k], hipEventDisableTiming));
+            T.record(gev.e[k], c->stream);
+        }
+    }
+    void wire_slice(u32 s) {
+        const CutPlan& M = plan();
+        const u64 N = psl[s].k_hi - psl[s].k_lo;
+        prev_work = FirstPass();  // (its kernels are queued on this stream in front of whatever takes the blocks next)
+        if (N >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "one slice takes fewer than 2^32-16 words (use more slices)");
+        FirstPass wk;
+        Sent& S = sent[s];
+        S.tot.assign(256, 0u);
+        if (N) {
+            first_pass_count<C>(c, wk, pb, PL, N, eh0, &psl[s]);
+            S.tot = d2h_vec<u32>(c, wk.coltot.get(), 256);
+        }
+        // header per destination: words, then words per cell of the destination's range
+        std::vector<u64> send((size_t)W * HDR, 0);
+        recvh[s].assign((size_t)W * HDR, 0);
+        S.own = wire_header(M, S.tot.data(), W, me, N, "slice", send.data());
+        T.all_to_all_u64(send.data(), recvh[s].data(), HDR);
+        const std::vector<u64>& recv = recvh[s];
+        u64 incoming = 0;
+        if (recv[(size_t)me * HDR] != S.own.n) throw Error(CBLX_EDEVICE, "sharded build: the count exchange returned another own count (transport error)");
+        for (u32 r = 0; r < W; ++r) incoming += recv[(size_t)r * HDR];
+        {   // a share that needs two rounds is an error of the JOB: every rank learns of it here and leaves together (a rank that threw on
+            // its own left its peers waiting in the next collective until the launcher's deadline)
+            u64 over = log.filled + incoming >= ROUND_LIMIT ? 1ull : 0ull;
+            T.all_reduce_sum_u64(&over, 1);
+            if (over) throw Error(CBLX_ERANGE, "a rank's share of the job takes more than one round: set CBLX_RECV_GROUPS=1 (ungrouped receiver) or use more ranks");
+        }
+        log.room(log.filled + incoming);
+        const u64 filled = log.filled;
+        push_pieces(recv.data(), W, me, filled, S.own.n, pbase, pcnt);  // (log layout of the slice as in sharded_insert_bins)
+        log.alloc_into(N - S.own.n, S.lo, S.hi, S.dig);  // (a send buffer is laid out as the log is)
+        if (N) {
+            if (single)  // one rank: every record is its own, the pass writes the log directly (measured: the redirecting instantiation costs the same)
+                first_pass_scatter<HiT, OutH, DigitCut, false>(c, wk, wk.t_lo.get(), (const HiT*)wk.t_hi.get(), fn, log.lo.get() + filled, OHS ? (OutH*)(log.hi.get() + filled * OHS) : (OutH*)nullptr, true,
+                                                               nextd, log.dig.get() + filled);
+            else
+                first_pass_scatter<HiT, OutH, DigitCut, true>(c, wk, wk.t_lo.get(), (const HiT*)wk.t_hi.get(), fn, S.lo.get(), (OutH*)S.hi.get(), true, nextd, wire_dig ? S.dig.get() : (u8*)nullptr,
+                                                              log.own_window(S.own));
+        }
+        if (trace) fprintf(stderr, "[cblx grouped] rank %u slice %u: N=%llu own=%llu incoming=%llu filled=%llu\n", me, s, (unsigned long long)N, (unsigned long long)S.own.n,
+                           (unsigned long long)incoming, (unsigned long long)filled);
+        log.filled += incoming;
+        prev_work = std::move(wk);
+    }
+
+    // -- senders, nothing on the wire. "replicate": KRN-1 + the first pass over EVERY rank's reads, piece by piece; the pass keeps the records of this
+    //    rank's prefix range (they go straight into the log) and drops the others. The own pieces first: the peers' planes are still crossing the links
+    //    meanwhile. One rank (`single`): every record is its own.
+    void send_local() {
+        const CutPlan& M = plan();
         if (rep->src.size() != W) throw Error(CBLX_EINVAL, "replicate: one source per rank (internal error)");
         const u32 Q = std::max(1u, rep->parts), NT = nslices * Q;  // parts per slice, parts per source
         pcnt.assign((size_t)NT * W * 256, 0u);
         pbase.assign((size_t)NT * W, 0u);
-        alloc_log(cap, a_lo, a_hi, a_dig);
+        log.alloc();
         u64 over = 0;
-        struct Late { size_t piece; u64 n; Buf<u32> coltot; };
-        std::vector<Late> late;
+        std::vector<DeferredTotals> late;
         for (u32 r = 0; r < W; ++r) if (rep->src[r].cuts.size() != (size_t)NT + 1) throw Error(CBLX_EINVAL, "replicate: slice cuts of a source (internal error)");
         // the own source is planned once (its parts are ranges of the plan) and goes first: the peers' planes are crossing the links meanwhile;
         // then the peers part-major — exchange t carries part t of every peer — each part planned on its own once it has landed
@@ -1038,254 +1054,121 @@ bool sharded_insert_grouped(cblx_ctx* c, cblx_comm* cm, const u8* d_bases, const
         std::vector<std::pair<u32, u32>> order;  // (source, part)
         for (u32 t = 0; t < NT; ++t) order.push_back({me, t});
         for (u32 t = 0; t < NT; ++t) for (u32 r = 0; r < W; ++r) if (r != me) order.push_back({r, t});
-        {
-            for (const auto& rt : order) {
-                if (over) break;
-                const u32 r = rt.first, t = rt.second, s = t / Q;
-                const ReplicaSource& R = rep->src[r];
-                if (R.nseq == 0) continue;
-                prev_work = Work();
-                Work wk;
-                const ChunkPlan* plan = &PLme;
-                const PlanSlice* part = &pslme[t];
-                BaseView vs = vme;
-                if (!(r == me && own_whole)) {  // the part is planned once it has landed
-                    if (rep->ready) rep->ready(t);
-                    if (r != me) {
-                        if (t < rep->part_ready.size() && rep->part_ready[t]) CBLX_HIP(hipStreamWaitEvent(c->stream, rep->part_ready[t], 0));
-                        else T.wait();
-                    }
-                    if (R.cuts[t + 1] == R.cuts[t]) continue;
-                    vs = R.view;
-                    plan_chunks(c, vs, R.d_off + R.cuts[t], R.cuts[t + 1] - R.cuts[t], wk.pl);
-                    plan = &wk.pl;
-                    part = nullptr;
+        for (const auto& rt : order) {
+            if (over) break;
+            const u32 r = rt.first, t = rt.second, s = t / Q;
+            const ReplicaSource& R = rep->src[r];
+            if (R.nseq == 0) continue;
+            prev_work = FirstPass();
+            FirstPass wk;
+            const ChunkPlan* pl = &PLme;
+            const PlanSlice* part = &pslme[t];
+            BaseView vs = vme;
+            if (!(r == me && own_whole)) {  // the part is planned once it has landed
+                if (rep->ready) rep->ready(t);
+                if (r != me) {
+                    if (t < rep->part_ready.size() && rep->part_ready[t]) CBLX_HIP(hipStreamWaitEvent(c->stream, rep->part_ready[t], 0));
+                    else T.wait();
                 }
-                const u64 N = part ? part->k_hi - part->k_lo : plan->n_kmers;
-                if (N >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "one slice takes fewer than 2^32-16 words (use more slices)");
-                if (!N) continue;
-                const u32 ntiles = (u32)ceil_div(N, RDX_TILE);
-                wk.coltot = Buf<u32>(c->pool, 256);
-                wk.adj = Buf<u32>(c->pool, 256);
-                const size_t hs = hi_elem_size(P);
-                wk.t_lo = Buf<u64>(c->pool, N + 2);
-                wk.t_hi = Buf<u8>(c->pool, hs ? (N + 2) * hs : 8);
-                wk.counts = Buf<u32>(c->pool, (size_t)256 * (ntiles + 2));
-                wk.colpre = Buf<u32>(c->pool, (size_t)256 * ntiles);
-                CBLX_HIP(hipMemsetAsync(wk.counts.get(), 0, (size_t)256 * (ntiles + 2) * 4, c->stream));
-                EncHist eh = eh0;
-                eh.counts = wk.counts.get();
-                encode<C>(c, vs, *plan, wk.t_lo.get(), (HiT*)wk.t_hi.get(), 0, eh, part);
-                { StageTimer t(c, ST_SCAN);
-                  colscan(c, wk.counts.get(), nullptr, ntiles, wk.colpre.get(), wk.coltot.get(), wk.scratch);
-                  hipLaunchKernelGGL(k_seg_adjust, dim3(1), dim3(256), 0, c->stream, wk.colpre.get(), wk.coltot.get(), (const u32*)nullptr, (const u32*)nullptr,
-                                     (const u32*)nullptr, ntiles, 1u, wk.adj.get()); }
-                CBLX_HIP(hipGetLastError());
-                const size_t piece = ((size_t)s * W + r) * Q + (t % Q);
-                if (single) {
-                    // one rank: every record is its own and the pass writes the log directly; the bin counts of the piece stay on the device until
-                    // the last slice is through (no host round trip between KRN-1 and the first pass: the next slice may be landing)
-                    if (filled + N >= LIMIT) { over = 1; break; }
-                    if (filled + N > cap) grow(filled + N);
-                    pbase[piece] = (u32)filled;
-                    const TileView tv{nullptr, nullptr, nullptr, nullptr, ntiles, N};
-                    { StageTimer t(c, ST_SCATTER);
-                      c->stages[ST_SCATTER].units += N;
-                      hipLaunchKernelGGL((k_radix_scatter<HiT, OutH, DigitCut, false>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, (const u64*)wk.t_lo.get(), (const HiT*)wk.t_hi.get(), tv, fn,
-                                         (const u32*)wk.colpre.get(), (const u32*)wk.adj.get(), a_lo.get() + filled, OHS ? (OutH*)(a_hi.get() + filled * OHS) : (OutH*)nullptr, nextd, a_dig.get() + filled); }
-                    CBLX_HIP(hipGetLastError());
-                    late.push_back(Late{piece, N, std::move(wk.coltot)});
-                    filled += N;
-                    prev_work = std::move(wk);
-                    continue;
-                }
-                const std::vector<u32> tot = d2h_vec<u32>(c, wk.coltot.get(), 256);
-                u64 sum = 0, own_a = 0, own = 0;
-                for (u32 bin = 0; bin < 256; ++bin) {
-                    if (!tot[bin]) continue;
-                    if (M.iv_of[bin] == 0xFFFFFFFFu) throw Error(CBLX_EDEVICE, "sharded build: a word fell into a bin no prefix maps to (internal error)");
-                    const u32 d = M.dest_of[M.iv_of[bin]];
-                    if (d < me) own_a += tot[bin];
-                    if (d == me) { own += tot[bin]; pcnt[piece * 256 + (bin - my_lo)] = tot[bin]; }
-                    sum += tot[bin];
-                }
-                if (sum != N) throw Error(CBLX_EDEVICE, "sharded build: the bin histogram counts " + std::to_string(sum) + " words, the piece has " + std::to_string(N) + " (internal error)");
-                if (filled + own >= LIMIT) { over = 1; break; }  // (settled with the other ranks below: the job leaves together)
-                if (filled + own > cap) grow(filled + own);
-                pbase[piece] = (u32)filled;
-                {
-                    const TileView tv{nullptr, nullptr, nullptr, nullptr, ntiles, N};
-                    const OwnWindow ow{own_a, own_a + own, a_lo.get() + filled, OHS ? (void*)(a_hi.get() + filled * OHS) : nullptr, a_dig.get() + filled};
-                    StageTimer t(c, ST_SCATTER);
-                    c->stages[ST_SCATTER].units += N;
-                    hipLaunchKernelGGL((k_radix_scatter<HiT, OutH, DigitCut, true>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, (const u64*)wk.t_lo.get(), (const HiT*)wk.t_hi.get(), tv, fn,
-                                       (const u32*)wk.colpre.get(), (const u32*)wk.adj.get(), (u64*)nullptr, (OutH*)nullptr, nextd, (u8*)nullptr, (u32*)nullptr, 0u, 0u, 0u, (u32*)nullptr, 0u, ow);
-                    CBLX_HIP(hipGetLastError());
-                }
-                if (trace) fprintf(stderr, "[cblx replicate] rank %u piece (slice %u, source %u, part %u): N=%llu kept=%llu filled=%llu\n", me, s, r, t % Q, (unsigned long long)N,
-                                   (unsigned long long)own, (unsigned long long)filled);
-                filled += own;
-                prev_work = std::move(wk);
+                if (R.cuts[t + 1] == R.cuts[t]) continue;
+                vs = R.view;
+                plan_chunks(c, vs, R.d_off + R.cuts[t], R.cuts[t + 1] - R.cuts[t], wk.pl);
+                pl = &wk.pl;
+                part = nullptr;
             }
-            CBLX_HIP(hipStreamSynchronize(c->stream));  // the own source's plan dies here
+            const u64 N = part ? part->k_hi - part->k_lo : pl->n_kmers;
+            if (N >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "one slice takes fewer than 2^32-16 words (use more slices)");
+            if (!N) continue;
+            first_pass_count<C>(c, wk, vs, *pl, N, eh0, part);
+            const size_t piece = ((size_t)s * W + r) * Q + (t % Q);
+            if (single) {
+                // one rank: every record is its own and the pass writes the log directly; the bin counts of the piece stay on the device until
+                // the last slice is through (no host round trip between KRN-1 and the first pass: the next slice may be landing)
+                if (log.filled + N >= ROUND_LIMIT) { over = 1; break; }
+                log.room(log.filled + N);
+                pbase[piece] = (u32)log.filled;
+                first_pass_scatter<HiT, OutH, DigitCut, false>(c, wk, wk.t_lo.get(), (const HiT*)wk.t_hi.get(), fn, log.lo.get() + log.filled,
+                                                               OHS ? (OutH*)(log.hi.get() + log.filled * OHS) : (OutH*)nullptr, true, nextd, log.dig.get() + log.filled);
+                late.push_back(DeferredTotals{piece, N, std::move(wk.coltot)});
+                log.filled += N;
+                prev_work = std::move(wk);
+                continue;
+            }
+            const std::vector<u32> tot = d2h_vec<u32>(c, wk.coltot.get(), 256);
+            std::vector<u64> hdr((size_t)W * HDR, 0);
+            const OwnShare own = wire_header(M, tot.data(), W, me, N, "piece", hdr.data());
+            for (u32 cl = 0; cl < 256; ++cl) pcnt[piece * 256 + cl] = (u32)hdr[(size_t)me * HDR + 1 + cl];
+            if (log.filled + own.n >= ROUND_LIMIT) { over = 1; break; }  // (settled with the other ranks below: the job leaves together)
+            log.room(log.filled + own.n);
+            pbase[piece] = (u32)log.filled;
+            // (no send buffer: the pass drops what is not this rank's)
+            first_pass_scatter<HiT, OutH, DigitCut, true>(c, wk, wk.t_lo.get(), (const HiT*)wk.t_hi.get(), fn, (u64*)nullptr, (OutH*)nullptr, true, nextd, (u8*)nullptr, log.own_window(own));
+            if (trace) fprintf(stderr, "[cblx replicate] rank %u piece (slice %u, source %u, part %u): N=%llu kept=%llu filled=%llu\n", me, s, r, t % Q, (unsigned long long)N,
+                               (unsigned long long)own.n, (unsigned long long)log.filled);
+            log.filled += own.n;
+            prev_work = std::move(wk);
         }
+        CBLX_HIP(hipStreamSynchronize(c->stream));  // the own source's plan dies here
         T.wait();
         T.all_reduce_sum_u64(&over, 1);
         if (over) throw Error(CBLX_ERANGE, "a rank's share of the job takes more than one round: use more ranks");
-        for (Late& l : late) {  // one rank: the bin counts of every piece, read once the passes are queued
-            const std::vector<u32> t = d2h_vec<u32>(c, l.coltot.get(), 256);
-            u64 sum = 0;
-            for (u32 bin = 0; bin < 256; ++bin) {
-                if (!t[bin]) continue;
-                if (M.iv_of[bin] == 0xFFFFFFFFu || bin < my_lo || bin - my_lo >= my_cells) throw Error(CBLX_EDEVICE, "sharded build: a word fell into a bin no prefix maps to (internal error)");
-                pcnt[l.piece * 256 + (bin - my_lo)] = t[bin];
-                sum += t[bin];
-            }
-            if (sum != l.n) throw Error(CBLX_EDEVICE, "sharded build: the bin histogram counts " + std::to_string(sum) + " words, the piece has " + std::to_string(l.n) + " (internal error)");
-        }
-    } else {
-    if (n1 > n0) {
-        std::vector<u64> marks(nslices + 1);
-        for (u32 s = 0; s <= nslices; ++s) marks[s] = cuts[s] - n0;
-        plan_chunks(c, pb, d_offsets + n0, n1 - n0, PL, nullptr, &marks, &psl);
+        fold_deferred(c, M, late, "piece", pcnt);  // one rank: the bin counts of every piece, read once the passes are queued
     }
-    for (u32 s = 0; s < nslices; ++s) {
-        const u64 N = psl[s].k_hi - psl[s].k_lo;
-        prev_work = Work();  // (its kernels are queued on this stream in front of whatever takes the blocks next)
-        if (N >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "one slice takes fewer than 2^32-16 words (use more slices)");
-        const u32 ntiles = (u32)ceil_div(N, RDX_TILE);
-        Work wk;
-        wk.coltot = Buf<u32>(c->pool, 256);
-        wk.adj = Buf<u32>(c->pool, 256);
-        Sent& S = sent[s];
-        S.tot.assign(256, 0u);
-        if (N) {
-            const size_t hs = hi_elem_size(P);
-            wk.t_lo = Buf<u64>(c->pool, N + 2);
-            wk.t_hi = Buf<u8>(c->pool, hs ? (N + 2) * hs : 8);
-            wk.counts = Buf<u32>(c->pool, (size_t)256 * (ntiles + 2));
-            wk.colpre = Buf<u32>(c->pool, (size_t)256 * ntiles);
-            CBLX_HIP(hipMemsetAsync(wk.counts.get(), 0, (size_t)256 * (ntiles + 2) * 4, c->stream));
-            EncHist eh = eh0;
-            eh.counts = wk.counts.get();
-            encode<C>(c, pb, PL, wk.t_lo.get(), (HiT*)wk.t_hi.get(), 0, eh, &psl[s]);
-            { StageTimer t(c, ST_SCAN);
-              colscan(c, wk.counts.get(), nullptr, ntiles, wk.colpre.get(), wk.coltot.get(), wk.scratch);
-              hipLaunchKernelGGL(k_seg_adjust, dim3(1), dim3(256), 0, c->stream, wk.colpre.get(), wk.coltot.get(), (const u32*)nullptr, (const u32*)nullptr,
-                                 (const u32*)nullptr, ntiles, 1u, wk.adj.get()); }
-            CBLX_HIP(hipGetLastError());
-            S.tot = d2h_vec<u32>(c, wk.coltot.get(), 256);
-        }
-        // header per destination: words, then words per cell of the destination's range
-        std::vector<u64> send((size_t)W * HDR, 0);
-        recvh[s].assign((size_t)W * HDR, 0);
-        u64 sum = 0;
-        for (u32 bin = 0; bin < 256; ++bin) {
-            if (!S.tot[bin]) continue;
-            if (M.iv_of[bin] == 0xFFFFFFFFu) throw Error(CBLX_EDEVICE, "sharded build: a word fell into a bin no prefix maps to (internal error)");
-            const u32 d = M.dest_of[M.iv_of[bin]];
-            send[(size_t)d * HDR] += S.tot[bin];
-            send[(size_t)d * HDR + 1 + (bin - M.bin_lo[d])] += S.tot[bin];
-            sum += S.tot[bin];
-        }
-        if (sum != N) throw Error(CBLX_EDEVICE, "sharded build: the bin histogram counts " + std::to_string(sum) + " words, the slice has " + std::to_string(N) + " (internal error)");
-        T.all_to_all_u64(send.data(), recvh[s].data(), HDR);
-        const std::vector<u64>& recv = recvh[s];
-        u64 incoming = 0;
-        for (u32 d = 0; d < me; ++d) S.own_a += send[(size_t)d * HDR];
-        S.own = send[(size_t)me * HDR];
-        if (recv[(size_t)me * HDR] != S.own) throw Error(CBLX_EDEVICE, "sharded build: the count exchange returned another own count (transport error)");
-        for (u32 r = 0; r < W; ++r) incoming += recv[(size_t)r * HDR];
-        {   // a share that needs two rounds is an error of the JOB: every rank learns of it here and leaves together (a rank that threw on
-            // its own left its peers waiting in the next collective until the launcher's deadline)
-            u64 over = filled + incoming >= LIMIT ? 1ull : 0ull;
-            T.all_reduce_sum_u64(&over, 1);
-            if (over) throw Error(CBLX_ERANGE, "a rank's share of the job takes more than one round: set CBLX_RECV_GROUPS=1 (ungrouped receiver) or use more ranks");
-        }
-        if (!a_lo.get()) alloc_log(cap, a_lo, a_hi, a_dig);
-        if (filled + incoming > cap) grow(filled + incoming);
-        // log layout of the slice as in sharded_insert_bins: the own piece first, then the other sources in rank order
-        u64 ro = 0;
-        for (u32 r = 0; r < W; ++r) {
-            pbase.push_back((u32)(r == me ? filled : filled + S.own + ro));
-            if (r != me) ro += recv[(size_t)r * HDR];
-            for (u32 cl = 0; cl < 256; ++cl) pcnt.push_back((u32)recv[(size_t)r * HDR + 1 + cl]);
-        }
-        const u64 nsend = N - S.own;
-        S.lo = Buf<u64>(c->pool, nsend + 2);
-        S.hi = Buf<u8>(c->pool, OHS ? (nsend + 2) * OHS : 8);
-        S.dig = Buf<u8>(c->pool, wire_dig ? nsend + 64 : 64);
-        if (N) {
-            const TileView tv{nullptr, nullptr, nullptr, nullptr, ntiles, N};
-            const OwnWindow ow{S.own_a, S.own_a + S.own, a_lo.get() + filled, OHS ? (void*)(a_hi.get() + filled * OHS) : nullptr, wire_dig ? a_dig.get() + filled : (u8*)nullptr};
-            StageTimer t(c, ST_SCATTER);
-            c->stages[ST_SCATTER].units += N;
-            if (single)  // one rank: every record is its own, the pass writes the log directly (measured: the redirecting instantiation costs the same)
-                hipLaunchKernelGGL((k_radix_scatter<HiT, OutH, DigitCut, false>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, (const u64*)wk.t_lo.get(), (const HiT*)wk.t_hi.get(), tv, fn,
-                                   (const u32*)wk.colpre.get(), (const u32*)wk.adj.get(), a_lo.get() + filled, OHS ? (OutH*)(a_hi.get() + filled * OHS) : (OutH*)nullptr, nextd, a_dig.get() + filled);
-            else
-            hipLaunchKernelGGL((k_radix_scatter<HiT, OutH, DigitCut, true>), dim3(xcd_grid(ntiles)), dim3(RDX_THREADS), 0, c->stream, (const u64*)wk.t_lo.get(), (const HiT*)wk.t_hi.get(), tv, fn,
-                               (const u32*)wk.colpre.get(), (const u32*)wk.adj.get(), S.lo.get(), (OutH*)S.hi.get(), nextd, wire_dig ? S.dig.get() : (u8*)nullptr, (u32*)nullptr, 0u, 0u, 0u, (u32*)nullptr, 0u, ow);
-            CBLX_HIP(hipGetLastError());
-        }
-        if (trace) fprintf(stderr, "[cblx grouped] rank %u slice %u: N=%llu own=%llu incoming=%llu filled=%llu\n", me, s, (unsigned long long)N, (unsigned long long)S.own,
-                           (unsigned long long)incoming, (unsigned long long)filled);
-        filled += incoming;
-        if (s + 1 < nslices) {  // the first group's share of this slice crosses the links under the next slice's kernels
-            std::vector<Transport::Item> items;
-            add_items(0, s, items);
-            T.exchange_items(items, c->stream);
-        }
-        prev_work = std::move(wk);
-    }
-    // -- the wire, group-major: exchange k carries group k of EVERY rank (ranks with fewer groups send nothing in the later ones)
-    for (u32 k = 0; k < Gmax; ++k) {
-        std::vector<Transport::Item> items;
-        // (group 0 of every slice but the last left right behind that slice's pass A, under the next slice's kernels)
-        for (u32 s = (k == 0 ? nslices - 1 : 0u); s < nslices; ++s) add_items(k, s, items);
-        T.exchange_items(items, c->stream);
-        CBLX_HIP(hipEventCreateWithFlags(&gev[k], hipEventDisableTiming));
-        T.record(gev[k], c->stream);
-    }
-    }  // (records on the wire)
-    prev_work = Work();  // (the stream is past the last slice's pass A once the first group is waited for; the workspace is only returned to the pool)
-    // -- the receiver, group by group behind the wire
-    const u64 nprefix = 1ull << P.PB, nwords = std::max<u64>(1, nprefix / 64);
-    Resident fin;
-    fin.bv = Buf<u64>(c->pool, nwords);
-    CBLX_HIP(hipMemsetAsync(fin.bv.get(), 0, nwords * 8, c->stream));
-    fin.a_lo = Buf<u64>(c->pool, filled + 2);
-    Buf<u64> fin_hi_keep;  // 16-byte records through the passes: a target for the hi parts even when the arena keeps none
-    if (WS) fin.a_hi = Buf<u64>(c->pool, filled + 2);
-    else if (OHS) fin_hi_keep = Buf<u64>(c->pool, filled + 2);
-    u64* fin_hi = WS ? fin.a_hi.get() : fin_hi_keep.get();
-    // words of every group of mine
-    std::vector<u64> gN(NG, 0);
-    const size_t np = pbase.size();  // nslices * W pieces (times the parts of a slice under "replicate")
-    for (size_t p = 0; p < np; ++p)
-        for (u32 g = 0; g < NG; ++g)
-            for (u32 cl = gc0[g]; cl < gc0[g + 1]; ++cl) gN[g] += pcnt[p * 256 + cl];
-    u64 gmax = 0;
-    for (u64 x : gN) gmax = std::max(gmax, x);
-    Buf<u64> scr_lo(c->pool, gmax + 2), scr_hi(c->pool, OHS ? gmax + 2 : 1);
-    Buf<u8> dig2(c->pool, gmax + 64);
-    std::vector<Resident> parts(NG);
-    std::vector<u64> gbase(NG + 1, 0);
+
     // prefix window of every group: its cuts (multiples of 64), the range's ends rounded outwards
-    auto group_first_prefix = [&](u32 g) -> u64 {
+    u64 group_first_prefix(u32 g) const {
+        const CutPlan& M = plan();
+        const u64 nprefix = 1ull << P.PB;
         if (g >= NG) return me + 1 < W ? ((u64)bounds[me] + 63) & ~63ull : nprefix;
         if (g == 0) return me ? (u64)bounds[me - 1] & ~63ull : 0ull;
         u32 cl = gc0[g];
         while (cl + 1 < my_cells && M.iv_of[my_lo + cl] == 0xFFFFFFFFu) ++cl;  // (an unused bin number in front of the group's first cell)
         const u32 iv = M.iv_of[my_lo + cl];
         return iv && iv != 0xFFFFFFFFu ? (u64)M.cuts[iv - 1] : 0ull;
-    };
-    for (u32 g = 0; g < NG; ++g) {
-        gbase[g + 1] = gbase[g] + gN[g];
-        if (g < Gmax && gev[g]) CBLX_HIP(hipStreamWaitEvent(c->stream, gev[g], 0));
-        if (gN[g] == 0) continue;
+    }
+    // -- the receiver, group by group behind the wire
+    void receive() {
+        prev_work = FirstPass();  // (the stream is past the last slice's pass A once the first group is waited for; the workspace is only returned to the pool)
+        const u64 filled = log.filled, nwords = std::max<u64>(1, (1ull << P.PB) / 64);
+        fin.bv = Buf<u64>(c->pool, nwords);
+        CBLX_HIP(hipMemsetAsync(fin.bv.get(), 0, nwords * 8, c->stream));
+        fin.a_lo = Buf<u64>(c->pool, filled + 2);
+        if (WS) fin.a_hi = Buf<u64>(c->pool, filled + 2);
+        else if (OHS) fin_hi_keep = Buf<u64>(c->pool, filled + 2);
+        fin_hi = WS ? fin.a_hi.get() : fin_hi_keep.get();
+        gN.assign(NG, 0);
+        const size_t np = pbase.size();  // nslices * W pieces (times the parts of a slice under "replicate")
+        for (size_t p = 0; p < np; ++p)
+            for (u32 g = 0; g < NG; ++g)
+                for (u32 cl = gc0[g]; cl < gc0[g + 1]; ++cl) gN[g] += pcnt[p * 256 + cl];
+        u64 gmax = 0;
+        for (u64 x : gN) gmax = std::max(gmax, x);
+        Buf<u64> scr_lo(c->pool, gmax + 2), scr_hi(c->pool, OHS ? gmax + 2 : 1);
+        Buf<u8> dig2(c->pool, gmax + 64);
+        parts.resize(NG);
+        gbase.assign(NG + 1, 0);
+        for (u32 g = 0; g < NG; ++g) {
+            gbase[g + 1] = gbase[g] + gN[g];
+            if (g < Gmax && gev.e[g]) CBLX_HIP(hipStreamWaitEvent(c->stream, gev.e[g], 0));
+            if (gN[g] == 0) continue;
+            GroupRegions R;
+            R.log_lo = log.lo.get(); R.log_hi = OHS ? (const void*)log.hi.get() : nullptr;
+            R.fin_lo = fin.a_lo.get() + gbase[g]; R.fin_hi = fin_hi ? fin_hi + gbase[g] : nullptr;
+            R.scr_lo = scr_lo.get(); R.scr_hi = OHS ? scr_hi.get() : nullptr;
+            receive_group(g, R, dig2.get());
+        }
+        T.wait();
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+        for (Sent& S : sent) { S.lo.reset(); S.hi.reset(); S.dig.reset(); }
+        log.reset();
+    }
+    // group g's pieces of the log through the LSD passes, its window of the directory and the bucket kernels
+    void receive_group(u32 g, const GroupRegions& R, u8* dig2) {
+        const CutPlan& M = plan();
+        const u64 nprefix = 1ull << P.PB;
+        const size_t np = pbase.size();
         // the group's share of every piece: counts per SEGMENT (inside a group a segment occurs in one cell only), first record
-        std::vector<u32> cnt_g(np * 256, 0u), pb_g(np), segp(256, 0xFFFFFFFFu);
+        std::vector<u32> cnt_g, pb_g, segp(256, 0xFFFFFFFFu);
         if (fine)  // a bin's records share their prefix bits from the bin's level up: the first prefix of its aligned block
             for (u32 cl = gc0[g]; cl < gc0[g + 1]; ++cl) {
                 const u32 bin = my_lo + cl, iv = M.iv_of[bin];
@@ -1296,22 +1179,10 @@ bool sharded_insert_grouped(cblx_ctx* c, cblx_comm* cm, const u8* d_bases, const
                 const u32 sbg = FM.sort_bits[me][g];
                 segp[FM.seg_of[bin]] = bin == 255 ? (u32)((((1ull << P.PB) - 1) >> sbg) << sbg) : (FM.first[iv] >> FM.level[iv]) << FM.level[iv];
             }
-        for (size_t p = 0; p < np; ++p) {
-            u64 before = 0;
-            for (u32 cl = 0; cl < gc0[g]; ++cl) before += pcnt[p * 256 + cl];
-            pb_g[p] = (u32)(pbase[p] + before);
-            for (u32 cl = gc0[g]; cl < gc0[g + 1]; ++cl) {
-                const u32 v = fine ? FM.seg_of[my_lo + cl] : M.v_of[my_lo + cl];
-                if (v == 0xFFFFFFFFu) { if (pcnt[p * 256 + cl]) throw Error(CBLX_EDEVICE, "grouped receiver: words in a bin no prefix maps to (internal error)"); continue; }
-                if (cnt_g[p * 256 + v] && pcnt[p * 256 + cl]) throw Error(CBLX_EDEVICE, "grouped receiver: a segment occurs in two cells of one group (internal error)");
-                cnt_g[p * 256 + v] += pcnt[p * 256 + cl];
-            }
-        }
+        group_piece_table((fine ? FM.seg_of : M.v_of) + my_lo, gc0[g], gc0[g + 1], pcnt, pbase, cnt_g, pb_g);
         PieceInput pin;
-        pin.np = (u32)np;
-        pin.cnt = cnt_g.data();
-        pin.pbase = pb_g.data();
-        if (wire_dig) { pin.dig_in = a_dig.get(); pin.dig_out = dig2.get(); }  // (else: the first histogram reads the records, the later passes' digits go to a buffer of the pass's own)
+        pin.np = (u32)np; pin.cnt = cnt_g.data(); pin.pbase = pb_g.data();
+        if (wire_dig) { pin.dig_in = log.dig.get(); pin.dig_out = dig2; }  // (else: the first histogram reads the records, the later passes' digits go to a buffer of the pass's own)
         if (fine) { pin.sort_bits = FM.sort_bits[me][g]; pin.seg_prefix = segp.data(); }
         DirWindow win;
         win.w_lo = (u32)group_first_prefix(g);
@@ -1325,56 +1196,56 @@ bool sharded_insert_grouped(cblx_ctx* c, cblx_comm* cm, const u8* d_bases, const
         }
         win.w_hi = (u32)std::min<u64>(whi, 0xFFFFFFC0ull);
         win.bv = fin.bv.get();
-        GroupRegions R;
-        R.log_lo = a_lo.get();
-        R.log_hi = OHS ? (const void*)a_hi.get() : nullptr;
-        R.fin_lo = fin.a_lo.get() + gbase[g];
-        R.fin_hi = fin_hi ? fin_hi + gbase[g] : nullptr;
-        R.scr_lo = scr_lo.get();
-        R.scr_hi = OHS ? scr_hi.get() : nullptr;
         if (trace) fprintf(stderr, "[cblx grouped] rank %u group %u: %llu words, prefixes [%u, %u), cells [%u, %u), %u bits sorted behind the first pass\n", me, g, (unsigned long long)gN[g], win.w_lo, win.w_hi,
                            gc0[g], gc0[g + 1], pin.sort_bits ? pin.sort_bits : RB);
         pipeline_group<C>(c, R, pin, gN[g], win, parts[g]);
         ++cm->groups_used;
         if (pin.sort_bits == FINE_LEVEL) ++cm->groups_fine;
     }
-    T.wait();
-    CBLX_HIP(hipStreamSynchronize(c->stream));
-    for (Sent& S : sent) { S.lo.reset(); S.hi.reset(); S.dig.reset(); }
-    a_lo.reset(); a_hi.reset(); a_dig.reset();
+
     // -- one index out of the groups: tables concatenated (starts made absolute), rank directory over the whole bitvector
-    if (filled) {
-        u64 nb = 0;
-        for (const Resident& r : parts) { nb += r.nb; fin.count += r.count; }
-        fin.nb = nb;
-        fin.prefix = Buf<u32>(c->pool, nb + 1);
-        fin.start = Buf<u64>(c->pool, nb + 1);
-        fin.cnt = Buf<u32>(c->pool, nb + 1);
-        fin.kind = Buf<u8>(c->pool, nb + 1);
-        u64 at = 0;
-        for (u32 g = 0; g < NG; ++g) {
-            const Resident& r = parts[g];
-            if (!r.nb) continue;
-            CBLX_HIP(hipMemcpyAsync(fin.prefix.get() + at, r.prefix.get(), r.nb * 4, hipMemcpyDeviceToDevice, c->stream));
-            CBLX_HIP(hipMemcpyAsync(fin.start.get() + at, r.start.get(), r.nb * 8, hipMemcpyDeviceToDevice, c->stream));
-            CBLX_HIP(hipMemcpyAsync(fin.cnt.get() + at, r.cnt.get(), r.nb * 4, hipMemcpyDeviceToDevice, c->stream));
-            CBLX_HIP(hipMemcpyAsync(fin.kind.get() + at, r.kind.get(), r.nb, hipMemcpyDeviceToDevice, c->stream));
-            if (gbase[g]) hipLaunchKernelGGL(k_add_u64, grid1(r.nb, 256), dim3(256), 0, c->stream, fin.start.get() + at, r.nb, gbase[g]);
-            at += r.nb;
+    void assemble() {
+        const u64 filled = log.filled, nwords = std::max<u64>(1, (1ull << P.PB) / 64);
+        if (filled) {
+            u64 nb = 0;
+            for (const Resident& r : parts) { nb += r.nb; fin.count += r.count; }
+            fin.nb = nb;
+            fin.prefix = Buf<u32>(c->pool, nb + 1); fin.start = Buf<u64>(c->pool, nb + 1);
+            fin.cnt = Buf<u32>(c->pool, nb + 1); fin.kind = Buf<u8>(c->pool, nb + 1);
+            u64 at = 0;
+            for (u32 g = 0; g < NG; ++g) {
+                const Resident& r = parts[g];
+                if (!r.nb) continue;
+                CBLX_HIP(hipMemcpyAsync(fin.prefix.get() + at, r.prefix.get(), r.nb * 4, hipMemcpyDeviceToDevice, c->stream));
+                CBLX_HIP(hipMemcpyAsync(fin.start.get() + at, r.start.get(), r.nb * 8, hipMemcpyDeviceToDevice, c->stream));
+                CBLX_HIP(hipMemcpyAsync(fin.cnt.get() + at, r.cnt.get(), r.nb * 4, hipMemcpyDeviceToDevice, c->stream));
+                CBLX_HIP(hipMemcpyAsync(fin.kind.get() + at, r.kind.get(), r.nb, hipMemcpyDeviceToDevice, c->stream));
+                if (gbase[g]) hipLaunchKernelGGL(k_add_u64, grid1(r.nb, 256), dim3(256), 0, c->stream, fin.start.get() + at, r.nb, gbase[g]);
+                at += r.nb;
+            }
+            hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, fin.start.get() + nb, filled);
+            Buf<u32> popc(c->pool, nwords);
+            fin.rank_dir = Buf<u64>(c->pool, nwords + 1);
+            hipLaunchKernelGGL(k_setop_bv, grid1(nwords, 256), dim3(256), 0, c->stream, nwords, (const u64*)fin.bv.get(), (const u64*)fin.bv.get(), SETOP_OR, fin.bv.get(), popc.get());
+            const u64 nb2 = exclusive_scan<u64>(c, popc.get(), nwords, fin.rank_dir.get());
+            CBLX_HIP(hipGetLastError());
+            if (nb2 != nb) throw Error(CBLX_EDEVICE, "grouped receiver: the groups hold " + std::to_string(nb) + " buckets, the bitvector " + std::to_string(nb2) + " (internal error)");
+            CBLX_HIP(hipStreamSynchronize(c->stream));
+            parts.clear();
+            c->res = std::move(fin);
+            c->kmers_inserted += filled;
         }
-        hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, fin.start.get() + nb, filled);
-        Buf<u32> popc(c->pool, nwords);
-        fin.rank_dir = Buf<u64>(c->pool, nwords + 1);
-        hipLaunchKernelGGL(k_setop_bv, grid1(nwords, 256), dim3(256), 0, c->stream, nwords, (const u64*)fin.bv.get(), (const u64*)fin.bv.get(), SETOP_OR, fin.bv.get(), popc.get());
-        const u64 nb2 = exclusive_scan<u64>(c, popc.get(), nwords, fin.rank_dir.get());
-        CBLX_HIP(hipGetLastError());
-        if (nb2 != nb) throw Error(CBLX_EDEVICE, "grouped receiver: the groups hold " + std::to_string(nb) + " buckets, the bitvector " + std::to_string(nb2) + " (internal error)");
         CBLX_HIP(hipStreamSynchronize(c->stream));
-        parts.clear();
-        c->res = std::move(fin);
-        c->kmers_inserted += filled;
     }
-    CBLX_HIP(hipStreamSynchronize(c->stream));
+};
+template <typename C>
+bool sharded_insert_grouped(cblx_ctx* c, cblx_comm* cm, const u8* d_bases, const u64* d_offsets, u64 n, const u64* cuts, u32 nslices, const u32* bounds, bool single = false,
+                            const Replica* rep = nullptr) {
+    GroupedInsert<C> J{c, cm, d_bases, d_offsets, n, cuts, nslices, bounds, single, rep};
+    if (!J.resolve()) return false;
+    if (rep) J.send_local(); else J.send_wire();
+    J.receive();
+    J.assemble();
     return true;
 }
 
@@ -1393,7 +1264,7 @@ bool sharded_insert_replicate(cblx_ctx* c, cblx_comm* cm, const u8* d_bases, con
     const u32 W = T.world, me = T.rank;
     if (W < 2 || nslices == 0) return false;
     check_aligned16(d_bases, "d_bases");
-    for (u32 s = 0; s < nslices; ++s) if (cuts[s + 1] < cuts[s] || cuts[s + 1] > n) throw Error(CBLX_EINVAL, "slice cuts must be ascending and at most n");
+    check_slice_cuts(cuts, nslices, n);
     const u64 n0 = cuts[0], n1 = cuts[nslices], nseq = n1 - n0;
     // The planes cross the links in PARTS (two per call at least: a one-slice call is cut in halves of its reads) so that a peer's first part can be
     // transformed while its later ones are still on the wire; parts cut the (slice, source) pieces, they do not reorder them. (Every part of every
@@ -1405,7 +1276,7 @@ bool sharded_insert_replicate(cblx_ctx* c, cblx_comm* cm, const u8* d_bases, con
     xcuts[NT] = nseq;
     if (nseq) {
         for (u32 t = 0; t <= NT; ++t) ox[t] = (t && xcuts[t] == xcuts[t - 1]) ? ox[t - 1] : d2h<u64>(c, d_offsets + n0 + xcuts[t]);
-        for (u32 t = 0; t < NT; ++t) if (ox[t + 1] < ox[t]) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
+        for (u32 t = 0; t < NT; ++t) (void)offsets_span(ox[t], ox[t + 1]);
     }
     const u64 first = ox[0], last = ox[NT];
     const u64 g0 = first >> 4, g1 = nseq ? (last + 15) >> 4 : g0, ng = g1 - g0;
@@ -1440,9 +1311,9 @@ bool sharded_insert_replicate(cblx_ctx* c, cblx_comm* cm, const u8* d_bases, con
     Buf<u64> all_off(c->pool, sqo[W] + 2);
     CBLX_HIP(hipMemsetAsync(all_codes.get(), 0, (gro[W] + 4) * 4, c->stream));
     CBLX_HIP(hipMemsetAsync(all_valid.get(), 0, (gro[W] + 4) * 2, c->stream));
-    std::vector<hipEvent_t> ev(NT, nullptr);
-    struct Events { std::vector<hipEvent_t>& v; ~Events() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); } } events{ev};
-    struct Drain { Transport& t; ~Drain() { try { t.wait(); } catch (...) {} } } drain{T};
+    EventOwner ev;
+    ev.e.assign(NT, nullptr);
+    Drain drain{&T};
     for (u32 t = 0; t < NT; ++t) {
         auto planes = [&](const void* src, void* dst, size_t es) {
             Transport::Item it{(const u8*)src, (u8*)dst, std::vector<u64>(W, 0), std::vector<u64>(W, 0), std::vector<u64>(W, 0), std::vector<u64>(W, 0)};
@@ -1469,13 +1340,13 @@ bool sharded_insert_replicate(cblx_ctx* c, cblx_comm* cm, const u8* d_bases, con
             items.push_back(std::move(it));
         }
         T.exchange_items(items, c->stream);
-        CBLX_HIP(hipEventCreateWithFlags(&ev[t], hipEventDisableTiming));
-        T.record(ev[t], c->stream);
+        CBLX_HIP(hipEventCreateWithFlags(&ev.e[t], hipEventDisableTiming));
+        T.record(ev.e[t], c->stream);
     }
     Replica rep;
     rep.src.resize(W);
     rep.parts = Q;
-    rep.part_ready = ev;
+    rep.part_ready = ev.e;
     for (u32 r = 0; r < W; ++r) {
         ReplicaSource& R = rep.src[r];
         R.nseq = recv[r * per];
@@ -1499,7 +1370,7 @@ void sharded_insert(cblx_ctx* c, cblx_comm* cm, const u8* d_bases, const u64* d_
     Transport& T = *cm->t;
     T.begin_job();
     if (nslices && !*bounds_valid) {
-        if (cuts[1] < cuts[0] || cuts[1] > n) throw Error(CBLX_EINVAL, "slice cuts must be ascending and at most n");
+        check_slice_cuts(cuts, 1, n);
         std::vector<u64> hist;
         const u32 asked = cm->protocol == CBLX_PROTO_AUTO ? auto_protocol(T.world) : cm->protocol;
         const bool want_bins = asked == CBLX_PROTO_BINS || asked == CBLX_PROTO_REPLICATE;
@@ -1548,6 +1419,12 @@ struct LocalTransport : Transport {
     void wait() override {}
     void exchange_items(const std::vector<Item>&, hipStream_t) override {}
 };
+// the one-rank communicator of the FINE-bins build: no wire, two "groups" cut at fine_single_cut
+inline void fine_local_comm(cblx_comm& cm, u32 PB) {
+    cm.t.reset(new LocalTransport());
+    cm.recv_groups = 2;
+    cm.g_cuts.assign(1, fine_single_cut(PB));
+}
 // ---- one GPU, PREFIX_BITS > 24, an empty index: the build on FINE bins --------------------------------------------------------------
 // The plain build sorts 24 prefix bits in three passes and finishes the last PREFIX_BITS - 24 run by run (k_prefix_split): four trips
 // of every record through HBM. Here the first pass runs on the FINE bins of the grouped receiver (cuts.hpp: make_fine_plan) with ONE
@@ -1556,401 +1433,14 @@ struct LocalTransport : Transport {
 // 8 bits). No sampling: the cut is fixed, and a batch whose words all lie above it simply takes three passes behind the first, as the
 // plain build does. Same index (tests run every PREFIX_BITS > 24 shape through both routes).
 bool insert_device_fine(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64 nseq) {
-    const char* fe = std::getenv("CBLX_FINE_BINS");
-    if ((fe && fe[0] == '0') || c->P.PB <= 24 || nseq == 0 || c->res.count != 0) return false;
+    if (!fine_bins_enabled() || c->P.PB <= 24 || nseq == 0 || c->res.count != 0) return false;
     check_aligned16(d_bases, "d_bases");
     cblx_comm cm;
-    cm.t.reset(new LocalTransport());
-    cm.recv_groups = 2;
-    cm.g_cuts.assign(1, fine_single_cut(c->P.PB));
+    fine_local_comm(cm, c->P.PB);
     const u64 cuts[2] = {0, nseq};
     bool done = false;
     dispatch(c->P, [&](auto cfg) { done = sharded_insert_grouped<decltype(cfg)>(c, &cm, d_bases, d_offsets, nseq, cuts, 1, nullptr, true); });
     if (done) ++c->fine_builds;
     return done;
 }
-}  // namespace (reopened below: insert_device_streamed is declared in ingest.hpp)
-
-namespace {
-// flush() of a batch sent from pinned host memory in slices (ingest_seqs): KRN-1 and the first partition pass of slice k run
-// as soon as the slice has landed, while the later slices are still crossing PCIe; when the last one is in, what is left is
-// the remaining passes and the bucket kernels. Same result as insert_device (the slices are pieces of the pass-A segments in
-// stream order, exactly what the receiver of the multi-GPU build gets from its senders).
-// `ready(s)`: returns once the ctx's stream may read slice s (s = ~0u: the offsets) — it makes the stream wait on the transfer's
-// events, blocking the host first if they are not recorded yet
-template <typename Ready>
-void insert_device_sliced(cblx_ctx* c, const BaseView& bases, const u64* d_offsets, u64 nseq, const std::vector<u64>& seq_cuts, Ready&& ready) {
-    const u32 ns = (u32)seq_cuts.size() - 1;
-    {   // PREFIX_BITS > 24 on an empty index: the FINE-bins build (insert_device_fine's plan: one rank, two groups, a fixed cut) slice by slice as
-        // the batch lands — two LSD passes behind the first one for the dense part of the prefix space instead of three for everything (round 6)
-        const char* fe = std::getenv("CBLX_FINE_BINS");
-        if (c->P.PB > 24 && c->res.count == 0 && nseq && ns && !(fe && fe[0] == '0')) {
-            cblx_comm cm;
-            cm.t.reset(new LocalTransport());
-            cm.recv_groups = 2;
-            cm.g_cuts.assign(1, fine_single_cut(c->P.PB));
-            Replica rep;
-            rep.src.resize(1);
-            rep.src[0].view = bases;
-            rep.src[0].d_off = d_offsets + seq_cuts[0];
-            rep.src[0].nseq = seq_cuts[ns] - seq_cuts[0];
-            for (u64 x : seq_cuts) rep.src[0].cuts.push_back(x - seq_cuts[0]);
-            rep.per_slice = true;
-            rep.ready = [&](u32 s) { ready(s); };
-            bool done = false;
-            dispatch(c->P, [&](auto cfg) { done = sharded_insert_grouped<decltype(cfg)>(c, &cm, nullptr, d_offsets, nseq, seq_cuts.data(), ns, nullptr, true, &rep); });
-            if (done) { ++c->fine_builds; collect_events(c); return; }
-        }
-    }
-    LocalTransport T;
-    u32 none = 0;
-    dispatch(c->P, [&](auto cfg) { sharded_insert_bins<decltype(cfg)>(c, T, bases, d_offsets, nseq, seq_cuts.data(), ns, &none, ready); });
-    collect_events(c);
-}
-void insert_device_streamed(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64 nseq, const Ingest::Streamed& plan) {
-    auto wait_for = [&](const std::vector<hipEvent_t>& evs) { for (hipEvent_t e : evs) CBLX_HIP(hipStreamWaitEvent(c->stream, e, 0)); };
-    if (c->P.PB < 9 || nseq == 0) {  // no LSD pass behind pass A: the plain path, once everything is there
-        wait_for(plan.offsets_ready);
-        for (auto& v : plan.ready) wait_for(v);
-        insert_device(c, d_bases, d_offsets, nseq);
-        return;
-    }
-    check_aligned16(d_bases, "d_bases");
-    const bool trace = std::getenv("CBLX_TRACE_H2D") != nullptr;  // dev: when every slice had landed / was handed to the kernels
-    const auto t0 = std::chrono::steady_clock::now();
-    auto ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-    insert_device_sliced(c, ascii_view(d_bases), d_offsets, nseq, plan.seq_cuts, [&](u32 s) {
-        if (s == ~0u) { wait_for(plan.offsets_ready); return; }
-        if (trace) {
-            const double a = ms();
-            for (hipEvent_t e : plan.ready[s]) CBLX_HIP(hipEventSynchronize(e));
-            fprintf(stderr, "[cblx h2d] slice %u: host arrives %.2f ms, landed %.2f ms\n", s, a, ms());
-        }
-        wait_for(plan.ready[s]);
-    });
-    if (trace) { CBLX_HIP(hipStreamSynchronize(c->stream)); fprintf(stderr, "[cblx h2d] done %.2f ms\n", ms()); }
-}
-
-// A big host batch as BIT PLANES (3 bits per base over PCIe instead of 8: the link is the bound of the host-input path). Host
-// threads pack the caller's ASCII bases unit by unit (xfer.hpp: pack_planes) into pinned staging, an issuer thread copies every
-// finished unit to the device on two streams, and THIS thread runs the sliced insert right behind them: slice s = the sequences
-// that end inside the units landed so far. The index is built when the call returns (the caller's buffers are borrowed for the call
-// only). Pageable or pinned source alike. Returns false when the batch does not qualify (the caller takes the other paths).
-// check_slice(i0, i1): throws unless sequences [i0, i1) of the batch are well-formed (offsets non-decreasing, every length >= K)
-template <typename V> bool ingest_seqs_planes(cblx_ctx* c, const u8* bases, const u64* offsets, u64 n, V&& check_slice) {
-    Ingest& g = c->ing;
-    const bool trace = std::getenv("CBLX_TRACE_H2D") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-    const u64 o0 = offsets[0], len = offsets[n] >= o0 ? offsets[n] - o0 : 0;
-    const char* pk = std::getenv("CBLX_H2D_PACK");  // 0 off, 1 on, default: by core count (read per call: tests switch it)
-    const int mode = pk ? std::atoi(pk) : -1;
-    const unsigned hc = std::thread::hardware_concurrency();
-    if (mode == 0 || (mode < 0 && hc < 16)) return false;
-    if (g.nseq || g.nbytes || g.query || g.staged || c->P.PB < 9 || len < (64u << 20) || n < 1024 || len >= ingest_flush_bytes()) return false;
-    // transfer units = slices of the insert. Few: every slice costs fixed work (chunk plan, column scans, piece: ~0.5 ms). Measured at
-    // cfg 2 with equal units: 4 / 6 / 8 / 12 / 16 / 32 units 38.8 / 37.6 / 37.8 / 39.2 / 40.5 / 46.5 ms. The kernel time line of that
-    // (tools/dev_h2d_timeline.py): the wire is the bound while the units arrive (0.64 GB = 11.7 ms; KRN-1 + pass A of all of them
-    // take 10.2), in front of it the packing of the first unit, behind it the kernels of the last — so the six default units
-    // are 1, 3, 4, 4, 3, 1 sixteenths of the batch: a short first one (the wire starts early) and a short last one.
-    const char* eu = std::getenv("CBLX_H2D_UNITS");
-    const u32 NU = eu && std::atoi(eu) > 0 ? (u32)std::min(std::atoi(eu), 64) : 6u;
-    std::vector<u64> ub(1, 0);  // unit k = bases [ub[k], ub[k + 1]), multiples of 1024
-    {
-        std::vector<u32> w;  // relative sizes (CBLX_H2D_TAPER="1,3,4,4,3,1" overrides; CBLX_H2D_UNITS = that many equal units)
-        if (const char* et = std::getenv("CBLX_H2D_TAPER")) {
-            for (const char* p = et; *p;) { char* q; const unsigned long v = std::strtoul(p, &q, 10); if (q == p) break; if (v) w.push_back((u32)v); p = *q ? q + 1 : q; }
-        }
-        if (w.empty()) { if (eu) w.assign(NU, 1u); else w = {1, 3, 4, 4, 3, 1}; }
-        u64 tot = 0, acc = 0;
-        for (u32 v : w) tot += v;
-        for (size_t k = 0; k < w.size(); ++k) {
-            acc += w[k];
-            const u64 b = k + 1 == w.size() ? len : std::min<u64>(len, ((u64)((double)len * (double)acc / (double)tot) + 1023) & ~(u64)1023);
-            if (b > ub.back()) ub.push_back(b);
-        }
-        if (ub.back() < len) ub.push_back(len);
-    }
-    const u32 nu = (u32)ub.size() - 1;
-    auto unit_at = [&](u64 base) -> u32 { return (u32)(std::upper_bound(ub.begin(), ub.end(), base) - ub.begin()) - 1u; };
-    const u64 ng = (len + 15) / 16;                                      // groups of 16 bases
-    // device planes, offsets, pinned staging (kept between calls)
-    if (g.d_codes.n < ng + 8) g.d_codes = Buf<u32>(c->pool, ng + 8);
-    if (g.d_valid.n < ng + 8) g.d_valid = Buf<u16>(c->pool, ng + 8);
-    ingest_reserve(c, 0, n);
-    const size_t need = (size_t)(ng + 8) * 6;
-    if (g.pin_cap < need) {
-        if (g.pin) { u8* old = g.pin; g.pin = nullptr; g.pin_cap = 0; CBLX_HIP(hipHostFree(old)); }
-        CBLX_HIP(hipHostMalloc((void**)&g.pin, need, hipHostMallocDefault));
-        g.pin_cap = need;
-    }
-    u32* h_codes = (u32*)g.pin;
-    u16* h_valid = (u16*)(g.pin + (size_t)(ng + 8) * 4);
-    Xfer& x = xfer(c);
-    hipStream_t cs[2] = {x.lane_stream(0), x.lane_stream(1)};
-    // offsets (relative to the batch's first base): straight from the caller's array when pinned and zero-based, else transformed
-    hipEvent_t off_ev = nullptr;
-    // pinned and zero-based: the offsets of a slice travel in front of its unit (all of them up front are 80 MB at cfg 2 — 1.4 ms of
-    // wire before the first base); only the last one, which sizes the arena, goes ahead
-    const bool off_by_slice = o0 == 0 && Xfer::is_pinned(offsets) && Xfer::is_pinned(offsets + n);
-    if (off_by_slice) x.h2d_pinned_lane0(g.d_off.get() + n, offsets + n, 8, off_ev);
-    else {
-        x.h2d(g.d_off.get() + 1, n * 8, [&](u8* dst, size_t off, size_t nb) {
-            u64* d = (u64*)dst;
-            const u64* src = offsets + off / 8 + 1;
-            for (size_t j = 0; j < nb / 8; ++j) d[j] = src[j] - o0;
-        });
-        x.sync();
-    }
-    // slices: slice k = the sequences that end inside units 0 .. k
-    std::vector<u64> cuts(1, 0);
-    std::vector<u32> unit_of;  // the last unit a slice needs
-    for (u32 k = 0; k < nu; ++k) {
-        const u64 lim = ub[k + 1];
-        const u64 i = k + 1 == nu ? n : (u64)(std::upper_bound(offsets + 1, offsets + n + 1, o0 + lim) - (offsets + 1));
-        if (i > cuts.back()) { cuts.push_back(i); unit_of.push_back(k); }
-    }
-    // packers: sub-blocks of a unit in order, so that the units complete one after the other
-    const u64 SB = 2u << 20;  // bases per sub-block (a multiple of 16)
-    const u64 nsb = (len + SB - 1) / SB;
-    std::vector<std::atomic<u32>> left(nu);
-    for (u32 k = 0; k < nu; ++k) {
-        const u64 a = ub[k], b = ub[k + 1];
-        left[k].store((u32)((b + SB - 1) / SB - a / SB) , std::memory_order_relaxed);
-    }
-    // (a unit boundary is a multiple of SB only by accident: a sub-block may straddle units — it then counts for each of them)
-    std::vector<std::atomic<u8>> dirty(nu);  // a base outside ACGTacgt in the unit: only then its validity plane is sent
-    for (u32 k = 0; k < nu; ++k) dirty[k].store(0, std::memory_order_relaxed);
-    std::atomic<u64> next_sb{0};
-    std::atomic<u32> issued{0};
-    std::atomic<bool> failed{false};
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<hipEvent_t> ev(nu, nullptr);
-    const int T = (int)std::max(2u, std::min(32u, hc / 2));
-    auto pack_worker = [&] {
-        for (u64 sb; (sb = next_sb.fetch_add(1)) < nsb;) {
-            const u64 a = sb * SB, b = std::min<u64>(len, a + SB);
-            const bool clean = pack_planes(bases + o0 + a, b - a, h_codes + a / 16, h_valid + a / 16);
-            for (u32 k = unit_at(a), k1 = unit_at(b - 1); k <= k1; ++k) {
-                if (!clean) dirty[k].store(1, std::memory_order_relaxed);
-                if (left[k].fetch_sub(1, std::memory_order_acq_rel) == 1) { std::lock_guard<std::mutex> l(mu); cv.notify_all(); }
-            }
-        }
-    };
-    auto issuer = [&] {
-        try {
-            CBLX_HIP(hipSetDevice(c->device));
-            for (u32 k = 0; k < nu; ++k) {
-                { std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return left[k].load(std::memory_order_acquire) == 0; }); }
-                const u64 g0 = ub[k] / 16, g1 = k + 1 == nu ? ng : ub[k + 1] / 16;
-                if (off_by_slice)
-                    for (size_t sl = 0; sl < unit_of.size(); ++sl)
-                        if (unit_of[sl] == k && cuts[sl + 1] > cuts[sl])
-                            CBLX_HIP(hipMemcpyAsync(g.d_off.get() + 1 + cuts[sl], offsets + 1 + cuts[sl], (cuts[sl + 1] - cuts[sl]) * 8, hipMemcpyHostToDevice, cs[k & 1]));
-                CBLX_HIP(hipMemcpyAsync(g.d_codes.get() + g0, h_codes + g0, (g1 - g0) * 4, hipMemcpyHostToDevice, cs[k & 1]));
-                if (dirty[k].load(std::memory_order_relaxed)) {
-                    CBLX_HIP(hipMemcpyAsync(g.d_valid.get() + g0, h_valid + g0, (g1 - g0) * 2, hipMemcpyHostToDevice, cs[k & 1]));
-                } else {
-                    // every base of the unit is valid: its validity plane is all ones and is filled in on the device (a third of
-                    // the unit's bytes stays off the link); the batch's last, partly filled word comes from the host
-                    CBLX_HIP(hipMemsetAsync(g.d_valid.get() + g0, 0xFF, (g1 - g0) * 2, cs[k & 1]));
-                    if (k + 1 == nu && (len & 15)) CBLX_HIP(hipMemcpyAsync(g.d_valid.get() + ng - 1, h_valid + ng - 1, 2, hipMemcpyHostToDevice, cs[k & 1]));
-                }
-                hipEvent_t e;
-                CBLX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                CBLX_HIP(hipEventRecord(e, cs[k & 1]));
-                ev[k] = e;
-                { std::lock_guard<std::mutex> l(mu); issued.store(k + 1, std::memory_order_release); }
-                cv.notify_all();
-            }
-        } catch (...) {
-            { std::lock_guard<std::mutex> l(mu); failed = true; issued.store(nu, std::memory_order_release); }
-            cv.notify_all();
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t) th.emplace_back(pack_worker);
-    th.emplace_back(issuer);
-    struct Join {
-        std::vector<std::thread>& th; std::vector<hipEvent_t>& ev; hipEvent_t& off_ev; Xfer& x;
-        ~Join() {
-            for (auto& t : th) if (t.joinable()) t.join();
-            try { x.sync(); } catch (...) {}
-            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-            if (off_ev) (void)hipEventDestroy(off_ev);
-        }
-    } join{th, ev, off_ev, x};
-    if (trace) fprintf(stderr, "[cblx h2d planes] threads started %.2f ms\n", ms());
-    const BaseView view{nullptr, g.d_codes.get(), g.d_valid.get()};
-    insert_device_sliced(c, view, g.d_off.get(), n, cuts, [&](u32 s) {
-        if (s == ~0u) { if (off_ev) CBLX_HIP(hipStreamWaitEvent(c->stream, off_ev, 0)); return; }
-        // The slice's offsets are checked before a kernel reads them (the resident index is not touched before the last slice is
-        // in: a failure here leaves it as it was), while its unit is on its way and the slices in front of it run.
-        check_slice(cuts[s], cuts[s + 1]);
-        const u32 k = unit_of[s];
-        const double a = trace ? ms() : 0;
-        { std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return issued.load(std::memory_order_acquire) > k; }); }
-        if (failed) throw Error(CBLX_EDEVICE, "host-to-device transfer of the batch failed");
-        CBLX_HIP(hipStreamWaitEvent(c->stream, ev[k], 0));               // units are copied in order on two streams:
-        if (k) CBLX_HIP(hipStreamWaitEvent(c->stream, ev[k - 1], 0));    // the last one on each of them
-        if (trace) fprintf(stderr, "[cblx h2d planes] slice %u (unit %u): host arrives %.2f ms, issued %.2f ms\n", s, k, a, ms());
-    });
-    if (trace) { CBLX_HIP(hipStreamSynchronize(c->stream)); fprintf(stderr, "[cblx h2d planes] done %.2f ms\n", ms()); }
-    CBLX_HIP(hipStreamSynchronize(c->stream));
-    return true;
-}
-
-// ---- a plain FASTA / FASTQ file as bit planes: the parser threads pack the sequence lines themselves -------------------------------
-// The file path was bound by its host side: every region's sequence lines were copied into pinned slots and sent as ASCII (1.5 GB
-// for cfg 2, 65 - 97 ms), then inserted window by window. Here a region's thread appends its lines to the batch's bit planes IN
-// PLACE (PlaneSink: 16 bytes -> three 16-bit words by SSE2 movemask, shifted to the region's bit offset; only the first and the last
-// word of a region are shared with its neighbours and take an atomic OR), the slices (groups of consecutive regions) are copied as
-// they complete, and the calling thread runs the sliced insert right behind them, as ingest_seqs_planes does for a host batch.
-bool fastx_parallel_planes(cblx_ctx* c, const char* path, u64* nrec_out) {
-    Ingest& g = c->ing;
-    const char* pk = std::getenv("CBLX_H2D_PACK");
-    const int mode = pk ? std::atoi(pk) : -1;
-    const unsigned hc = std::thread::hardware_concurrency();
-    if (mode == 0 || (mode < 0 && hc < 16)) return false;
-    if (g.nseq || g.nbytes || g.query || g.staged || c->P.PB < 9) return false;
-    const size_t MIN_BYTES = fastx_env_bytes("CBLX_FASTX_PARALLEL_MIN", 32u << 20), REGION = fastx_env_bytes("CBLX_FASTX_REGION_BYTES", 16u << 20);
-    const bool trace = std::getenv("CBLX_INGEST_TRACE") != nullptr;
-    const auto t00 = std::chrono::steady_clock::now();
-    auto ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t00).count(); };
-    FastxMap m;
-    if (!m.open(path, MIN_BYTES)) return false;
-    std::vector<FastxRegion> regs;
-    fx_make_regions(m, m.first, m.size, REGION, regs);
-    if (trace) fprintf(stderr, "[fastx planes] mapped, %zu regions at %.2f ms\n", regs.size(), ms());
-    const unsigned TP = (unsigned)fastx_env_bytes("CBLX_FASTX_THREADS", std::min(32u, std::max(2u, hc / 2)));  // parser threads (both passes)
-    if (!fx_count_regions(m, regs, c->P.K, TP)) return false;
-    if (trace) fprintf(stderr, "[fastx planes] counted at %.2f ms\n", ms());
-    const u32 K = c->P.K;
-    const u64 window = std::min<u64>(ingest_flush_bytes(), 0x78000000ull);  // bases per batch (one batch = fewer than 2^32 words)
-    u64 total_rec = 0;
-    Xfer& x = xfer(c);
-    hipStream_t cs[2] = {x.lane_stream(0), x.lane_stream(1)};
-    for (size_t w0 = 0; w0 < regs.size();) {
-        size_t w1 = w0;
-        u64 nbases = 0, nrec = 0;
-        while (w1 < regs.size() && (w1 == w0 || nbases + regs[w1].nbases <= window)) { nbases += regs[w1].nbases; nrec += regs[w1].nrec; ++w1; }
-        const size_t nr = w1 - w0;
-        if (nrec == 0) { w0 = w1; continue; }
-        const u64 ng = (nbases + 15) / 16;
-        if (g.d_codes.n < ng + 8) g.d_codes = Buf<u32>(c->pool, ng + 8);
-        if (g.d_valid.n < ng + 8) g.d_valid = Buf<u16>(c->pool, ng + 8);
-        ingest_reserve(c, 0, nrec);
-        const size_t need = (size_t)(ng + 8) * 6 + (size_t)nrec * 8 + 64;
-        if (g.pin_cap < need) {
-            if (g.pin) { u8* old = g.pin; g.pin = nullptr; g.pin_cap = 0; CBLX_HIP(hipHostFree(old)); }
-            CBLX_HIP(hipHostMalloc((void**)&g.pin, need, hipHostMallocDefault));
-            g.pin_cap = need;
-        }
-        u32* h_codes = (u32*)g.pin;
-        u16* h_valid = (u16*)(g.pin + (size_t)(ng + 8) * 4);
-        u64* h_ends = (u64*)(g.pin + (((size_t)(ng + 8) * 6 + 63) & ~(size_t)63));
-        // the last offset (= the window's bases, known from the count) goes ahead of everything: the sliced insert sizes its arena
-        // from it before the first slice (the offsets themselves travel with their slices)
-        CBLX_HIP(hipMemcpy(g.d_off.get() + nrec, &nbases, 8, hipMemcpyHostToDevice));
-        std::vector<u64> base(nr + 1, 0), rec0(nr + 1, 0);
-        for (size_t i = 0; i < nr; ++i) { base[i + 1] = base[i] + regs[w0 + i].nbases; rec0[i + 1] = rec0[i] + regs[w0 + i].nrec; }
-        fx_planes_prezero(base, ng + 8, h_codes, h_valid);
-        // slices = groups of consecutive regions of about 1 / NS of the bases
-        const u32 NS = 6;
-        std::vector<size_t> sl(1, 0);
-        for (u32 k = 1; k <= NS; ++k) {
-            size_t i = sl.back();
-            while (i < nr && base[i] < nbases * k / NS) ++i;
-            if (k == NS) i = nr;
-            if (i > sl.back()) sl.push_back(i);
-        }
-        const u32 ns = (u32)sl.size() - 1;
-        std::vector<u64> cuts(ns + 1);
-        for (u32 k = 0; k <= ns; ++k) cuts[k] = rec0[sl[k]];
-        std::vector<u32> slice_of(nr);
-        std::vector<std::atomic<u32>> left(ns);
-        for (u32 k = 0; k < ns; ++k) { left[k].store((u32)(sl[k + 1] - sl[k])); for (size_t i = sl[k]; i < sl[k + 1]; ++i) slice_of[i] = k; }
-        std::atomic<size_t> next{0};
-        std::atomic<u32> issued{0};
-        std::atomic<bool> failed{false};
-        std::mutex mu;
-        std::condition_variable cv;
-        std::vector<hipEvent_t> ev(ns, nullptr);
-        const u8* d = m.d;
-        const char fmt = m.fmt;
-        auto worker = [&] {
-            for (size_t i; (i = next.fetch_add(1)) < nr;) {
-                const FastxRegion& r = regs[w0 + i];
-                PlaneSink sink(h_codes, h_valid, base[i], h_ends + rec0[i], r.nrec, base[i + 1]);
-                if (!fx_walk(d, r, fmt, K, sink) || sink.overflow || sink.pos != base[i + 1] || sink.nrec != r.nrec) failed = true;
-                sink.finish();
-                if (left[slice_of[i]].fetch_sub(1, std::memory_order_acq_rel) == 1) { std::lock_guard<std::mutex> l(mu); cv.notify_all(); }
-            }
-        };
-        auto issuer = [&] {
-            try {
-                CBLX_HIP(hipSetDevice(c->device));
-                for (u32 k = 0; k < ns; ++k) {
-                    { std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return left[k].load(std::memory_order_acquire) == 0; }); }
-                    // the slice's groups, its last, possibly shared word included. A slice that STARTS inside a group shares that
-                    // word with its predecessor, whose copy of it (taken before this slice's bits were all there) runs on the other
-                    // stream: two DMA writes of one word with nothing between them — whichever lands last stays. So the word this
-                    // slice shares with its predecessor is copied separately, BEHIND the predecessor's event; the bulk does not wait.
-                    const bool shared_front = k > 0 && (base[sl[k]] & 15) != 0;
-                    const u64 g0 = base[sl[k]] >> 4, g1 = std::min<u64>(ng, (base[sl[k + 1]] + 15) >> 4), gb = std::min(g1, g0 + (shared_front ? 1 : 0));
-                    hipStream_t st = cs[k & 1];
-                    if (g1 > gb) {
-                        CBLX_HIP(hipMemcpyAsync(g.d_codes.get() + gb, h_codes + gb, (g1 - gb) * 4, hipMemcpyHostToDevice, st));
-                        CBLX_HIP(hipMemcpyAsync(g.d_valid.get() + gb, h_valid + gb, (g1 - gb) * 2, hipMemcpyHostToDevice, st));
-                    }
-                    if (gb > g0) {
-                        CBLX_HIP(hipStreamWaitEvent(st, ev[k - 1], 0));
-                        CBLX_HIP(hipMemcpyAsync(g.d_codes.get() + g0, h_codes + g0, 4, hipMemcpyHostToDevice, st));
-                        CBLX_HIP(hipMemcpyAsync(g.d_valid.get() + g0, h_valid + g0, 2, hipMemcpyHostToDevice, st));
-                    }
-                    if (cuts[k + 1] > cuts[k]) CBLX_HIP(hipMemcpyAsync(g.d_off.get() + 1 + cuts[k], h_ends + cuts[k], (cuts[k + 1] - cuts[k]) * 8, hipMemcpyHostToDevice, st));
-                    hipEvent_t e;
-                    CBLX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                    CBLX_HIP(hipEventRecord(e, st));
-                    ev[k] = e;
-                    { std::lock_guard<std::mutex> l(mu); issued.store(k + 1, std::memory_order_release); }
-                    cv.notify_all();
-                }
-            } catch (...) {
-                { std::lock_guard<std::mutex> l(mu); failed = true; issued.store(ns, std::memory_order_release); }
-                cv.notify_all();
-            }
-        };
-        const int T = (int)std::max<size_t>(1, std::min<size_t>(TP, nr));
-        std::vector<std::thread> th;
-        for (int t = 0; t < T; ++t) th.emplace_back(worker);
-        th.emplace_back(issuer);
-        struct Join {
-            std::vector<std::thread>& th; std::vector<hipEvent_t>& ev; Xfer& x;
-            ~Join() {
-                for (auto& t : th) if (t.joinable()) t.join();
-                try { x.sync(); } catch (...) {}
-                for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-            }
-        } join{th, ev, x};
-        const BaseView view{nullptr, g.d_codes.get(), g.d_valid.get()};
-        insert_device_sliced(c, view, g.d_off.get(), nrec, cuts, [&](u32 s) {
-            if (s == ~0u) s = 0;  // the offsets of a slice travel with it: the first read needs slice 0
-            { std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return issued.load(std::memory_order_acquire) > s; }); }
-            if (failed) throw Error(CBLX_EDEVICE, "fastx: the file changed while it was being read");
-            CBLX_HIP(hipStreamWaitEvent(c->stream, ev[s], 0));
-            if (s) CBLX_HIP(hipStreamWaitEvent(c->stream, ev[s - 1], 0));
-            if (trace) fprintf(stderr, "[fastx planes] slice %u handed over at %.2f ms\n", s, ms());
-        });
-        CBLX_HIP(hipStreamSynchronize(c->stream));
-        if (failed) throw Error(CBLX_EDEVICE, "fastx: the file changed while it was being read");
-        total_rec += nrec;
-        if (trace) fprintf(stderr, "[fastx planes] window of %llu records done at %.2f ms\n", (unsigned long long)nrec, ms());
-        w0 = w1;
-    }
-    if (nrec_out) *nrec_out = total_rec;
-    return true;
-}
-
 }  // namespace

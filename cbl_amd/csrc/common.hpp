@@ -5,9 +5,10 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "error.hpp"
 
 namespace cblx {
 
@@ -28,11 +29,6 @@ struct Consts {
 
 static const u32 CHUNK_KMERS = 2048;   // src/cbl.rs:67
 static const u32 VEC_THRESHOLD = 1024; // src/wordset/mod.rs:34
-
-struct Error : std::runtime_error {
-    int code;
-    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
 
 #define CBLX_HIP(expr)                                                                                  \
     do {                                                                                                \

@@ -220,6 +220,8 @@ struct StageTimer {  // brackets a group of launches with HIP events when profil
     }
     ~StageTimer() { if (idx >= 0) (void)hipEventRecord(c->evs[idx].b, c->stream); }
 };
+// the events of a call, destroyed on every way out
+struct EventOwner { std::vector<hipEvent_t> e; ~EventOwner() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } };
 void collect_events(cblx_ctx* c) {
     if (c->evs.empty()) return;
     CBLX_HIP(hipStreamSynchronize(c->stream));

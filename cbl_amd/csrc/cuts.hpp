@@ -71,7 +71,6 @@ inline std::vector<u32> choose_group_cuts(const std::vector<u64>& hist, const u3
     return cuts;
 }
 
-
 struct CutPlan {
     bool ok = false;
     std::vector<u32> cuts;              // ascending, distinct, non-zero: rank bounds and group cuts
@@ -185,7 +184,6 @@ inline FinePlan make_fine_plan(u32 PB, u32 lmax, const u32* bounds, u32 W, const
     std::sort(cuts.begin(), cuts.end());
     for (size_t i = 1; i < cuts.size(); ++i) if (cuts[i].first == cuts[i - 1].first) return M;
     if (cuts.empty() || cuts.front().first == 0) return M;
-    const size_t nforced = cuts.size();
     auto has = [&](u64 v) { return std::binary_search(cuts.begin(), cuts.end(), std::make_pair((u32)v, 0u), [](const std::pair<u32, u32>& a, const std::pair<u32, u32>& b) { return a.first < b.first; }); };
     // structural cuts at the multiples of 2^lmax up to 2^(PB-1): everything above is one never-used bin in front of the all-ones one
     {
@@ -220,7 +218,6 @@ inline FinePlan make_fine_plan(u32 PB, u32 lmax, const u32* bounds, u32 W, const
         cuts.insert(cuts.end(), add.begin(), add.end());
         std::sort(cuts.begin(), cuts.end());
     }
-    (void)nforced;
     const u32 nc = (u32)cuts.size();
     for (const auto& c : cuts) M.cuts.push_back(c.first);
     // intervals: owner, group, first prefix, level
@@ -287,9 +284,13 @@ inline u64 fine_tail_weight_pct() {  // (job-wide like every switch that shapes 
     const char* we = std::getenv("CBLX_FINE_TAIL_WEIGHT");
     return we ? std::strtoull(we, nullptr, 10) : 120;
 }
-inline void weigh_tail_for_fine_bins(std::vector<u64>& hist, u32 PB, u32 W, u32 G, u32 hb) {
+// CBLX_FINE_BINS=0 switches the FINE bins off (read per call: tests switch it; job-wide like the tail weight)
+inline bool fine_bins_enabled() {
     const char* fe = std::getenv("CBLX_FINE_BINS");
-    if (PB <= 24 || PB > 28 || W < 2 || (fe && fe[0] == '0') || hb + FINE_LEVEL < PB) return;  // (cells must not be wider than 2^16 prefixes)
+    return !(fe && fe[0] == '0');
+}
+inline void weigh_tail_for_fine_bins(std::vector<u64>& hist, u32 PB, u32 W, u32 G, u32 hb) {
+    if (PB <= 24 || PB > 28 || W < 2 || !fine_bins_enabled() || hb + FINE_LEVEL < PB) return;  // (cells must not be wider than 2^16 prefixes)
     const u64 pct = fine_tail_weight_pct();
     if (pct == 100 || pct == 0) return;
     const u64 forced = (u64)W * G - 1, fixed = 8;  // rank bounds + group cuts, the multiples of 2^lmax

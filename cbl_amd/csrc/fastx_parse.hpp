@@ -1,4 +1,4 @@
-// fastx_parse.hpp — the host-only part of the parallel FASTA / FASTQ readers (ingest.hpp, comm.hpp): a mapped file cut into regions
+// fastx_parse.hpp — the host-only part of the parallel FASTA / FASTQ readers (ingest.hpp, host_input.hpp): a mapped file cut into regions
 // at record starts, one walk over a region (what needletail's `seq()` yields for every record: the sequence lines with their line
 // ends stripped, FASTQ qualities dropped; /root/reference/examples/cbl.rs:112-115,154-163), the counting pass, and PlaneSink, which
 // appends a region's sequence lines to a batch's bit planes (kernels_encode.hpp BaseView). No HIP in here: tests/host/fastx_planes_unit.cpp

@@ -380,10 +380,7 @@ template <typename C> bool serialize_device(cblx_ctx* c, bool emit, DevBlob& blo
                 }
             }
             const u32 NG = (u32)grp.size() - 1;
-            struct Events {
-                std::vector<hipEvent_t> e;
-                ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-            } ev;
+            EventOwner ev;
             ev.e.assign(NG, nullptr);
             for (u32 g = 0; g < NG; ++g) {
                 buckets(std::true_type(), body, grp[g], grp[g + 1]);

@@ -80,7 +80,7 @@ void ingest_reserve(cblx_ctx* c, u64 add_bytes, u64 add_seqs) {
     }
 }
 void flush(cblx_ctx* c);
-// (comm.hpp) insert of device-resident sequences in slices, slice k as soon as ready[k] has fired
+// (host_input.hpp) insert of device-resident sequences in slices, slice k as soon as ready[k] has fired
 void insert_device_streamed(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64 nseq, const Ingest::Streamed& plan);
 // slices of a batch that is streamed from pinned host memory (CBLX_H2D_SLICES overrides; 1 = no streaming)
 inline u32 h2d_slices() {

@@ -976,6 +976,18 @@ __global__ void k_plan_marks(const u64* __restrict__ chunk_base, const u64* __re
 // `B`: where the bases live (ASCII bytes, or the bit planes a big host batch crossed PCIe as); advanced to the slice's aligned start
 // `seq_marks` / `slices`: sequence indices m[0] <= m[1] <= ... (relative to d_offsets) -> the slices [m[i], m[i+1]) of the plan, so that a caller
 // that works slice by slice plans ONCE (a plan costs half a dozen host round trips)
+// bases between the first and the last offset of a batch read back from the device
+inline u64 offsets_span(u64 first, u64 last) {
+    if (last < first) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
+    return last - first;
+}
+// upper bound on the k-mers of sequences [n0, n1) of a batch: its bases less K - 1 per sequence
+inline u64 kmers_upper_bound(cblx_ctx* c, const u64* d_offsets, u64 n0, u64 n1) {
+    if (n1 <= n0) return 0;
+    const u64 first = d2h<u64>(c, d_offsets + n0), last = d2h<u64>(c, d_offsets + n1);
+    const u64 span = offsets_span(first, last), sub = (n1 - n0) * (u64)(c->P.K - 1);
+    return span > sub ? span - sub : 0;
+}
 void plan_chunks(cblx_ctx* c, BaseView& d_bases, const u64* d_offsets, u64 nseq, ChunkPlan& pl, const u64* ends = nullptr, const std::vector<u64>* seq_marks = nullptr,
                  std::vector<PlanSlice>* slices = nullptr) {
     StageTimer t(c, ST_CHUNKS);
@@ -991,8 +1003,7 @@ void plan_chunks(cblx_ctx* c, BaseView& d_bases, const u64* d_offsets, u64 nseq,
         first = rg.get<u64>(h_first); last = rg.get<u64>(h_last);
     }
     pl.bias = first & ~(u64)15;
-    if (last < first) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
-    pl.total_bases = last - pl.bias;
+    pl.total_bases = offsets_span(first, last) + (first - pl.bias);
     d_bases.advance16(pl.bias);
     bool probed_clean = false;  // the probe ran and found every byte of the batch valid
     if (pl.allow_uniform && !pl.keep_seq_chunk && !seq_marks && nseq && uniform_plan_enabled()) {
@@ -1112,6 +1123,52 @@ template <typename C> void encode(cblx_ctx* c, const u8* d_bases, const ChunkPla
     encode<C>(c, ascii_view(d_bases), pl, out_lo, out_hi, out_base, eh);
 }
 
+// ---- the FIRST partition pass of one piece of reads (a slice of a sharded build, a part of a peer's reads, a whole batch): KRN-1 with the
+// pass's histogram fused in, the column prefixes, and the scatter on the digit the caller chose. The workspace lives until the stream is
+// past the scatter (callers that queue the next piece's kernels meanwhile keep it in a `prev` of theirs). `coltot` (the 256 bin totals)
+// stays on the device: the CALLER decides when it is read back — a read between KRN-1 and the scatter is a host round trip on the stream.
+struct FirstPass {
+    ChunkPlan pl;  // (the piece's own plan, where it has one)
+    Buf<u64> t_lo;  // the words KRN-1 wrote ...
+    Buf<u8> t_hi;
+    Buf<u32> counts, colpre, scratch, adj, coltot;  // ... their count matrix [tile][256], its column prefixes, what the scatter adds, the bin totals
+    u64 n = 0;
+    u32 ntiles = 0;
+};
+inline void first_pass_prefixes(cblx_ctx* c, FirstPass& wk) {
+    StageTimer t(c, ST_SCAN);
+    colscan(c, wk.counts.get(), nullptr, wk.ntiles, wk.colpre.get(), wk.coltot.get(), wk.scratch);
+    hipLaunchKernelGGL(k_seg_adjust, dim3(1), dim3(256), 0, c->stream, wk.colpre.get(), wk.coltot.get(), (const u32*)nullptr, (const u32*)nullptr,
+                       (const u32*)nullptr, wk.ntiles, 1u, wk.adj.get());
+}
+// count: the N words of (a slice `sl` of) the plan into wk.t_lo / wk.t_hi, binned by `eh` (its `counts` is set here); N > 0
+template <typename C> void first_pass_count(cblx_ctx* c, FirstPass& wk, const BaseView& bases, const ChunkPlan& pl, u64 N, EncHist eh, const PlanSlice* sl = nullptr) {
+    typedef typename C::HiT HiT;
+    const size_t hs = hi_elem_size(c->P);
+    wk.n = N;
+    wk.ntiles = (u32)ceil_div(N, RDX_TILE);
+    wk.coltot = Buf<u32>(c->pool, 256); wk.adj = Buf<u32>(c->pool, 256);
+    wk.t_lo = Buf<u64>(c->pool, N + 2); wk.t_hi = Buf<u8>(c->pool, hs ? (N + 2) * hs : 8);
+    wk.counts = Buf<u32>(c->pool, (size_t)256 * (wk.ntiles + 2)); wk.colpre = Buf<u32>(c->pool, (size_t)256 * wk.ntiles);
+    CBLX_HIP(hipMemsetAsync(wk.counts.get(), 0, (size_t)256 * (wk.ntiles + 2) * 4, c->stream));
+    eh.counts = wk.counts.get();
+    encode<C>(c, bases, pl, wk.t_lo.get(), (HiT*)wk.t_hi.get(), 0, eh, sl);
+    first_pass_prefixes(c, wk);
+    CBLX_HIP(hipGetLastError());
+}
+// scatter of `lo` / `hi` (wk.n records: the words of first_pass_count, or a caller's) by `fn`. REDIR: positions [ow.a, ow.b) of the output
+// order go to the own window's arrays, the rest closes up in out_* (null: dropped). `tally`: the records count as a pass of a build.
+template <typename HiT, typename OutH, typename Fn, bool REDIR = false>
+void first_pass_scatter(cblx_ctx* c, const FirstPass& wk, const u64* lo, const HiT* hi, const Fn& fn, u64* out_lo, OutH* out_hi, bool tally = false,
+                        DigitBits nextd = DigitBits{0, 0}, u8* out_next = nullptr, OwnWindow ow = OwnWindow{0, 0, nullptr, nullptr, nullptr}) {
+    const TileView tv{nullptr, nullptr, nullptr, nullptr, wk.ntiles, wk.n};
+    StageTimer t(c, ST_SCATTER);
+    if (tally) c->stages[ST_SCATTER].units += wk.n;
+    hipLaunchKernelGGL((k_radix_scatter<HiT, OutH, Fn, REDIR>), dim3(xcd_grid(wk.ntiles)), dim3(RDX_THREADS), 0, c->stream, lo, hi, tv, fn, (const u32*)wk.colpre.get(),
+                       (const u32*)wk.adj.get(), out_lo, out_hi, nextd, out_next, (u32*)nullptr, 0u, 0u, 0u, (u32*)nullptr, 0u, ow);
+    CBLX_HIP(hipGetLastError());
+}
+
 void check_aligned16(const void* p, const char* what) {
     if (((uintptr_t)p) & 15) throw Error(CBLX_EINVAL, std::string(what) + " must be 16-byte aligned");
 }
@@ -1136,8 +1193,7 @@ void insert_device(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64 nse
     const size_t h_first = rg.add(d_offsets), h_last = rg.add(d_offsets + nseq);
     rg.wait();
     const u64 first = rg.get<u64>(h_first), last = rg.get<u64>(h_last);
-    if (last < first) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
-    if (last - first <= cap) {
+    if (offsets_span(first, last) <= cap) {
         const u64 ends[2] = {first, last};
         insert_device_one(c, d_bases, d_offsets, nseq, ends);
         return;

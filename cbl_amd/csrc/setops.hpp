@@ -596,8 +596,7 @@ void remove_device(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64 nse
     check_aligned16(d_bases, "d_bases");
     const u64 cap = batch_max_bases();
     const u64 first = d2h<u64>(c, d_offsets), last = d2h<u64>(c, d_offsets + nseq);
-    if (last < first) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
-    if (last - first <= cap) {
+    if (offsets_span(first, last) <= cap) {
         const u64 ends[2] = {first, last};
         remove_device_one(c, d_bases, d_offsets, nseq, ends);
         return;

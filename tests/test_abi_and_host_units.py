@@ -138,6 +138,17 @@ def test_cut_plan_host_unit(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+def test_wire_layout_host_unit(tmp_path):
+    """Layout arithmetic of the "bins" protocols (cbl_amd/csrc/wire_layout.hpp: bin totals -> per-destination header, own share, send
+    ranges, the cells and piece tables of a rank's groups) against a record-by-record assignment of words to (destination, group,
+    segment), under AddressSanitizer + UBSan; plans from make_bin_map, make_cut_plan and make_fine_plan."""
+    exe = tmp_path / "wire_layout_unit"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", str(exe),
+                    str(ROOT / "tests" / "host" / "wire_layout_unit.cpp")], check=True, capture_output=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
 @pytest.mark.parametrize("k,pb,nreads,L", [(31, 24, 3000, 150), (9, 4, 1500, 100), (59, 28, 400, 250), (15, 6, 1500, 150), (11, 8, 40, 3000)])
 def test_index_shard_cuts_speculative_equals_sequential(k, pb, nreads, L, tmp_path):
     """Host-only half of cblx_load_shard_from_file: the speculative search for the entry starts of `world` prefix ranges

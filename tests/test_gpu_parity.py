@@ -1357,7 +1357,7 @@ def test_parallel_fastx_reader(tmp_path, planes):
     """Large plain FASTA / FASTQ files are read by several threads (regions cut at record starts, two passes). With the
     thresholds lowered (child process) small files take that path: many regions, several flush windows; irregular input
     falls back to the sequential reader and fails exactly as it does. planes = 1: the parser threads pack the lines into bit
-    planes and the insert runs behind them (comm.hpp fastx_parallel_planes); 0: ASCII through the transfer lanes."""
+    planes and the insert runs behind them (host_input.hpp fastx_parallel_planes); 0: ASCII through the transfer lanes."""
     _need_gpu()
     import subprocess
     import sys
@@ -2311,6 +2311,74 @@ def test_native_sharded_insert_on_one_gpu_through_callbacks(world, k, pb, canoni
         oq.insert_seq(r)
     assert fblob[0] == (len(recs), of.serialize()) and fblob[1] == (len(recs), of.serialize())
     assert fblob[2] == (len(qrecs), oq.serialize())
+
+
+def _log_growth_worker(rank, world, port, groups, q, threaded=False):
+    from cbl_amd import sharded
+
+    torch.cuda.set_device(0)
+    dist = rank_threads.group(rank, world, port, threaded)
+    try:
+        comm = cbl_amd.Comm.over_group(dist, rank, world, 0)
+        comm.set_recv_groups(groups)
+        g = cbl_amd.CBL(31, 24, device=0)
+        sb = sharded.ShardedBuilder(g, dist, slices=3, comm=comm, protocol="bins")
+        sb.bounds = np.array([1], dtype=np.uint32)  # rank 1 owns every prefix but 0: practically every word of the job
+        d_b, d_o = synth.reads_torch(23, _GROWTH_READS, 150, first_read=rank * _GROWTH_READS, device="cuda:0")
+        sb.insert_seqs_device(d_b, d_o, _GROWTH_READS)
+        blob = sharded.gather_serialized(g.serialize(), dist)
+        if rank == 0:
+            q.put((blob, g.count(), comm.groups_used()))
+        comm.close()
+    finally:
+        rank_threads.release(dist)
+
+
+_GROWTH_READS = 16000
+_growth_oracle_blob = []
+
+
+def _growth_oracle():
+    """The one-process index of the growth job in its stream order (slice-major, rank-minor), computed once for both cases."""
+    if not _growth_oracle_blob:
+        from cbl_amd.sharded import ShardedBuilder
+
+        one = Oracle(31, 24, False)
+        for a, b in ShardedBuilder.slice_bounds(_GROWTH_READS, 3):
+            for r in range(2):
+                hb, ho = synth.reads(23, b - a, 150, first_read=r * _GROWTH_READS + a)
+                one.insert_seqs(hb, ho)
+        _growth_oracle_blob.append((one.serialize(), one.count()))
+    return _growth_oracle_blob[0]
+
+
+@pytest.mark.parametrize("groups", [1, 0])
+def test_native_sharded_insert_grows_the_receive_log(groups):
+    """The receive log of a rank outgrows its first capacity while it already holds earlier slices: two ranks (threads of one child,
+    host callbacks) with the bounds preset to [1], so rank 1 receives the whole job — 2 x 16,000 reads of 150 bases = 3,840,000 words at
+    K = 31 — in slices of 4,000 / 8,000 / 4,000 reads per rank against a capacity of min(job, job/2 + job/8 + 2^20) = 3,448,576 records.
+    groups = 1: the plain receiver; groups = 0: the grouped one (the first group's early shares are in the log when it grows).
+    Byte-identical to the one-process oracle in the job's stream order.
+    Seen with CBLX_TRACE_SHARDED=1 on rank 1 at the last slice, in both cases: incoming=959999 filled=2879999 (cap=3448576): the log
+    grows to hold 3,839,998 records."""
+    _need_gpu()
+    import socket
+
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    ctx = _spawn_context()
+    q = ctx.Queue()
+    p = ctx.Process(target=rank_threads._host, args=(_log_growth_worker, [(r, 2, port, groups, q) for r in range(2)]))
+    p.start()
+    blob, count0, used = q.get(timeout=300)
+    p.join(timeout=120)
+    assert p.exitcode == 0
+    want, total = _growth_oracle()
+    assert blob == want
+    assert count0 < total // 100  # rank 0 kept prefix 0 alone: the log that grew is rank 1's
+    assert used == 0 if groups == 1 else used <= 4
 
 
 @pytest.mark.parametrize("world,k,pb,canonical,protocol,all_n_rank,fastx", [
