@@ -135,6 +135,8 @@ SIGNATURES = {
     "cblx_set_op": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "cblx_set_op_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "cblx_set_op_many": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]),
+    "cblx_intersection_count": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_intersection_counts": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_uint64)]),
     "cblx_get_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "cblx_stage_units": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]),
     "cblx_export_buckets": (C.c_int, [C.c_void_p, BUCKET_CB, C.c_void_p]),
@@ -1034,6 +1036,61 @@ class CBL:
         """The k-mers all of up to 64 indexes hold, as the reference's `CBL::intersect`: only prefixes every index holds are visited; there every Vec
         bucket ends up sorted and the result is an ascending Vec, dropped when empty."""
         return CBL._set_op_many(cbls, "and", out)
+
+    # ---- comparing two sets: |a AND b| without building an index and without touching the operands (DESIGN.md section 6g) -------
+    COMMON_ROUTES = ("wave", "workgroup", "merge_path", "sliced")  # cblx_intersection_count's stats[1 .. 4]
+
+    def intersection_count(self, other: "CBL", stats: bool = False):
+        """The number of k-mers `self` and `other` both hold. Nothing is built and nothing is sorted: unlike `&`, both operands serialize to the same
+        bytes before and after. With `stats`: (count, {"both": prefixes both hold, "wave" | "workgroup" | "merge_path" | "sliced": buckets by route})."""
+        n = C.c_uint64(0)
+        st = (C.c_uint64 * 5)()
+        self._chk(self._L.cblx_intersection_count(self._h, other._h, C.byref(n), st if stats else None))
+        if not stats:
+            return n.value
+        return n.value, dict(zip(("both",) + CBL.COMMON_ROUTES, (int(v) for v in st)))
+
+    @staticmethod
+    def similarity(na: int, nb: int, common: int) -> dict:
+        """Everything the three sizes |A|, |B|, |A AND B| say about two sets (host only, pure): the sizes of union, differences and symmetric
+        difference, Jaccard (1.0 for two empty sets) and the two containments (1.0 for an empty contained set)."""
+        na, nb, common = int(na), int(nb), int(common)
+        if common < 0 or common > min(na, nb):
+            raise ValueError("similarity: 0 <= common <= min(na, nb)")
+        union = na + nb - common
+        return {"common": common, "union": union, "only_a": na - common, "only_b": nb - common, "sym_diff": na + nb - 2 * common,
+                "jaccard": common / union if union else 1.0, "containment_a_in_b": common / na if na else 1.0,
+                "containment_b_in_a": common / nb if nb else 1.0}
+
+    @staticmethod
+    def set_op_count(a: "CBL", b: "CBL", op: str) -> int:
+        """The size `a OP b` would have (op: "or" | "and" | "sub" | "xor"), from the two counts and the intersection: no index is built."""
+        if op not in SETOPS:
+            raise ValueError("set_op_count: op must be one of %s" % ", ".join(repr(o) for o in SETOPS))
+        s = CBL.similarity(a.count(), b.count(), a.intersection_count(b))
+        return s[{"or": "union", "and": "common", "sub": "only_a", "xor": "sym_diff"}[op]]
+
+    def jaccard(self, other: "CBL") -> float:
+        return CBL.similarity(self.count(), other.count(), self.intersection_count(other))["jaccard"]
+
+    def containment(self, other: "CBL") -> float:
+        """The fraction of self's k-mers that `other` holds (1.0 for an empty self)."""
+        return CBL.similarity(self.count(), other.count(), self.intersection_count(other))["containment_a_in_b"]
+
+    @staticmethod
+    def intersection_matrix(cbls):
+        """numpy uint64 (n, n): entry [i, j] = the k-mers indexes i and j share, the diagonal their counts; 1 to 64 different indexes."""
+        import numpy as np
+
+        cbls = list(cbls)
+        n = len(cbls)
+        out = np.zeros((n, n), dtype=np.uint64)
+        srcs = (C.c_void_p * max(n, 1))(*[c._h for c in cbls])
+        L = cbls[0]._L if cbls else lib()
+        rc = L.cblx_intersection_counts(srcs, n, out.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if rc != 0:
+            raise CblxError(rc, (L.cblx_last_error(cbls[0]._h) if cbls else L.cblx_last_global_error()).decode())
+        return out
 
     def device(self) -> int:
         """The HIP device ordinal the index lives on (`device=-1` resolved when it was created)."""

@@ -1,6 +1,7 @@
 """`python -m cbl_amd <command>` — the build / insert / remove / merge / inter / diff / sym-diff / count / query / list / repartition subcommands of the
 reference CLI (/root/reference/examples/cbl.rs:147-167,230-269,270-309,168-229,310-366) on the MI355X path, and merge-all / inter-all: the library's `CBL::merge` and
-`CBL::intersect` (src/cbl.rs:106-124) over two or more index files, which the reference's CLI does not expose.
+`CBL::intersect` (src/cbl.rs:106-124) over two or more index files, which the reference's CLI does not expose; `compare` prints the shared k-mers, Jaccard and
+containment of every pair of two or more index files.
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
 here they are flags with the same defaults (K=25, PREFIX_BITS=24). Index files are interchangeable with the reference's.
@@ -60,6 +61,22 @@ def repartition_report(prefix_bits, prefix, length, nodes):
     return lines, f"{load} {total_buckets} {total_items} {max_prefix} {max_size} {vec_count} {vec_nodes} {trie_count} {trie_nodes} {total}"
 
 
+def compare_report(counts):
+    """What `cbl compare` prints, from the (n, n) matrix of CBL.intersection_matrix (diagonal: the counts). Per unordered pair i < j one stdout line
+    `i j count_i count_j common union jaccard containment_i_in_j containment_j_in_i`, tab-separated, the three ratios with six decimals, and one
+    sentence for stderr. Host only."""
+    n = len(counts)
+    lines, human = [], []
+    for i in range(n):
+        for j in range(i + 1, n):
+            ci, cj = int(counts[i][i]), int(counts[j][j])
+            s = CBL.similarity(ci, cj, int(counts[i][j]))
+            lines.append("\t".join([str(i), str(j), str(ci), str(cj), str(s["common"]), str(s["union"]), f"{s['jaccard']:.6f}",
+                                    f"{s['containment_a_in_b']:.6f}", f"{s['containment_b_in_a']:.6f}"]))
+            human.append(f"Indexes {i} and {j} share {s['common']} of {ci} and {cj} k-mers (Jaccard {s['jaccard']:.6f})")
+    return lines, human
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cbl_amd")
     ap.add_argument("-k", type=int, default=25, help="k-mer size (odd, <= 59); the reference bakes it in at build time")
@@ -91,6 +108,9 @@ def main(argv=None):
         s = sub.add_parser(name, help=f"Compute the {what} of two or more indexes")
         s.add_argument("indexes", nargs="+", metavar="index")
         s.add_argument("-o", "--output")
+    cmp_ = sub.add_parser("compare", help="Compare two or more indexes pairwise: shared k-mers, union, Jaccard, containment. Every file is loaded first, so "
+                                           "all of them sit in device memory at once; no index is built or changed")
+    cmp_.add_argument("indexes", nargs="+", metavar="index")
     c = sub.add_parser("count", help="Count the k-mers contained in an index")
     c.add_argument("index")
     q = sub.add_parser("query", help="Query an index for every k-mer contained in a FASTA/Q file")
@@ -151,6 +171,13 @@ def main(argv=None):
         if a.output:
             print(f"Writing the index to {a.output}", file=sys.stderr)
             cbl.save_to_file(a.output)
+    elif a.cmd == "compare":
+        if len(a.indexes) < 2:
+            ap.error("compare takes two or more index files")
+        cbls = [CBL.load_from_file(path, a.k, a.prefix_bits, device=a.device) for path in a.indexes]
+        lines, human = compare_report(CBL.intersection_matrix(cbls))
+        print("\n".join(human), file=sys.stderr)
+        print("\n".join(lines))
     elif a.cmd == "count":
         cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
         print(f"It contains {cbl.count()} {a.k}-mers", file=sys.stderr)

@@ -1086,6 +1086,42 @@ int cblx_set_op_many(cblx_ctx* dst, cblx_ctx* const* srcs, uint32_t n, uint32_t 
         CBLX_HIP(hipStreamSynchronize(dst->stream));
     });
 }
+int cblx_intersection_count(cblx_ctx* a, cblx_ctx* b, uint64_t* common, uint64_t* stats) {
+    return guard(a, [&] {
+        if (!a || !b || !common) throw Error(CBLX_EINVAL, "null argument");
+        if (a->P.K != b->P.K || a->P.PB != b->P.PB) throw Error(CBLX_EINVAL, "intersection_count: K / PREFIX_BITS mismatch");
+        if (a->P.canonical != b->P.canonical) throw Error(CBLX_EINVAL, "One of the index is canonical while the other isn't");
+        if (a->device != b->device) throw Error(CBLX_EINVAL, "intersection_count: a and b must live on the same device");
+        for (cblx_ctx* x : {a, b}) {  // an observer: pending inserts are part of the sets
+            flush(x);
+            CBLX_HIP(hipStreamSynchronize(x->stream));
+        }
+        *common = intersection_count_ctx(a, b, stats);
+    });
+}
+int cblx_intersection_counts(cblx_ctx* const* srcs, uint32_t n, uint64_t* out) {
+    return guard(srcs && n ? srcs[0] : nullptr, [&] {
+        if (!srcs || !out) throw Error(CBLX_EINVAL, "null argument");
+        if (n == 0 || n > CBLX_SETOP_MAX_OPERANDS) throw Error(CBLX_EINVAL, "intersection_counts: 1 to " + std::to_string(CBLX_SETOP_MAX_OPERANDS) + " operands, not " + std::to_string(n));
+        for (uint32_t i = 0; i < n; ++i) {
+            cblx_ctx* x = srcs[i];
+            if (!x) throw Error(CBLX_EINVAL, "null argument");
+            for (uint32_t j = 0; j < i; ++j)
+                if (srcs[j] == x) throw Error(CBLX_EINVAL, "intersection_counts: the operands must be different contexts");
+            if (srcs[0]->P.K != x->P.K || srcs[0]->P.PB != x->P.PB) throw Error(CBLX_EINVAL, "intersection_counts: K / PREFIX_BITS mismatch");
+            if (x->P.canonical != srcs[0]->P.canonical) throw Error(CBLX_EINVAL, "One of the index is canonical while the other isn't");
+            if (srcs[0]->device != x->device) throw Error(CBLX_EINVAL, "intersection_counts: the operands must live on the same device");
+        }
+        for (uint32_t i = 0; i < n; ++i) {  // an observer: pending inserts are part of the sets
+            flush(srcs[i]);
+            CBLX_HIP(hipStreamSynchronize(srcs[i]->stream));
+        }
+        for (uint32_t i = 0; i < n; ++i) {
+            out[(size_t)i * n + i] = srcs[i]->res.count;
+            for (uint32_t j = i + 1; j < n; ++j) out[(size_t)i * n + j] = out[(size_t)j * n + i] = intersection_count_ctx(srcs[i], srcs[j], nullptr);
+        }
+    });
+}
 int cblx_set_op_assign(cblx_ctx* a, cblx_ctx* b, uint32_t op) {
     const int rc = guard(a, [&] {
         if (!a || !b) throw Error(CBLX_EINVAL, "null argument");

@@ -1,8 +1,9 @@
 // kernels_setops.hpp — set algebra between resident indexes, bucket by bucket: `self |= other` of two Tries (k_bucket_union), `a OP b` into a new index
 // (k_setop_plan, k_setop_gather, k_bucket_setop), CBL::merge / CBL::intersect of n operands (k_many_*, k_bucket_setop_many) and the assigning forms
 // `a &= b`, `a -= b`, `a ^= b` (k_bucket_setop_assign). The directory kernels they share with the build (k_setop_bv, k_merge_table, k_merge_gather,
-// k_classify_merge) are in kernels_bucket.hpp; the host side is setops.hpp.
+// k_classify_merge) are in kernels_bucket.hpp; the host side is setops.hpp. At the end: |a AND b| without a result index (k_common_*).
 #pragma once
+#include "common_route.hpp"
 #include "kernels_bucket.hpp"
 
 namespace cblx {
@@ -857,6 +858,249 @@ __global__ __launch_bounds__(SA_THREADS) void k_bucket_setop_assign(const BDesc*
         if constexpr (WS) dsth[i] = e.hi;
     }
     if (tid == 0) { out_count[r] = L; out_kind[r] = KIND_VEC; }
+}
+
+// ---- |a AND b| alone (cblx_intersection_count): one u32 per bucket both hold, nothing else is written and nothing is sorted ----
+// To intersect two duplicate-free lists neither has to be ascending: the shorter (STAGED) side goes into LDS as stored, masked to the suffix, under an
+// open-addressing table of u32 entries — index + 1, 0 = empty, twice as many slots as the side may have words, filled by atomicCAS on a mixed hash of the
+// suffix with linear probing — and every word of the other (PROBE) side is looked up: the hits are the intersection. The table holds INDICES, so no suffix
+// value is set apart as "empty": SUFFIX_BITS = 64 has no spare bit and the all-ones suffix is legal. No kind is consulted; common_route (common_route.hpp)
+// picks the kernel by the two lengths, and by the kinds only where two Tries longer than a table can be merged instead.
+// The lists of a route are walked by a grid-stride loop over *list_n, so the host launches all four kernels before it has read a single list length.
+static const u32 COMMON_WAVE_CAP = COMMON_SMALL / 2;  // the staged side of a bucket of the wave route
+static const int COMMON_THREADS = 256;
+// murmur3's 64-bit finaliser over lo ^ hi * phi: consecutive suffixes, multiples of a power of two and values that differ in their top bits alone all spread
+__device__ __forceinline__ u32 common_hash(u64 lo, u64 hi) {
+    u64 x = lo ^ (hi * 0x9E3779B97F4A7C15ull);
+    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
+    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
+    x ^= x >> 33;
+    return (u32)x;
+}
+// The staged words and their table; the LDS arrays belong to the kernel (CAP words, CAP high halves when wide, 2 * CAP entries).
+template <bool WS, u32 CAP> struct CommonTable {
+    static_assert((CAP & (CAP - 1)) == 0, "the table indexes by hash mod 2 CAP");
+    static constexpr u32 SLOTS = 2 * CAP, M = SLOTS - 1;
+    u64 *s_lo, *s_hi;
+    u32* s_tab;
+    // n <= CAP words from (lo, hi), by all THREADS threads of the workgroup; the table can be probed when it returns. The caller synchronises
+    // before it fills again.
+    template <int THREADS> __device__ __forceinline__ void fill(const u64* __restrict__ lo, const u64* __restrict__ hi, u32 n, u64 mask) const {
+        for (u32 i = threadIdx.x; i < SLOTS; i += THREADS) s_tab[i] = 0u;
+        for (u32 i = threadIdx.x; i < n; i += THREADS) {
+            if constexpr (WS) { s_lo[i] = lo[i]; s_hi[i] = hi[i] & mask; }
+            else s_lo[i] = lo[i] & mask;
+        }
+        __syncthreads();
+        for (u32 i = threadIdx.x; i < n; i += THREADS) {
+            u32 h = common_hash(s_lo[i], WS ? s_hi[i] : 0ull) & M;
+            while (atomicCAS(&s_tab[h], 0u, i + 1u) != 0u) h = (h + 1u) & M;  // (n <= CAP < SLOTS: a free slot exists)
+        }
+        __syncthreads();
+    }
+    // is the masked suffix (lo, hi) one of the staged words? (an empty slot ends every probe sequence: the table is never more than half full)
+    __device__ __forceinline__ bool holds(u64 lo, u64 hi) const {
+        u32 h = common_hash(lo, WS ? hi : 0ull) & M;
+        for (;;) {
+            const u32 e = s_tab[h];
+            if (e == 0u) return false;
+            if (s_lo[e - 1u] == lo && (!WS || s_hi[e - 1u] == hi)) return true;
+            h = (h + 1u) & M;
+        }
+    }
+};
+// one thread per candidate (every candidate of a.bv & b.bv is held by both): b's count, and the bucket joins the list of its route
+__global__ __launch_bounds__(CLASSIFY_THREADS) void k_common_plan(u64 nb, const u32* __restrict__ raw_cnt, const u32* __restrict__ m_cs, u32* __restrict__ m_co,
+                                                                   const u8* __restrict__ m_skind, const u8* __restrict__ m_okind,
+                                                                   BDesc* __restrict__ lists /* [COMMON_ROUTES][nb] */, u32* __restrict__ list_n) {
+    const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    int cls = -1;
+    if (r < nb) {
+        const u32 cs = m_cs[r], co = raw_cnt[r] - cs;
+        m_co[r] = co;
+        if (cs != 0 && co != 0) cls = common_route(cs, co, m_skind[r] == KIND_TRIE, m_okind[r] == KIND_TRIE);
+    }
+    const u32 slot = block_append<CLASSIFY_THREADS, COMMON_ROUTES>(cls, list_n);
+    if (cls >= 0) lists[(u64)cls * nb + slot] = BDesc{0, 0, (u32)r};
+}
+// what the four kernels are given: the route's list, the tables of k_merge_table / k_common_plan, the two arenas, the counters
+struct CommonArgs {
+    const BDesc* list; const u32* list_n;
+    const u32 *cs, *co;
+    const u64 *sstart, *ostart;
+    const u64 *a_lo, *a_hi, *b_lo, *b_hi;
+    u32 SB;
+    u32* common;
+};
+// the sum of a workgroup's per-thread counts, valid in thread 0; `s_w`: one word per wave, the caller synchronises before it is used again
+template <int NW> __device__ __forceinline__ u32 common_block_sum(u32 v, u32* s_w) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u32 tot = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) tot += s_w[w];
+    return tot;
+}
+// Route 1, ca + cb <= COMMON_SMALL: one wave per bucket (a workgroup IS one wave, so its barriers are wave-level: no other wave waits at them). The
+// staged side is at most 128 words; the probe side is read 64 words per step, coalesced, the hits counted by ballot.
+template <bool WS>
+__global__ __launch_bounds__(64) void k_common_wave(const CommonArgs g) {
+    __shared__ u64 s_lo[COMMON_WAVE_CAP];
+    __shared__ u64 s_hi[WS ? COMMON_WAVE_CAP : 1];
+    __shared__ u32 s_tab[2 * COMMON_WAVE_CAP];
+    const CommonTable<WS, COMMON_WAVE_CAP> t{s_lo, s_hi, s_tab};
+    const u64 mask = suffix_mask<WS>(g.SB);
+    const u32 lane = threadIdx.x, n = *g.list_n;
+    for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
+        const u32 r = g.list[i].r, ca = g.cs[r], cb = g.co[r];
+        const bool sa = common_stage_a(ca, cb);
+        const u64 s0 = sa ? g.sstart[r] : g.ostart[r], p0 = sa ? g.ostart[r] : g.sstart[r];
+        const u64* __restrict__ S = (sa ? g.a_lo : g.b_lo) + s0;
+        const u64* __restrict__ Sh = WS ? (sa ? g.a_hi : g.b_hi) + s0 : nullptr;
+        const u64* __restrict__ Q = (sa ? g.b_lo : g.a_lo) + p0;
+        const u64* __restrict__ Qh = WS ? (sa ? g.b_hi : g.a_hi) + p0 : nullptr;
+        const u32 ns0 = sa ? ca : cb, ns = ns0 < COMMON_WAVE_CAP ? ns0 : COMMON_WAVE_CAP, np = sa ? cb : ca;  // (the route says ns0 <= the table's capacity)
+        t.template fill<64>(S, Sh, ns, mask);
+        u32 hits = 0;
+        for (u32 j0 = 0; j0 < np; j0 += 64) {
+            const u32 j = j0 + lane;
+            bool hit = false;
+            if (j < np) hit = WS ? t.holds(Q[j], Qh[j] & mask) : t.holds(Q[j] & mask, 0ull);
+            hits += (u32)__builtin_popcountll(__ballot(hit));
+        }
+        if (lane == 0) g.common[r] = hits;
+        __syncthreads();  // the table is rewritten
+    }
+}
+// Routes 2 and 4: 256 threads per bucket. The staged side goes through the table in slices of COMMON_LDS words — ONE slice on route 2, whose staged side is
+// that short — and the probe side, of any length, is streamed from HBM once per slice, two words per 16-byte load where the run starts on a 16-byte
+// boundary (one word in front of the pairs where it does not). LDS: 16 KB, 24 KB wide.
+template <bool WS, bool SLICED>
+__device__ __forceinline__ void common_lds_run(const CommonArgs& g) {
+    constexpr int NW = COMMON_THREADS / 64;
+    __shared__ u64 s_lo[COMMON_LDS];
+    __shared__ u64 s_hi[WS ? COMMON_LDS : 1];
+    __shared__ u32 s_tab[2 * COMMON_LDS];
+    __shared__ u32 s_w[NW];
+    const CommonTable<WS, COMMON_LDS> t{s_lo, s_hi, s_tab};
+    const u64 mask = suffix_mask<WS>(g.SB);
+    const u32 tid = threadIdx.x, n = *g.list_n;
+    for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
+        const u32 r = g.list[i].r, ca = g.cs[r], cb = g.co[r];
+        const bool sa = common_stage_a(ca, cb);
+        const u64 s0 = sa ? g.sstart[r] : g.ostart[r], p0 = sa ? g.ostart[r] : g.sstart[r];
+        const u64* __restrict__ S = (sa ? g.a_lo : g.b_lo) + s0;
+        const u64* __restrict__ Sh = WS ? (sa ? g.a_hi : g.b_hi) + s0 : nullptr;
+        const u64* __restrict__ Q = (sa ? g.b_lo : g.a_lo) + p0;
+        const u64* __restrict__ Qh = WS ? (sa ? g.b_hi : g.a_hi) + p0 : nullptr;
+        const u32 ns0 = sa ? ca : cb, ns = SLICED || ns0 < COMMON_LDS ? ns0 : COMMON_LDS, np = sa ? cb : ca;  // (route 2 says ns0 <= COMMON_LDS)
+        // the probe run as [head words one by one][pairs][tail words one by one]
+        const bool odd = ((uintptr_t)Q & 8u) != 0;
+        const bool paired = !WS || (((uintptr_t)Qh & 8u) != 0) == odd;  // (both halves start on the same side of a 16-byte boundary: always, with the pool's arenas)
+        const u32 head = !paired ? np : (odd && np ? 1u : 0u), npair = (np - head) >> 1, tail = head + 2u * npair;
+        const ulonglong2* __restrict__ Q2 = (const ulonglong2*)(Q + head);
+        const ulonglong2* __restrict__ Q2h = WS ? (const ulonglong2*)(Qh + head) : nullptr;
+        auto one = [&](u32 j) { return (WS ? t.holds(Q[j], Qh[j] & mask) : t.holds(Q[j] & mask, 0ull)) ? 1u : 0u; };
+        u32 hits = 0;
+        for (u32 sl = 0; sl < ns; sl += COMMON_LDS) {
+            const u32 n1 = ns - sl < COMMON_LDS ? ns - sl : COMMON_LDS;
+            t.template fill<COMMON_THREADS>(S + sl, WS ? Sh + sl : nullptr, n1, mask);
+            for (u32 j = tid; j < head; j += COMMON_THREADS) hits += one(j);
+            for (u32 q = tid; q < npair; q += COMMON_THREADS) {
+                const ulonglong2 v = Q2[q];
+                if constexpr (WS) {
+                    const ulonglong2 vh = Q2h[q];
+                    hits += (t.holds(v.x, vh.x & mask) ? 1u : 0u) + (t.holds(v.y, vh.y & mask) ? 1u : 0u);
+                } else hits += (t.holds(v.x & mask, 0ull) ? 1u : 0u) + (t.holds(v.y & mask, 0ull) ? 1u : 0u);
+            }
+            for (u32 j = tail + tid; j < np; j += COMMON_THREADS) hits += one(j);
+            __syncthreads();  // the table is rewritten
+        }
+        const u32 tot = common_block_sum<NW>(hits, s_w);
+        if (tid == 0) g.common[r] = tot;
+    }
+}
+template <bool WS>
+__global__ __launch_bounds__(COMMON_THREADS) void k_common_lds(const CommonArgs g) { common_lds_run<WS, false>(g); }
+// Route 4: both sides are longer than COMMON_LDS words and at least one of them is a Vec — only set operations and `|=` leave such Vecs behind. QUADRATIC BY
+// DESIGN: ceil(staged / COMMON_LDS) passes over the probe side. It is rare, it is correct at any length, and it keeps the operands unsorted; sorting the Vec
+// in its arena, which is what makes `&` linear here, is exactly what a comparison must not do.
+template <bool WS>
+__global__ __launch_bounds__(COMMON_THREADS) void k_common_sliced(const CommonArgs g) { common_lds_run<WS, true>(g); }
+// Route 3, two Tries of any length: UniRounds as k_bucket_union drives it, with AND's predicate — an output that equals its predecessor is b's copy of a word a
+// holds — counted in a register instead of compacted; nothing is written back to the rings. The outputs stay in the registers that merged them: a thread
+// compares its own four in place and gets the predecessor of its first from its neighbour through one LDS word per thread. Across a round edge only the VALUE
+// of the last output is carried (UniRounds::carry): its pair partner can only be the first output of the next round.
+template <bool WS>
+__global__ __launch_bounds__(UNI_THREADS) void k_common_merge(const CommonArgs g) {
+    typedef UniE<WS> E;
+    typedef UniRounds<WS> R;
+    constexpr int NW = R::NW;
+    __shared__ u64 s_in[R::SLOTS];
+    __shared__ u64 s_inh[WS ? R::SLOTS : 1];
+    __shared__ u32 s_split[NW + 1];
+    __shared__ u64 s_edge[UNI_THREADS + 1];  // [t]: thread t's last output; [UNI_THREADS]: the round's last output
+    __shared__ u64 s_edgeh[WS ? UNI_THREADS + 1 : 1];
+    __shared__ u32 s_w[NW];
+    const u64 mask = suffix_mask<WS>(g.SB);
+    const u32 tid = threadIdx.x, n = *g.list_n;
+    for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
+        const u32 r = g.list[i].r;
+        const u64 a0 = g.sstart[r], b0 = g.ostart[r];
+        R m{s_in, s_inh, s_split, g.a_lo + a0, g.b_lo + b0, WS ? g.a_hi + a0 : nullptr, WS ? g.b_hi + b0 : nullptr, mask, g.cs[r], g.co[r]};
+        u32 cnt = 0;
+        while (m.more()) {
+            m.stage();
+            m.split();
+            E a[UNI_ITEMS], o[UNI_ITEMS];
+            m.merge(a, o);
+            const u32 q0 = tid * UNI_ITEMS, nout = m.nout;
+            s_edge[tid] = o[UNI_ITEMS - 1].lo;
+            if constexpr (WS) s_edgeh[tid] = o[UNI_ITEMS - 1].hi;
+#pragma unroll
+            for (int k = 0; k < UNI_ITEMS; ++k)
+                if (q0 + k + 1 == nout) {
+                    s_edge[UNI_THREADS] = o[k].lo;
+                    if constexpr (WS) s_edgeh[UNI_THREADS] = o[k].hi;
+                }
+            __syncthreads();
+            E pred = m.carry, last;
+            bool have = m.have_carry;
+            if (tid) {  // (thread tid - 1's outputs all lie below nout wherever this thread's first one does)
+                pred.lo = s_edge[tid - 1];
+                if constexpr (WS) pred.hi = s_edgeh[tid - 1];
+                have = true;
+            }
+#pragma unroll
+            for (int k = 0; k < UNI_ITEMS; ++k) {
+                cnt += (q0 + k < nout && have && uni_eq<WS>(o[k], pred)) ? 1u : 0u;
+                pred = o[k];
+                have = true;
+            }
+            last.lo = s_edge[UNI_THREADS];
+            if constexpr (WS) last.hi = s_edgeh[UNI_THREADS];
+            m.advance(0, last);
+        }
+        const u32 tot = common_block_sum<NW>(cnt, s_w);
+        if (tid == 0) g.common[r] = tot;
+        __syncthreads();  // s_w and the rings are rewritten
+    }
+}
+// The sum of n counters, one u64 per workgroup (no atomics: the order of an integer sum does not matter, and the result is the same on every run). Run twice:
+// over the buckets into up to COMMON_SUM_GROUPS partial sums, then over those by one workgroup.
+static const u32 COMMON_SUM_GROUPS = 1024;
+template <typename T>
+__global__ __launch_bounds__(256) void k_common_sum(const T* __restrict__ v, u64 n, u64* __restrict__ out) {
+    __shared__ u64 s_w[4];
+    u64 s = 0;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) s += v[i];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d, 64);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
 }
 
 }  // namespace cblx

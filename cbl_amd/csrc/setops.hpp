@@ -1,5 +1,5 @@
 // setops.hpp — set algebra between resident indexes and k-mer removal, on the host: `self |= other` (merge_direct), `a OP b` into a new index and the
-// assigning forms (set_op_build), CBL::merge / CBL::intersect of n operands (set_op_many_build), WordSet::remove_batch (remove_words). They share the
+// assigning forms (set_op_build), CBL::merge / CBL::intersect of n operands (set_op_many_build), |a AND b| alone (intersection_count), WordSet::remove_batch (remove_words). They share the
 // bucket stages of pipeline.hpp and the end of a result (set_op_tail). Kernels: kernels_setops.hpp, kernels_remove.hpp. Included by cblx.cpp only.
 #pragma once
 #include "kernels_remove.hpp"
@@ -463,6 +463,69 @@ template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, 
 template <typename C> void set_op_assign_direct(cblx_ctx* c, Resident& b, u32 op) {
     Resident nr = set_op_build<C>(c, c->res, b, op, true);
     c->res = std::move(nr);
+}
+
+// ---- |a AND b| of two resident indexes on this device, and nothing else (cblx_intersection_count) ----------------------------------
+// The candidates are a.bv & b.bv with their popcount scan, as set_op_build finds AND's; k_merge_table gives both sides' (count, kind, start) per candidate,
+// k_common_plan the four route lists, the four kernels one u32 per candidate, two sum passes the total. The scratch is sized by the candidate BUCKETS, never
+// by words, and neither operand is written: no Vec is sorted, no kind changes. The total and the four list lengths come back in one read (the kernels walk
+// their lists by *list_n on the device). `c` is a's context: its stream, pool and mailbox; b's stream is idle (the caller's business).
+// stats (COMMON_ROUTES + 1 entries, or null): candidates, then the buckets of every route in common_route's order.
+template <typename C> u64 intersection_count(cblx_ctx* c, const Resident& a, const Resident& b, u64* stats) {
+    constexpr bool WS = C::WS;
+    const Consts& P = c->P;
+    const u64 nprefix = 1ull << P.PB, nwords = std::max<u64>(1, nprefix / 64);
+    StageTimer t(c, ST_COMMON);
+    Buf<u64> bv(c->pool, nwords), rank_dir(c->pool, nwords + 1);
+    Buf<u32> popc(c->pool, nwords);
+    hipLaunchKernelGGL(k_setop_bv, grid1(nwords, 256), dim3(256), 0, c->stream, nwords, a.bv.get(), b.bv.get(), SETOP_AND, bv.get(), popc.get());
+    const u64 nb = exclusive_scan<u64>(c, popc.get(), nwords, rank_dir.get());
+    if (nb == 0) { CBLX_HIP(hipStreamSynchronize(c->stream)); return 0; }  // no prefix is held by both
+    Buf<u32> prefix(c->pool, nb + 1), raw(c->pool, nb + 1), m_cs(c->pool, nb + 1), m_co(c->pool, nb + 1), common(c->pool, nb), list_n(c->pool, COMMON_ROUTES);
+    Buf<u64> m_sstart(c->pool, nb + 1), m_ostart(c->pool, nb + 1), partial(c->pool, COMMON_SUM_GROUPS), total(c->pool, 1);
+    Buf<u8> m_skind(c->pool, nb + 1), m_okind(c->pool, nb + 1);
+    Buf<BDesc> lists(c->pool, (size_t)COMMON_ROUTES * nb);
+    CBLX_HIP(hipMemsetAsync(list_n.get(), 0, COMMON_ROUTES * 4, c->stream));
+    CBLX_HIP(hipMemsetAsync(common.get(), 0, nb * 4, c->stream));
+    hipLaunchKernelGGL(k_merge_table, grid1(nprefix, 256), dim3(256), 0, c->stream, nprefix, bv.get(), rank_dir.get(), a.view(), b.view(), prefix.get(), raw.get(), m_cs.get(),
+                       m_sstart.get(), m_ostart.get(), m_skind.get(), m_okind.get());
+    hipLaunchKernelGGL(k_common_plan, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, (const u32*)raw.get(), (const u32*)m_cs.get(), m_co.get(),
+                       (const u8*)m_skind.get(), (const u8*)m_okind.get(), lists.get(), list_n.get());
+    CBLX_HIP(hipGetLastError());
+    // a grid no larger than a few residencies of the chip: a workgroup takes the buckets blockIdx.x, + gridDim.x, ... of its list
+    auto args = [&](int route) {
+        return CommonArgs{lists.get() + (size_t)route * nb, list_n.get() + route, m_cs.get(), m_co.get(), m_sstart.get(), m_ostart.get(), a.a_lo.get(), a.a_hi.get(),
+                          b.a_lo.get(), b.a_hi.get(), P.SB, common.get()};
+    };
+    auto groups = [&](u64 most) { return dim3((unsigned)std::min<u64>(nb, most)); };
+    hipLaunchKernelGGL((k_common_wave<WS>), groups(1u << 16), dim3(64), 0, c->stream, args(COMMON_WAVE));
+    hipLaunchKernelGGL((k_common_lds<WS>), groups(1u << 14), dim3(COMMON_THREADS), 0, c->stream, args(COMMON_WG));
+    hipLaunchKernelGGL((k_common_merge<WS>), groups(1u << 14), dim3(UNI_THREADS), 0, c->stream, args(COMMON_MERGE));
+    hipLaunchKernelGGL((k_common_sliced<WS>), groups(1u << 14), dim3(COMMON_THREADS), 0, c->stream, args(COMMON_SLICED));
+    CBLX_HIP(hipGetLastError());
+    const u32 ng = (u32)std::min<u64>(COMMON_SUM_GROUPS, ceil_div(nb, 256));
+    hipLaunchKernelGGL(k_common_sum<u32>, dim3(ng), dim3(256), 0, c->stream, (const u32*)common.get(), nb, partial.get());
+    hipLaunchKernelGGL(k_common_sum<u64>, dim3(1), dim3(256), 0, c->stream, (const u64*)partial.get(), (u64)ng, total.get());
+    CBLX_HIP(hipGetLastError());
+    ReadGroup rg(c);
+    const size_t h_tot = rg.add(total.get()), h_ln = rg.add(list_n.get(), COMMON_ROUTES);
+    rg.wait();  // the tables and lists of this call die here
+    if (stats) {
+        stats[0] = nb;
+        for (int k = 0; k < COMMON_ROUTES; ++k) stats[1 + k] = rg.get<u32>(h_ln, k);
+    }
+    return rg.get<u64>(h_tot);
+}
+// |a AND b| of two flushed contexts on one device; a == b and an empty operand are answered without a kernel (stats: all zero)
+u64 intersection_count_ctx(cblx_ctx* a, cblx_ctx* b, u64* stats) {
+    if (stats) for (int k = 0; k <= COMMON_ROUTES; ++k) stats[k] = 0;
+    if (a == b) return a->res.count;
+    if (a->res.count == 0 || b->res.count == 0) return 0;
+    CBLX_HIP(hipStreamSynchronize(b->stream));
+    u64 n = 0;
+    dispatch(a->P, [&](auto cfg) { n = intersection_count<decltype(cfg)>(a, a->res, b->res, stats); });
+    collect_events(a);
+    return n;
 }
 
 // ---- WordSet::remove_batch (src/wordset/mod.rs:218-237) over n device words ------------------------------------------------

@@ -31,7 +31,8 @@ extern "C" {
  * Added under 3 (a new symbol is compatible): cblx_set_op with CBLX_SETOP_OR / AND / SUB / XOR, cblx_get_device, cblx_set_op_assign, and cblx_set_op_many with
  * CBLX_SETOP_MAX_OPERANDS; cblx_remove_words_device, cblx_remove_seq, cblx_remove_seqs, cblx_remove_seqs_device, cblx_remove_fastx_file and cblx_remove_kmers;
  * cblx_export_kmers_range, cblx_export_kmers_range_device, cblx_list_range, cblx_list_range_device, cblx_list_to_fd, cblx_list_to_file and cblx_bucket_nodes;
- * cblx_contains_seqs_counts, cblx_contains_seqs_counts_device, cblx_contains_seqs_flags_counts_device and cblx_query_fastx_file_counts. */
+ * cblx_contains_seqs_counts, cblx_contains_seqs_counts_device, cblx_contains_seqs_flags_counts_device and cblx_query_fastx_file_counts;
+ * cblx_intersection_count with CBLX_COMMON_STATS, and cblx_intersection_counts. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -339,6 +340,19 @@ int cblx_set_op_assign(cblx_ctx* a, cblx_ctx* b, uint32_t op);
  * `canonical` / device differ, or op is CBLX_SETOP_SUB / XOR (the reference has no n-ary form of them). */
 #define CBLX_SETOP_MAX_OPERANDS 64
 int cblx_set_op_many(cblx_ctx* dst, cblx_ctx* const* srcs, uint32_t n, uint32_t op);
+/* *common = |a AND b|, the number of k-mers both indexes hold, without building an index and without touching the operands: unlike
+ * cblx_set_op with CBLX_SETOP_AND nothing is sorted — cblx_serialize of a and of b gives the same bytes before and after the call, kinds and stored order of the
+ * Vec buckets included. With |a| and |b| (cblx_count) this one number gives the sizes of union, difference and symmetric difference, Jaccard and containment.
+ * Pending inserts of both operands are applied first (an observer, as cblx_set_op is). a == b is allowed and gives cblx_count(a); an empty operand gives 0;
+ * neither launches a kernel. stats (CBLX_COMMON_STATS entries, or NULL) receives [0] the prefixes both hold and [1] .. [4] how many of those buckets each route
+ * took: one wave, one workgroup, merge path, sliced (all zero where no kernel ran). CBLX_EINVAL, with both contexts unchanged: a null argument, K / PREFIX_BITS
+ * differ, a and b differ in `canonical`, or the contexts live on different devices. */
+#define CBLX_COMMON_STATS 5
+int cblx_intersection_count(cblx_ctx* a, cblx_ctx* b, uint64_t* common, uint64_t* stats);
+/* The same for every pair of the n operands srcs[0 .. n): out[i * n + j] = out[j * n + i] = |S_i AND S_j| (every unordered pair computed once),
+ * out[i * n + i] = cblx_count(S_i); out holds n * n entries, row-major. Every operand's pending inserts are applied once, up front. CBLX_EINVAL, with every
+ * context unchanged: n == 0, n > CBLX_SETOP_MAX_OPERANDS, a null entry, the same context twice, or K / PREFIX_BITS / `canonical` / device differ. */
+int cblx_intersection_counts(cblx_ctx* const* srcs, uint32_t n, uint64_t* out);
 /* The HIP device ordinal the context lives on (cblx_params.device = -1 resolved at creation). */
 int cblx_get_device(const cblx_ctx* ctx, int32_t* out);
 

@@ -426,6 +426,15 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         s.check(unsafe { sys::cblx_merge_from(s.ctx, self.ctx, other.ctx) });
         s
     }
+
+    /// `(&mut a & &mut b).count()` without the result and without `iter_sorted`'s side effect (no reference counterpart as a method,
+    /// `cblx_intersection_count`): the number of k-mers both sets hold; neither set is changed, not even the order inside its Vec buckets.
+    pub fn intersection_count(&self, other: &Self) -> usize {
+        assert_eq!(self.is_canonical(), other.is_canonical(), "One of the index is canonical while the other isn't");
+        let mut n = 0u64;
+        self.check(unsafe { sys::cblx_intersection_count(self.ctx, other.ctx, &mut n, std::ptr::null_mut()) });
+        n as usize
+    }
 }
 
 impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BITS> {

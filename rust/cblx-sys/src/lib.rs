@@ -29,6 +29,7 @@ pub const CBLX_SETOP_AND: u32 = 1;
 pub const CBLX_SETOP_SUB: u32 = 2;
 pub const CBLX_SETOP_XOR: u32 = 3;
 pub const CBLX_SETOP_MAX_OPERANDS: u32 = 64;
+pub const CBLX_COMMON_STATS: u32 = 5;
 
 #[repr(C)]
 pub struct cblx_ctx {
@@ -275,6 +276,8 @@ extern "C" {
     pub fn cblx_set_op(dst: *mut cblx_ctx, a: *mut cblx_ctx, b: *mut cblx_ctx, op: u32) -> c_int;
     pub fn cblx_set_op_assign(a: *mut cblx_ctx, b: *mut cblx_ctx, op: u32) -> c_int;
     pub fn cblx_set_op_many(dst: *mut cblx_ctx, srcs: *const *mut cblx_ctx, n: u32, op: u32) -> c_int;
+    pub fn cblx_intersection_count(a: *mut cblx_ctx, b: *mut cblx_ctx, common: *mut u64, stats: *mut u64) -> c_int;
+    pub fn cblx_intersection_counts(srcs: *const *mut cblx_ctx, n: u32, out: *mut u64) -> c_int;
     pub fn cblx_get_device(ctx: *const cblx_ctx, out: *mut i32) -> c_int;
     pub fn cblx_stage_units(ctx: *mut cblx_ctx, units: *mut u64, cap: u32, n: *mut u32) -> c_int;
 
