@@ -135,6 +135,8 @@ SIGNATURES = {
     "cblx_set_op": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "cblx_set_op_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "cblx_set_op_many": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]),
+    "cblx_set_at_least": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]),
+    "cblx_occupancy_counts": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_uint64)]),
     "cblx_intersection_count": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_intersection_counts": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_uint64)]),
     "cblx_get_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
@@ -1036,6 +1038,48 @@ class CBL:
         """The k-mers all of up to 64 indexes hold, as the reference's `CBL::intersect`: only prefixes every index holds are visited; there every Vec
         bucket ends up sorted and the result is an ascending Vec, dropped when empty."""
         return CBL._set_op_many(cbls, "and", out)
+
+    # ---- between merge and intersect: held by at least t of n, and the occupancy histogram (ours; DESIGN.md section 6h) -------
+    @staticmethod
+    def _many_operands(cbls, who: str):
+        cbls = list(cbls)
+        if not cbls:
+            raise ValueError("%s: at least one index" % who)
+        if len(set(map(id, cbls))) != len(cbls):
+            raise ValueError("%s: the same index twice" % who)
+        return cbls
+
+    @staticmethod
+    def at_least(cbls, t: int, out: "CBL" = None) -> "CBL":
+        """The k-mers at least `t` of up to 64 indexes hold (1 <= t <= n) into a new index, or into `out`, whose content is replaced. t = 1 is `CBL.merge`
+        and, for n >= 2, t = n is `CBL.intersect`, byte for byte, operands included. In between: a prefix fewer than t indexes hold is not visited; on
+        the others every holder's Vec bucket ends up sorted and the result bucket is an ascending Vec, dropped when empty. Empty indexes count
+        towards n."""
+        cbls = CBL._many_operands(cbls, "at_least")
+        t = int(t)
+        if not 1 <= t <= len(cbls):
+            raise ValueError("at_least: the threshold is 1 to the number of indexes (%d), not %d" % (len(cbls), t))
+        if out is None:
+            a = cbls[0]
+            out = CBL(a.k, a.prefix_bits, canonical=a.is_canonical(), device=a.device())
+        srcs = (C.c_void_p * len(cbls))(*[c._h for c in cbls])
+        out._chk(out._L.cblx_set_at_least(out._h, srcs, len(cbls), t))
+        return out
+
+    @staticmethod
+    def occupancy(cbls):
+        """numpy uint64 [n + 1]: entry j = the distinct k-mers exactly j of the n indexes hold (entry 0 is 0). Their sum is the size of the merge,
+        entry n the size of the intersection, the sum of j * entry j the sum of the counts. No index is built, but this is NOT
+        `intersection_count`'s untouched-operands guarantee: the operands are left as `CBL.merge` leaves them — on every prefix two or more
+        indexes hold, their Vec buckets end up sorted; the sets are unchanged."""
+        import numpy as np
+
+        cbls = CBL._many_operands(cbls, "occupancy")
+        n = len(cbls)
+        hist = np.zeros(n + 1, dtype=np.uint64)
+        srcs = (C.c_void_p * n)(*[c._h for c in cbls])
+        cbls[0]._chk(cbls[0]._L.cblx_occupancy_counts(srcs, n, hist.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return hist
 
     # ---- comparing two sets: |a AND b| without building an index and without touching the operands (DESIGN.md section 6g) -------
     COMMON_ROUTES = ("wave", "workgroup", "merge_path", "sliced")  # cblx_intersection_count's stats[1 .. 4]

@@ -77,6 +77,18 @@ def compare_report(counts):
     return lines, human
 
 
+def occupancy_report(hist):
+    """What `cbl occupancy` prints, from CBL.occupancy's hist[0 .. n]: one stdout line `j<TAB>count` for j = 1 .. n — the distinct k-mers exactly j of
+    the n indexes hold — and sentences for stderr: the size of the union, of the core (held by all) and of the cloud (held by one). Host only."""
+    hist = [int(v) for v in hist]
+    n = len(hist) - 1
+    if n < 1 or hist[0] != 0:
+        raise ValueError("occupancy_report: hist[0 .. n] of n >= 1 indexes, hist[0] = 0")
+    lines = [f"{j}\t{hist[j]}" for j in range(1, n + 1)]
+    human = [f"The {n} indexes hold {sum(hist)} distinct k-mers", f"{hist[n]} are held by all of them, {hist[1]} by exactly one"]
+    return lines, human
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cbl_amd")
     ap.add_argument("-k", type=int, default=25, help="k-mer size (odd, <= 59); the reference bakes it in at build time")
@@ -108,6 +120,13 @@ def main(argv=None):
         s = sub.add_parser(name, help=f"Compute the {what} of two or more indexes")
         s.add_argument("indexes", nargs="+", metavar="index")
         s.add_argument("-o", "--output")
+    al = sub.add_parser("at-least", help="Compute the k-mers held by at least T of two or more indexes")
+    al.add_argument("-t", "--threshold", type=int, required=True, metavar="T")
+    al.add_argument("indexes", nargs="+", metavar="index")
+    al.add_argument("-o", "--output")
+    oc = sub.add_parser("occupancy", help="Count the distinct k-mers held by exactly j of two or more indexes, j = 1 .. n. No index is built; Vec buckets on "
+                                          "prefixes several indexes hold are sorted in memory, as a merge does")
+    oc.add_argument("indexes", nargs="+", metavar="index")
     cmp_ = sub.add_parser("compare", help="Compare two or more indexes pairwise: shared k-mers, union, Jaccard, containment. Every file is loaded first, so "
                                            "all of them sit in device memory at once; no index is built or changed")
     cmp_.add_argument("indexes", nargs="+", metavar="index")
@@ -171,6 +190,24 @@ def main(argv=None):
         if a.output:
             print(f"Writing the index to {a.output}", file=sys.stderr)
             cbl.save_to_file(a.output)
+    elif a.cmd == "at-least":
+        if len(a.indexes) < 2:
+            ap.error("at-least takes two or more index files")
+        if not 1 <= a.threshold <= len(a.indexes):
+            ap.error(f"at-least: the threshold is 1 to the number of index files ({len(a.indexes)})")
+        cbls = [CBL.load_from_file(path, a.k, a.prefix_bits, device=a.device) for path in a.indexes]
+        cbl = CBL.at_least(cbls, a.threshold)
+        print(f"{cbl.count()} {a.k}-mers are held by at least {a.threshold} of the {len(cbls)} indexes", file=sys.stderr)
+        if a.output:
+            print(f"Writing the index to {a.output}", file=sys.stderr)
+            cbl.save_to_file(a.output)
+    elif a.cmd == "occupancy":
+        if len(a.indexes) < 2:
+            ap.error("occupancy takes two or more index files")
+        cbls = [CBL.load_from_file(path, a.k, a.prefix_bits, device=a.device) for path in a.indexes]
+        lines, human = occupancy_report(CBL.occupancy(cbls))
+        print("\n".join(human), file=sys.stderr)
+        print("\n".join(lines))
     elif a.cmd == "compare":
         if len(a.indexes) < 2:
             ap.error("compare takes two or more index files")

@@ -1086,6 +1086,75 @@ int cblx_set_op_many(cblx_ctx* dst, cblx_ctx* const* srcs, uint32_t n, uint32_t 
         CBLX_HIP(hipStreamSynchronize(dst->stream));
     });
 }
+// the argument checks cblx_set_at_least and cblx_occupancy_counts share with cblx_set_op_many (dst: null where no index is written)
+static void check_many_operands(const char* who, cblx_ctx* dst, cblx_ctx* const* srcs, uint32_t n) {
+    const std::string w(who);
+    if (!srcs) throw Error(CBLX_EINVAL, "null argument");
+    if (n == 0 || n > CBLX_SETOP_MAX_OPERANDS) throw Error(CBLX_EINVAL, w + ": 1 to " + std::to_string(CBLX_SETOP_MAX_OPERANDS) + " operands, not " + std::to_string(n));
+    for (uint32_t i = 0; i < n; ++i) {
+        cblx_ctx* x = srcs[i];
+        if (!x) throw Error(CBLX_EINVAL, "null argument");
+        if (x == dst) throw Error(CBLX_EINVAL, w + ": dst must not be one of the operands");
+        for (uint32_t j = 0; j < i; ++j)
+            if (srcs[j] == x) throw Error(CBLX_EINVAL, w + ": the operands must be different contexts");
+        const cblx_ctx* ref = dst ? dst : srcs[0];
+        if (ref->P.K != x->P.K || ref->P.PB != x->P.PB) throw Error(CBLX_EINVAL, w + ": K / PREFIX_BITS mismatch");
+        if (x->P.canonical != srcs[0]->P.canonical) throw Error(CBLX_EINVAL, "One of the index is canonical while the other isn't");
+        if (ref->device != x->device) throw Error(CBLX_EINVAL, w + ": " + (dst ? "dst and the operands" : "the operands") + " must live on the same device");
+    }
+}
+int cblx_set_at_least(cblx_ctx* dst, cblx_ctx* const* srcs, uint32_t n, uint32_t t) {
+    return guard(dst, [&] {
+        if (!dst) throw Error(CBLX_EINVAL, "null argument");
+        check_many_operands("set_at_least", dst, srcs, n);
+        if (t == 0 || t > n) throw Error(CBLX_EINVAL, "set_at_least: the threshold is 1 to the number of operands (" + std::to_string(n) + "), not " + std::to_string(t));
+        CBLX_HIP(hipStreamSynchronize(dst->stream));
+        dst->res = Resident();
+        dst->batch = SortedBatch();
+        ingest_drop(dst);
+        dst->P.canonical = srcs[0]->P.canonical;  // the result is as canonical as its operands
+        std::vector<cblx_ctx*> live;  // an empty operand counts towards n and holds nothing
+        for (uint32_t i = 0; i < n; ++i) {  // an observer: pending inserts are part of the sets
+            flush(srcs[i]);
+            CBLX_HIP(hipStreamSynchronize(srcs[i]->stream));
+            if (srcs[i]->res.count != 0) live.push_back(srcs[i]);
+        }
+        if (live.size() < t) return;  // no prefix has t holders: nothing is visited, nothing is sorted
+        if (t == 1 && live.size() == 1) { dst->res = clone_resident(dst, live[0]); return; }  // every bucket has one holder: cloned as stored
+        std::vector<Resident*> xs;
+        for (cblx_ctx* x : live) xs.push_back(&x->res);
+        dispatch(dst->P, [&](auto cfg) {
+            typedef decltype(cfg) C;
+            if (t == 1) set_op_many_direct<C>(dst, xs, CBLX_SETOP_OR);  // CBL::merge, byte for byte
+            else dst->res = at_least_build<C>(dst, xs, t, nullptr);
+        });
+        collect_events(dst);
+        CBLX_HIP(hipStreamSynchronize(dst->stream));
+    });
+}
+int cblx_occupancy_counts(cblx_ctx* const* srcs, uint32_t n, uint64_t* hist) {
+    return guard(srcs && n ? srcs[0] : nullptr, [&] {
+        if (!hist) throw Error(CBLX_EINVAL, "null argument");
+        check_many_operands("occupancy_counts", nullptr, srcs, n);
+        for (uint32_t j = 0; j <= n; ++j) hist[j] = 0;
+        std::vector<cblx_ctx*> live;
+        for (uint32_t i = 0; i < n; ++i) {  // an observer: pending inserts are part of the sets
+            flush(srcs[i]);
+            CBLX_HIP(hipStreamSynchronize(srcs[i]->stream));
+            if (srcs[i]->res.count != 0) live.push_back(srcs[i]);
+        }
+        if (live.empty()) return;
+        if (live.size() == 1) { hist[1] = live[0]->res.count; return; }  // every bucket has one holder: the directory alone
+        std::vector<Resident*> xs;
+        for (cblx_ctx* x : live) xs.push_back(&x->res);
+        cblx_ctx* c = live[0];  // its stream, pool and mailbox
+        std::vector<uint64_t> h(live.size() + 1);
+        dispatch(c->P, [&](auto cfg) { at_least_build<decltype(cfg)>(c, xs, 1, h.data()); });
+        for (size_t j = 0; j < h.size(); ++j) hist[j] = h[j];
+        collect_events(c);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
 int cblx_intersection_count(cblx_ctx* a, cblx_ctx* b, uint64_t* common, uint64_t* stats) {
     return guard(a, [&] {
         if (!a || !b || !common) throw Error(CBLX_EINVAL, "null argument");

@@ -736,6 +736,359 @@ __global__ __launch_bounds__(256) void k_many_long_finish(const BDesc* __restric
     if (threadIdx.x == 0) out_count[r] = c;
 }
 
+// ---- k-mers at least t of n operands hold, and how many k-mers exactly j hold (cblx_set_at_least / cblx_occupancy_counts) --------
+// Ours, not the reference's. A prefix m operands hold is visited when m >= t (t >= 2; t = 1 is cblx_set_op_many's merge): every holder's Vec is sorted, the
+// result is Vec(ascending {v : t holders or more hold v}), dropped when empty. The occupancy count visits what a merge visits, sorts what a merge sorts and
+// writes no index: a one-holder bucket adds its length to hist[1] from the directory, a multi-held one tallies the holders of every distinct value.
+// The candidates: per 64 prefixes a vertical counter over the n bitvector words — seven bit planes, a ripple-carry add per operand — compared with t
+// bit-sliced from the lowest plane up (ge = the planes so far are >= t's bits so far).
+__global__ void k_thresh_bv(u64 nwords, const ManyOp* __restrict__ ops, u32 n, u32 t, u64* __restrict__ out, u32* __restrict__ popc) {
+    const u64 w = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= nwords) return;
+    u64 c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0;
+    for (u32 i = 0; i < n; ++i) {
+        u64 carry = ops[i].d.bv ? ops[i].d.bv[w] : 0ull, x;
+        x = c0 & carry; c0 ^= carry; carry = x;
+        x = c1 & carry; c1 ^= carry; carry = x;
+        x = c2 & carry; c2 ^= carry; carry = x;
+        x = c3 & carry; c3 ^= carry; carry = x;
+        x = c4 & carry; c4 ^= carry; carry = x;
+        x = c5 & carry; c5 ^= carry; carry = x;
+        c6 ^= carry;  // (n <= 64: the count fits seven planes)
+    }
+    u64 ge = ~0ull;
+    ge = (t & 1u) ? (c0 & ge) : (c0 | ge);
+    ge = (t & 2u) ? (c1 & ge) : (c1 | ge);
+    ge = (t & 4u) ? (c2 & ge) : (c2 | ge);
+    ge = (t & 8u) ? (c3 & ge) : (c3 | ge);
+    ge = (t & 16u) ? (c4 & ge) : (c4 | ge);
+    ge = (t & 32u) ? (c5 & ge) : (c5 | ge);
+    ge = (t & 64u) ? (c6 & ge) : (c6 | ge);
+    out[w] = ge;
+    popc[w] = (u32)__builtin_popcountll(ge);
+}
+// k_many_table's twin, one thread per prefix slot of the candidate bitvector: holder mask and the list of the bucket's route by the words of all holders.
+// t >= 2 (`single` null): every candidate has t holders or more; its run takes sum / t words, since every output consumes t staged words or more.
+// Counting (`single` given, t = 1): nothing has a run; a one-holder bucket leaves its length in single[r] and joins no list.
+__global__ __launch_bounds__(CLASSIFY_THREADS) void k_thresh_table(u64 nprefix, const u64* __restrict__ bv, const u64* __restrict__ rank_dir, const ManyOp* __restrict__ ops, u32 n,
+                                                                    u32 t, u64 nb, u32* __restrict__ bucket_prefix, u64* __restrict__ hmask, u32* __restrict__ cap,
+                                                                    u32* __restrict__ out_count, u8* __restrict__ out_kind, BDesc* __restrict__ lists /* [3][nb] */,
+                                                                    u32* __restrict__ list_n, u32* __restrict__ single) {
+    const u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    int cls = -1;
+    u64 r = 0;
+    u32 sum = 0;
+    if (p < nprefix) {
+        const u64 w = bv[p >> 6];
+        if ((w >> (p & 63)) & 1ull) {
+            r = rank_dir[p >> 6] + (u64)__builtin_popcountll(w & ((1ull << (p & 63)) - 1ull));
+            u64 mask = 0;
+            for (u32 i = 0; i < n; ++i) {
+                u64 rank;
+                if (!dir_lookup(ops[i].d, (u32)p, rank)) continue;
+                mask |= 1ull << i;
+                sum += ops[i].d.count[rank];
+            }
+            bucket_prefix[r] = (u32)p;
+            hmask[r] = mask;
+            const bool one = (mask & (mask - 1ull)) == 0;
+            if (single) single[r] = one ? sum : 0u;
+            else {
+                cap[r] = sum / t;
+                out_count[r] = 0;  // (written by the bucket's kernel)
+                out_kind[r] = KIND_VEC;
+            }
+            if (!(single && one)) cls = sum <= MANY_SMALL ? 0 : sum <= MANY_LDS ? 1 : 2;
+        }
+    }
+    const u32 slot = block_append<CLASSIFY_THREADS, 3>(cls, list_n);
+    if (cls >= 0) lists[(u64)cls * nb + slot] = BDesc{0, sum, (u32)r};
+}
+// One tally per holder count in LDS: the lanes of a wave that saw the same count h (0: nothing to tally) add their number with one LDS atomic. Every lane
+// of the wave must call it.
+__device__ __forceinline__ void tally_holders(u32 h, unsigned long long* s_tally) {
+    const u32 lane = threadIdx.x & 63;
+    u64 todo = __ballot(h != 0);
+    while (todo) {
+        const u32 leader = (u32)__builtin_ctzll(todo);
+        const u32 hv = (u32)__shfl((int)h, (int)leader, 64);
+        const u64 same = __ballot(h == hv);
+        if (lane == leader) atomicAdd(&s_tally[hv], (unsigned long long)__builtin_popcountll(same));
+        todo &= ~same;
+    }
+}
+// the tallies of one workgroup become its row of `tally` ([gridDim.x][MANY_MAX + 1]); k_tally_sum adds the rows up
+template <int THREADS> __device__ __forceinline__ void tally_flush(const unsigned long long* s_tally, u64* __restrict__ tally) {
+    __syncthreads();
+    for (u32 j = threadIdx.x; j <= MANY_MAX; j += THREADS) tally[(u64)blockIdx.x * (MANY_MAX + 1) + j] = s_tally[j];
+}
+// One round over the words staged in LDS, shared by the short routes and the long one. s_lo / s_hi hold m ascending, duplicate-free windows back to
+// back, window k at [s_off[k], s_off[k + 1]), `total` words in all. It is k_bucket_setop_many's OR path — position search, (element, kept) to the merged
+// position, ordered compaction by ballot / mbcnt / wave totals — plus a holder count per element: the search in a lower window (upper bound) says whether
+// that window holds the value, as there; the search in a higher window (lower bound) needs one comparison at the bound. An element is kept when it is the
+// lowest holder's copy and t windows or more hold it. ROUNDS: only the first s_act[k] elements of window k take part (`active` in all): they are the
+// elements up to a value every window reaches, so every copy of them is staged and they stand at the merged positions 0 .. active - 1.
+// COUNT: nothing is written but the tallies — the holders of every lowest copy. Otherwise the kept elements go to dst[written ...) below `room`; returns
+// how many. Every thread of the workgroup must call it; s_perm and s_wtot are free again when it returns.
+template <bool WS, bool COUNT, bool ROUNDS, int THREADS>
+__device__ __forceinline__ u32 atleast_round(const u64* s_lo, const u64* s_hi, u32* s_perm, const u32* s_off, const u32* s_act, u32 m, u32 total, u32 active, u32 t,
+                                             u32* s_wtot, unsigned long long* s_tally, u64* __restrict__ dst, u64* __restrict__ dsth, u32 written, u32 room) {
+    typedef UniE<WS> E;
+    constexpr int NW = THREADS / 64;
+    const u32 tid = threadIdx.x;
+    auto run_of = [&](u32 e) { u32 k = 0; while (k + 1 < m && s_off[k + 1] <= e) ++k; return k; };
+    auto get = [&](u32 i) { E e; e.lo = s_lo[i]; if constexpr (WS) e.hi = s_hi[i]; return e; };
+    // first index in [a, b) whose element is not below v (UPPER: is above v)
+    auto bound = [&](u32 a, u32 b, const E& v, bool upper) {
+        while (a < b) {
+            const u32 mid = (a + b) >> 1;
+            const E x = get(mid);
+            if (upper ? !uni_lt<WS>(v, x) : uni_lt<WS>(x, v)) a = mid + 1; else b = mid;
+        }
+        return a;
+    };
+    for (u32 base = 0; base < total; base += THREADS) {  // (whole waves: tally_holders is called by every lane)
+        const u32 e = base + tid;
+        u32 h = 0;
+        if (e < total) {
+            const u32 k = run_of(e);
+            u32 pos = e - s_off[k];
+            bool live = true;
+            if constexpr (ROUNDS) live = pos < s_act[k];
+            if (live) {
+                const E v = get(e);
+                bool dup = false;
+                h = 1;
+                for (u32 kk = 0; kk < m; ++kk) {
+                    if (kk == k) continue;
+                    const u32 a = s_off[kk], end = s_off[kk + 1], at = bound(a, end, v, kk < k);
+                    pos += at - a;
+                    if (kk < k) { if (at > a && uni_eq<WS>(get(at - 1), v)) { dup = true; ++h; } }
+                    else if (at < end && uni_eq<WS>(get(at), v)) ++h;
+                }
+                if constexpr (!COUNT) { if (pos < active) s_perm[pos] = e | (!dup && h >= t ? 0x80000000u : 0u); }
+                if (dup) h = 0;
+            }
+        }
+        if constexpr (COUNT) tally_holders(h, s_tally);
+    }
+    u32 kept = 0;
+    if constexpr (!COUNT) {
+        __syncthreads();
+        for (u32 base = 0; base < active; base += THREADS) {
+            const u32 q = base + tid;
+            const u32 pe = q < active ? s_perm[q] : 0u;
+            const bool keep = (pe >> 31) != 0;
+            const u32 src = pe & 0x7FFFFFFFu;
+            u32 before;
+            const u32 tot = count_before<NW>(keep, s_wtot, before);
+            const u32 at = written + kept + before;
+            if (keep && at < room) {
+                dst[at] = s_lo[src];
+                if constexpr (WS) dsth[at] = s_hi[src];
+            }
+            kept += tot;
+            __syncthreads();  // s_wtot is rewritten
+        }
+    }
+    return kept;
+}
+// The short routes: one workgroup per bucket of up to CAP words over all its m holders, whose runs are ascending and duplicate-free by now, staged back to
+// back in LDS exactly as k_bucket_setop_many stages them; one round over all of them. COUNT: a workgroup takes the buckets blockIdx.x, + gridDim.x, ...
+// of its list and leaves one row of tallies.
+template <bool WS, u32 CAP, int THREADS, bool COUNT>
+__global__ __launch_bounds__(THREADS) void k_bucket_atleast(const BDesc* __restrict__ list, const u32* __restrict__ list_n, const u32* __restrict__ bucket_prefix,
+                                                            const u64* __restrict__ hmask, const ManyOp* __restrict__ ops, const u64* __restrict__ run_start,
+                                                            const u32* __restrict__ cap, u64* __restrict__ out_lo, u64* __restrict__ out_hi, u32 SB,
+                                                            u32* __restrict__ out_count, u32 t, u64* __restrict__ tally) {
+    static_assert(THREADS % 64 == 0, "whole waves");
+    constexpr int NW = THREADS / 64;
+    __shared__ u64 s_lo[CAP];
+    __shared__ u64 s_hi[WS ? CAP : 1];
+    __shared__ u32 s_perm[COUNT ? 1 : CAP];  // merged position -> element | kept << 31
+    __shared__ u64 s_src[MANY_MAX];           // holder k: first arena slot of its run,
+    __shared__ u32 s_opi[MANY_MAX];           // its operand,
+    __shared__ u32 s_off[MANY_MAX + 1];       // and where its run starts in s_lo; [m] = words of all holders
+    __shared__ u32 s_wtot[NW];
+    __shared__ unsigned long long s_tally[COUNT ? MANY_MAX + 1 : 1];
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u64 mask = suffix_mask<WS>(SB);
+    const u32 nlist = *list_n;
+    if constexpr (COUNT) {
+        for (u32 j = tid; j <= MANY_MAX; j += THREADS) s_tally[j] = 0ull;
+    }
+    for (u32 b = blockIdx.x; b < nlist; b += gridDim.x) {
+        __syncthreads();  // the tables of the bucket before are rewritten (and s_tally is cleared)
+        const u32 r = list[b].r;
+        const u64 holders = hmask[r];
+        const u32 p = bucket_prefix[r], m = (u32)__builtin_popcountll(holders);
+        if (tid < 64) {
+            const bool holds = ((holders >> tid) & 1ull) != 0;
+            u32 c = 0;
+            u64 st = 0, rank;
+            if (holds && dir_lookup(ops[tid].d, p, rank)) { c = ops[tid].d.count[rank]; st = ops[tid].d.start[rank]; }
+            u32 inc = c;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) { const u32 up = __shfl_up(inc, d, 64); if ((int)lane >= d) inc += up; }
+            if (holds) {
+                const u32 k = (u32)__builtin_popcountll(holders & ((1ull << tid) - 1ull));
+                s_off[k] = inc - c < CAP ? inc - c : CAP;  // (the list's class says words of all holders <= CAP)
+                s_src[k] = st;
+                s_opi[k] = tid;
+            }
+            if (tid == 63) s_off[m] = inc < CAP ? inc : CAP;
+        }
+        __syncthreads();
+        const u32 total = s_off[m];
+        for (u32 e = tid; e < total; e += THREADS) {
+            u32 k = 0;
+            while (k + 1 < m && s_off[k + 1] <= e) ++k;
+            const ManyOp& o = ops[s_opi[k]];
+            const u64 g = s_src[k] + (e - s_off[k]);
+            if constexpr (WS) { s_lo[e] = o.lo[g]; s_hi[e] = o.hi[g] & mask; }
+            else s_lo[e] = o.lo[g] & mask;
+            if constexpr (!COUNT) s_perm[e] = 0;
+        }
+        __syncthreads();
+        const u64 d0 = COUNT ? 0ull : run_start[r];
+        const u32 kept = atleast_round<WS, COUNT, false, THREADS>(s_lo, s_hi, s_perm, s_off, nullptr, m, total, total, t, s_wtot, s_tally, out_lo + d0, WS ? out_hi + d0 : nullptr, 0u,
+                                                                  COUNT ? 0u : cap[r]);
+        if constexpr (!COUNT) { if (tid == 0) out_count[r] = kept < cap[r] ? kept : cap[r]; }
+    }
+    if constexpr (COUNT) tally_flush<THREADS>(s_tally, tally);
+}
+// The long route: a bucket whose holders have more than MANY_LDS words, exact at any length with the LDS of the workgroup route. One workgroup walks the
+// holders' ascending, duplicate-free runs where they lie in the operands' arenas, in rounds. A round stages the next MANY_LDS / (runs with words left)
+// words of every run. `limit` = the smallest last staged word among the runs that have words beyond their window: every run reaches it, so every copy of a
+// value <= limit is staged, and the elements <= limit — the first s_act[k] of window k, found by one search per window — are settled by atleast_round as
+// on the short routes; the others are staged again in the next round. With no run beyond its window the round takes everything and is the last. The run
+// that sets the limit gives up its whole window, so every round but the last settles MANY_LDS / 64 words or more. Rounds cover ascending ranges of values:
+// appended one after the other, the kept elements of the bucket come out ascending, with no table in global memory.
+// COUNT: the tallies only; a workgroup takes the buckets blockIdx.x, + gridDim.x, ... of the list.
+template <bool WS, bool COUNT>
+__global__ __launch_bounds__(256) void k_bucket_atleast_long(const BDesc* __restrict__ list, u32 nlong, const u32* __restrict__ bucket_prefix, const u64* __restrict__ hmask,
+                                                             const ManyOp* __restrict__ ops, const u64* __restrict__ run_start, const u32* __restrict__ cap,
+                                                             u64* __restrict__ out_lo, u64* __restrict__ out_hi, u32 SB, u32* __restrict__ out_count, u32 t,
+                                                             u64* __restrict__ tally) {
+    typedef UniE<WS> E;
+    constexpr int THREADS = 256, NW = THREADS / 64;
+    constexpr u32 CAP = MANY_LDS;
+    __shared__ u64 s_lo[CAP];
+    __shared__ u64 s_hi[WS ? CAP : 1];
+    __shared__ u32 s_perm[COUNT ? 1 : CAP];
+    __shared__ const u64* s_plo[MANY_MAX];  // holder k: its run in its operand's arena,
+    __shared__ const u64* s_phi[MANY_MAX];
+    __shared__ u32 s_cnt[MANY_MAX];         // its length,
+    __shared__ u32 s_pos[MANY_MAX];         // how much of it is settled,
+    __shared__ u32 s_act[MANY_MAX];         // how much of its window this round settles,
+    __shared__ u32 s_off[MANY_MAX + 1];     // and where its window starts in s_lo; [m] = staged words
+    __shared__ u32 s_active;                // the sum of s_act
+    __shared__ u32 s_wtot[NW];
+    __shared__ unsigned long long s_tally[COUNT ? MANY_MAX + 1 : 1];
+    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u64 mask = suffix_mask<WS>(SB);
+    if constexpr (COUNT) {
+        for (u32 j = tid; j <= MANY_MAX; j += THREADS) s_tally[j] = 0ull;
+    }
+    for (u32 q = blockIdx.x; q < nlong; q += gridDim.x) {
+        __syncthreads();  // the tables of the bucket before are rewritten (and s_tally is cleared)
+        const u32 r = list[q].r;
+        const u64 holders = hmask[r];
+        const u32 p = bucket_prefix[r], m = (u32)__builtin_popcountll(holders);
+        if (tid < 64 && ((holders >> tid) & 1ull)) {
+            const u32 k = (u32)__builtin_popcountll(holders & ((1ull << tid) - 1ull));
+            u32 c = 0;
+            u64 st = 0, rank;
+            if (dir_lookup(ops[tid].d, p, rank)) { c = ops[tid].d.count[rank]; st = ops[tid].d.start[rank]; }
+            s_cnt[k] = c;
+            s_pos[k] = 0;
+            s_plo[k] = ops[tid].lo + st;
+            s_phi[k] = WS ? ops[tid].hi + st : nullptr;
+        }
+        const u64 d0 = COUNT ? 0ull : run_start[r];
+        const u32 room = COUNT ? 0u : cap[r];
+        u32 written = 0;
+        for (;;) {
+            __syncthreads();  // s_pos is settled; the windows of the round before are rewritten
+            if (tid < 64) {   // the windows of this round
+                const u32 rem = tid < m ? s_cnt[tid] - s_pos[tid] : 0u;
+                const u32 left = (u32)__builtin_popcountll(__ballot(rem != 0));
+                const u32 per = left ? CAP / left : 0u;
+                const u32 take = rem < per ? rem : per;
+                u32 inc = take;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) { const u32 up = __shfl_up(inc, d, 64); if ((int)lane >= d) inc += up; }
+                if (tid < m) s_off[tid] = inc - take;
+                if (tid == 63) s_off[m] = inc;
+            }
+            __syncthreads();
+            const u32 total = s_off[m];  // <= CAP
+            if (total == 0) break;       // every run is settled
+            for (u32 e = tid; e < total; e += THREADS) {
+                u32 k = 0;
+                while (k + 1 < m && s_off[k + 1] <= e) ++k;
+                const u32 i = s_pos[k] + (e - s_off[k]);
+                if constexpr (WS) { s_lo[e] = s_plo[k][i]; s_hi[e] = s_phi[k][i] & mask; }
+                else s_lo[e] = s_plo[k][i] & mask;
+                if constexpr (!COUNT) s_perm[e] = 0;
+            }
+            __syncthreads();
+            if (tid < 64) {  // the limit, and what every window settles
+                const u32 a = tid < m ? s_off[tid] : 0u, end = tid < m ? s_off[tid + 1] : 0u;
+                bool has = tid < m && end > a && s_pos[tid] + (end - a) < s_cnt[tid];  // words beyond the window
+                E x;
+                x.lo = has ? s_lo[end - 1] : 0ull;
+                if constexpr (WS) x.hi = has ? s_hi[end - 1] : 0ull;
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) {
+                    E o;
+                    o.lo = __shfl_xor(x.lo, d, 64);
+                    if constexpr (WS) o.hi = __shfl_xor(x.hi, d, 64);
+                    const bool ohas = __shfl_xor((int)has, d, 64) != 0;
+                    if (ohas && (!has || uni_lt<WS>(o, x))) { x = o; has = true; }
+                }
+                u32 act = end - a;
+                if (has) {  // the elements of the window that are not above the limit
+                    u32 lo = a, hi = end;
+                    while (lo < hi) {
+                        const u32 mid = (lo + hi) >> 1;
+                        E y;
+                        y.lo = s_lo[mid];
+                        if constexpr (WS) y.hi = s_hi[mid];
+                        if (!uni_lt<WS>(x, y)) lo = mid + 1; else hi = mid;
+                    }
+                    act = lo - a;
+                }
+                if (tid < m) s_act[tid] = act;
+                u32 sum = act;
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+                if (tid == 0) s_active = sum;
+            }
+            __syncthreads();
+            written += atleast_round<WS, COUNT, true, THREADS>(s_lo, s_hi, s_perm, s_off, s_act, m, total, s_active, t, s_wtot, s_tally, out_lo + d0, WS ? out_hi + d0 : nullptr,
+                                                               written, room);
+            __syncthreads();  // every lane has read s_act and s_pos
+            if (tid < m) s_pos[tid] += s_act[tid];
+        }
+        if constexpr (!COUNT) { if (tid == 0) out_count[r] = written < room ? written : room; }
+    }
+    if constexpr (COUNT) tally_flush<THREADS>(s_tally, tally);
+}
+// hist[j] = the sum of column j over the `rows` rows of `tally`, plus the words of the one-holder buckets for j = 1; one workgroup per j (no atomics: exact
+// integers, the same on every run)
+__global__ __launch_bounds__(256) void k_tally_sum(const u64* __restrict__ tally, u32 rows, const u64* __restrict__ single_total, u64* __restrict__ hist) {
+    __shared__ u64 s_w[4];
+    const u32 j = blockIdx.x;
+    u64 s = 0;
+    for (u32 i = threadIdx.x; i < rows; i += 256) s += tally[(u64)i * (MANY_MAX + 1) + j];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d, 64);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) hist[j] = s_w[0] + s_w[1] + s_w[2] + s_w[3] + (j == 1 ? *single_total : 0ull);
+}
+
 // ---- `a &= &mut b`, `a -= &mut b`, `a ^= &mut b` (cblx_set_op_assign; src/wordset/set_ops.rs:192-239, 281-317, 366-410 walk the prefixes,
 // src/trievec/set_ops.rs:101-129, 163-187, 226-257 the buckets). A bucket both hold keeps a's KIND. A Trie is the ascending result (Trie::remove
 // prunes empty nodes, so the trie is a function of its set): k_bucket_setop's output. A Vec is sorted by iter_sorted, takes the ascending words

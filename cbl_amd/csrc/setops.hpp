@@ -1,5 +1,5 @@
 // setops.hpp — set algebra between resident indexes and k-mer removal, on the host: `self |= other` (merge_direct), `a OP b` into a new index and the
-// assigning forms (set_op_build), CBL::merge / CBL::intersect of n operands (set_op_many_build), |a AND b| alone (intersection_count), WordSet::remove_batch (remove_words). They share the
+// assigning forms (set_op_build), CBL::merge / CBL::intersect of n operands (set_op_many_build), the k-mers at least t of n hold and the occupancy histogram (at_least_build), |a AND b| alone (intersection_count), WordSet::remove_batch (remove_words). They share the
 // bucket stages of pipeline.hpp and the end of a result (set_op_tail). Kernels: kernels_setops.hpp, kernels_remove.hpp. Included by cblx.cpp only.
 #pragma once
 #include "kernels_remove.hpp"
@@ -341,6 +341,23 @@ template <typename C> Resident set_op_build(cblx_ctx* c, Resident& a, Resident& 
     CBLX_HIP(hipStreamSynchronize(c->stream));  // the lists and tables of this call die here
     return nr;
 }
+// The Vec sides of an n-ary operation, one operand after the other through the same two lists (the launches of one operand are behind it when its counts are
+// read). `op` is k_many_sortplan's rule: SETOP_OR — candidates two or more hold; SETOP_AND — every candidate the operand holds.
+template <typename C> void sort_many_sides(cblx_ctx* c, const std::vector<Resident*>& xs, const ManyOp* ops, u64 nb, const u32* prefix, const u64* hmask, u32 op) {
+    Resident junk;
+    junk.cnt = Buf<u32>(c->pool, nb + 1);
+    junk.kind = Buf<u8>(c->pool, nb + 1);
+    Buf<BDesc> sort_lists(c->pool, 2 * nb);
+    Buf<u32> sort_n(c->pool, 2);
+    for (u32 i = 0; i < (u32)xs.size(); ++i) {
+        CBLX_HIP(hipMemsetAsync(sort_n.get(), 0, 2 * 4, c->stream));
+        hipLaunchKernelGGL(k_many_sortplan, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, prefix, hmask, op, ops, i, sort_lists.get(), sort_n.get());
+        CBLX_HIP(hipGetLastError());
+        const std::vector<u32> sn = d2h_vec<u32>(c, sort_n.get(), 2);
+        sort_vec_sides<C>(c, *xs[i], sort_lists.get(), sort_lists.get() + nb, sort_n.get(), sn[0], sn[1], junk);
+        CBLX_HIP(hipStreamSynchronize(c->stream));  // the lists are rewritten for the next operand
+    }
+}
 // ---- CBL::merge / CBL::intersect of n operands into a new index (src/cbl.rs:106-124 -> src/wordset/set_ops.rs:11-42, 49-75), all resident on this device ----
 // `xs`: 1 .. 64 non-empty operands in the caller's order (an empty one contributes nothing to a merge and empties an intersection: the caller's business).
 // op: SETOP_OR (merge) | SETOP_AND (intersect). Every operand keeps its set; its Vec buckets on the prefixes the reference visits with iter_sorted — merge:
@@ -387,23 +404,7 @@ template <typename C> Resident set_op_many_build(cblx_ctx* c, const std::vector<
         CBLX_HIP(hipGetLastError());
     }
     const std::vector<u32> ln = d2h_vec<u32>(c, list_n.get(), 3);
-    if (ln[0] || ln[1] || ln[2]) {
-        // the Vec sides, one operand after the other through the same two lists (the launches of one operand are behind it when its counts are read)
-        Resident junk;
-        junk.cnt = Buf<u32>(c->pool, nb + 1);
-        junk.kind = Buf<u8>(c->pool, nb + 1);
-        Buf<BDesc> sort_lists(c->pool, 2 * nb);
-        Buf<u32> sort_n(c->pool, 2);
-        for (u32 i = 0; i < n; ++i) {
-            CBLX_HIP(hipMemsetAsync(sort_n.get(), 0, 2 * 4, c->stream));
-            hipLaunchKernelGGL(k_many_sortplan, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, (const u32*)nr.prefix.get(), (const u64*)hmask.get(), op,
-                               (const ManyOp*)ops.get(), i, sort_lists.get(), sort_n.get());
-            CBLX_HIP(hipGetLastError());
-            const std::vector<u32> sn = d2h_vec<u32>(c, sort_n.get(), 2);
-            sort_vec_sides<C>(c, *xs[i], sort_lists.get(), sort_lists.get() + nb, sort_n.get(), sn[0], sn[1], junk);
-            CBLX_HIP(hipStreamSynchronize(c->stream));  // the lists are rewritten for the next operand
-        }
-    }
+    if (ln[0] || ln[1] || ln[2]) sort_many_sides<C>(c, xs, ops.get(), nb, nr.prefix.get(), hmask.get(), op);
     if (ln[0] || ln[1]) {
         StageTimer t(c, ST_BBIG);
         with_setop(op, [&](auto opc) {
@@ -457,6 +458,99 @@ template <typename C> Resident set_op_many_build(cblx_ctx* c, const std::vector<
     return nr;
 }
 template <typename C> void set_op_many_direct(cblx_ctx* c, const std::vector<Resident*>& xs, u32 op) { c->res = set_op_many_build<C>(c, xs, op); }
+
+// ---- k-mers at least t of the n operands hold into a new index, or the occupancy histogram alone (cblx_set_at_least / cblx_occupancy_counts) ----
+// `xs`: 2 .. 64 non-empty operands, all resident on this device. hist == null: 2 <= t <= n, the result is returned (t = 1 is set_op_many_build's merge, the
+// caller's business). hist given (n + 1 entries): t must be 1 — a merge's visit in a count-only mode: no arena, no output runs, no gather; hist[j] = distinct
+// k-mers exactly j operands hold, read back once through the mailbox; the returned index is empty. Either way the Vec buckets of every operand on the visited
+// prefixes — m >= max(t, 2) holders — are sorted in its own arena.
+template <typename C> Resident at_least_build(cblx_ctx* c, const std::vector<Resident*>& xs, u32 t, u64* hist) {
+    constexpr bool WS = C::WS;
+    const Consts& P = c->P;
+    const u32 n = (u32)xs.size();
+    const bool count_only = hist != nullptr;
+    const u64 nprefix = 1ull << P.PB, nwords = std::max<u64>(1, nprefix / 64);
+    if (count_only) for (u32 j = 0; j <= n; ++j) hist[j] = 0;
+    std::vector<ManyOp> h_ops(n);
+    for (u32 i = 0; i < n; ++i) h_ops[i] = ManyOp{xs[i]->view(), xs[i]->a_lo.get(), xs[i]->a_hi.get()};
+    Buf<ManyOp> ops(c->pool, n);
+    h2d(c, ops.get(), h_ops.data(), n);
+    Resident nr;
+    Buf<u32> cap, single, popc(c->pool, nwords), list_n(c->pool, 3);
+    Buf<u64> hmask;
+    Buf<BDesc> lists;  // [3][nb]: the visited multi-held buckets by route
+    u64 N = 0;
+    {
+        StageTimer tm(c, ST_DIR);
+        nr.bv = Buf<u64>(c->pool, nwords);
+        nr.rank_dir = Buf<u64>(c->pool, nwords + 1);
+        hipLaunchKernelGGL(k_thresh_bv, grid1(nwords, 256), dim3(256), 0, c->stream, nwords, (const ManyOp*)ops.get(), n, t, nr.bv.get(), popc.get());
+        nr.nb = exclusive_scan<u64>(c, popc.get(), nwords, nr.rank_dir.get());
+        if (nr.nb == 0) { CBLX_HIP(hipStreamSynchronize(c->stream)); return Resident(); }  // no prefix has t holders
+        const u64 nb = nr.nb;
+        if (count_only) { nr.prefix = Buf<u32>(c->pool, nb + 1); single = Buf<u32>(c->pool, nb + 1); }
+        else { alloc_dir_rows(c, nr); cap = Buf<u32>(c->pool, nb + 1); }
+        hmask = Buf<u64>(c->pool, nb + 1);
+        lists = Buf<BDesc>(c->pool, 3 * nb);
+        CBLX_HIP(hipMemsetAsync(list_n.get(), 0, 3 * 4, c->stream));
+        hipLaunchKernelGGL(k_thresh_table, grid1(nprefix, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nprefix, (const u64*)nr.bv.get(), (const u64*)nr.rank_dir.get(),
+                           (const ManyOp*)ops.get(), n, t, nb, nr.prefix.get(), hmask.get(), cap.get(), nr.cnt.get(), nr.kind.get(), lists.get(), list_n.get(), single.get());
+        CBLX_HIP(hipGetLastError());
+        if (!count_only) N = seal_runs<WS>(c, nr, cap.get());
+    }
+    const u64 nb = nr.nb;
+    const std::vector<u32> ln = d2h_vec<u32>(c, list_n.get(), 3);
+    if (ln[0] || ln[1] || ln[2]) sort_many_sides<C>(c, xs, ops.get(), nb, nr.prefix.get(), hmask.get(), t >= 2 ? SETOP_AND : SETOP_OR);  // visited: m >= max(t, 2)
+    // counting: a grid of a few residencies of the chip, one row of tallies per workgroup
+    const u32 g0 = count_only ? std::min<u32>(ln[0], 1u << 14) : ln[0], g1 = count_only ? std::min<u32>(ln[1], 1u << 13) : ln[1], g2 = count_only ? std::min<u32>(ln[2], 1u << 12) : ln[2];
+    Buf<u64> tally;
+    if (count_only) tally = Buf<u64>(c->pool, (size_t)(g0 + g1 + g2 + 1) * (MANY_MAX + 1));
+    auto with_mode = [&](auto&& f) { if (count_only) f(std::true_type()); else f(std::false_type()); };
+    if (ln[0] || ln[1]) {
+        StageTimer tm(c, ST_BBIG);
+        with_mode([&](auto mode) {
+            constexpr bool COUNT = decltype(mode)::value;
+            if (ln[0])
+                hipLaunchKernelGGL((k_bucket_atleast<WS, MANY_SMALL, 64, COUNT>), dim3(g0), dim3(64), 0, c->stream, (const BDesc*)lists.get(), (const u32*)list_n.get(),
+                                   (const u32*)nr.prefix.get(), (const u64*)hmask.get(), (const ManyOp*)ops.get(), (const u64*)nr.start.get(), (const u32*)cap.get(), nr.a_lo.get(),
+                                   nr.a_hi.get(), P.SB, nr.cnt.get(), t, tally.get());
+            if (ln[1])
+                hipLaunchKernelGGL((k_bucket_atleast<WS, MANY_LDS, 256, COUNT>), dim3(g1), dim3(256), 0, c->stream, (const BDesc*)lists.get() + nb, (const u32*)list_n.get() + 1,
+                                   (const u32*)nr.prefix.get(), (const u64*)hmask.get(), (const ManyOp*)ops.get(), (const u64*)nr.start.get(), (const u32*)cap.get(), nr.a_lo.get(),
+                                   nr.a_hi.get(), P.SB, nr.cnt.get(), t, tally.get() + (size_t)g0 * (MANY_MAX + 1));
+        });
+        CBLX_HIP(hipGetLastError());
+    }
+    if (ln[2]) {
+        StageTimer tm(c, ST_BHUGE);
+        const u32 nl = ln[2];
+        const BDesc* ll = lists.get() + 2 * nb;
+        with_mode([&](auto mode) {
+            constexpr bool COUNT = decltype(mode)::value;
+            hipLaunchKernelGGL((k_bucket_atleast_long<WS, COUNT>), dim3(g2), dim3(256), 0, c->stream, ll, nl, (const u32*)nr.prefix.get(), (const u64*)hmask.get(),
+                               (const ManyOp*)ops.get(), (const u64*)nr.start.get(), (const u32*)cap.get(), nr.a_lo.get(), nr.a_hi.get(), P.SB,
+                               nr.cnt.get(), t, tally.get() + (size_t)(g0 + g1) * (MANY_MAX + 1));
+        });
+        CBLX_HIP(hipGetLastError());
+    }
+    if (count_only) {
+        StageTimer tm(c, ST_COMMON);
+        Buf<u64> partial(c->pool, COMMON_SUM_GROUPS), total(c->pool, 1), d_hist(c->pool, MANY_MAX + 1);
+        const u32 ng = (u32)std::min<u64>(COMMON_SUM_GROUPS, ceil_div(nb, 256));
+        hipLaunchKernelGGL(k_common_sum<u32>, dim3(ng), dim3(256), 0, c->stream, (const u32*)single.get(), nb, partial.get());
+        hipLaunchKernelGGL(k_common_sum<u64>, dim3(1), dim3(256), 0, c->stream, (const u64*)partial.get(), (u64)ng, total.get());
+        hipLaunchKernelGGL(k_tally_sum, dim3(MANY_MAX + 1), dim3(256), 0, c->stream, (const u64*)tally.get(), g0 + g1 + g2, (const u64*)total.get(), d_hist.get());
+        CBLX_HIP(hipGetLastError());
+        ReadGroup rg(c);
+        const size_t h = rg.add(d_hist.get(), MANY_MAX + 1);
+        rg.wait();  // the tables and lists of this call die here
+        for (u32 j = 0; j <= n; ++j) hist[j] = rg.get<u64>(h, j);
+        return Resident();
+    }
+    if (!set_op_tail(c, nr, popc, nwords, N)) return Resident();
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // the lists and tables of this call die here
+    return nr;
+}
 
 template <typename C> void set_op_direct(cblx_ctx* c, Resident& a, Resident& b, u32 op) { c->res = set_op_build<C>(c, a, b, op, false); }
 // `a OP= &mut b` for AND / SUB / XOR, a = c->res: built beside a from a and b, then moved into a, as merge_direct does for `|=`

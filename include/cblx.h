@@ -32,7 +32,7 @@ extern "C" {
  * CBLX_SETOP_MAX_OPERANDS; cblx_remove_words_device, cblx_remove_seq, cblx_remove_seqs, cblx_remove_seqs_device, cblx_remove_fastx_file and cblx_remove_kmers;
  * cblx_export_kmers_range, cblx_export_kmers_range_device, cblx_list_range, cblx_list_range_device, cblx_list_to_fd, cblx_list_to_file and cblx_bucket_nodes;
  * cblx_contains_seqs_counts, cblx_contains_seqs_counts_device, cblx_contains_seqs_flags_counts_device and cblx_query_fastx_file_counts;
- * cblx_intersection_count with CBLX_COMMON_STATS, and cblx_intersection_counts. */
+ * cblx_intersection_count with CBLX_COMMON_STATS, and cblx_intersection_counts; cblx_set_at_least and cblx_occupancy_counts. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -340,6 +340,22 @@ int cblx_set_op_assign(cblx_ctx* a, cblx_ctx* b, uint32_t op);
  * `canonical` / device differ, or op is CBLX_SETOP_SUB / XOR (the reference has no n-ary form of them). */
 #define CBLX_SETOP_MAX_OPERANDS 64
 int cblx_set_op_many(cblx_ctx* dst, cblx_ctx* const* srcs, uint32_t n, uint32_t op);
+/* dst = the k-mers at least t of the n operands srcs[0 .. n) hold, 1 <= t <= n (the reference has no such operation, the rules are
+ * fixed here). t = 1 is cblx_set_op_many with CBLX_SETOP_OR byte for byte, result and operands. t >= 2: a prefix fewer than t operands hold is not visited —
+ * no result bucket, no operand changes there; on a prefix t or more hold every holder's Vec bucket is sorted ascending (Tries are untouched) and the result
+ * bucket is a Vec of the ascending values t holders or more hold, whatever its length, dropped when empty. So for n >= 2, t = n is cblx_set_op_many with
+ * CBLX_SETOP_AND byte for byte. An empty operand counts towards n and holds nothing; with fewer than t non-empty operands the result is empty and nothing is
+ * sorted. dst's content is replaced; pending inserts of every operand are applied first. CBLX_EINVAL, with every context unchanged: as cblx_set_op_many —
+ * n == 0, n > CBLX_SETOP_MAX_OPERANDS, a null entry, dst among srcs, the same context twice, K / PREFIX_BITS / `canonical` / device differ — or t == 0 or
+ * t > n. */
+int cblx_set_at_least(cblx_ctx* dst, cblx_ctx* const* srcs, uint32_t n, uint32_t t);
+/* hist[j] = the number of distinct k-mers exactly j of the n operands hold, j = 0 .. n (hist has n + 1 entries, hist[0] = 0): sum of j * hist[j] = the sum of
+ * the counts, sum of hist[j] = the size of the merge, hist[n] = the size of the intersection. No index is built, but this is NOT cblx_intersection_count's
+ * untouched-operands guarantee: it visits what a merge visits and leaves the operands as a merge does — on every prefix two or more operands hold, their Vec
+ * buckets end up sorted ascending; the sets are unchanged. Buckets one operand holds add their length from the directory alone. Pending inserts of every
+ * operand are applied first. CBLX_EINVAL, with every context unchanged: n == 0, n > CBLX_SETOP_MAX_OPERANDS, a null argument or entry, the same context
+ * twice, or K / PREFIX_BITS / `canonical` / device differ. */
+int cblx_occupancy_counts(cblx_ctx* const* srcs, uint32_t n, uint64_t* hist);
 /* *common = |a AND b|, the number of k-mers both indexes hold, without building an index and without touching the operands: unlike
  * cblx_set_op with CBLX_SETOP_AND nothing is sorted — cblx_serialize of a and of b gives the same bytes before and after the call, kinds and stored order of the
  * Vec buckets included. With |a| and |b| (cblx_count) this one number gives the sizes of union, difference and symmetric difference, Jaccard and containment.

@@ -276,6 +276,8 @@ extern "C" {
     pub fn cblx_set_op(dst: *mut cblx_ctx, a: *mut cblx_ctx, b: *mut cblx_ctx, op: u32) -> c_int;
     pub fn cblx_set_op_assign(a: *mut cblx_ctx, b: *mut cblx_ctx, op: u32) -> c_int;
     pub fn cblx_set_op_many(dst: *mut cblx_ctx, srcs: *const *mut cblx_ctx, n: u32, op: u32) -> c_int;
+    pub fn cblx_set_at_least(dst: *mut cblx_ctx, srcs: *const *mut cblx_ctx, n: u32, t: u32) -> c_int;
+    pub fn cblx_occupancy_counts(srcs: *const *mut cblx_ctx, n: u32, hist: *mut u64) -> c_int;
     pub fn cblx_intersection_count(a: *mut cblx_ctx, b: *mut cblx_ctx, common: *mut u64, stats: *mut u64) -> c_int;
     pub fn cblx_intersection_counts(srcs: *const *mut cblx_ctx, n: u32, out: *mut u64) -> c_int;
     pub fn cblx_get_device(ctx: *const cblx_ctx, out: *mut i32) -> c_int;
