@@ -156,6 +156,10 @@ SIGNATURES = {
                                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_query_fastx_file_counts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                                C.POINTER(C.c_uint64)]),
+    "cblx_contains_seqs_counts_many": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_contains_seqs_counts_many_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_contains_all": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_int)]),
     "cblx_insert_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cblx_remove_words_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
@@ -741,6 +745,64 @@ class CBL:
     def matching_seqs(self, bases, offsets, min_fraction: float = 0.5, min_hits: int = 0):
         """Which sequences of the batch match the index: the boolean mask `matching` of contains_seqs_counts."""
         return self.matching(*self.contains_seqs_counts(bases, offsets), min_fraction=min_fraction, min_hits=min_hits)
+
+    # ---- a batch against a panel of up to 64 indexes in one pass (ours; DESIGN.md section 6i) ----------------------------------------
+    @staticmethod
+    def contains_seqs_counts_many(cbls, bases, offsets, masks: bool = False):
+        """contains_seqs_counts against every index of `cbls` at once: (total uint32[nseq], positive uint32[n, nseq]) — row j is what
+        cbls[j].contains_seqs_counts(bases, offsets) returns — and with `masks` also mask uint64[nk]: one word per k-mer, in the order of
+        contains_seqs' flags, bit j = cbls[j] holds it. The k-mers are encoded and partitioned once for the whole panel; no index is modified or
+        sorted, an empty one counts and holds nothing (include/cblx.h cblx_contains_seqs_counts_many)."""
+        import numpy as np
+
+        cbls = CBL._many_operands(cbls, "contains_seqs_counts_many")
+        n, nseq = len(cbls), max(len(offsets) - 1, 0)
+        total, positive = np.empty(nseq, dtype=np.uint32), np.empty((n, nseq), dtype=np.uint32)
+        mask, cap = None, 0
+        if masks:
+            lens = np.diff(np.asarray(offsets).astype(np.int64)) if nseq else np.zeros(0, dtype=np.int64)
+            cap = int(np.maximum(lens - cbls[0].k + 1, 0).sum())  # no sequence holds more k-mers
+            mask = np.empty(max(cap, 1), dtype=np.uint64)
+        srcs = (C.c_void_p * n)(*[c._h for c in cbls])
+        tot = C.c_uint64(0)
+        cbls[0]._chk(cbls[0]._L.cblx_contains_seqs_counts_many(srcs, n, _ptr(bases), _ptr(offsets), nseq, _ptr(total), _ptr(positive), _ptr(mask), cap, C.byref(tot), None))
+        return (total, positive, mask[: tot.value]) if masks else (total, positive)
+
+    @staticmethod
+    def contains_seqs_counts_many_device(cbls, d_bases, d_offsets, n: int, d_total=None, d_positive=None, d_mask=None):
+        """Device-resident batch of `n` sequences; returns (d_total int32[n], d_positive int32[len(cbls), n]) — uint32 values in int32 storage,
+        as contains_seqs_counts_device — allocated on d_bases' device when not given. d_mask (int64 tensor of at least as many words as the
+        batch has k-mers) also receives the masks; it is then returned as a third value."""
+        import torch
+
+        cbls = CBL._many_operands(cbls, "contains_seqs_counts_many_device")
+        if d_total is None:
+            d_total = torch.empty(n, dtype=torch.int32, device=d_bases.device)
+        if d_positive is None:
+            d_positive = torch.empty((len(cbls), n), dtype=torch.int32, device=d_bases.device)
+        srcs = (C.c_void_p * len(cbls))(*[c._h for c in cbls])
+        tot = C.c_uint64(0)
+        cbls[0]._chk(cbls[0]._L.cblx_contains_seqs_counts_many_device(srcs, len(cbls), _ptr(d_bases), _ptr(d_offsets), n, _ptr(d_total), _ptr(d_positive), _ptr(d_mask),
+                                                                      d_mask.numel() if d_mask is not None else 0, C.byref(tot), None))
+        return (d_total, d_positive) if d_mask is None else (d_total, d_positive, d_mask)
+
+    @staticmethod
+    def classify(total, positive, min_fraction: float = 0.5, min_hits: int = 0):
+        """One index per sequence from the table of contains_seqs_counts_many (host, numpy): int64[nseq], the index with the most hits among
+        those whose row passes `matching`'s rule — positive >= max(min_hits, ceil(min_fraction * total)) and total > 0 — ties to the lowest
+        index, -1 where no index passes."""
+        import numpy as np
+
+        total = np.asarray(total, dtype=np.int64)
+        positive = np.atleast_2d(np.asarray(positive, dtype=np.int64))
+        if positive.shape[1] != len(total):
+            raise ValueError("classify: positive is [n, nseq] for total[nseq]")
+        if positive.shape[0] == 0 or len(total) == 0:
+            return np.full(len(total), -1, dtype=np.int64)
+        ok = np.stack([CBL.matching(total, row, min_fraction=min_fraction, min_hits=min_hits) for row in positive])
+        score = np.where(ok, positive, -1)
+        best = np.argmax(score, axis=0).astype(np.int64)  # (argmax keeps the first of equal maxima: the lowest index)
+        return np.where(ok.any(axis=0), best, -1).astype(np.int64)
 
     def contains_all(self, seq: bytes) -> bool:
         """True if the set contains all the k-mers of a sequence (src/cbl.rs:293-307)."""

@@ -1,7 +1,7 @@
 """`python -m cbl_amd <command>` — the build / insert / remove / merge / inter / diff / sym-diff / count / query / list / repartition subcommands of the
 reference CLI (/root/reference/examples/cbl.rs:147-167,230-269,270-309,168-229,310-366) on the MI355X path, and merge-all / inter-all: the library's `CBL::merge` and
 `CBL::intersect` (src/cbl.rs:106-124) over two or more index files, which the reference's CLI does not expose; `compare` prints the shared k-mers, Jaccard and
-containment of every pair of two or more index files.
+containment of every pair of two or more index files; `classify` assigns every record of a FASTA/Q file to one of two or more index files.
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
 here they are flags with the same defaults (K=25, PREFIX_BITS=24). Index files are interchangeable with the reference's.
@@ -89,6 +89,25 @@ def occupancy_report(hist):
     return lines, human
 
 
+def classify_report(total, positive, assigned):
+    """What `cbl classify` prints, from the table of CBL.contains_seqs_counts_many (total[nseq], positive[n][nseq]) and CBL.classify's
+    assigned[nseq]: one stdout line per record — its 0-based position in the file, the k-mers queried, the n hit counts and the assigned index or
+    `-`, tab-separated — then the summary: one line `index<TAB>reads` per index and `unassigned<TAB>reads`; and sentences for stderr. Host only."""
+    total = [int(t) for t in total]
+    positive = [[int(v) for v in row] for row in positive]
+    assigned = [int(a) for a in assigned]
+    n = len(positive)
+    if any(len(row) != len(total) for row in positive) or len(assigned) != len(total) or any(not -1 <= a < n for a in assigned):
+        raise ValueError("classify_report: positive[n][nseq] and assigned[nseq] in -1 .. n - 1 for total[nseq]")
+    lines = ["\t".join([str(s), str(t)] + [str(row[s]) for row in positive] + [str(assigned[s]) if assigned[s] >= 0 else "-"]) for s, t in enumerate(total)]
+    per = [sum(1 for a in assigned if a == j) for j in range(n)]
+    none = sum(1 for a in assigned if a < 0)
+    summary = [f"{j}\t{per[j]}" for j in range(n)] + [f"unassigned\t{none}"]
+    human = [f"{len(total)} records against {n} indexes: {len(total) - none} assigned, {none} unassigned"]
+    human += [f"Index {j} takes {per[j]} records" for j in range(n)]
+    return lines, summary, human
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cbl_amd")
     ap.add_argument("-k", type=int, default=25, help="k-mer size (odd, <= 59); the reference bakes it in at build time")
@@ -130,6 +149,12 @@ def main(argv=None):
     cmp_ = sub.add_parser("compare", help="Compare two or more indexes pairwise: shared k-mers, union, Jaccard, containment. Every file is loaded first, so "
                                            "all of them sit in device memory at once; no index is built or changed")
     cmp_.add_argument("indexes", nargs="+", metavar="index")
+    cl = sub.add_parser("classify", help="Assign every record of a FASTA/Q file to the index, of two or more, that holds most of its k-mers. The whole "
+                                         "file is staged in device memory at once; no index is changed")
+    cl.add_argument("inputs", nargs="+", metavar="index ... reads", help="two or more index files, then the FASTA/Q file")
+    cl.add_argument("--min-fraction", type=float, default=0.5, metavar="F", help="an index takes a record only if it holds at least this share of its k-mers")
+    cl.add_argument("--min-hits", type=int, default=0, metavar="H", help="... and at least this many of them")
+    cl.add_argument("-o", "--output", help="write the per-record lines and the summary there instead of stdout")
     c = sub.add_parser("count", help="Count the k-mers contained in an index")
     c.add_argument("index")
     q = sub.add_parser("query", help="Query an index for every k-mer contained in a FASTA/Q file")
@@ -215,6 +240,34 @@ def main(argv=None):
         lines, human = compare_report(CBL.intersection_matrix(cbls))
         print("\n".join(human), file=sys.stderr)
         print("\n".join(lines))
+    elif a.cmd == "classify":
+        if len(a.inputs) < 3:
+            ap.error("classify takes two or more index files and a FASTA/Q file")
+        import torch
+
+        cbls = [CBL.load_from_file(path, a.k, a.prefix_bits, device=a.device) for path in a.inputs[:-1]]
+        reads = a.inputs[-1]
+        print(f"Classifying the records of {reads} against {len(cbls)} indexes of {'canonical ' if cbls[0].is_canonical() else ''}{a.k}-mers", file=sys.stderr)
+        stager = cbls[0]  # the whole file at once: one rank, one block no smaller than the record count
+        nrec = stager.count_fastx_records(reads)
+        d_bases, d_offsets, n, _ = stager.stage_fastx_blocks(reads, max(nrec, 1), 0, 1)
+        try:
+            dev = torch.device("cuda", stager.device())
+            d_total = torch.empty(n, dtype=torch.int32, device=dev)
+            d_positive = torch.empty((len(cbls), n), dtype=torch.int32, device=dev)
+            if n:
+                CBL.contains_seqs_counts_many_device(cbls, d_bases, d_offsets, n, d_total, d_positive)
+        finally:
+            stager.stage_release()
+        total, positive = d_total.cpu().numpy().view("uint32"), d_positive.cpu().numpy().view("uint32")
+        lines, summary, human = classify_report(total, positive, CBL.classify(total, positive, min_fraction=a.min_fraction, min_hits=a.min_hits))
+        print("\n".join(human), file=sys.stderr)
+        out = open(a.output, "w") if a.output else sys.stdout
+        try:
+            out.write("".join(line + "\n" for line in lines + summary))
+        finally:
+            if out is not sys.stdout:
+                out.close()
     elif a.cmd == "count":
         cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
         print(f"It contains {cbl.count()} {a.k}-mers", file=sys.stderr)

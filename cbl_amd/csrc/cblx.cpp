@@ -1385,6 +1385,73 @@ int cblx_contains_seqs_counts_device(cblx_ctx* c, const uint8_t* d_bases, const 
                                      uint64_t* n_out, uint64_t* positive) {
     return cblx_contains_seqs_flags_counts_device(c, d_bases, d_offsets, n, nullptr, 0, d_seq_total, d_seq_positive, n_out, positive);
 }
+// the operands of a panel query, checked, flushed and idle; returns the context whose stream, pool and mailbox the work uses: the first non-empty
+// operand, as cblx_occupancy_counts takes it (srcs[0] when every operand is empty)
+static cblx_ctx* panel_operands(cblx_ctx* const* srcs, uint32_t n) {
+    check_many_operands("contains_seqs_counts_many", nullptr, srcs, n);
+    cblx_ctx* c = nullptr;
+    for (uint32_t i = 0; i < n; ++i) {  // an observer: pending inserts are part of the sets
+        flush(srcs[i]);
+        CBLX_HIP(hipStreamSynchronize(srcs[i]->stream));
+        if (!c && srcs[i]->res.count != 0) c = srcs[i];
+    }
+    return c ? c : srcs[0];
+}
+int cblx_contains_seqs_counts_many(cblx_ctx* const* srcs, uint32_t n, const uint8_t* bases, const uint64_t* offsets, uint64_t nseq, uint32_t* seq_total,
+                                   uint32_t* seq_positive, uint64_t* kmer_mask, uint64_t mask_cap, uint64_t* n_out, uint64_t* positive) {
+    return guard(srcs && n ? srcs[0] : nullptr, [&] {
+        cblx_ctx* c = panel_operands(srcs, n);
+        if (nseq == 0) {  // (a refusal writes nothing, n_out and positive included)
+            if (n_out) *n_out = 0;
+            if (positive) for (uint32_t j = 0; j < n; ++j) positive[j] = 0;
+            return;
+        }
+        if (!bases || !offsets) throw Error(CBLX_EINVAL, "null argument");
+        u64 minlen = ~0ull, ub = 0;
+        bool mono = true;
+        for (u64 i = 0; i < nseq; ++i) {
+            mono &= offsets[i + 1] >= offsets[i];
+            const u64 len = offsets[i + 1] - offsets[i];
+            minlen = std::min(minlen, len);
+            ub += len >= c->P.K ? len - c->P.K + 1 : 0;  // no sequence holds more k-mers
+        }
+        if (!mono) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
+        if (minlen < c->P.K) throw Error(CBLX_ESHORT, "Sequence size (" + std::to_string(minlen) + ") is smaller than K (" + std::to_string(c->P.K) + ")");
+        const u64 b0 = offsets[0], nb = offsets[nseq] - b0, mcap = kmer_mask ? std::min<u64>(ub, mask_cap) : 0;
+        Buf<u8> d_b(c->pool, nb + 64);
+        Buf<u64> d_o(c->pool, nseq + 1), d_mask(c->pool, mcap + 2);
+        Buf<u32> d_tot(c->pool, seq_total ? nseq : 1), d_pos(c->pool, seq_positive ? (size_t)n * nseq : 1);
+        std::vector<u64> rel(nseq + 1), pos(n);
+        for (u64 i = 0; i <= nseq; ++i) rel[i] = offsets[i] - b0;
+        xfer(c).h2d_copy(d_b.get(), bases + b0, nb);  // pinned lanes: the caller's buffers are pageable
+        xfer(c).h2d_copy(d_o.get(), rel.data(), (nseq + 1) * 8);
+        xfer(c).sync();
+        u64 tot = 0;
+        query_panel_device(c, srcs, n, d_b.get(), d_o.get(), nseq, seq_total ? d_tot.get() : nullptr, seq_positive ? d_pos.get() : nullptr,
+                           kmer_mask ? d_mask.get() : nullptr, mcap, &tot, pos.data());  // (ERANGE: tot > mcap means tot > mask_cap, as tot <= ub)
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+        if (n_out) *n_out = tot;
+        if (positive) for (uint32_t j = 0; j < n; ++j) positive[j] = pos[j];
+        if (seq_total) xfer(c).d2h_copy(seq_total, d_tot.get(), nseq * 4);
+        if (seq_positive) xfer(c).d2h_copy(seq_positive, d_pos.get(), (size_t)n * nseq * 4);
+        if (kmer_mask && tot) xfer(c).d2h_copy(kmer_mask, d_mask.get(), tot * 8);
+    });
+}
+int cblx_contains_seqs_counts_many_device(cblx_ctx* const* srcs, uint32_t n, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t nseq, uint32_t* d_seq_total,
+                                          uint32_t* d_seq_positive, uint64_t* d_kmer_mask, uint64_t mask_cap, uint64_t* n_out, uint64_t* positive) {
+    return guard(srcs && n ? srcs[0] : nullptr, [&] {
+        cblx_ctx* c = panel_operands(srcs, n);
+        u64 tot = 0;
+        std::vector<u64> pos(n, 0);
+        if (nseq) {
+            if (!d_bases || !d_offsets) throw Error(CBLX_EINVAL, "null argument");
+            query_panel_device(c, srcs, n, d_bases, d_offsets, nseq, d_seq_total, d_seq_positive, d_kmer_mask, mask_cap, &tot, pos.data());
+            CBLX_HIP(hipStreamSynchronize(c->stream));
+        }
+        if (n_out) *n_out = tot;  // (a refusal writes nothing, n_out and positive included)
+        if (positive) for (uint32_t j = 0; j < n; ++j) positive[j] = pos[j];
+    });
+}
 int cblx_contains_all(cblx_ctx* c, const uint8_t* seq, uint64_t len, int* out) {
     return guard(c, [&] {
         if (!out) throw Error(CBLX_EINVAL, "null argument");

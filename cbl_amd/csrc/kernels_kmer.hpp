@@ -90,15 +90,102 @@ __global__ void k_query_tag(u64 n, const HiT* __restrict__ hi, u64* __restrict__
 }
 
 static const u32 JOIN_THREADS = 256, JOIN_FULL_MAX = 2730, JOIN_TAB_MAX = 4095, JOIN_SLOTS = 8192;
+// One resident bucket as a join workgroup sees it, and its class (uniform over the workgroup): `full` and `table` build an LDS table
+// (join_build), a longer Trie is searched and a longer Vec scanned in place (join_probe). k_query_join and k_panel_join share the two.
+template <bool WS> struct JoinBucket {
+    const u64 *lo, *hi;  // the bucket's first arena slot
+    u32 rc, SB;
+    bool trie, full, table;
+    __device__ __forceinline__ Sfx<WS> at(u32 j) const { return load_sfx<WS, u64>(lo, hi, j, SB); }
+};
+template <bool WS>
+__device__ __forceinline__ JoinBucket<WS> join_bucket(const DirView& dir, u64 r, const u64* __restrict__ a_lo, const u64* __restrict__ a_hi, u32 SB) {
+    const u64 rs = dir.start[r];  // the three directory reads first: they are in flight together
+    const u32 rc = dir.count[r];
+    const bool trie = dir.kind[r] == KIND_TRIE;
+    JoinBucket<WS> B;
+    B.lo = a_lo + rs;
+    B.hi = WS ? a_hi + rs : a_hi;
+    B.rc = rc;
+    B.SB = SB;
+    B.trie = trie;
+    // Up to JOIN_TAB_MAX elements (Vec or Trie alike: the elements of a bucket are distinct) go into an open-addressing
+    // table in LDS, at most half full; the tag keeps the probes off global memory until a candidate matches.
+    B.full = !WS && SB < 64 && B.rc <= JOIN_FULL_MAX;
+    B.table = !B.full && B.rc <= JOIN_TAB_MAX;
+    return B;
+}
+// 32 KB of LDS, one of two tables: FULL = 4096 slots holding the suffix itself (narrow suffixes, up to JOIN_FULL_MAX
+// elements: a probe never leaves LDS — a verifying read per hit cost 40 ps, 4x the rest of the join), or 8192 slots of
+// 20-bit tag << 12 | element index (0xFFFFFFFF = empty; index 4095 is never used), verified in the bucket on a tag match.
+// Every thread of the workgroup calls it (barriers inside); nobody may still probe what the table held before.
+template <bool WS> __device__ __forceinline__ void join_build(u64* s_full, const JoinBucket<WS>& B, u32 tid) {
+    u32* s_tab = reinterpret_cast<u32*>(s_full);
+    if (B.full) {
+        for (u32 i = tid; i < JOIN_SLOTS / 2; i += JOIN_THREADS) s_full[i] = ~0ull;
+        __syncthreads();
+        for (u32 j = tid; j < B.rc; j += JOIN_THREADS) {
+            const Sfx<WS> e = B.at(j);
+            u32 h = sfx_hash_bits<WS>(e, 12);
+            while (atomicCAS((unsigned long long*)&s_full[h], ~0ull, (unsigned long long)e.lo) != ~0ull) h = (h + 1u) & (JOIN_SLOTS / 2 - 1u);
+        }
+        __syncthreads();
+    }
+    if (B.table) {
+        for (u32 i = tid; i < JOIN_SLOTS; i += JOIN_THREADS) s_tab[i] = 0xFFFFFFFFu;
+        __syncthreads();
+        for (u32 j = tid; j < B.rc; j += JOIN_THREADS) {
+            const u32 hv = sfx_hash_bits<WS>(B.at(j), 32);
+            u32 h = hv >> 19;
+            const u32 e = ((hv & 0xFFFFFu) << 12) | j;
+            while (atomicCAS(&s_tab[h], 0xFFFFFFFFu, e) != 0xFFFFFFFFu) h = (h + 1u) & (JOIN_SLOTS - 1u);
+        }
+        __syncthreads();
+    }
+}
+template <bool WS> __device__ __forceinline__ bool join_probe(const u64* s_full, const JoinBucket<WS>& B, const Sfx<WS>& key) {
+    const u32* s_tab = reinterpret_cast<const u32*>(s_full);
+    bool hit = false;
+    if (B.full) {
+        u32 h = sfx_hash_bits<WS>(key, 12);
+        for (;;) {
+            const u64 e = s_full[h];
+            if (e == key.lo) { hit = true; break; }
+            if (e == ~0ull) break;
+            h = (h + 1u) & (JOIN_SLOTS / 2 - 1u);
+        }
+    } else if (B.table) {
+        const u32 hv = sfx_hash_bits<WS>(key, 32);
+        u32 h = hv >> 19;
+        const u32 tag = hv & 0xFFFFFu;
+        for (;;) {
+            const u32 e = s_tab[h];
+            if (e == 0xFFFFFFFFu) break;
+            if ((e >> 12) == tag && B.at(e & 0xFFFu) == key) { hit = true; break; }
+            h = (h + 1u) & (JOIN_SLOTS - 1u);
+        }
+    } else if (B.trie) {  // ascending: binary search, the probes of the run's queries share the cache
+        auto less = [](const Sfx<WS>& x, const Sfx<WS>& y) -> bool {
+            if constexpr (WS) { if (x.hi != y.hi) return x.hi < y.hi; }
+            return x.lo < y.lo;
+        };
+        u32 l = 0, h = B.rc;
+        while (l < h) {
+            const u32 mid = (l + h) >> 1;
+            if (less(B.at(mid), key)) l = mid + 1; else h = mid;
+        }
+        hit = l < B.rc && B.at(l) == key;
+    } else {  // a Vec this long only comes out of `|=`
+        for (u32 j = 0; j < B.rc && !hit; ++j) hit = B.at(j) == key;
+    }
+    return hit;
+}
 template <bool WS, typename HiT>
 __global__ __launch_bounds__(JOIN_THREADS) void k_query_join(u64 nbq, u64 b0, const u32* __restrict__ q_prefix, const u64* __restrict__ q_start,
                                                              const u64* __restrict__ q_lo, const HiT* __restrict__ q_hi, u32 SB, DirView dir,
                                                              const u64* __restrict__ a_lo, const u64* __restrict__ a_hi,
                                                              u32* __restrict__ per_run /* zero-filled, one per run */,
                                                              u8* __restrict__ flags = nullptr /* zero-filled; ordinal = q_hi >> 32 */) {
-    // 32 KB of LDS, one of two tables: FULL = 4096 slots holding the suffix itself (narrow suffixes, up to JOIN_FULL_MAX
-    // elements: a probe never leaves LDS — a verifying read per hit cost 40 ps, 4x the rest of the join), or 8192 slots of
-    // 20-bit tag << 12 | element index (0xFFFFFFFF = empty; index 4095 is never used), verified in the bucket on a tag match
     __shared__ u64 s_full[JOIN_SLOTS / 2];
     u32* s_tab = reinterpret_cast<u32*>(s_full);
     const u64 b = b0 + blockIdx.x;
@@ -106,72 +193,12 @@ __global__ __launch_bounds__(JOIN_THREADS) void k_query_join(u64 nbq, u64 b0, co
     u64 r;
     if (!dir_lookup(dir, q_prefix[b], r)) return;  // no resident bucket: every query of the run misses
     const u64 qs = q_start[b], qe = q_start[b + 1];
-    const u64 rs = dir.start[r];
-    const u32 rc = dir.count[r];
-    const bool trie = dir.kind[r] == KIND_TRIE;
     const u32 tid = threadIdx.x;
-    auto res_at = [&](u32 j) -> Sfx<WS> { return load_sfx<WS, u64>(a_lo + rs, WS ? a_hi + rs : a_hi, j, SB); };
-    auto less = [&](const Sfx<WS>& x, const Sfx<WS>& y) -> bool {
-        if constexpr (WS) { if (x.hi != y.hi) return x.hi < y.hi; }
-        return x.lo < y.lo;
-    };
-    // Up to JOIN_TAB_MAX elements (Vec or Trie alike: the elements of a bucket are distinct) go into an open-addressing
-    // table in LDS, at most half full; the tag keeps the probes off global memory until a candidate matches.
-    const bool full = !WS && SB < 64 && rc <= JOIN_FULL_MAX;
-    const bool table = !full && rc <= JOIN_TAB_MAX;
-    if (full) {
-        for (u32 i = tid; i < JOIN_SLOTS / 2; i += JOIN_THREADS) s_full[i] = ~0ull;
-        __syncthreads();
-        for (u32 j = tid; j < rc; j += JOIN_THREADS) {
-            const Sfx<WS> e = res_at(j);
-            u32 h = sfx_hash_bits<WS>(e, 12);
-            while (atomicCAS((unsigned long long*)&s_full[h], ~0ull, (unsigned long long)e.lo) != ~0ull) h = (h + 1u) & (JOIN_SLOTS / 2 - 1u);
-        }
-        __syncthreads();
-    }
-    if (table) {
-        for (u32 i = tid; i < JOIN_SLOTS; i += JOIN_THREADS) s_tab[i] = 0xFFFFFFFFu;
-        __syncthreads();
-        for (u32 j = tid; j < rc; j += JOIN_THREADS) {
-            const u32 hv = sfx_hash_bits<WS>(res_at(j), 32);
-            u32 h = hv >> 19;
-            const u32 e = ((hv & 0xFFFFFu) << 12) | j;
-            while (atomicCAS(&s_tab[h], 0xFFFFFFFFu, e) != 0xFFFFFFFFu) h = (h + 1u) & (JOIN_SLOTS - 1u);
-        }
-        __syncthreads();
-    }
+    const JoinBucket<WS> B = join_bucket<WS>(dir, r, a_lo, a_hi, SB);
+    join_build<WS>(s_full, B, tid);
     u32 found = 0;
     for (u64 q = qs + tid; q < qe; q += JOIN_THREADS) {
-        const Sfx<WS> key = load_sfx<WS, HiT>(q_lo, q_hi, q, SB);
-        bool hit = false;
-        if (full) {
-            u32 h = sfx_hash_bits<WS>(key, 12);
-            for (;;) {
-                const u64 e = s_full[h];
-                if (e == key.lo) { hit = true; break; }
-                if (e == ~0ull) break;
-                h = (h + 1u) & (JOIN_SLOTS / 2 - 1u);
-            }
-        } else if (table) {
-            const u32 hv = sfx_hash_bits<WS>(key, 32);
-            u32 h = hv >> 19;
-            const u32 tag = hv & 0xFFFFFu;
-            for (;;) {
-                const u32 e = s_tab[h];
-                if (e == 0xFFFFFFFFu) break;
-                if ((e >> 12) == tag && res_at(e & 0xFFFu) == key) { hit = true; break; }
-                h = (h + 1u) & (JOIN_SLOTS - 1u);
-            }
-        } else if (trie) {  // ascending: binary search, the probes of the run's queries share the cache
-            u32 l = 0, h = rc;
-            while (l < h) {
-                const u32 mid = (l + h) >> 1;
-                if (less(res_at(mid), key)) l = mid + 1; else h = mid;
-            }
-            hit = l < rc && res_at(l) == key;
-        } else {  // a Vec this long only comes out of `|=`
-            for (u32 j = 0; j < rc && !hit; ++j) hit = res_at(j) == key;
-        }
+        const bool hit = join_probe<WS>(s_full, B, load_sfx<WS, HiT>(q_lo, q_hi, q, SB));
         found += hit ? 1u : 0u;
         if constexpr (std::is_same<HiT, u64>::value && !WS) {  // per-query flags: the query's ordinal rides in the upper half of hi
             if (flags && hit) flags[q_hi[q] >> 32] = 1;
@@ -185,6 +212,52 @@ __global__ __launch_bounds__(JOIN_THREADS) void k_query_join(u64 nbq, u64 b0, co
     if ((tid & 63u) == 0 && found) atomicAdd(&s_tab[0], found);
     __syncthreads();
     if (tid == 0) per_run[b] = s_tab[0];
+}
+
+// ---- a PANEL of indexes in one pass (cblx_contains_seqs_counts_many*): the query words are encoded, tagged with
+// their ordinals and partitioned ONCE; one workgroup then walks a query run through the bucket its prefix has in each of up to 64
+// indexes, and leaves one 64-bit membership mask per k-mer: bit j = index j holds it. The tallies are reduced from the masks. ---------
+struct PanelEntry {  // one index of the panel; an empty index stays in its place with dir.bv = null, dir.nb = 0
+    DirView dir;
+    const u64 *a_lo, *a_hi;
+};
+// mask[ordinal of query q] |= 1 << j for every entry j whose bucket holds q. Lane `tid` owns the queries qs + tid + 256 i in every
+// round: a mask word has one writing lane for the whole kernel, so plain read-modify-writes do (the first query's word stays in a
+// register: most runs are shorter than a workgroup). Everything around a barrier is uniform: dir_lookup and the class depend on (run, j).
+__global__ __launch_bounds__(JOIN_THREADS) void k_panel_join(u64 nbq, u64 b0, const u32* __restrict__ q_prefix, const u64* __restrict__ q_start,
+                                                             const u64* __restrict__ q_lo, const u64* __restrict__ q_hi /* ordinal << 32 | hi bits */,
+                                                             u32 SB, const PanelEntry* __restrict__ panel, u32 n,
+                                                             u64* __restrict__ mask /* zero-filled, one word per query */) {
+    __shared__ u64 s_full[JOIN_SLOTS / 2];
+    const u64 b = b0 + blockIdx.x;
+    if (b >= nbq) return;
+    const u32 p = q_prefix[b], tid = threadIdx.x;
+    const u64 qs = q_start[b], qe = q_start[b + 1];
+    const bool mine = qs + tid < qe;  // the lane's first query: key, ordinal and mask word in registers
+    Sfx<false> key0;
+    key0.lo = 0;
+    u64 m0 = 0;
+    if (mine) key0 = load_sfx<false, u64>(q_lo, q_hi, qs + tid, SB);
+    bool built = false;
+    for (u32 j = 0; j < n; ++j) {
+        const PanelEntry E = panel[j];
+        u64 r;
+        if (!dir_lookup(E.dir, p, r)) continue;  // entry j holds nothing on this prefix
+        const JoinBucket<false> B = join_bucket<false>(E.dir, r, E.a_lo, E.a_hi, SB);
+        if (built) __syncthreads();  // every probe of the previous entry's table is done before it is rebuilt
+        join_build<false>(s_full, B, tid);
+        built = B.full || B.table;
+        const u64 bit = 1ull << j;
+        if (mine && join_probe<false>(s_full, B, key0)) m0 |= bit;
+        for (u64 q = qs + tid + JOIN_THREADS; q < qe; q += JOIN_THREADS)
+            if (join_probe<false>(s_full, B, load_sfx<false, u64>(q_lo, q_hi, q, SB))) mask[q_hi[q] >> 32] |= bit;
+    }
+    if (mine && m0) mask[q_hi[qs + tid] >> 32] = m0;
+}
+// the fallback's per-index flags into the masks: mask[i] |= flag[i] << j (one lane per k-mer)
+__global__ __launch_bounds__(256) void k_mask_or_flags(const u8* __restrict__ flag, u64 nk, u32 j, u64* __restrict__ mask) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nk && flag[i]) mask[i] |= 1ull << j;
 }
 
 // ---- per-sequence tallies (cblx_contains_seqs_counts*): k-mers queried and k-mers found of EVERY sequence of a batch, from the
@@ -260,6 +333,70 @@ __global__ __launch_bounds__(SEQ_TALLY_LONG_THREADS) void k_seq_tally_long(const
         u32 t = 0;
         for (u32 i = 0; i < NW; ++i) t += s_sum[i];
         seq_pos[s] = t;
+    }
+}
+
+// ---- the same two levels from membership MASKS (k_panel_join): n tallies per chunk and per sequence, one per index of the panel.
+// chunk_pos[c * n + j] = k-mers of chunk c that index j holds. One wave per chunk, 64 mask words per round (8-byte loads, coalesced); for
+// j < n the ballot of bit j over the round's words is a row of the transposed 64 x 64 bit matrix, and lane j adds its popcount. The
+// accumulator is one register per lane, selected by lane == j: no per-lane array, no scratch.
+__global__ __launch_bounds__(256) void k_chunk_tally_mask(const u64* __restrict__ mask, const u64* __restrict__ kmer_off /* nchunks + 1 */, u64 c0, u64 nchunks, u32 n,
+                                                          u32* __restrict__ chunk_pos /* nchunks * n */) {
+    const u64 c = c0 + (((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const u32 lane = threadIdx.x & 63;
+    if (c >= nchunks) return;  // whole waves leave together
+    const u64 a = kmer_off[c];
+    const u32 cnt = (u32)(kmer_off[c + 1] - a);
+    u32 acc = 0;
+    for (u32 i0 = 0; i0 < cnt; i0 += 64) {
+        const u64 m = i0 + lane < cnt ? mask[a + i0 + lane] : 0ull;  // a short last round: the lanes past the end hold no bit
+        if (!__any(m != 0)) continue;
+        for (u32 j = 0; j < n; ++j) {
+            const u64 row = __ballot((int)((m >> j) & 1ull));
+            if (lane == j) acc += (u32)__popcll(row);
+        }
+    }
+    if (lane < n) chunk_pos[c * n + lane] = acc;
+}
+// seq_pos[j * nseq + s] = the sum of chunk_pos[. * n + j] over the chunks of sequence s: one lane per (sequence, index), the n lanes of a
+// sequence side by side (their reads of a chunk's n tallies coalesce). Sequences of more than SEQ_TALLY_LANE_MAX chunks go through the long
+// list (entered once per sequence, by its lane of index 0) to k_seq_tally_long_mask: one workgroup per (long sequence, index).
+__global__ __launch_bounds__(256) void k_seq_tally_mask(const u64* __restrict__ seq_chunk /* nseq + 1 */, const u32* __restrict__ chunk_pos, u64 s0, u64 s1 /* this launch's sequences */,
+                                                        u64 nseq, u32 n, u32* __restrict__ seq_pos /* n * nseq */, u32* __restrict__ long_list, u32* __restrict__ long_n,
+                                                        u32 long_cap) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const u64 s = s0 + i / n;
+    const u32 j = (u32)(i % n);
+    if (s >= s1) return;
+    const u64 a = seq_chunk[s], b = seq_chunk[s + 1];
+    if (b - a > SEQ_TALLY_LANE_MAX) {
+        if (j == 0) {
+            const u32 at = atomicAdd(long_n, 1u);  // one per long sequence
+            if (at < long_cap) long_list[at] = (u32)s;
+        }
+        return;
+    }
+    u32 p = 0;
+    for (u64 ch = a; ch < b; ++ch) p += chunk_pos[ch * n + j];
+    seq_pos[(u64)j * nseq + s] = p;
+}
+__global__ __launch_bounds__(SEQ_TALLY_LONG_THREADS) void k_seq_tally_long_mask(const u32* __restrict__ long_list, const u32* __restrict__ long_n,
+                                                                                const u64* __restrict__ seq_chunk, const u32* __restrict__ chunk_pos, u64 nseq, u32 n,
+                                                                                u32* __restrict__ seq_pos) {
+    constexpr u32 NW = SEQ_TALLY_LONG_THREADS / 64;
+    __shared__ u32 s_sum[NW];
+    if (blockIdx.x >= *long_n) return;
+    const u32 s = long_list[blockIdx.x], j = blockIdx.y, tid = threadIdx.x;
+    const u64 a = seq_chunk[s], b = seq_chunk[s + 1];
+    u32 p = 0;
+    for (u64 ch = a + tid; ch < b; ch += SEQ_TALLY_LONG_THREADS) p += chunk_pos[ch * n + j];
+    p = wave_reduce_sum(p);
+    if ((tid & 63u) == 0) s_sum[tid >> 6] = p;
+    __syncthreads();
+    if (tid == 0) {
+        u32 t = 0;
+        for (u32 w = 0; w < NW; ++w) t += s_sum[w];
+        seq_pos[(u64)j * nseq + s] = t;
     }
 }
 

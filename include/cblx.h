@@ -32,7 +32,8 @@ extern "C" {
  * CBLX_SETOP_MAX_OPERANDS; cblx_remove_words_device, cblx_remove_seq, cblx_remove_seqs, cblx_remove_seqs_device, cblx_remove_fastx_file and cblx_remove_kmers;
  * cblx_export_kmers_range, cblx_export_kmers_range_device, cblx_list_range, cblx_list_range_device, cblx_list_to_fd, cblx_list_to_file and cblx_bucket_nodes;
  * cblx_contains_seqs_counts, cblx_contains_seqs_counts_device, cblx_contains_seqs_flags_counts_device and cblx_query_fastx_file_counts;
- * cblx_intersection_count with CBLX_COMMON_STATS, and cblx_intersection_counts; cblx_set_at_least and cblx_occupancy_counts. */
+ * cblx_intersection_count with CBLX_COMMON_STATS, and cblx_intersection_counts; cblx_set_at_least and cblx_occupancy_counts;
+ * cblx_contains_seqs_counts_many and cblx_contains_seqs_counts_many_device. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -413,6 +414,21 @@ int cblx_contains_seqs_flags_counts_device(cblx_ctx* ctx, const uint8_t* d_bases
  * cblx_query_fastx_file. */
 int cblx_query_fastx_file_counts(cblx_ctx* ctx, const char* path, uint32_t* rec_total, uint32_t* rec_positive, uint64_t cap, uint64_t* n_records,
                                  uint64_t* total, uint64_t* positive);
+/* ---- a batch against a PANEL of up to CBLX_SETOP_MAX_OPERANDS indexes in one pass (ours): for every sequence, how many of its k-mers
+ * each of srcs[0 .. n) holds — screening against several references, classification. The k-mers, their order and seq_total[nseq] are exactly those of
+ * cblx_contains_seqs_counts; row j of seq_positive (n * nseq entries, [j * nseq + s]) is what cblx_contains_seqs_counts(srcs[j], ...) returns; bit j of
+ * kmer_mask[i] (mask_cap words, one per k-mer) is flag i of cblx_contains_seqs(srcs[j], ...), bits n and above are 0; positive[j] (n entries) is the sum of
+ * row j and *n_out the number of k-mers. Any of the arrays may be NULL; every entry of every given array is written. The operands are observers: pending
+ * inserts are applied first, nothing is modified or sorted (cblx_serialize of every operand gives the same bytes before and after). An empty operand counts
+ * towards n: its row and its bit are 0. CBLX_EINVAL: n == 0, n > CBLX_SETOP_MAX_OPERANDS, a null argument or entry, the same context twice, or K /
+ * PREFIX_BITS / `canonical` / device differ. A sequence shorter than K is CBLX_ESHORT and mask_cap smaller than the number of k-mers CBLX_ERANGE: nothing is
+ * written then. nseq == 0 writes *n_out = 0 and positive[j] = 0. One call takes fewer than 2^32 - 16 k-mers. The work runs on the stream of the first
+ * non-empty operand. _device: device pointers for bases, offsets (as for cblx_contains_seqs_device) and the three arrays; n_out and positive stay host. */
+int cblx_contains_seqs_counts_many(cblx_ctx* const* srcs, uint32_t n, const uint8_t* bases, const uint64_t* offsets, uint64_t nseq, uint32_t* seq_total,
+                                   uint32_t* seq_positive, uint64_t* kmer_mask, uint64_t mask_cap, uint64_t* n_out, uint64_t* positive);
+int cblx_contains_seqs_counts_many_device(cblx_ctx* const* srcs, uint32_t n, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t nseq,
+                                          uint32_t* d_seq_total, uint32_t* d_seq_positive, uint64_t* d_kmer_mask, uint64_t mask_cap, uint64_t* n_out,
+                                          uint64_t* positive);
 /* CBL::contains_all (src/cbl.rs:293-307): *out = 1 iff every k-mer of the sequence is in the set. */
 int cblx_contains_all(cblx_ctx* ctx, const uint8_t* seq, uint64_t len, int* out);
 

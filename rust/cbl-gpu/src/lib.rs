@@ -469,6 +469,40 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
     pub fn intersect(cbls: Vec<&mut Self>) -> Self {
         Self::set_op_many(cbls, sys::CBLX_SETOP_AND)
     }
+
+    /// `contains_seq` of every sequence against every set of a panel in one pass (no reference counterpart, `cblx_contains_seqs_counts_many`): sequence `i` is
+    /// `bases[offsets[i]..offsets[i + 1]]`. Returns `(total, positive)`: `total[i]` k-mers of sequence `i` were queried and `positive[j][i]` of them are
+    /// in `cbls[j]`. The k-mers are encoded and partitioned once for the whole panel; no set is changed, not even the order inside its Vec buckets.
+    pub fn contains_seqs_counts_many(cbls: Vec<&mut Self>, bases: &[u8], offsets: &[u64]) -> (Vec<u32>, Vec<Vec<u32>>) {
+        assert!(!cbls.is_empty() && cbls.len() <= sys::CBLX_SETOP_MAX_OPERANDS as usize);
+        let canonical = cbls[0].is_canonical();
+        assert!(cbls.iter().all(|c| c.is_canonical() == canonical), "One of the index is canonical while the other isn't");
+        let nseq = offsets.len().saturating_sub(1);
+        for w in offsets.windows(2) {
+            assert!(w[1] >= w[0] && (w[1] - w[0]) as usize >= K, "Sequence size ({}) is smaller than K ({})", w[1].saturating_sub(w[0]), K);
+        }
+        assert!(offsets.last().map_or(true, |&e| e as usize <= bases.len()));
+        let srcs: Vec<*mut sys::cblx_ctx> = cbls.iter().map(|c| c.ctx).collect();
+        let mut total = vec![0u32; nseq];
+        let mut rows = vec![0u32; srcs.len() * nseq];
+        cbls[0].check(unsafe {
+            sys::cblx_contains_seqs_counts_many(
+                srcs.as_ptr(),
+                srcs.len() as u32,
+                bases.as_ptr(),
+                offsets.as_ptr(),
+                nseq as u64,
+                total.as_mut_ptr(),
+                rows.as_mut_ptr(),
+                std::ptr::null_mut(),
+                0,
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+            )
+        });
+        let positive = if nseq == 0 { vec![Vec::new(); srcs.len()] } else { rows.chunks(nseq).map(|r| r.to_vec()).collect() };
+        (total, positive)
+    }
 }
 
 impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> BitAnd<Self> for &mut CBL<K, T, PREFIX_BITS> {

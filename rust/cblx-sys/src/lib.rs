@@ -327,6 +327,32 @@ extern "C" {
         n_out: *mut u64,
         positive: *mut u64,
     ) -> c_int;
+    pub fn cblx_contains_seqs_counts_many(
+        srcs: *const *mut cblx_ctx,
+        n: u32,
+        bases: *const u8,
+        offsets: *const u64,
+        nseq: u64,
+        seq_total: *mut u32,
+        seq_positive: *mut u32,
+        kmer_mask: *mut u64,
+        mask_cap: u64,
+        n_out: *mut u64,
+        positive: *mut u64,
+    ) -> c_int;
+    pub fn cblx_contains_seqs_counts_many_device(
+        srcs: *const *mut cblx_ctx,
+        n: u32,
+        d_bases: *const u8,
+        d_offsets: *const u64,
+        nseq: u64,
+        d_seq_total: *mut u32,
+        d_seq_positive: *mut u32,
+        d_kmer_mask: *mut u64,
+        mask_cap: u64,
+        n_out: *mut u64,
+        positive: *mut u64,
+    ) -> c_int;
     pub fn cblx_contains_seqs_flags_counts_device(
         ctx: *mut cblx_ctx,
         d_bases: *const u8,
