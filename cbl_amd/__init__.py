@@ -172,6 +172,11 @@ SIGNATURES = {
     "cblx_export_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_export_kmers_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "cblx_export_kmers_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cblx_neighbors_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cblx_neighbors_kmers_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cblx_neighbors_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cblx_neighbors_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cblx_degree_table": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cblx_list_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -890,6 +895,105 @@ class CBL:
         got = C.c_uint64(0)
         self._chk(self._L.cblx_export_kmers_range_device(self._h, first, n, _ptr(d_lo), _ptr(d_hi), C.byref(got)))
         return got.value
+
+    # ---- the index as the node set of a de Bruijn graph (Kmer::successors / predecessors, src/kmer.rs:82-90) ---------
+    @staticmethod
+    def neighbor_kmers(kmer: int, k: int):
+        """The eight packed neighbours of a packed k-mer in the bit order of a neighbour mask (host only): [0 .. 3] the successors
+        ((x << 2) | c) & MASK, [4 .. 7] the predecessors (x >> 2) | (c << 2 (K - 1)), c = 0 .. 3 (A C T G)."""
+        x = int(kmer)
+        if k < 1 or x < 0 or x >> (2 * k):
+            raise ValueError("neighbor_kmers: a packed k-mer has 2K bits")
+        mask = (1 << (2 * k)) - 1
+        return [((x << 2) | c) & mask for c in range(4)] + [(x >> 2) | (c << (2 * (k - 1))) for c in range(4)]
+
+    def neighbors_np(self, kmers):
+        """The neighbour mask of every packed k-mer, a uint8 array: bit c = the set holds the successor by base c, bit 4 + c = the
+        predecessor by base c (a canonical index canonicalises the neighbour; the k-mer itself is taken as given and need not be in
+        the set). `kmers`: an iterable of Python ints, or the (lo, hi) uint64 arrays kmers_np returns (hi None for K <= 31)."""
+        import numpy as np
+
+        if isinstance(kmers, tuple) and len(kmers) == 2 and hasattr(kmers[0], "dtype"):
+            lo = np.ascontiguousarray(kmers[0], dtype=np.uint64)
+            hi = None if kmers[1] is None else np.ascontiguousarray(kmers[1], dtype=np.uint64)
+            if hi is not None and len(hi) != len(lo):
+                raise ValueError("neighbors_np: lo and hi differ in length")
+        else:
+            lo, hi = self._split_kmers(kmers)
+        out = np.zeros(max(len(lo), 1), dtype=np.uint8)
+        self._chk(self._L.cblx_neighbors_kmers(self._h, _ptr(lo), _ptr(hi), len(lo), _ptr(out)))
+        return out[: len(lo)]
+
+    def neighbors_device(self, d_lo, d_hi, n: int, d_masks=None):
+        """The same on device arrays (torch int64 / uint64 CUDA tensors or raw device addresses; d_hi may be None for K <= 31);
+        returns d_masks, a torch uint8 CUDA tensor of n bytes allocated here when it is not given."""
+        if d_masks is None:
+            import torch
+
+            d_masks = torch.empty(max(n, 1), dtype=torch.uint8, device=torch.device("cuda", self.device()))[:n]
+        self._chk(self._L.cblx_neighbors_kmers_device(self._h, _ptr(d_lo), _ptr(d_hi), n, _ptr(d_masks)))
+        return d_masks
+
+    def neighbors_range_np(self, first: int = 0, n=None):
+        """The neighbour masks of elements [first, first + n) of the iteration order, a uint8 array: entry i belongs to k-mer i of
+        kmers_np(first, n). The k-mers never leave the device."""
+        import numpy as np
+
+        total = self.count()
+        n = max(min(total - first, total if n is None else n), 0)  # (first > count: the library refuses it)
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        got = C.c_uint64(0)
+        self._chk(self._L.cblx_neighbors_range(self._h, first, n, _ptr(out), C.byref(got)))
+        return out[: got.value]
+
+    def neighbors_range_device(self, first: int, n: int, d_masks) -> int:
+        """The same into device memory (a torch uint8 CUDA tensor or raw device address of n bytes); returns the masks written."""
+        got = C.c_uint64(0)
+        self._chk(self._L.cblx_neighbors_range_device(self._h, first, n, _ptr(d_masks), C.byref(got)))
+        return got.value
+
+    def degree_table(self):
+        """table[out, in] = the k-mers of the set with `out` successors and `in` predecessors in the set: a (5, 5) uint64 array that sums to
+        count(). Computed on the device over the whole index; 200 bytes come back."""
+        import numpy as np
+
+        table = np.zeros(25, dtype=np.uint64)
+        self._chk(self._L.cblx_degree_table(self._h, _ptr(table)))
+        return table.reshape(5, 5)
+
+    @staticmethod
+    def degree_summary(table) -> dict:
+        """What a degree table says about the graph (host only): nodes; out_edges = sum of out * T and in_edges = sum of in * T; isolated
+        (out = in = 0), sources (in = 0 < out), sinks (out = 0 < in), simple (out = in = 1) and branching (out > 1 or in > 1) nodes. Every
+        node is in at least one class, and in two only where a source or a sink has degree 2 or more: it is branching as well."""
+        import numpy as np
+
+        t = np.asarray(table, dtype=np.uint64).reshape(5, 5)
+        T = [[int(v) for v in row] for row in t.tolist()]
+        cells = [(o, i, T[o][i]) for o in range(5) for i in range(5)]
+        return {
+            "nodes": sum(v for _, _, v in cells),
+            "out_edges": sum(o * v for o, _, v in cells),
+            "in_edges": sum(i * v for _, i, v in cells),
+            "isolated": T[0][0],
+            "sources": sum(v for o, i, v in cells if i == 0 and o > 0),
+            "sinks": sum(v for o, i, v in cells if o == 0 and i > 0),
+            "simple": T[1][1],
+            "branching": sum(v for o, i, v in cells if o > 1 or i > 1),
+        }
+
+    def _held_neighbors(self, kmer: int, shift: int):
+        mask = int(self.neighbors_np([kmer])[0]) >> shift
+        nb = self.neighbor_kmers(kmer, self.k)[shift: shift + 4]
+        return [nb[c] for c in range(4) if (mask >> c) & 1]
+
+    def successors(self, kmer: int):
+        """The successors of a packed k-mer that the set holds, as packed k-mers in ascending base code (src/kmer.rs:82-85)."""
+        return self._held_neighbors(kmer, 0)
+
+    def predecessors(self, kmer: int):
+        """The predecessors of a packed k-mer that the set holds, as packed k-mers in ascending base code (src/kmer.rs:87-90)."""
+        return self._held_neighbors(kmer, 4)
 
     def iter(self, chunk: int = 1 << 22):
         """Iterator over the packed k-mers of the set (src/cbl.rs:358-361), pulled from the device `chunk` k-mers at a time: the first

@@ -1,7 +1,8 @@
 """`python -m cbl_amd <command>` — the build / insert / remove / merge / inter / diff / sym-diff / count / query / list / repartition subcommands of the
 reference CLI (/root/reference/examples/cbl.rs:147-167,230-269,270-309,168-229,310-366) on the MI355X path, and merge-all / inter-all: the library's `CBL::merge` and
 `CBL::intersect` (src/cbl.rs:106-124) over two or more index files, which the reference's CLI does not expose; `compare` prints the shared k-mers, Jaccard and
-containment of every pair of two or more index files; `classify` assigns every record of a FASTA/Q file to one of two or more index files.
+containment of every pair of two or more index files; `classify` assigns every record of a FASTA/Q file to one of two or more index files; `graph` prints
+the degree table of the de Bruijn graph whose nodes are the k-mers of an index.
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
 here they are flags with the same defaults (K=25, PREFIX_BITS=24). Index files are interchangeable with the reference's.
@@ -108,6 +109,20 @@ def classify_report(total, positive, assigned):
     return lines, summary, human
 
 
+def graph_report(table):
+    """What `cbl graph` prints, from CBL.degree_table's table[out][in]: five stdout lines, row `out` = 0 .. 4 with its five counts for `in` = 0 .. 4,
+    tab-separated, then one line `key<TAB>value` per entry of CBL.degree_summary in its order; and sentences for stderr. Host only."""
+    rows = [[int(v) for v in row] for row in table]
+    if len(rows) != 5 or any(len(row) != 5 for row in rows):
+        raise ValueError("graph_report: table[5][5], indexed [out][in]")
+    s = CBL.degree_summary(rows)
+    lines = ["\t".join(str(v) for v in row) for row in rows]
+    summary = [f"{key}\t{value}" for key, value in s.items()]
+    human = [f"The de Bruijn graph of the index has {s['nodes']} nodes, {s['out_edges']} outgoing and {s['in_edges']} incoming edges",
+             f"{s['simple']} nodes lie on simple paths, {s['branching']} branch, {s['sources']} are sources, {s['sinks']} sinks and {s['isolated']} isolated"]
+    return lines, summary, human
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cbl_amd")
     ap.add_argument("-k", type=int, default=25, help="k-mer size (odd, <= 59); the reference bakes it in at build time")
@@ -168,6 +183,9 @@ def main(argv=None):
     rp = sub.add_parser("repartition", help="Show statistics about the buckets of an index: sizes, node counts. An empty index prints the prefix load "
                                             "and zeros (the reference panics on an empty index)")
     rp.add_argument("index")
+    gr = sub.add_parser("graph", help="Show the degree table of the de Bruijn graph whose nodes are the k-mers of an index: how many k-mers have `out` "
+                                      "successors and `in` predecessors in the index, and a summary. The index is not changed")
+    gr.add_argument("index")
     a = ap.parse_args(argv)
 
     if a.cmd == "build":
@@ -305,6 +323,12 @@ def main(argv=None):
         sys.stderr.buffer.write(("\n".join(lines) + "\n").encode("utf-8"))
         sys.stderr.buffer.flush()
         print(summary)
+    elif a.cmd == "graph":  # ours (the reference's CLI has no such command): Kmer::successors / predecessors (src/kmer.rs:82-90) over CBL::iter
+        cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
+        print(f"Counting the neighbours of the {'canonical ' if cbl.is_canonical() else ''}{a.k}-mers contained in {a.index}", file=sys.stderr)
+        lines, summary, human = graph_report(cbl.degree_table())
+        print("\n".join(human), file=sys.stderr)
+        print("\n".join(lines + summary))
 
 if __name__ == "__main__":
     main()

@@ -8,6 +8,7 @@
 #include "comm.hpp"
 #include "host_input.hpp"
 #include "kernels_list.hpp"
+#include "kernels_graph.hpp"
 
 namespace {
 
@@ -196,6 +197,82 @@ void range_clamp(cblx_ctx* c, u64 first, u64 n, u64* m) {
     flush(c);
     if (first > c->res.count) throw Error(CBLX_EINVAL, "first = " + std::to_string(first) + " is past the end: the index holds " + std::to_string(c->res.count) + " k-mers");
     *m = std::min<u64>(n, c->res.count - first);
+}
+
+// ---- de Bruijn neighbourhoods (kernels_graph.hpp) ------------------------------------------------------
+// k-mers per pass: 8 words and 8 flag bytes of scratch each. CBLX_NEIGHBOR_PASS overrides the default; at most 2^28, so that the 8 x pass
+// ordinals of a pass stay below 2^32 - 16 and its lanes fit one grid.
+static const u64 NEIGHBOR_PASS_DEFAULT = 1ull << 22, NEIGHBOR_PASS_MAX = 1ull << 28;
+u64 neighbor_pass() {  // read per call: tests switch it
+    const char* e = std::getenv("CBLX_NEIGHBOR_PASS");
+    const u64 p = e ? std::strtoull(e, nullptr, 10) : NEIGHBOR_PASS_DEFAULT;
+    return std::min(std::max<u64>(p, 1), NEIGHBOR_PASS_MAX);
+}
+// d_masks[i] = the neighbour mask of packed k-mer i of device arrays (d_hi may be null for K <= 31) against c's resident index, in passes of at most
+// neighbor_pass() k-mers: k_neighbor_words makes the 8 m words of a pass, a flags query answers them — by the join on tagged records where
+// query_flags_by_join holds and 8 m >= query_join_min(), by k_contains otherwise and on an empty index — and k_fold_neighbor_flags leaves m bytes.
+// `check`: the arrays are a caller's; all of them are checked before the first pass writes a mask (a refusal writes nothing).
+template <typename C> void neighbor_masks_device(cblx_ctx* c, const u64* d_lo, const u64* d_hi, u64 n, u8* d_masks, bool check = true) {
+    typedef typename C::HiT HiT;
+    const Consts& P = c->P;
+    if (n == 0) return;
+    const char* not_kmer = "k-mer has bits set above 2K (not an IntKmer<K>)";
+    Buf<u32> bad(c->pool, 1);
+    CBLX_HIP(hipMemsetAsync(bad.get(), 0, 4, c->stream));
+    if (check) {
+        for (u64 a = 0; a < n; a += 1ull << 31)
+            hipLaunchKernelGGL((k_kmers_check<C::WIDE>), grid1(std::min<u64>(1ull << 31, n - a), 256), dim3(256), 0, c->stream, d_lo + a, d_hi ? d_hi + a : d_hi,
+                               std::min<u64>(1ull << 31, n - a), P, bad.get());
+        CBLX_HIP(hipGetLastError());
+        if (d2h<u32>(c, bad.get())) throw Error(CBLX_EINVAL, not_kmer);
+    }
+    const u64 pass = std::min(neighbor_pass(), n);
+    const bool by_join = query_flags_by_join(P) && c->res.count != 0;
+    const u64 join_min = query_join_min();
+    Buf<u8> flags(c->pool, 8 * pass + 16);
+    for (u64 a = 0; a < n; a += pass) {
+        const u64 m = std::min(pass, n - a), nw = 8 * m;
+        const u64* k_hi = d_hi ? d_hi + a : d_hi;
+        if (by_join && nw >= join_min) {
+            Records rec;
+            begin_tagged_records(c, rec, nw);
+            hipLaunchKernelGGL((k_neighbor_words<C::WIDE, HiT, true>), grid1(nw, 256), dim3(256), 0, c->stream, d_lo + a, k_hi, m, P, rec.lo.get(), (u64*)rec.hi.get(), bad.get());
+            CBLX_HIP(hipGetLastError());
+            CBLX_HIP(hipMemsetAsync(flags.get(), 0, nw, c->stream));
+            join_tagged_records<C>(c, rec, nw, Buf<u32>(), flags.get());  // no fused histogram: the partition counts its first pass itself
+        } else {
+            Buf<u64> w_lo(c->pool, nw + 2);
+            Buf<u8> w_hi(c->pool, (nw + 2) * std::max<size_t>(1, hi_elem_size(P)));
+            hipLaunchKernelGGL((k_neighbor_words<C::WIDE, HiT, false>), grid1(nw, 256), dim3(256), 0, c->stream, d_lo + a, k_hi, m, P, w_lo.get(), (HiT*)w_hi.get(), bad.get());
+            contains_words<C>(c, w_lo.get(), (const HiT*)w_hi.get(), nw, flags.get());
+            CBLX_HIP(hipStreamSynchronize(c->stream));  // the words die here
+        }
+        hipLaunchKernelGGL(k_fold_neighbor_flags, grid1(m, 256), dim3(256), 0, c->stream, (const u64*)flags.get(), m, d_masks + a);
+        CBLX_HIP(hipGetLastError());
+    }
+    if (d2h<u32>(c, bad.get())) throw Error(CBLX_EINVAL, not_kmer);  // (not after the check, and not on exported k-mers) — also: the flags may go back to the pool
+}
+// The same for elements [first, first + n) of the iteration order (n != 0, inside the index), pass by pass: the export path of
+// cblx_export_kmers_range_device fills a scratch k-mer array, which goes through the device form. d_masks (n bytes) and / or d_table (25 words,
+// zeroed by the caller: k_degree_tally adds every pass's masks) take the result.
+void neighbor_masks_range(cblx_ctx* c, u64 first, u64 n, u8* d_masks, u64* d_table) {
+    const u64 pass = std::min(neighbor_pass(), n);
+    const bool wide = c->P.wide_kmer();
+    Buf<u64> res_off, k_lo(c->pool, pass), k_hi(c->pool, wide ? pass : 1);
+    Buf<u8> tmp;
+    if (!d_masks) tmp = Buf<u8>(c->pool, pass);
+    iteration_offsets(c, res_off);
+    for (u64 a = 0; a < n; a += pass) {
+        const u64 m = std::min(pass, n - a);
+        u8* out = d_masks ? d_masks + a : tmp.get();
+        export_range_launch(c, res_off.get(), first + a, m, k_lo.get(), wide ? k_hi.get() : (u64*)nullptr, nullptr);
+        dispatch(c->P, [&](auto cfg) { neighbor_masks_device<decltype(cfg)>(c, k_lo.get(), wide ? k_hi.get() : (const u64*)nullptr, m, out, false); });
+        if (d_table) {
+            hipLaunchKernelGGL(k_degree_tally, dim3((unsigned)std::min<u64>(1024, ceil_div(m, 256))), dim3(256), 0, c->stream, (const u8*)out, m, d_table);
+            CBLX_HIP(hipGetLastError());
+        }
+    }
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // the scratch k-mers and masks die here
 }
 
 // `cbl list`: the lines of the whole index to a file descriptor, chunk by chunk. Two device buffers and two pinned ones: while the device emits
@@ -1671,6 +1748,69 @@ int cblx_export_kmers_range(cblx_ctx* c, uint64_t first, uint64_t n, uint64_t* l
         CBLX_HIP(hipStreamSynchronize(c->stream));
         xfer(c).d2h_copy(lo, d_lo.get(), m * 8);
         if (hi) xfer(c).d2h_copy(hi, d_hi.get(), m * 8);
+    });
+}
+// ---- de Bruijn neighbourhoods: observers, nothing is modified or sorted
+int cblx_neighbors_kmers_device(cblx_ctx* c, const uint64_t* d_lo, const uint64_t* d_hi, uint64_t n, uint8_t* d_masks) {
+    return guard(c, [&] {
+        flush(c);
+        if (n == 0) return;
+        if (!d_masks || !d_lo || (c->P.wide_kmer() && !d_hi)) throw Error(CBLX_EINVAL, c->P.wide_kmer() ? "null argument (K >= 33 needs the hi halves of the k-mers)" : "null argument");
+        dispatch(c->P, [&](auto cfg) { neighbor_masks_device<decltype(cfg)>(c, d_lo, d_hi, n, d_masks); });
+        collect_events(c);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+int cblx_neighbors_kmers(cblx_ctx* c, const uint64_t* lo, const uint64_t* hi, uint64_t n, uint8_t* masks) {
+    return guard(c, [&] {
+        flush(c);
+        if (n == 0) return;
+        if (!masks || !lo || (c->P.wide_kmer() && !hi)) throw Error(CBLX_EINVAL, c->P.wide_kmer() ? "null argument (K >= 33 needs the hi halves of the k-mers)" : "null argument");
+        Buf<u64> k_lo(c->pool, n + 1), k_hi(c->pool, hi ? n + 1 : 1);
+        Buf<u8> d_masks(c->pool, n + 8);
+        xfer(c).h2d_copy(k_lo.get(), lo, n * 8);
+        if (hi) xfer(c).h2d_copy(k_hi.get(), hi, n * 8);
+        xfer(c).sync();
+        dispatch(c->P, [&](auto cfg) { neighbor_masks_device<decltype(cfg)>(c, k_lo.get(), hi ? k_hi.get() : (const u64*)nullptr, n, d_masks.get()); });
+        collect_events(c);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+        xfer(c).d2h_copy(masks, d_masks.get(), n);
+    });
+}
+int cblx_neighbors_range_device(cblx_ctx* c, uint64_t first, uint64_t n, uint8_t* d_masks, uint64_t* written) {
+    return guard(c, [&] {
+        u64 m;
+        range_clamp(c, first, n, &m);
+        if (m && !d_masks) throw Error(CBLX_EINVAL, "null argument");
+        if (written) *written = m;
+        if (m == 0) return;
+        neighbor_masks_range(c, first, m, d_masks, nullptr);
+        collect_events(c);
+    });
+}
+int cblx_neighbors_range(cblx_ctx* c, uint64_t first, uint64_t n, uint8_t* masks, uint64_t* written) {
+    return guard(c, [&] {
+        u64 m;
+        range_clamp(c, first, n, &m);
+        if (m && !masks) throw Error(CBLX_EINVAL, "null argument");
+        if (written) *written = m;
+        if (m == 0) return;
+        Buf<u8> d_masks(c->pool, m + 8);
+        neighbor_masks_range(c, first, m, d_masks.get(), nullptr);
+        collect_events(c);
+        xfer(c).d2h_copy(masks, d_masks.get(), m);
+    });
+}
+int cblx_degree_table(cblx_ctx* c, uint64_t table[25]) {
+    return guard(c, [&] {
+        if (!table) throw Error(CBLX_EINVAL, "null argument");
+        flush(c);
+        Buf<u64> d_table(c->pool, DEGREE_BINS);
+        CBLX_HIP(hipMemsetAsync(d_table.get(), 0, DEGREE_BINS * 8, c->stream));
+        if (c->res.count) neighbor_masks_range(c, 0, c->res.count, nullptr, d_table.get());
+        collect_events(c);
+        const std::vector<u64> t = d2h_vec<u64>(c, d_table.get(), DEGREE_BINS);  // the one read-back: 200 bytes
+        for (u32 i = 0; i < DEGREE_BINS; ++i) table[i] = t[i];
     });
 }
 int cblx_list_range_device(cblx_ctx* c, uint64_t first, uint64_t n, uint8_t* d_buf, uint64_t cap, uint64_t* written_bytes) {

@@ -1280,15 +1280,24 @@ inline EncHist query_hist(cblx_ctx* c, u64 nk, Buf<u32>& countsA) {
 }
 // Queries that keep their positions (words of at most 96 bits, narrow suffix): 16-byte records (lo, ordinal << 32 | hi bits) through the
 // partition of the 64-bit-hi layout. rec.lo / rec.hi end up as the partitioned records, qd as the batch's directory (prefixes, run starts).
-template <typename C> void query_partition_tagged(cblx_ctx* c, const u8* d_bases, const ChunkPlan& pl, Buf<u32>&& countsA, const EncHist& eh, Records& rec, Resident& qd) {
-    typedef typename C::HiT HiT;
-    typedef Cfg<C::WIDE, u64, false> QC;
-    const Consts& P = c->P;
-    const u64 nk = pl.n_kmers;
+// the four buffers of nk tagged records (rec.hi / hi2 hold 64-bit hi parts)
+inline void begin_tagged_records(cblx_ctx* c, Records& rec, u64 nk) {
     rec.lo = Buf<u64>(c->pool, nk + 2);
     rec.lo2 = Buf<u64>(c->pool, nk + 2);
     rec.hi = Buf<u8>(c->pool, (nk + 2) * 8);
     rec.hi2 = Buf<u8>(c->pool, (nk + 2) * 8);
+}
+// nk tagged records in rec.lo / rec.hi, already encoded (by KRN-1 + k_query_tag, or by k_neighbor_words), through the partition. `countsA`: the first pass's
+// tile histogram where the encoder accumulated it (KRN-1), empty where it did not: the partition then counts it itself.
+template <typename C> void partition_tagged(cblx_ctx* c, Records& rec, u64 nk, Buf<u32>&& countsA, Resident& qd) {
+    typedef Cfg<C::WIDE, u64, false> QC;
+    partition_and_directory<QC>(c, rec, nk, std::move(countsA), qd);
+}
+template <typename C> void query_partition_tagged(cblx_ctx* c, const u8* d_bases, const ChunkPlan& pl, Buf<u32>&& countsA, const EncHist& eh, Records& rec, Resident& qd) {
+    typedef typename C::HiT HiT;
+    const Consts& P = c->P;
+    const u64 nk = pl.n_kmers;
+    begin_tagged_records(c, rec, nk);
     {
         Buf<u8> hi_tmp(c->pool, (nk + 2) * std::max<size_t>(1, hi_elem_size(P)));
         encode<C>(c, d_bases, pl, rec.lo.get(), (HiT*)hi_tmp.get(), 0, eh);
@@ -1296,11 +1305,39 @@ template <typename C> void query_partition_tagged(cblx_ctx* c, const u8* d_bases
         CBLX_HIP(hipGetLastError());
         CBLX_HIP(hipStreamSynchronize(c->stream));  // hi_tmp dies here
     }
-    partition_and_directory<QC>(c, rec, nk, std::move(countsA), qd);
+    partition_tagged<C>(c, rec, nk, std::move(countsA), qd);
+}
+// One workgroup per prefix run of the partitioned query records (rec, directory qd) against c's resident index: pos[0] (device, zeroed by the caller) += the
+// queries found; `flags` (zero-filled, or null) takes flag 1 at the ordinal of every query found — tagged records, H = u64, only.
+template <typename C, typename H> void join_runs(cblx_ctx* c, const Records& rec, const Resident& qd, u8* flags, u64* pos) {
+    const Consts& P = c->P;
+    const u64 step = 1ull << 23;  // workgroups per launch (x 256 threads < 2^32 work items)
+    Buf<u32> per_run(c->pool, qd.nb + 1);
+    CBLX_HIP(hipMemsetAsync(per_run.get(), 0, (qd.nb + 1) * 4, c->stream));
+    for (u64 b0 = 0; b0 < qd.nb; b0 += step)
+        hipLaunchKernelGGL((k_query_join<C::WS, H>), dim3((unsigned)std::min(step, qd.nb - b0)), dim3(JOIN_THREADS), 0, c->stream, qd.nb, b0, qd.prefix.get(),
+                           qd.start.get(), rec.lo.get(), (const H*)rec.hi.get(), P.SB, c->res.view(), c->res.a_lo.get(),
+                           P.wide_suffix() ? c->res.a_hi.get() : (const u64*)nullptr, per_run.get(), flags);
+    hipLaunchKernelGGL(k_sum_u32, dim3((unsigned)std::min<u64>(2048, std::max<u64>(1, ceil_div(qd.nb, 256)))), dim3(256), 0, c->stream, per_run.get(), qd.nb, pos);
+    CBLX_HIP(hipGetLastError());
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // per_run dies here
+}
+// The flag join on records that are already encoded and tagged (rec.lo / rec.hi of begin_tagged_records, ordinals 0 .. nk - 1 in the upper halves): partition,
+// then one workgroup per run. d_flags: nk bytes, zero-filled by the caller; returns the number of records found. Narrow suffixes only (query_flags_by_join).
+template <typename C> u64 join_tagged_records(cblx_ctx* c, Records& rec, u64 nk, Buf<u32>&& countsA, u8* d_flags) {
+    if constexpr (!C::WS) {
+        Resident qd;  // directory of the query batch: prefixes and run starts
+        Buf<u64> pos(c->pool, 1);
+        CBLX_HIP(hipMemsetAsync(pos.get(), 0, 8, c->stream));
+        partition_tagged<C>(c, rec, nk, std::move(countsA), qd);
+        join_runs<C, u64>(c, rec, qd, d_flags, pos.get());
+        return d2h<u64>(c, pos.get());  // also: the temporaries may go back to the pool
+    } else {
+        throw Error(CBLX_EDEVICE, "flag join of a wide suffix (internal error)");
+    }
 }
 template <typename C> u64 query_join(cblx_ctx* c, const u8* d_bases /* as left by plan_chunks */, const ChunkPlan& pl, u8* d_flags /* nk bytes or null */) {
     typedef typename C::HiT HiT;
-    const Consts& P = c->P;
     const u64 nk = pl.n_kmers;
     if (d_flags && nk) CBLX_HIP(hipMemsetAsync(d_flags, 0, nk, c->stream));
     if (nk == 0 || c->res.count == 0) return 0;
@@ -1310,30 +1347,17 @@ template <typename C> u64 query_join(cblx_ctx* c, const u8* d_bases /* as left b
     Resident qd;  // directory of the query batch: prefixes and run starts
     Buf<u64> pos(c->pool, 1);
     CBLX_HIP(hipMemsetAsync(pos.get(), 0, 8, c->stream));
-    const u64 step = 1ull << 23;  // workgroups per launch (x 256 threads < 2^32 work items)
-    auto join = [&](auto hi_tag, u8* flags) {
-        typedef decltype(hi_tag) H;
-        Buf<u32> per_run(c->pool, qd.nb + 1);
-        CBLX_HIP(hipMemsetAsync(per_run.get(), 0, (qd.nb + 1) * 4, c->stream));
-        for (u64 b0 = 0; b0 < qd.nb; b0 += step)
-            hipLaunchKernelGGL((k_query_join<C::WS, H>), dim3((unsigned)std::min(step, qd.nb - b0)), dim3(JOIN_THREADS), 0, c->stream, qd.nb, b0, qd.prefix.get(),
-                               qd.start.get(), rec.lo.get(), (const H*)rec.hi.get(), P.SB, c->res.view(), c->res.a_lo.get(),
-                               P.wide_suffix() ? c->res.a_hi.get() : (const u64*)nullptr, per_run.get(), flags);
-        hipLaunchKernelGGL(k_sum_u32, dim3((unsigned)std::min<u64>(2048, std::max<u64>(1, ceil_div(qd.nb, 256)))), dim3(256), 0, c->stream, per_run.get(), qd.nb, pos.get());
-        CBLX_HIP(hipGetLastError());
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // per_run dies here
-    };
     if constexpr (!C::WS) {
         if (d_flags) {
             query_partition_tagged<C>(c, d_bases, pl, std::move(countsA), eh, rec, qd);
-            join(u64(), d_flags);
+            join_runs<C, u64>(c, rec, qd, d_flags, pos.get());
             return d2h<u64>(c, pos.get());
         }
     }
     begin_records<C>(c, rec, nk);
     encode<C>(c, d_bases, pl, rec.lo.get(), (HiT*)rec.hi.get(), 0, eh);
     partition_and_directory<C>(c, rec, nk, std::move(countsA), qd);
-    join(HiT(), (u8*)nullptr);
+    join_runs<C, HiT>(c, rec, qd, (u8*)nullptr, pos.get());
     return d2h<u64>(c, pos.get());  // also: the temporaries may go back to the pool
 }
 // words whose hi part leaves 32 bits for the query's ordinal, and whose suffix fits 64 bits: flags can come from the join

@@ -33,7 +33,8 @@ extern "C" {
  * cblx_export_kmers_range, cblx_export_kmers_range_device, cblx_list_range, cblx_list_range_device, cblx_list_to_fd, cblx_list_to_file and cblx_bucket_nodes;
  * cblx_contains_seqs_counts, cblx_contains_seqs_counts_device, cblx_contains_seqs_flags_counts_device and cblx_query_fastx_file_counts;
  * cblx_intersection_count with CBLX_COMMON_STATS, and cblx_intersection_counts; cblx_set_at_least and cblx_occupancy_counts;
- * cblx_contains_seqs_counts_many and cblx_contains_seqs_counts_many_device. */
+ * cblx_contains_seqs_counts_many and cblx_contains_seqs_counts_many_device;
+ * cblx_neighbors_kmers, cblx_neighbors_kmers_device, cblx_neighbors_range, cblx_neighbors_range_device and cblx_degree_table. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -477,6 +478,27 @@ int cblx_export_kmers(cblx_ctx* ctx, uint64_t* lo, uint64_t* hi, uint64_t cap, u
  * K <= 31, is CBLX_EINVAL when K >= 33. */
 int cblx_export_kmers_range(cblx_ctx* ctx, uint64_t first, uint64_t n, uint64_t* lo, uint64_t* hi, uint64_t* written);
 int cblx_export_kmers_range_device(cblx_ctx* ctx, uint64_t first, uint64_t n, uint64_t* d_lo, uint64_t* d_hi, uint64_t* written);
+/* ---- the index as the node set of a de Bruijn graph: Kmer::successors / Kmer::predecessors (src/kmer.rs:82-90), each looked up with
+ * CBL::contains (src/cbl.rs:219-221). With MASK = 2^(2K) - 1, append(x, c) = ((x << 2) | c) & MASK and prepend(x, c) = (x >> 2) | (c << 2(K - 1)) for a base
+ * code c = 0 .. 3 (A 0, C 1, T 2, G 3), the NEIGHBOUR MASK of a packed k-mer x is one byte: bit c = contains(append(x, c)), bit 4 + c = contains(prepend(x, c)).
+ * A canonical index canonicalises the neighbour, as cblx_contains_kmers does; x itself is taken as given and need not be in the set. A self-loop sets its
+ * bits like any other neighbour, and in a canonical index two bits may name the same stored k-mer: both are set. All five calls are observers: pending inserts
+ * are applied first, nothing is modified or sorted (cblx_serialize gives the same bytes before and after). An empty index gives zero masks and a zero table.
+ * The work runs in passes of CBLX_NEIGHBOR_PASS k-mers (environment, read per call; default 2^22, at most 2^28): 8 words and 8 flag bytes of device scratch per
+ * k-mer of a pass. The 8 m words of a pass are answered as a flags query is: by the join where the word has at most 96 bits and a suffix of at most 64, and
+ * 8 m >= CBLX_QUERY_JOIN_MIN (default 2^22); one bucket read per word otherwise. */
+/* masks[i] = the neighbour mask of packed k-mer i (lo / hi as for cblx_contains_kmers: hi may be NULL when K <= 31). A refusal writes nothing: a null
+ * argument with n > 0 or a k-mer with bits set above 2K is CBLX_EINVAL, wherever in the batch it stands. n == 0 succeeds and writes nothing.
+ * _device: device pointers for the three arrays. */
+int cblx_neighbors_kmers(cblx_ctx* ctx, const uint64_t* lo, const uint64_t* hi, uint64_t n, uint8_t* masks);
+int cblx_neighbors_kmers_device(cblx_ctx* ctx, const uint64_t* d_lo, const uint64_t* d_hi, uint64_t n, uint8_t* d_masks);
+/* The masks of elements [first, first + n) of the iteration order: masks[i] belongs to the k-mer cblx_export_kmers_range writes at index i. Argument rules
+ * and status codes of the range calls above; *written = min(n, count - first). Device workspace is O(CBLX_NEIGHBOR_PASS), not O(n). */
+int cblx_neighbors_range(cblx_ctx* ctx, uint64_t first, uint64_t n, uint8_t* masks, uint64_t* written);
+int cblx_neighbors_range_device(cblx_ctx* ctx, uint64_t first, uint64_t n, uint8_t* d_masks, uint64_t* written);
+/* The degree table of the graph: table[5 * out + in] = the k-mers of the index with out = popcount(mask & 15) successors and in = popcount(mask >> 4)
+ * predecessors in the set; the 25 entries add up to cblx_count. The masks stay on the device: 200 bytes come back. */
+int cblx_degree_table(cblx_ctx* ctx, uint64_t table[25]);
 /* The same elements as text: K bytes of IntKmer::to_nucs (b"ACTG"[code], first base first: src/kmer.rs:26-27) + '\n' each (examples/cbl.rs:190-193). cap in
  * bytes; *written_bytes = (K + 1) * min(n, count - first). When cap is smaller than that the call returns CBLX_ERANGE, *written_bytes is the need and
  * nothing is written. */

@@ -236,6 +236,29 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         out != 0
     }
 
+    /// The neighbour mask of a k-mer against the set, the set as the node set of a de Bruijn graph (`Kmer::successors` /
+    /// `Kmer::predecessors`, `src/kmer.rs:82-90`, each through `contains`): bit `c` = the successor by base `c` is in the set,
+    /// bit `4 + c` = the predecessor by base `c`. The k-mer itself need not be in the set.
+    #[inline]
+    pub fn neighbors(&self, kmer: IntKmer<K, T>) -> u8 {
+        let (lo, hi) = kmer.to_int().split();
+        let mut mask = 0u8;
+        self.check(unsafe { sys::cblx_neighbors_kmers(self.ctx, &lo, &hi, 1, &mut mask) });
+        mask
+    }
+
+    /// `table[out][in]` = the k-mers of the set with `out` successors and `in` predecessors in the set; the entries add up to
+    /// `count()`. Computed on the device over the whole set.
+    pub fn degree_table(&self) -> [[u64; 5]; 5] {
+        let mut flat = [0u64; 25];
+        self.check(unsafe { sys::cblx_degree_table(self.ctx, flat.as_mut_ptr()) });
+        let mut table = [[0u64; 5]; 5];
+        for (i, v) in flat.iter().enumerate() {
+            table[i / 5][i % 5] = *v;
+        }
+        table
+    }
+
     /// Adds a k-mer; returns `true` if it was absent (`src/cbl.rs:226-228`). One device round trip per call: a caller with
     /// many k-mers uses `insert_kmers`.
     #[inline]

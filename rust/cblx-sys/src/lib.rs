@@ -389,6 +389,11 @@ extern "C" {
     pub fn cblx_bucket_sizes(ctx: *mut cblx_ctx, prefix: *mut u32, len: *mut u32, kind: *mut u8, cap: u64, n: *mut u64) -> c_int;
     pub fn cblx_export_kmers_range(ctx: *mut cblx_ctx, first: u64, n: u64, lo: *mut u64, hi: *mut u64, written: *mut u64) -> c_int;
     pub fn cblx_export_kmers_range_device(ctx: *mut cblx_ctx, first: u64, n: u64, d_lo: *mut u64, d_hi: *mut u64, written: *mut u64) -> c_int;
+    pub fn cblx_neighbors_kmers(ctx: *mut cblx_ctx, lo: *const u64, hi: *const u64, n: u64, masks: *mut u8) -> c_int;
+    pub fn cblx_neighbors_kmers_device(ctx: *mut cblx_ctx, d_lo: *const u64, d_hi: *const u64, n: u64, d_masks: *mut u8) -> c_int;
+    pub fn cblx_neighbors_range(ctx: *mut cblx_ctx, first: u64, n: u64, masks: *mut u8, written: *mut u64) -> c_int;
+    pub fn cblx_neighbors_range_device(ctx: *mut cblx_ctx, first: u64, n: u64, d_masks: *mut u8, written: *mut u64) -> c_int;
+    pub fn cblx_degree_table(ctx: *mut cblx_ctx, table: *mut u64) -> c_int;
     pub fn cblx_list_range(ctx: *mut cblx_ctx, first: u64, n: u64, buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_range_device(ctx: *mut cblx_ctx, first: u64, n: u64, d_buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_kmers: u64, n_kmers: *mut u64) -> c_int;
