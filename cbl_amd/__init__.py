@@ -18,6 +18,7 @@ _LIB = None
 
 OK, EINVAL, ESHORT, EFORMAT, EDEVICE, ENOMEM, ERANGE = range(7)
 FLAG_PROFILE = 1
+RANK_ABSENT = (1 << 64) - 1  # what rank_np gives for a k-mer the set does not hold
 
 
 class CblxError(RuntimeError):
@@ -177,6 +178,15 @@ SIGNATURES = {
     "cblx_neighbors_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "cblx_neighbors_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "cblx_degree_table": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cblx_rank_kmers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cblx_rank_kmers_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cblx_unitig_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_unitig_table_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_unitigs_text_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_unitigs_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_unitigs_to_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_list_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -1059,6 +1069,138 @@ class CBL:
         n = C.c_uint64(0)
         self._chk(self._L.cblx_list_to_fd(self._h, fd, chunk, C.byref(n)))
         return n.value
+
+    # ---- unitigs: the non-branching paths of the de Bruijn graph -----------------------------------------
+    def rank_np(self, kmers):
+        """The ordinal of every packed k-mer in the iteration order — the index at which kmers_np / iter give it — as a uint64 array;
+        RANK_ABSENT (2^64 - 1) where the set does not hold the k-mer. A canonical index canonicalises the query, as contains does.
+        `kmers`: an iterable of Python ints, or the (lo, hi) uint64 arrays kmers_np returns (hi None for K <= 31)."""
+        import numpy as np
+
+        if isinstance(kmers, tuple) and len(kmers) == 2 and hasattr(kmers[0], "dtype"):
+            lo = np.ascontiguousarray(kmers[0], dtype=np.uint64)
+            hi = None if kmers[1] is None else np.ascontiguousarray(kmers[1], dtype=np.uint64)
+            if hi is not None and len(hi) != len(lo):
+                raise ValueError("rank_np: lo and hi differ in length")
+        else:
+            lo, hi = self._split_kmers(kmers)
+        out = np.zeros(max(len(lo), 1), dtype=np.uint64)
+        self._chk(self._L.cblx_rank_kmers(self._h, _ptr(lo), _ptr(hi), len(lo), _ptr(out)))
+        return out[: len(lo)]
+
+    def rank_device(self, d_lo, d_hi, n: int, d_rank=None):
+        """The same on device arrays (torch int64 / uint64 CUDA tensors or raw device addresses; d_hi may be None for K <= 31); returns
+        d_rank, a torch int64 CUDA tensor of n elements allocated here when it is not given (an absent k-mer reads -1 in it)."""
+        if d_rank is None:
+            import torch
+
+            d_rank = torch.empty(max(n, 1), dtype=torch.int64, device=torch.device("cuda", self.device()))[:n]
+        self._chk(self._L.cblx_rank_kmers_device(self._h, _ptr(d_lo), _ptr(d_hi), n, _ptr(d_rank)))
+        return d_rank
+
+    def unitig_counts(self):
+        """(k-mers, unitigs, circular unitigs) of a non-canonical index; the whole compaction runs on the device, three numbers come back."""
+        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_unitig_table(self._h, None, None, 0, None, None, None, 0, C.byref(n), C.byref(u), C.byref(c)))
+        return n.value, u.value, c.value
+
+    def unitig_table_np(self) -> dict:
+        """The compaction table of a non-canonical index: per k-mer, by ordinal, `unitig` and `offset` (uint32); per unitig `head` (the
+        ordinal of its first k-mer), `length` (k-mers; uint32) and `flags` (uint8, bit 0 = circular); and `n_circular`. The unitigs are
+        the paths and cycles of the simple edges (x -> y with one successor of x and one predecessor of y in the set), numbered by
+        ascending ordinal of their heads; the head of a cycle is its member with the smallest ordinal."""
+        import numpy as np
+
+        cap = max(self.count(), 1)
+        unitig, offset, head, length = (np.zeros(cap, dtype=np.uint32) for _ in range(4))
+        flags = np.zeros(cap, dtype=np.uint8)
+        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_unitig_table(self._h, _ptr(unitig), _ptr(offset), cap, _ptr(head), _ptr(length), _ptr(flags), cap, C.byref(n), C.byref(u), C.byref(c)))
+        return {"unitig": unitig[: n.value], "offset": offset[: n.value], "head": head[: u.value].copy(), "length": length[: u.value].copy(),
+                "flags": flags[: u.value].copy(), "n_circular": c.value}
+
+    def unitig_table_device(self) -> dict:
+        """The same table as torch CUDA tensors (int32 holding the unsigned 32-bit values, uint8 for `flags`); nothing crosses to the host but
+        the three counts."""
+        import torch
+
+        dev = torch.device("cuda", self.device())
+        cap = max(self.count(), 1)
+        unitig, offset, head, length = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(4))
+        flags = torch.empty(cap, dtype=torch.uint8, device=dev)
+        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_unitig_table_device(self._h, _ptr(unitig), _ptr(offset), cap, _ptr(head), _ptr(length), _ptr(flags), cap, C.byref(n), C.byref(u),
+                                                   C.byref(c)))
+        return {"unitig": unitig[: n.value], "offset": offset[: n.value], "head": head[: u.value].clone(), "length": length[: u.value].clone(),
+                "flags": flags[: u.value].clone(), "n_circular": c.value}
+
+    def unitigs_text_device(self, d_buf=None, cap: int = 0):
+        """(bytes, unitigs) of the unitig text: count() + unitigs * K bytes, one line per unitig — the K letters of its head, the last
+        letter of every following k-mer, '\n'. With d_buf (a torch uint8 CUDA tensor or raw device address of `cap` bytes) the text is
+        written there; without, only the two sizes are computed. A buffer too small raises CblxError(ERANGE) and is left untouched."""
+        nbytes, u = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_unitigs_text_device(self._h, _ptr(d_buf), cap, C.byref(nbytes), C.byref(u)))
+        return nbytes.value, u.value
+
+    def unitigs_text_np(self):
+        """The unitig text as a uint8 array (see unitigs_text_device), built on the device and streamed out once."""
+        import numpy as np
+
+        r, w = os.pipe()
+        got = []
+
+        def reader():
+            with os.fdopen(r, "rb") as f:
+                got.append(f.read())
+
+        import threading
+
+        t = threading.Thread(target=reader)
+        t.start()
+        try:
+            self.unitigs_to_fd(w)
+        finally:
+            os.close(w)
+            t.join()
+        return np.frombuffer(got[0], dtype=np.uint8)
+
+    def unitigs(self):
+        """Generator of the unitigs as str, in unitig order (the text is built once, before the first one is yielded)."""
+        for line in self.unitigs_text_np().tobytes().split(b"\n")[:-1]:
+            yield line.decode("ascii")
+
+    def unitigs_to_file(self, path, chunk_bytes: int = 0):
+        """Writes the unitig text to `path` (created / truncated), streamed from the device in chunks of chunk_bytes (0 = the library's
+        default); returns (unitigs, bytes)."""
+        u, nbytes = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_unitigs_to_file(self._h, os.fsencode(path), chunk_bytes, C.byref(u), C.byref(nbytes)))
+        return u.value, nbytes.value
+
+    def unitigs_to_fd(self, fd: int, chunk_bytes: int = 0):
+        """The same to an open file descriptor (flush any Python-level buffer over it first)."""
+        u, nbytes = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_unitigs_to_fd(self._h, fd, chunk_bytes, C.byref(u), C.byref(nbytes)))
+        return u.value, nbytes.value
+
+    @staticmethod
+    def unitig_summary(length, flags, k: int) -> dict:
+        """What the `length` and `flags` of a compaction table say (host only): unitigs, circular ones, kmers = sum of the lengths,
+        bases = sum of (length + k - 1), the longest unitig in k-mers, and n50: the largest L in bases such that the unitigs of at
+        least L bases hold at least half of all bases (0 for an empty table)."""
+        ls = [int(v) for v in length]
+        fs = [int(v) for v in flags]
+        if len(ls) != len(fs):
+            raise ValueError("unitig_summary: length and flags differ in length")
+        if k < 1 or any(v < 1 for v in ls):
+            raise ValueError("unitig_summary: k and every length are at least 1")
+        bases = sorted((v + k - 1 for v in ls), reverse=True)
+        total, acc, n50 = sum(bases), 0, 0
+        for b in bases:
+            acc += b
+            if 2 * acc >= total:
+                n50 = b
+                break
+        return {"unitigs": len(ls), "circular": sum(f & 1 for f in fs), "kmers": sum(ls), "bases": total, "longest": max(ls, default=0), "n50": n50}
 
     # ---- bucket statistics (src/cbl.rs:364-386) ---------------------------------------------------------------------
     def bucket_table_np(self):

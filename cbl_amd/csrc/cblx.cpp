@@ -9,6 +9,7 @@
 #include "host_input.hpp"
 #include "kernels_list.hpp"
 #include "kernels_graph.hpp"
+#include "kernels_unitig.hpp"
 
 namespace {
 
@@ -278,17 +279,12 @@ void neighbor_masks_range(cblx_ctx* c, u64 first, u64 n, u8* d_masks, u64* d_tab
 // `cbl list`: the lines of the whole index to a file descriptor, chunk by chunk. Two device buffers and two pinned ones: while the device emits
 // chunk i, chunk i - 1 crosses to its pinned buffer and a writer thread hands chunk i - 2 to write(), in order.
 static const u64 LIST_CHUNK_DEFAULT = 1ull << 21;
-void list_to_fd(cblx_ctx* c, int fd, u64 chunk, u64* n_kmers) {
-    flush(c);
-    const Resident& r = c->res;
-    if (n_kmers) *n_kmers = r.count;
-    if (r.count == 0) return;
-    if (chunk == 0) chunk = LIST_CHUNK_DEFAULT;
-    chunk = std::min<u64>(chunk, r.count);
-    const u64 LINE = c->P.K + 1, cbytes = chunk * LINE, nch = ceil_div(r.count, chunk);
-    Buf<u64> res_off;
-    iteration_offsets(c, res_off);
-    Buf<u8> dev[2] = {Buf<u8>(c->pool, cbytes), Buf<u8>(c->pool, nch > 1 ? cbytes : 1)};
+// The stream itself: `total` bytes (not 0) in chunks of `cbytes`. emit(i, len) queues on the ctx's stream whatever makes chunk i and returns where its
+// len bytes will be on the device; what it returned for chunk i - 2 is free again when it is called for chunk i. `what` names the text in the message
+// of a failed write.
+template <typename Emit> void stream_chunks_to_fd(cblx_ctx* c, int fd, u64 total, u64 cbytes, const char* what, Emit&& emit) {
+    const u64 nch = ceil_div(total, cbytes);
+    const u8* src_dev[2] = {nullptr, nullptr};
     struct Pinned {
         u8* p[2] = {nullptr, nullptr};
         hipEvent_t ev[2] = {nullptr, nullptr};
@@ -310,7 +306,7 @@ void list_to_fd(cblx_ctx* c, int fd, u64 chunk, u64* n_kmers) {
         std::thread th;
         ~Writer() { { std::lock_guard<std::mutex> g(mu); quit = true; } cv.notify_all(); if (th.joinable()) th.join(); }
     } wr;
-    auto chunk_len = [&](u64 i) { return std::min<u64>(chunk, r.count - i * chunk) * LINE; };
+    auto chunk_len = [&](u64 i) { return std::min<u64>(cbytes, total - i * cbytes); };
     wr.th = std::thread([&] {
         for (u64 i = 0;; ++i) {
             {
@@ -333,10 +329,10 @@ void list_to_fd(cblx_ctx* c, int fd, u64 chunk, u64* n_kmers) {
             wr.cv.notify_all();
         }
     });
-    auto fail_if_bad = [&] { if (wr.err) throw Error(CBLX_EINVAL, std::string("Failed to write the list: ") + std::strerror(wr.err)); };
+    auto fail_if_bad = [&] { if (wr.err) throw Error(CBLX_EINVAL, std::string("Failed to write the ") + what + ": " + std::strerror(wr.err)); };
     for (u64 i = 0; i <= nch; ++i) {
-        if (i < nch) {  // dev[i & 1] is free: chunk i - 2 was downloaded in the previous round
-            export_range_launch(c, res_off.get(), i * chunk, std::min<u64>(chunk, r.count - i * chunk), nullptr, nullptr, dev[i & 1].get());
+        if (i < nch) {  // chunk i - 2 was downloaded in the previous round
+            src_dev[i & 1] = emit(i, chunk_len(i));
             CBLX_HIP(hipEventRecord(pin.ev[i & 1], c->stream));
         }
         if (i >= 1) {
@@ -347,7 +343,7 @@ void list_to_fd(cblx_ctx* c, int fd, u64 chunk, u64* n_kmers) {
                 wr.cv.wait(g, [&] { return wr.err || wr.written + 2 > j; });
                 fail_if_bad();
             }
-            xfer(c).d2h_copy(pin.p[j & 1], dev[j & 1].get(), chunk_len(j));
+            xfer(c).d2h_copy(pin.p[j & 1], src_dev[j & 1], chunk_len(j));
             { std::lock_guard<std::mutex> g(wr.mu); wr.handed = j + 1; }
             wr.cv.notify_all();
         }
@@ -355,6 +351,197 @@ void list_to_fd(cblx_ctx* c, int fd, u64 chunk, u64* n_kmers) {
     std::unique_lock<std::mutex> g(wr.mu);
     wr.cv.wait(g, [&] { return wr.err || wr.written == nch; });
     fail_if_bad();
+}
+void list_to_fd(cblx_ctx* c, int fd, u64 chunk, u64* n_kmers) {
+    flush(c);
+    const Resident& r = c->res;
+    if (n_kmers) *n_kmers = r.count;
+    if (r.count == 0) return;
+    if (chunk == 0) chunk = LIST_CHUNK_DEFAULT;
+    chunk = std::min<u64>(chunk, r.count);
+    const u64 LINE = c->P.K + 1, cbytes = chunk * LINE, nch = ceil_div(r.count, chunk);
+    Buf<u64> res_off;
+    iteration_offsets(c, res_off);
+    Buf<u8> dev[2] = {Buf<u8>(c->pool, cbytes), Buf<u8>(c->pool, nch > 1 ? cbytes : 1)};
+    stream_chunks_to_fd(c, fd, r.count * LINE, cbytes, "list", [&](u64 i, u64) -> const u8* {
+        export_range_launch(c, res_off.get(), i * chunk, std::min<u64>(chunk, r.count - i * chunk), nullptr, nullptr, dev[i & 1].get());
+        return dev[i & 1].get();
+    });
+}
+// ---- unitigs (kernels_unitig.hpp) ----------------------------------------------------------------------------------
+// rank[i] = the ordinal of word i in the iteration order, ~0 when the index does not hold it (`res_off` of iteration_offsets)
+template <typename C> void rank_words(cblx_ctx* c, const u64* res_off, const u64* w_lo, const typename C::HiT* w_hi, u64 n, u64* d_rank) {
+    typedef typename C::HiT HiT;
+    const u64 step = 1ull << 28;  // QL lanes per query: 2^31 work items per launch
+    for (u64 a = 0; a < n; a += step) {
+        const u64 m = std::min(step, n - a);
+        hipLaunchKernelGGL(k_rank<HiT>, grid1(m * QL, 256), dim3(256), 0, c->stream, w_lo + a, HiTraits<HiT>::has ? w_hi + a : w_hi, m, c->P.SB, c->P.PB, c->res.view(),
+                           c->res.a_lo.get(), c->P.wide_suffix() ? c->res.a_hi.get() : (const u64*)nullptr, res_off, d_rank + a);
+    }
+    CBLX_HIP(hipGetLastError());
+}
+// The ranks of n packed k-mers of device arrays (d_hi may be null for K <= 31; n != 0), in passes of RANK_PASS k-mers: the whole batch is checked
+// before the first pass writes a rank, then k_kmers_to_words (which canonicalises where the index is canonical) and k_rank.
+static const u64 RANK_PASS = 1ull << 24;
+template <typename C> void rank_kmers_device(cblx_ctx* c, const u64* d_lo, const u64* d_hi, u64 n, u64* d_rank) {
+    typedef typename C::HiT HiT;
+    const Consts& P = c->P;
+    Buf<u32> bad(c->pool, 1);
+    CBLX_HIP(hipMemsetAsync(bad.get(), 0, 4, c->stream));
+    for (u64 a = 0; a < n; a += 1ull << 31)
+        hipLaunchKernelGGL((k_kmers_check<C::WIDE>), grid1(std::min<u64>(1ull << 31, n - a), 256), dim3(256), 0, c->stream, d_lo + a, d_hi ? d_hi + a : d_hi,
+                           std::min<u64>(1ull << 31, n - a), P, bad.get());
+    CBLX_HIP(hipGetLastError());
+    if (d2h<u32>(c, bad.get())) throw Error(CBLX_EINVAL, "k-mer has bits set above 2K (not an IntKmer<K>)");
+    const u64 pass = std::min(RANK_PASS, n);
+    Buf<u64> res_off, w_lo(c->pool, pass + 2);
+    Buf<u8> w_hi(c->pool, (pass + 2) * std::max<size_t>(1, hi_elem_size(P)));
+    iteration_offsets(c, res_off);
+    for (u64 a = 0; a < n; a += pass) {
+        const u64 m = std::min(pass, n - a);
+        hipLaunchKernelGGL((k_kmers_to_words<C::WIDE, HiT>), grid1(m, 256), dim3(256), 0, c->stream, d_lo + a, d_hi ? d_hi + a : d_hi, m, P, w_lo.get(), (HiT*)w_hi.get(),
+                           bad.get());
+        rank_words<C>(c, res_off.get(), w_lo.get(), (const HiT*)w_hi.get(), m, d_rank + a);
+    }
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // the words die here
+}
+
+// The compaction of the resident index: links, list ranking and the cut of the pure cycles (compute), then numbering into whatever arrays the
+// caller has (number). Ordinals are 32-bit inside. Every call recomputes.
+struct UnitigRun {
+    u64 n = 0, n_unitigs = 0, n_circular = 0;
+    u32 rounds = 0;  // jump rounds, the ones after a cycle cut included
+    Buf<u32> next, prev, anc[2], dist[2];
+    Buf<u8> circular;
+    int cur = 0;  // anc[cur] / dist[cur] hold the ranking; the other pair is scratch (the head flags and their scan, in the end)
+};
+void unitig_compute(cblx_ctx* c, UnitigRun& u) {
+    flush(c);
+    if (c->P.canonical) throw Error(CBLX_EINVAL, "unitigs of a canonical index (bidirected unitigs) are not supported");
+    const u64 n = c->res.count;
+    if (n >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "the index holds " + std::to_string(n) + " k-mers: unitigs need fewer than 2^32 - 16");
+    u.n = n;
+    if (n == 0) return;
+    const dim3 gn = grid1(n, 256), b256(256);
+    u.next = Buf<u32>(c->pool, n); u.prev = Buf<u32>(c->pool, n);
+    u.circular = Buf<u8>(c->pool, n);
+    for (int i = 0; i < 2; ++i) { u.anc[i] = Buf<u32>(c->pool, n); u.dist[i] = Buf<u32>(c->pool, n); }
+    Buf<u64> counters(c->pool, 130);  // [r] unfinished k-mers of round r; [129] circular unitigs
+    CBLX_HIP(hipMemsetAsync(u.next.get(), 0xFF, n * 4, c->stream));
+    CBLX_HIP(hipMemsetAsync(u.prev.get(), 0xFF, n * 4, c->stream));
+    CBLX_HIP(hipMemsetAsync(u.circular.get(), 0, n, c->stream));
+    CBLX_HIP(hipMemsetAsync(counters.get(), 0, 130 * 8, c->stream));
+    {   // (a) all masks, (b) the links, pass by pass
+        Buf<u8> masks(c->pool, n + 8);
+        neighbor_masks_range(c, 0, n, masks.get(), nullptr);
+        const u64 pass = std::min(neighbor_pass(), n);
+        const bool wide = c->P.wide_kmer();
+        Buf<u64> res_off, k_lo(c->pool, pass), k_hi(c->pool, wide ? pass : 1);
+        iteration_offsets(c, res_off);
+        for (u64 a = 0; a < n; a += pass) {
+            const u64 m = std::min(pass, n - a);
+            export_range_launch(c, res_off.get(), a, m, k_lo.get(), wide ? k_hi.get() : (u64*)nullptr, nullptr);
+            dispatch(c->P, [&](auto cfg) {
+                typedef decltype(cfg) C;
+                hipLaunchKernelGGL((k_unitig_links<C::WIDE>), grid1(m * QL, 256), b256, 0, c->stream, k_lo.get(), wide ? k_hi.get() : (const u64*)nullptr, a, m, masks.get(), c->P,
+                                   c->res.view(), c->res.a_lo.get(), c->P.wide_suffix() ? c->res.a_hi.get() : (const u64*)nullptr, res_off.get(), u.next.get(), u.prev.get());
+            });
+            CBLX_HIP(hipGetLastError());
+        }
+        CBLX_HIP(hipStreamSynchronize(c->stream));  // the masks and the scratch k-mers die here
+    }
+    // (c) pointer jumping; (d) the cycle cut when the count of unfinished k-mers repeats
+    hipLaunchKernelGGL(k_unitig_rank_init, gn, b256, 0, c->stream, u.prev.get(), n, u.anc[0].get(), u.dist[0].get());
+    u.cur = 0;
+    u64 last = ~0ull;
+    bool cut = false;
+    for (u32 r = 0;; ++r) {
+        if (r >= 128) throw Error(CBLX_EDEVICE, "unitig ranking did not end (internal error)");
+        const int o = u.cur ^ 1;
+        hipLaunchKernelGGL(k_unitig_jump, gn, b256, 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), n, u.anc[o].get(), u.dist[o].get(), counters.get() + r);
+        CBLX_HIP(hipGetLastError());
+        u.cur = o;
+        ++u.rounds;
+        const u64 open = d2h<u64>(c, counters.get() + r);  // the k-mers that were unfinished when the round began
+        if (open == 0) break;
+        if (open != last) { last = open; continue; }
+        // every path is finished: the `open` unfinished k-mers are the members of the pure cycles
+        if (cut) throw Error(CBLX_EDEVICE, "unitig ranking stalled after the cycle cut (internal error)");
+        cut = true;
+        last = ~0ull;
+        Buf<u32> lo[2] = {Buf<u32>(c->pool, n), Buf<u32>(c->pool, n)}, ptr[2] = {Buf<u32>(c->pool, n), Buf<u32>(c->pool, n)};
+        hipLaunchKernelGGL(k_cycle_init, gn, b256, 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), u.next.get(), n, lo[0].get(), ptr[0].get());
+        int lc = 0;
+        for (u64 span = 1; span < open; span <<= 1, lc ^= 1)  // a cycle has at most `open` members
+            hipLaunchKernelGGL(k_cycle_min, gn, b256, 0, c->stream, lo[lc].get(), ptr[lc].get(), n, lo[lc ^ 1].get(), ptr[lc ^ 1].get());
+        hipLaunchKernelGGL(k_cycle_cut, gn, b256, 0, c->stream, lo[lc].get(), n, u.next.get(), u.prev.get(), u.circular.get(), u.anc[u.cur].get(), u.dist[u.cur].get(),
+                           counters.get() + 129);
+        CBLX_HIP(hipGetLastError());
+        CBLX_HIP(hipStreamSynchronize(c->stream));  // lo / ptr die here
+    }
+    u.n_circular = d2h<u64>(c, counters.get() + 129);
+    // (e) head flags -> exclusive scan -> unitig numbers, in the scratch pair
+    const int o = u.cur ^ 1;
+    hipLaunchKernelGGL(k_unitig_heads, gn, b256, 0, c->stream, u.prev.get(), n, u.anc[o].get());
+    CBLX_HIP(hipGetLastError());
+    u.n_unitigs = exclusive_scan<u32>(c, u.anc[o].get(), n, u.dist[o].get());
+}
+// per k-mer unitig / offset, per unitig head / length / flags (device arrays of u.n and u.n_unitigs elements; any may be null); u.n != 0
+void unitig_number(cblx_ctx* c, const UnitigRun& u, u32* d_unitig, u32* d_offset, u32* d_head, u32* d_length, u8* d_flags) {
+    hipLaunchKernelGGL(k_unitig_number, grid1(u.n, 256), dim3(256), 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), u.next.get(), u.dist[u.cur ^ 1].get(),
+                       u.circular.get(), u.n, d_unitig, d_offset, d_head, d_length, d_flags);
+    CBLX_HIP(hipGetLastError());
+    CBLX_HIP(hipStreamSynchronize(c->stream));
+}
+void unitig_caps(const UnitigRun& u, bool per_kmer, u64 cap_kmers, bool per_unitig, u64 cap_unitigs) {
+    if ((per_kmer && cap_kmers < u.n) || (per_unitig && cap_unitigs < u.n_unitigs))
+        throw Error(CBLX_ERANGE, "output capacity too small: the index holds " + std::to_string(u.n) + " k-mers in " + std::to_string(u.n_unitigs) + " unitigs");
+}
+// The text of all unitigs in device memory: n + U K bytes, lines in unitig order (text.get() is null for an empty index).
+struct UnitigText {
+    Buf<u8> text;
+    u64 bytes = 0, n_unitigs = 0;
+};
+// `d_out`: the caller's buffer, or null: t.text is allocated. fits(need) is called once the need is known: it may refuse (throw), or return false when the
+// size is all that is wanted.
+template <typename Fits> void unitig_text(cblx_ctx* c, UnitigText& t, u8* d_out, Fits&& fits) {
+    UnitigRun u;
+    unitig_compute(c, u);
+    const u64 n = u.n, nu = u.n_unitigs, K = c->P.K;
+    t.n_unitigs = nu;
+    t.bytes = n + nu * K;
+    if (!fits(t.bytes) || n == 0) return;
+    if (!d_out) { t.text = Buf<u8>(c->pool, t.bytes); d_out = t.text.get(); }
+    Buf<u32> unitig(c->pool, n), offset(c->pool, n), length(c->pool, nu), line(c->pool, nu);
+    Buf<u64> base(c->pool, nu);
+    unitig_number(c, u, unitig.get(), offset.get(), nullptr, length.get(), nullptr);
+    u = UnitigRun();  // the ranking's arrays go back to the pool
+    hipLaunchKernelGGL(k_unitig_line_bytes, grid1(nu, 256), dim3(256), 0, c->stream, length.get(), nu, (u32)K, line.get());
+    CBLX_HIP(hipGetLastError());
+    if (exclusive_scan<u64>(c, line.get(), nu, base.get()) != t.bytes) throw Error(CBLX_EDEVICE, "unitig lengths do not add up (internal error)");
+    const u64 pass = std::min(neighbor_pass(), n);
+    const bool wide = c->P.wide_kmer();
+    Buf<u64> res_off, k_lo(c->pool, pass), k_hi(c->pool, wide ? pass : 1);
+    iteration_offsets(c, res_off);
+    for (u64 a = 0; a < n; a += pass) {
+        const u64 m = std::min(pass, n - a);
+        export_range_launch(c, res_off.get(), a, m, k_lo.get(), wide ? k_hi.get() : (u64*)nullptr, nullptr);
+        hipLaunchKernelGGL(k_unitig_text, grid1(m, 256), dim3(256), 0, c->stream, k_lo.get(), wide ? k_hi.get() : (const u64*)nullptr, a, m, unitig.get(), offset.get(),
+                           length.get(), base.get(), (u32)K, d_out);
+        CBLX_HIP(hipGetLastError());
+    }
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // the table and the scratch k-mers die here
+}
+// `cbl unitigs`: the text is built once on the device and leaves through the two pinned buffers of the list
+void unitigs_to_fd(cblx_ctx* c, int fd, u64 chunk_bytes, u64* n_unitigs, u64* bytes) {
+    UnitigText t;
+    unitig_text(c, t, nullptr, [](u64) { return true; });
+    if (n_unitigs) *n_unitigs = t.n_unitigs;
+    if (bytes) *bytes = t.bytes;
+    if (t.bytes == 0) return;
+    if (chunk_bytes == 0) chunk_bytes = LIST_CHUNK_DEFAULT * (c->P.K + 1);
+    const u64 cbytes = std::min<u64>(chunk_bytes, t.bytes);
+    stream_chunks_to_fd(c, fd, t.bytes, cbytes, "unitigs", [&](u64 i, u64) -> const u8* { return t.text.get() + i * cbytes; });
 }
 }  // namespace
 
@@ -1859,6 +2046,92 @@ int cblx_list_to_file(cblx_ctx* c, const char* path, uint64_t chunk_kmers, uint6
         if (fd < 0) throw Error(CBLX_EINVAL, std::string("Failed to open ") + path);
         try { list_to_fd(c, fd, chunk_kmers, n_kmers); } catch (...) { (void)::close(fd); throw; }
         if (::close(fd) != 0) throw Error(CBLX_EINVAL, std::string("Failed to write the list to ") + path);
+    });
+}
+// ---- unitigs: observers, nothing is modified or sorted
+int cblx_rank_kmers_device(cblx_ctx* c, const uint64_t* d_lo, const uint64_t* d_hi, uint64_t n, uint64_t* d_rank) {
+    return guard(c, [&] {
+        flush(c);
+        if (n == 0) return;
+        if (!d_rank || !d_lo || (c->P.wide_kmer() && !d_hi)) throw Error(CBLX_EINVAL, c->P.wide_kmer() ? "null argument (K >= 33 needs the hi halves of the k-mers)" : "null argument");
+        dispatch(c->P, [&](auto cfg) { rank_kmers_device<decltype(cfg)>(c, d_lo, d_hi, n, d_rank); });
+    });
+}
+int cblx_rank_kmers(cblx_ctx* c, const uint64_t* lo, const uint64_t* hi, uint64_t n, uint64_t* rank) {
+    return guard(c, [&] {
+        flush(c);
+        if (n == 0) return;
+        if (!rank || !lo || (c->P.wide_kmer() && !hi)) throw Error(CBLX_EINVAL, c->P.wide_kmer() ? "null argument (K >= 33 needs the hi halves of the k-mers)" : "null argument");
+        Buf<u64> k_lo(c->pool, n + 1), k_hi(c->pool, hi ? n + 1 : 1), d_rank(c->pool, n + 1);
+        xfer(c).h2d_copy(k_lo.get(), lo, n * 8);
+        if (hi) xfer(c).h2d_copy(k_hi.get(), hi, n * 8);
+        xfer(c).sync();
+        dispatch(c->P, [&](auto cfg) { rank_kmers_device<decltype(cfg)>(c, k_lo.get(), hi ? k_hi.get() : (const u64*)nullptr, n, d_rank.get()); });
+        xfer(c).d2h_copy(rank, d_rank.get(), n * 8);
+    });
+}
+int cblx_unitig_table_device(cblx_ctx* c, uint32_t* d_unitig, uint32_t* d_offset, uint64_t cap_kmers, uint32_t* d_head, uint32_t* d_length, uint8_t* d_flags,
+                             uint64_t cap_unitigs, uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular) {
+    return guard(c, [&] {
+        UnitigRun u;
+        unitig_compute(c, u);
+        collect_events(c);
+        if (n_kmers) *n_kmers = u.n;
+        if (n_unitigs) *n_unitigs = u.n_unitigs;
+        if (n_circular) *n_circular = u.n_circular;
+        unitig_caps(u, d_unitig || d_offset, cap_kmers, d_head || d_length || d_flags, cap_unitigs);
+        if (u.n == 0 || !(d_unitig || d_offset || d_head || d_length || d_flags)) return;
+        unitig_number(c, u, d_unitig, d_offset, d_head, d_length, d_flags);
+    });
+}
+int cblx_unitig_table(cblx_ctx* c, uint32_t* unitig, uint32_t* offset, uint64_t cap_kmers, uint32_t* head, uint32_t* length, uint8_t* flags, uint64_t cap_unitigs,
+                      uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular) {
+    return guard(c, [&] {
+        UnitigRun u;
+        unitig_compute(c, u);
+        collect_events(c);
+        if (n_kmers) *n_kmers = u.n;
+        if (n_unitigs) *n_unitigs = u.n_unitigs;
+        if (n_circular) *n_circular = u.n_circular;
+        unitig_caps(u, unitig || offset, cap_kmers, head || length || flags, cap_unitigs);
+        if (u.n == 0 || !(unitig || offset || head || length || flags)) return;
+        const u64 n = u.n, nu = u.n_unitigs;
+        Buf<u32> d_unitig(c->pool, unitig ? n : 1), d_offset(c->pool, offset ? n : 1), d_head(c->pool, head ? nu : 1), d_length(c->pool, length ? nu : 1);
+        Buf<u8> d_flags(c->pool, flags ? nu : 1);
+        unitig_number(c, u, unitig ? d_unitig.get() : nullptr, offset ? d_offset.get() : nullptr, head ? d_head.get() : nullptr, length ? d_length.get() : nullptr,
+                      flags ? d_flags.get() : nullptr);
+        if (unitig) xfer(c).d2h_copy(unitig, d_unitig.get(), n * 4);
+        if (offset) xfer(c).d2h_copy(offset, d_offset.get(), n * 4);
+        if (head) xfer(c).d2h_copy(head, d_head.get(), nu * 4);
+        if (length) xfer(c).d2h_copy(length, d_length.get(), nu * 4);
+        if (flags) xfer(c).d2h_copy(flags, d_flags.get(), nu);
+    });
+}
+int cblx_unitigs_text_device(cblx_ctx* c, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs) {
+    return guard(c, [&] {
+        UnitigText t;
+        unitig_text(c, t, d_buf, [&](u64 need) {
+            if (bytes) *bytes = need;
+            if (n_unitigs) *n_unitigs = t.n_unitigs;
+            if (d_buf && need > cap) throw Error(CBLX_ERANGE, "buffer too small: need " + std::to_string(need) + " bytes");
+            return d_buf != nullptr;  // null: the size is all that was asked for
+        });
+        collect_events(c);
+    });
+}
+int cblx_unitigs_to_fd(cblx_ctx* c, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes) {
+    return guard(c, [&] {
+        if (fd < 0) throw Error(CBLX_EINVAL, "bad file descriptor");
+        unitigs_to_fd(c, fd, chunk_bytes, n_unitigs, bytes);
+    });
+}
+int cblx_unitigs_to_file(cblx_ctx* c, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes) {
+    return guard(c, [&] {
+        if (!path) throw Error(CBLX_EINVAL, "null argument");
+        const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) throw Error(CBLX_EINVAL, std::string("Failed to open ") + path);
+        try { unitigs_to_fd(c, fd, chunk_bytes, n_unitigs, bytes); } catch (...) { (void)::close(fd); throw; }
+        if (::close(fd) != 0) throw Error(CBLX_EINVAL, std::string("Failed to write the unitigs to ") + path);
     });
 }
 int cblx_bucket_nodes(cblx_ctx* c, uint64_t* nodes, uint64_t cap, uint64_t* n) {

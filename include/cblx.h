@@ -34,7 +34,8 @@ extern "C" {
  * cblx_contains_seqs_counts, cblx_contains_seqs_counts_device, cblx_contains_seqs_flags_counts_device and cblx_query_fastx_file_counts;
  * cblx_intersection_count with CBLX_COMMON_STATS, and cblx_intersection_counts; cblx_set_at_least and cblx_occupancy_counts;
  * cblx_contains_seqs_counts_many and cblx_contains_seqs_counts_many_device;
- * cblx_neighbors_kmers, cblx_neighbors_kmers_device, cblx_neighbors_range, cblx_neighbors_range_device and cblx_degree_table. */
+ * cblx_neighbors_kmers, cblx_neighbors_kmers_device, cblx_neighbors_range, cblx_neighbors_range_device and cblx_degree_table;
+ * cblx_rank_kmers, cblx_rank_kmers_device, cblx_unitig_table, cblx_unitig_table_device, cblx_unitigs_text_device, cblx_unitigs_to_fd and cblx_unitigs_to_file. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -510,6 +511,37 @@ int cblx_list_range_device(cblx_ctx* ctx, uint64_t first, uint64_t n, uint8_t* d
  * before it stays written. *n_kmers = count(). */
 int cblx_list_to_fd(cblx_ctx* ctx, int fd, uint64_t chunk_kmers, uint64_t* n_kmers);
 int cblx_list_to_file(cblx_ctx* ctx, const char* path, uint64_t chunk_kmers, uint64_t* n_kmers);   /* create / truncate, then the above */
+/* ---- unitigs. The ORDINAL of a k-mer is its index in the iteration order: the index at which cblx_export_kmers_range writes it.
+ * rank[i] = the ordinal of packed k-mer i, UINT64_MAX when the set does not hold it: the inverse of the iteration order. Argument rules of
+ * cblx_neighbors_kmers: hi may be NULL when K <= 31; a null argument with n > 0 or a k-mer with bits set above 2K, wherever in the batch, is CBLX_EINVAL
+ * and nothing is written; n == 0 succeeds. A canonical index canonicalises the query, as cblx_contains_kmers does. An observer: pending inserts are
+ * applied first, nothing is modified or sorted. _device: device pointers for the three arrays. */
+int cblx_rank_kmers(cblx_ctx* ctx, const uint64_t* lo, const uint64_t* hi, uint64_t n, uint64_t* rank);
+int cblx_rank_kmers_device(cblx_ctx* ctx, const uint64_t* d_lo, const uint64_t* d_hi, uint64_t n, uint64_t* d_rank);
+/* The compaction table of a NON-CANONICAL index. An edge x -> y (y = append(x, c), both in the set) is SIMPLE when x has one successor and y one
+ * predecessor in the set (the degrees of the neighbour masks; a self-loop counts on both sides). The simple edges cut the set into disjoint paths and
+ * cycles: the UNITIGS. The head of a path is its k-mer without a simple in-edge; a cycle of simple edges only has none: its head is its member with the
+ * smallest ordinal, and the unitig is CIRCULAR. Unitigs are numbered 0 .. U - 1 by ascending ordinal of their heads.
+ *   per k-mer:   unitig[ordinal], offset[ordinal] = the simple edges from the head to it                          (cap_kmers elements each)
+ *   per unitig:  head[u] = the head's ordinal, length[u] = its k-mers, flags[u] bit 0 = circular                   (cap_unitigs elements each)
+ * Any array may be NULL and is then not written; with all five NULL the call only counts. *n_kmers = count(), *n_unitigs = U, *n_circular are always
+ * set (any may be NULL). A capacity below the need of an array that is given is CBLX_ERANGE: the counts are set and nothing is written. A canonical
+ * index is CBLX_EINVAL (bidirected unitigs are not built); 2^32 - 16 k-mers or more are CBLX_ERANGE (ordinals are 32-bit inside). An empty index
+ * gives U = 0. Numbering and the rotation of a circular unitig follow the iteration order, so they follow the Vec buckets' first-occurrence order.
+ * An observer; every call recomputes. Device workspace: about 25 bytes per k-mer. _device: device pointers for the five arrays. */
+int cblx_unitig_table(cblx_ctx* ctx, uint32_t* unitig, uint32_t* offset, uint64_t cap_kmers, uint32_t* head, uint32_t* length, uint8_t* flags,
+                      uint64_t cap_unitigs, uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular);
+int cblx_unitig_table_device(cblx_ctx* ctx, uint32_t* d_unitig, uint32_t* d_offset, uint64_t cap_kmers, uint32_t* d_head, uint32_t* d_length, uint8_t* d_flags,
+                             uint64_t cap_unitigs, uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular);
+/* The text of the unitigs, lines in unitig order: the K letters of the head (b"ACTG"[code], first base first, as cblx_list_range writes them), then the
+ * last letter of every following k-mer in offset order, then '\n': K + length bytes a line, count() + U * K bytes in all. A circular unitig is written
+ * open, from its head. *bytes = the need, *n_unitigs = U. d_buf == NULL gives the sizes only; cap < need is CBLX_ERANGE with the need reported and
+ * nothing written. */
+int cblx_unitigs_text_device(cblx_ctx* ctx, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs);
+/* The same text streamed to a file descriptor: it is built once on the device and leaves in chunks of chunk_bytes (0 = default: the bytes of a
+ * cblx_list_to_fd chunk) through two pinned buffers, as the list does; the error rules are cblx_list_to_fd's. */
+int cblx_unitigs_to_fd(cblx_ctx* ctx, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes);
+int cblx_unitigs_to_file(cblx_ctx* ctx, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes);   /* create / truncate, then the above */
 /* CBL::buckets_nodes (src/cbl.rs:386-390): per non-empty prefix ascending, TrieVec::count_nodes (src/trievec/mod.rs:37-42) — a Vec's length, a Trie's
  * nodes (src/trie.rs:90-102: the root and one node per distinct proper byte prefix of its suffixes). Pairs with cblx_bucket_sizes. */
 int cblx_bucket_nodes(cblx_ctx* ctx, uint64_t* nodes, uint64_t cap, uint64_t* n);

@@ -259,6 +259,36 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         table
     }
 
+    /// The ordinal of a k-mer in the iteration order (the index at which `iter` yields it), `None` when the set does not
+    /// hold it: the inverse of `iter`.
+    #[inline]
+    pub fn rank(&self, kmer: IntKmer<K, T>) -> Option<u64> {
+        let (lo, hi) = kmer.to_int().split();
+        let mut rank = u64::MAX;
+        self.check(unsafe { sys::cblx_rank_kmers(self.ctx, &lo, &hi, 1, &mut rank) });
+        if rank == u64::MAX { None } else { Some(rank) }
+    }
+
+    /// `(k-mers, unitigs, circular unitigs)` of the de Bruijn graph whose nodes are the k-mers of a non-canonical set: the
+    /// non-branching paths and the cycles that its simple edges make. Computed on the device; only the counts come back.
+    pub fn unitig_counts(&self) -> (u64, u64, u64) {
+        let (mut n, mut u, mut c) = (0u64, 0u64, 0u64);
+        let null32 = std::ptr::null_mut::<u32>();
+        self.check(unsafe {
+            sys::cblx_unitig_table(self.ctx, null32, null32, 0, null32, null32, std::ptr::null_mut(), 0, &mut n, &mut u, &mut c)
+        });
+        (n, u, c)
+    }
+
+    /// Writes the unitigs as text to `path` (created or truncated), one line each: the `K` letters of the head, then the
+    /// last letter of every following k-mer. Returns `(unitigs, bytes)`.
+    pub fn unitigs_to_file<P: AsRef<Path>>(&self, path: P) -> (u64, u64) {
+        let cpath = Self::cpath(path);
+        let (mut u, mut bytes) = (0u64, 0u64);
+        self.check(unsafe { sys::cblx_unitigs_to_file(self.ctx, cpath.as_ptr(), 0, &mut u, &mut bytes) });
+        (u, bytes)
+    }
+
     /// Adds a k-mer; returns `true` if it was absent (`src/cbl.rs:226-228`). One device round trip per call: a caller with
     /// many k-mers uses `insert_kmers`.
     #[inline]
