@@ -33,11 +33,16 @@ __global__ __launch_bounds__(256) void k_boundaries(const u64* __restrict__ lo, 
     const u64 i0 = ((u64)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i0 >= n) return;
     u32 p[4];
+    u64 vlo[4];
+    u64 vhi[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < 4; ++k) {  // the four loads first: a prefix computed beside its load kept the next load behind a full wait
         const u64 i = i0 + k < n ? i0 + k : n - 1;
-        p[k] = get_bits(lo[i], ld_hi<HiT>(hi, i), SB, PB);
+        vlo[k] = lo[i];
+        vhi[k] = (u64)ld_hi<HiT>(hi, i);
     }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = get_bits(vlo[k], vhi[k], SB, PB);
     u32 q = __shfl_up(p[3], 1, 64);
     if ((threadIdx.x & 63) == 0) q = i0 > 0 ? get_bits(lo[i0 - 1], ld_hi<HiT>(hi, i0 - 1), SB, PB) : EMPTY32;
 #pragma unroll

@@ -610,11 +610,15 @@ __global__ __launch_bounds__(RDX_THREADS, (HiTraits<HiT>::has && HiTraits<OutHiT
 #pragma unroll
         for (int j = 0; j < RDX_ITEMS; ++j) {
             const u32 e = w * (64 * RDX_ITEMS) + j * 64 + lane;
-            const bool valid = e < n_tile;
-            const u32 eo = valid ? e : 0u;  // tail slots re-read slot 0 and are never written back
+            const u32 eo = e < n_tile ? e : 0u;  // tail slots re-read slot 0 and are never written back
             klo[j] = __builtin_nontemporal_load(&lo_t[eo]);
             if constexpr (HiTraits<HiT>::has) khi[j] = __builtin_nontemporal_load(&hi_t[eo]); else khi[j] = 0;
-            if constexpr (!TABLE) digit[j] = valid ? dfn(klo[j], (u64)khi[j]) : 255u;
+        }
+        // the digits in a loop of their own: computed beside its load, each digit's conditional block kept the next load behind a
+        // full wait (eight memory round trips per tile instead of one)
+        if constexpr (!TABLE) {
+#pragma unroll
+            for (int j = 0; j < RDX_ITEMS; ++j) digit[j] = w * (64 * RDX_ITEMS) + j * 64 + lane < n_tile ? dfn(klo[j], (u64)khi[j]) : 255u;
         }
     }
     if constexpr (TABLE) {
@@ -989,15 +993,18 @@ __global__ __launch_bounds__(THREADS) void k_prefix_split(const SplitRun* __rest
         for (u32 t = 0; t < ntiles; ++t) {
             const u32 t0 = t * TILE, n_tile = c - t0 < (u32)TILE ? c - t0 : (u32)TILE;
             u32 dg[SPLIT_ITEMS];
+            u64 v[SPLIT_ITEMS], h[HAS ? SPLIT_ITEMS : 1];
+            // every load of the tile first, the digits in a loop of their own (as in k_radix_scatter: a digit computed beside its load
+            // kept the next load behind a full wait)
 #pragma unroll
             for (int j = 0; j < SPLIT_ITEMS; ++j) {
                 const u32 e = j * THREADS + tid;  // (order does not matter for counting: coalesced rows)
-                const bool valid = e < n_tile;
-                const u64 v = lo_r[t0 + (valid ? e : 0u)];
-                u64 h = 0;
-                if constexpr (HAS) h = (u64)hi_r[t0 + (valid ? e : 0u)];
-                dg[j] = valid ? (u32)get_bits(v, h, SB, xb) : 0xFFu;
+                const u32 eo = e < n_tile ? e : 0u;
+                v[j] = lo_r[t0 + eo];
+                if constexpr (HAS) h[j] = (u64)hi_r[t0 + eo];
             }
+#pragma unroll
+            for (int j = 0; j < SPLIT_ITEMS; ++j) dg[j] = (u32)j * THREADS + tid < n_tile ? (u32)get_bits(v[j], HAS ? h[j] : 0ull, SB, xb) : 0xFFu;
 #pragma unroll
             for (int j = 0; j < SPLIT_ITEMS; ++j)
 #pragma unroll
@@ -1030,9 +1037,13 @@ __global__ __launch_bounds__(THREADS) void k_prefix_split(const SplitRun* __rest
 #pragma unroll
         for (int j = 0; j < SPLIT_ITEMS; ++j) {
             const u32 e = w * EPW + j * 64 + lane;
-            const bool valid = (u32)j < R && e < n_tile;
-            klo[j] = lo_r[t0 + (valid ? e : 0u)];  // (non-temporal loads here: +0.5 ms at cfg 3, measured)
-            if constexpr (HAS) khi[j] = (u64)hi_r[t0 + (valid ? e : 0u)];
+            const u32 eo = (u32)j < R && e < n_tile ? e : 0u;
+            klo[j] = lo_r[t0 + eo];  // (non-temporal loads here: +0.5 ms at cfg 3, measured)
+            if constexpr (HAS) khi[j] = (u64)hi_r[t0 + eo];
+        }
+#pragma unroll
+        for (int j = 0; j < SPLIT_ITEMS; ++j) {  // the digits behind all the loads
+            const bool valid = (u32)j < R && w * EPW + j * 64 + lane < n_tile;
             dp[j] = valid ? (u32)get_bits(klo[j], HAS ? khi[j] : 0ull, SB, xb) : 0xFFu;
         }
 #pragma unroll
