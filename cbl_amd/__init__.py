@@ -187,6 +187,13 @@ SIGNATURES = {
     "cblx_unitigs_text_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_unitigs_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_unitigs_to_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_biunitig_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_biunitig_table_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_biunitigs_text_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_biunitigs_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_biunitigs_to_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_list_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -1142,8 +1149,10 @@ class CBL:
         self._chk(self._L.cblx_unitigs_text_device(self._h, _ptr(d_buf), cap, C.byref(nbytes), C.byref(u)))
         return nbytes.value, u.value
 
-    def unitigs_text_np(self):
-        """The unitig text as a uint8 array (see unitigs_text_device), built on the device and streamed out once."""
+    def _text_np(self, to_fd):
+        """What to_fd(descriptor) writes, as a uint8 array: a pipe, read by a thread while the library streams into it."""
+        import threading
+
         import numpy as np
 
         r, w = os.pipe()
@@ -1153,16 +1162,18 @@ class CBL:
             with os.fdopen(r, "rb") as f:
                 got.append(f.read())
 
-        import threading
-
         t = threading.Thread(target=reader)
         t.start()
         try:
-            self.unitigs_to_fd(w)
+            to_fd(w)
         finally:
             os.close(w)
             t.join()
         return np.frombuffer(got[0], dtype=np.uint8)
+
+    def unitigs_text_np(self):
+        """The unitig text as a uint8 array (see unitigs_text_device), built on the device and streamed out once."""
+        return self._text_np(self.unitigs_to_fd)
 
     def unitigs(self):
         """Generator of the unitigs as str, in unitig order (the text is built once, before the first one is yielded)."""
@@ -1184,7 +1195,7 @@ class CBL:
 
     @staticmethod
     def unitig_summary(length, flags, k: int) -> dict:
-        """What the `length` and `flags` of a compaction table say (host only): unitigs, circular ones, kmers = sum of the lengths,
+        """What the `length` and `flags` of a compaction table — unitig_table_np's or biunitig_table_np's — say (host only): unitigs, circular ones, kmers = sum of the lengths,
         bases = sum of (length + k - 1), the longest unitig in k-mers, and n50: the largest L in bases such that the unitigs of at
         least L bases hold at least half of all bases (0 for an empty table)."""
         ls = [int(v) for v in length]
@@ -1201,6 +1212,75 @@ class CBL:
                 n50 = b
                 break
         return {"unitigs": len(ls), "circular": sum(f & 1 for f in fs), "kmers": sum(ls), "bases": total, "longest": max(ls, default=0), "n50": n50}
+
+    # ---- bidirected unitigs: the unitigs of a canonical index with odd K --------------------------------------
+    def biunitig_counts(self):
+        """(k-mers, unitigs, circular unitigs) of a canonical index with odd K: the compaction over oriented k-mers runs on the device,
+        three numbers come back."""
+        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_biunitig_table(self._h, None, None, None, 0, None, None, None, 0, C.byref(n), C.byref(u), C.byref(c)))
+        return n.value, u.value, c.value
+
+    def biunitig_table_np(self) -> dict:
+        """The compaction table of a canonical index: the dict of unitig_table_np plus `reversed` (uint8 per k-mer, by ordinal): 1 where the
+        unitig runs through the reverse complement of the stored form. An edge joins two ORIENTED k-mers; it is simple when the one has
+        one successor, the other one predecessor, and they are not the same stored k-mer (so poly-A alone is a unitig of length 1 that is
+        not circular, unlike unitig_table_np). Of a unitig's two mirror images the one whose head has the smaller ordinal than its tail
+        is kept (a cycle: the one whose smallest member is not reversed)."""
+        import numpy as np
+
+        cap = max(self.count(), 1)
+        unitig, offset, head, length = (np.zeros(cap, dtype=np.uint32) for _ in range(4))
+        rev, flags = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype=np.uint8)
+        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_biunitig_table(self._h, _ptr(unitig), _ptr(offset), _ptr(rev), cap, _ptr(head), _ptr(length), _ptr(flags), cap, C.byref(n), C.byref(u),
+                                              C.byref(c)))
+        return {"unitig": unitig[: n.value], "offset": offset[: n.value], "reversed": rev[: n.value], "head": head[: u.value].copy(),
+                "length": length[: u.value].copy(), "flags": flags[: u.value].copy(), "n_circular": c.value}
+
+    def biunitig_table_device(self) -> dict:
+        """The same table as torch CUDA tensors (int32 holding the unsigned 32-bit values, uint8 for `reversed` and `flags`); nothing crosses
+        to the host but the three counts."""
+        import torch
+
+        dev = torch.device("cuda", self.device())
+        cap = max(self.count(), 1)
+        unitig, offset, head, length = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(4))
+        rev, flags = torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(cap, dtype=torch.uint8, device=dev)
+        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_biunitig_table_device(self._h, _ptr(unitig), _ptr(offset), _ptr(rev), cap, _ptr(head), _ptr(length), _ptr(flags), cap, C.byref(n),
+                                                     C.byref(u), C.byref(c)))
+        return {"unitig": unitig[: n.value], "offset": offset[: n.value], "reversed": rev[: n.value], "head": head[: u.value].clone(),
+                "length": length[: u.value].clone(), "flags": flags[: u.value].clone(), "n_circular": c.value}
+
+    def biunitigs_text_device(self, d_buf=None, cap: int = 0):
+        """(bytes, unitigs) of the bidirected unitig text: count() + unitigs * K bytes, one line per unitig — the K letters its head spells
+        in its orientation, the last letter every following member spells in its own, '\n'. d_buf and cap as in unitigs_text_device."""
+        nbytes, u = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_biunitigs_text_device(self._h, _ptr(d_buf), cap, C.byref(nbytes), C.byref(u)))
+        return nbytes.value, u.value
+
+    def biunitigs_text_np(self):
+        """The bidirected unitig text as a uint8 array, built on the device and streamed out once."""
+        return self._text_np(self.biunitigs_to_fd)
+
+    def biunitigs(self):
+        """Generator of the bidirected unitigs as str, in unitig order (the text is built once, before the first one is yielded)."""
+        for line in self.biunitigs_text_np().tobytes().split(b"\n")[:-1]:
+            yield line.decode("ascii")
+
+    def biunitigs_to_file(self, path, chunk_bytes: int = 0):
+        """Writes the bidirected unitig text to `path` (created / truncated), streamed from the device in chunks of chunk_bytes (0 = the
+        library's default); returns (unitigs, bytes)."""
+        u, nbytes = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_biunitigs_to_file(self._h, os.fsencode(path), chunk_bytes, C.byref(u), C.byref(nbytes)))
+        return u.value, nbytes.value
+
+    def biunitigs_to_fd(self, fd: int, chunk_bytes: int = 0):
+        """The same to an open file descriptor (flush any Python-level buffer over it first)."""
+        u, nbytes = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_biunitigs_to_fd(self._h, fd, chunk_bytes, C.byref(u), C.byref(nbytes)))
+        return u.value, nbytes.value
 
     # ---- bucket statistics (src/cbl.rs:364-386) ---------------------------------------------------------------------
     def bucket_table_np(self):

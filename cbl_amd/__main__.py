@@ -2,7 +2,8 @@
 reference CLI (/root/reference/examples/cbl.rs:147-167,230-269,270-309,168-229,310-366) on the MI355X path, and merge-all / inter-all: the library's `CBL::merge` and
 `CBL::intersect` (src/cbl.rs:106-124) over two or more index files, which the reference's CLI does not expose; `compare` prints the shared k-mers, Jaccard and
 containment of every pair of two or more index files; `classify` assigns every record of a FASTA/Q file to one of two or more index files; `graph` prints
-the degree table of the de Bruijn graph whose nodes are the k-mers of an index; `unitigs` writes the non-branching paths of that graph, one line each.
+the degree table of the de Bruijn graph whose nodes are the k-mers of an index; `unitigs` writes the non-branching paths of that graph, one line each
+(of a canonical index: the bidirected unitigs).
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
 here they are flags with the same defaults (K=25, PREFIX_BITS=24). Index files are interchangeable with the reference's.
@@ -195,8 +196,9 @@ def main(argv=None):
     gr = sub.add_parser("graph", help="Show the degree table of the de Bruijn graph whose nodes are the k-mers of an index: how many k-mers have `out` "
                                       "successors and `in` predecessors in the index, and a summary. The index is not changed")
     gr.add_argument("index")
-    un = sub.add_parser("unitigs", help="Write the unitigs of a non-canonical index, one line each: the maximal non-branching paths (and cycles) of the de Bruijn "
-                                        "graph whose nodes are its k-mers. The index is not changed")
+    un = sub.add_parser("unitigs", help="Write the unitigs of an index, one line each: the maximal non-branching paths (and cycles) of the de Bruijn "
+                                        "graph whose nodes are its k-mers; of a canonical index the bidirected unitigs, each in one of its two "
+                                        "orientations. The index is not changed")
     un.add_argument("index")
     un.add_argument("-o", "--output")
     un.add_argument("--stats", action="store_true", help="print a summary (unitigs, circular, k-mers, bases, longest, N50) instead of the lines")
@@ -345,9 +347,10 @@ def main(argv=None):
         print("\n".join(lines + summary))
     elif a.cmd == "unitigs":  # ours (the reference's CLI has no such command): compaction over Kmer::successors / predecessors (src/kmer.rs:82-90)
         cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
-        print(f"Compacting the {a.k}-mers contained in {a.index} into unitigs", file=sys.stderr)
+        bi = cbl.is_canonical()  # a canonical index: the bidirected unitigs, over oriented k-mers
+        print(f"Compacting the {'canonical ' if bi else ''}{a.k}-mers contained in {a.index} into {'bidirected ' if bi else ''}unitigs", file=sys.stderr)
         if a.stats:
-            t = cbl.unitig_table_np()
+            t = cbl.biunitig_table_np() if bi else cbl.unitig_table_np()
             lines, human = unitigs_report(CBL.unitig_summary(t["length"], t["flags"], a.k))
             print("\n".join(human), file=sys.stderr)
             out = "\n".join(lines) + "\n"
@@ -357,10 +360,10 @@ def main(argv=None):
             else:
                 sys.stdout.write(out)
         elif a.output:
-            cbl.unitigs_to_file(a.output)
+            (cbl.biunitigs_to_file if bi else cbl.unitigs_to_file)(a.output)
         else:
             sys.stdout.flush()
-            cbl.unitigs_to_fd(sys.stdout.fileno())
+            (cbl.biunitigs_to_fd if bi else cbl.unitigs_to_fd)(sys.stdout.fileno())
 
 if __name__ == "__main__":
     main()

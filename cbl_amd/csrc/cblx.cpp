@@ -10,6 +10,7 @@
 #include "kernels_list.hpp"
 #include "kernels_graph.hpp"
 #include "kernels_unitig.hpp"
+#include "kernels_biunitig.hpp"
 
 namespace {
 
@@ -415,6 +416,39 @@ struct UnitigRun {
     Buf<u8> circular;
     int cur = 0;  // anc[cur] / dist[cur] hold the ranking; the other pair is scratch (the head flags and their scan, in the end)
 };
+// List ranking over u.prev / u.next, arrays of n ids (the k-mers of section 6k, the oriented k-mers of section 6l): pointer jumping, and the cut of the
+// pure cycles when the count of unfinished ids repeats. `counters`: 130 zeroed words — [r] the unfinished ids of round r, [129] the cycles cut.
+void unitig_rank(cblx_ctx* c, UnitigRun& u, u64 n, Buf<u64>& counters) {
+    const dim3 gn = grid1(n, 256), b256(256);
+    hipLaunchKernelGGL(k_unitig_rank_init, gn, b256, 0, c->stream, u.prev.get(), n, u.anc[0].get(), u.dist[0].get());
+    u.cur = 0;
+    u64 last = ~0ull;
+    bool cut = false;
+    for (u32 r = 0;; ++r) {
+        if (r >= 128) throw Error(CBLX_EDEVICE, "unitig ranking did not end (internal error)");
+        const int o = u.cur ^ 1;
+        hipLaunchKernelGGL(k_unitig_jump, gn, b256, 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), n, u.anc[o].get(), u.dist[o].get(), counters.get() + r);
+        CBLX_HIP(hipGetLastError());
+        u.cur = o;
+        ++u.rounds;
+        const u64 open = d2h<u64>(c, counters.get() + r);  // the k-mers that were unfinished when the round began
+        if (open == 0) break;
+        if (open != last) { last = open; continue; }
+        // every path is finished: the `open` unfinished k-mers are the members of the pure cycles
+        if (cut) throw Error(CBLX_EDEVICE, "unitig ranking stalled after the cycle cut (internal error)");
+        cut = true;
+        last = ~0ull;
+        Buf<u32> lo[2] = {Buf<u32>(c->pool, n), Buf<u32>(c->pool, n)}, ptr[2] = {Buf<u32>(c->pool, n), Buf<u32>(c->pool, n)};
+        hipLaunchKernelGGL(k_cycle_init, gn, b256, 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), u.next.get(), n, lo[0].get(), ptr[0].get());
+        int lc = 0;
+        for (u64 span = 1; span < open; span <<= 1, lc ^= 1)  // a cycle has at most `open` members
+            hipLaunchKernelGGL(k_cycle_min, gn, b256, 0, c->stream, lo[lc].get(), ptr[lc].get(), n, lo[lc ^ 1].get(), ptr[lc ^ 1].get());
+        hipLaunchKernelGGL(k_cycle_cut, gn, b256, 0, c->stream, lo[lc].get(), n, u.next.get(), u.prev.get(), u.circular.get(), u.anc[u.cur].get(), u.dist[u.cur].get(),
+                           counters.get() + 129);
+        CBLX_HIP(hipGetLastError());
+        CBLX_HIP(hipStreamSynchronize(c->stream));  // lo / ptr die here
+    }
+}
 void unitig_compute(cblx_ctx* c, UnitigRun& u) {
     flush(c);
     if (c->P.canonical) throw Error(CBLX_EINVAL, "unitigs of a canonical index (bidirected unitigs) are not supported");
@@ -451,34 +485,7 @@ void unitig_compute(cblx_ctx* c, UnitigRun& u) {
         CBLX_HIP(hipStreamSynchronize(c->stream));  // the masks and the scratch k-mers die here
     }
     // (c) pointer jumping; (d) the cycle cut when the count of unfinished k-mers repeats
-    hipLaunchKernelGGL(k_unitig_rank_init, gn, b256, 0, c->stream, u.prev.get(), n, u.anc[0].get(), u.dist[0].get());
-    u.cur = 0;
-    u64 last = ~0ull;
-    bool cut = false;
-    for (u32 r = 0;; ++r) {
-        if (r >= 128) throw Error(CBLX_EDEVICE, "unitig ranking did not end (internal error)");
-        const int o = u.cur ^ 1;
-        hipLaunchKernelGGL(k_unitig_jump, gn, b256, 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), n, u.anc[o].get(), u.dist[o].get(), counters.get() + r);
-        CBLX_HIP(hipGetLastError());
-        u.cur = o;
-        ++u.rounds;
-        const u64 open = d2h<u64>(c, counters.get() + r);  // the k-mers that were unfinished when the round began
-        if (open == 0) break;
-        if (open != last) { last = open; continue; }
-        // every path is finished: the `open` unfinished k-mers are the members of the pure cycles
-        if (cut) throw Error(CBLX_EDEVICE, "unitig ranking stalled after the cycle cut (internal error)");
-        cut = true;
-        last = ~0ull;
-        Buf<u32> lo[2] = {Buf<u32>(c->pool, n), Buf<u32>(c->pool, n)}, ptr[2] = {Buf<u32>(c->pool, n), Buf<u32>(c->pool, n)};
-        hipLaunchKernelGGL(k_cycle_init, gn, b256, 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), u.next.get(), n, lo[0].get(), ptr[0].get());
-        int lc = 0;
-        for (u64 span = 1; span < open; span <<= 1, lc ^= 1)  // a cycle has at most `open` members
-            hipLaunchKernelGGL(k_cycle_min, gn, b256, 0, c->stream, lo[lc].get(), ptr[lc].get(), n, lo[lc ^ 1].get(), ptr[lc ^ 1].get());
-        hipLaunchKernelGGL(k_cycle_cut, gn, b256, 0, c->stream, lo[lc].get(), n, u.next.get(), u.prev.get(), u.circular.get(), u.anc[u.cur].get(), u.dist[u.cur].get(),
-                           counters.get() + 129);
-        CBLX_HIP(hipGetLastError());
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // lo / ptr die here
-    }
+    unitig_rank(c, u, n, counters);
     u.n_circular = d2h<u64>(c, counters.get() + 129);
     // (e) head flags -> exclusive scan -> unitig numbers, in the scratch pair
     const int o = u.cur ^ 1;
@@ -536,6 +543,115 @@ template <typename Fits> void unitig_text(cblx_ctx* c, UnitigText& t, u8* d_out,
 void unitigs_to_fd(cblx_ctx* c, int fd, u64 chunk_bytes, u64* n_unitigs, u64* bytes) {
     UnitigText t;
     unitig_text(c, t, nullptr, [](u64) { return true; });
+    if (n_unitigs) *n_unitigs = t.n_unitigs;
+    if (bytes) *bytes = t.bytes;
+    if (t.bytes == 0) return;
+    if (chunk_bytes == 0) chunk_bytes = LIST_CHUNK_DEFAULT * (c->P.K + 1);
+    const u64 cbytes = std::min<u64>(chunk_bytes, t.bytes);
+    stream_chunks_to_fd(c, fd, t.bytes, cbytes, "unitigs", [&](u64 i, u64) -> const u8* { return t.text.get() + i * cbytes; });
+}
+
+// ---- bidirected unitigs (kernels_biunitig.hpp) ----------------------------------------------------------------------
+// The compaction of a canonical index with odd K: section 6k's run on the 2 n oriented k-mers (u.next .. u.circular hold 2 n elements, u.n stays the
+// number of stored k-mers), then the choice of one image of every mirror pair. In the end the scratch pair holds the kept-head flags (anc) and their
+// exclusive scan (dist). About twice the workspace of unitig_compute: six 32-bit arrays and a byte array of 2 n, and the n masks while the links are made.
+void biunitig_require(const cblx_ctx* c) {
+    if (!c->P.canonical) throw Error(CBLX_EINVAL, "bidirected unitigs are those of a canonical index: a non-canonical index has cblx_unitig_table and cblx_unitigs_*");
+    if ((c->P.K & 1u) == 0) throw Error(CBLX_EINVAL, "bidirected unitigs need an odd K (a k-mer of even K can be its own reverse complement)");
+}
+void biunitig_compute(cblx_ctx* c, UnitigRun& u) {
+    flush(c);
+    biunitig_require(c);
+    const u64 n = c->res.count;
+    if (n >= 0x7FFFFFF8ull) throw Error(CBLX_ERANGE, "the index holds " + std::to_string(n) + " k-mers: bidirected unitigs need fewer than 2^31 - 8");
+    u.n = n;
+    if (n == 0) return;
+    const u64 n2 = 2 * n;
+    const dim3 g2 = grid1(n2, 256), b256(256);
+    u.next = Buf<u32>(c->pool, n2); u.prev = Buf<u32>(c->pool, n2);
+    u.circular = Buf<u8>(c->pool, n2);
+    for (int i = 0; i < 2; ++i) { u.anc[i] = Buf<u32>(c->pool, n2); u.dist[i] = Buf<u32>(c->pool, n2); }
+    Buf<u64> counters(c->pool, 130);  // [r] unfinished ids of round r; [129] cycles cut: two per circular unitig
+    CBLX_HIP(hipMemsetAsync(u.next.get(), 0xFF, n2 * 4, c->stream));
+    CBLX_HIP(hipMemsetAsync(u.prev.get(), 0xFF, n2 * 4, c->stream));
+    CBLX_HIP(hipMemsetAsync(u.circular.get(), 0, n2, c->stream));
+    CBLX_HIP(hipMemsetAsync(counters.get(), 0, 130 * 8, c->stream));
+    {   // (a) all masks, (b) the links, pass by pass
+        Buf<u8> masks(c->pool, n + 8);
+        neighbor_masks_range(c, 0, n, masks.get(), nullptr);
+        const u64 pass = std::min(neighbor_pass(), n);
+        const bool wide = c->P.wide_kmer();
+        Buf<u64> res_off, k_lo(c->pool, pass), k_hi(c->pool, wide ? pass : 1);
+        iteration_offsets(c, res_off);
+        for (u64 a = 0; a < n; a += pass) {
+            const u64 m = std::min(pass, n - a);
+            export_range_launch(c, res_off.get(), a, m, k_lo.get(), wide ? k_hi.get() : (u64*)nullptr, nullptr);
+            dispatch(c->P, [&](auto cfg) {
+                typedef decltype(cfg) C;
+                const u64 step = 1ull << 27;  // 2 QL lanes per k-mer: 2^31 work items per launch
+                for (u64 b = 0; b < m; b += step) {
+                    const u64 mb = std::min(step, m - b);
+                    hipLaunchKernelGGL((k_biunitig_links<C::WIDE>), grid1(2 * mb * QL, 256), b256, 0, c->stream, k_lo.get() + b, wide ? k_hi.get() + b : (const u64*)nullptr, a + b, mb,
+                                       masks.get(), c->P, c->res.view(), c->res.a_lo.get(), c->P.wide_suffix() ? c->res.a_hi.get() : (const u64*)nullptr, res_off.get(),
+                                       u.next.get(), u.prev.get());
+                }
+            });
+            CBLX_HIP(hipGetLastError());
+        }
+        CBLX_HIP(hipStreamSynchronize(c->stream));  // the masks and the scratch k-mers die here
+    }
+    // (c) the ranking of section 6k over the 2 n ids: a cycle and its mirror are both cut, in front of the same stored k-mer
+    unitig_rank(c, u, n2, counters);
+    const u64 cuts = d2h<u64>(c, counters.get() + 129);
+    if (cuts & 1) throw Error(CBLX_EDEVICE, "a cycle of oriented k-mers without its mirror (internal error)");
+    u.n_circular = cuts / 2;
+    // (d) tails -> kept heads -> exclusive scan -> unitig numbers, in the scratch pair
+    const int o = u.cur ^ 1;
+    hipLaunchKernelGGL(k_biunitig_tails, g2, b256, 0, c->stream, u.anc[u.cur].get(), u.next.get(), n2, u.anc[o].get());
+    hipLaunchKernelGGL(k_biunitig_keep, g2, b256, 0, c->stream, u.prev.get(), u.circular.get(), n2, u.anc[o].get());
+    CBLX_HIP(hipGetLastError());
+    u.n_unitigs = exclusive_scan<u32>(c, u.anc[o].get(), n2, u.dist[o].get());
+}
+// per stored k-mer unitig / offset / reversed, per unitig head / length / flags (device arrays of u.n and u.n_unitigs elements; any may be null); u.n != 0
+void biunitig_number(cblx_ctx* c, const UnitigRun& u, u32* d_unitig, u32* d_offset, u8* d_reversed, u32* d_head, u32* d_length, u8* d_flags) {
+    hipLaunchKernelGGL(k_biunitig_number, grid1(2 * u.n, 256), dim3(256), 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), u.next.get(), u.anc[u.cur ^ 1].get(),
+                       u.dist[u.cur ^ 1].get(), u.circular.get(), 2 * u.n, d_unitig, d_offset, d_reversed, d_head, d_length, d_flags);
+    CBLX_HIP(hipGetLastError());
+    CBLX_HIP(hipStreamSynchronize(c->stream));
+}
+// unitig_text for the bidirected form: the same sizes and the same layout
+template <typename Fits> void biunitig_text(cblx_ctx* c, UnitigText& t, u8* d_out, Fits&& fits) {
+    UnitigRun u;
+    biunitig_compute(c, u);
+    const u64 n = u.n, nu = u.n_unitigs, K = c->P.K;
+    t.n_unitigs = nu;
+    t.bytes = n + nu * K;
+    if (!fits(t.bytes) || n == 0) return;
+    if (!d_out) { t.text = Buf<u8>(c->pool, t.bytes); d_out = t.text.get(); }
+    Buf<u32> unitig(c->pool, n), offset(c->pool, n), length(c->pool, nu), line(c->pool, nu);
+    Buf<u8> reversed(c->pool, n);
+    Buf<u64> base(c->pool, nu);
+    biunitig_number(c, u, unitig.get(), offset.get(), reversed.get(), nullptr, length.get(), nullptr);
+    u = UnitigRun();  // the ranking's arrays go back to the pool
+    hipLaunchKernelGGL(k_unitig_line_bytes, grid1(nu, 256), dim3(256), 0, c->stream, length.get(), nu, (u32)K, line.get());
+    CBLX_HIP(hipGetLastError());
+    if (exclusive_scan<u64>(c, line.get(), nu, base.get()) != t.bytes) throw Error(CBLX_EDEVICE, "unitig lengths do not add up (internal error)");
+    const u64 pass = std::min(neighbor_pass(), n);
+    const bool wide = c->P.wide_kmer();
+    Buf<u64> res_off, k_lo(c->pool, pass), k_hi(c->pool, wide ? pass : 1);
+    iteration_offsets(c, res_off);
+    for (u64 a = 0; a < n; a += pass) {
+        const u64 m = std::min(pass, n - a);
+        export_range_launch(c, res_off.get(), a, m, k_lo.get(), wide ? k_hi.get() : (u64*)nullptr, nullptr);
+        hipLaunchKernelGGL(k_biunitig_text, grid1(m, 256), dim3(256), 0, c->stream, k_lo.get(), wide ? k_hi.get() : (const u64*)nullptr, a, m, unitig.get(), offset.get(),
+                           reversed.get(), length.get(), base.get(), (u32)K, d_out);
+        CBLX_HIP(hipGetLastError());
+    }
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // the table and the scratch k-mers die here
+}
+void biunitigs_to_fd(cblx_ctx* c, int fd, u64 chunk_bytes, u64* n_unitigs, u64* bytes) {
+    UnitigText t;
+    biunitig_text(c, t, nullptr, [](u64) { return true; });
     if (n_unitigs) *n_unitigs = t.n_unitigs;
     if (bytes) *bytes = t.bytes;
     if (t.bytes == 0) return;
@@ -2131,6 +2247,73 @@ int cblx_unitigs_to_file(cblx_ctx* c, const char* path, uint64_t chunk_bytes, ui
         const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (fd < 0) throw Error(CBLX_EINVAL, std::string("Failed to open ") + path);
         try { unitigs_to_fd(c, fd, chunk_bytes, n_unitigs, bytes); } catch (...) { (void)::close(fd); throw; }
+        if (::close(fd) != 0) throw Error(CBLX_EINVAL, std::string("Failed to write the unitigs to ") + path);
+    });
+}
+// ---- bidirected unitigs: the same conventions for a canonical index
+int cblx_biunitig_table_device(cblx_ctx* c, uint32_t* d_unitig, uint32_t* d_offset, uint8_t* d_reversed, uint64_t cap_kmers, uint32_t* d_head, uint32_t* d_length,
+                               uint8_t* d_flags, uint64_t cap_unitigs, uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular) {
+    return guard(c, [&] {
+        UnitigRun u;
+        biunitig_compute(c, u);
+        collect_events(c);
+        if (n_kmers) *n_kmers = u.n;
+        if (n_unitigs) *n_unitigs = u.n_unitigs;
+        if (n_circular) *n_circular = u.n_circular;
+        unitig_caps(u, d_unitig || d_offset || d_reversed, cap_kmers, d_head || d_length || d_flags, cap_unitigs);
+        if (u.n == 0 || !(d_unitig || d_offset || d_reversed || d_head || d_length || d_flags)) return;
+        biunitig_number(c, u, d_unitig, d_offset, d_reversed, d_head, d_length, d_flags);
+    });
+}
+int cblx_biunitig_table(cblx_ctx* c, uint32_t* unitig, uint32_t* offset, uint8_t* reversed, uint64_t cap_kmers, uint32_t* head, uint32_t* length, uint8_t* flags,
+                        uint64_t cap_unitigs, uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular) {
+    return guard(c, [&] {
+        UnitigRun u;
+        biunitig_compute(c, u);
+        collect_events(c);
+        if (n_kmers) *n_kmers = u.n;
+        if (n_unitigs) *n_unitigs = u.n_unitigs;
+        if (n_circular) *n_circular = u.n_circular;
+        unitig_caps(u, unitig || offset || reversed, cap_kmers, head || length || flags, cap_unitigs);
+        if (u.n == 0 || !(unitig || offset || reversed || head || length || flags)) return;
+        const u64 n = u.n, nu = u.n_unitigs;
+        Buf<u32> d_unitig(c->pool, unitig ? n : 1), d_offset(c->pool, offset ? n : 1), d_head(c->pool, head ? nu : 1), d_length(c->pool, length ? nu : 1);
+        Buf<u8> d_reversed(c->pool, reversed ? n : 1), d_flags(c->pool, flags ? nu : 1);
+        biunitig_number(c, u, unitig ? d_unitig.get() : nullptr, offset ? d_offset.get() : nullptr, reversed ? d_reversed.get() : nullptr, head ? d_head.get() : nullptr,
+                        length ? d_length.get() : nullptr, flags ? d_flags.get() : nullptr);
+        if (unitig) xfer(c).d2h_copy(unitig, d_unitig.get(), n * 4);
+        if (offset) xfer(c).d2h_copy(offset, d_offset.get(), n * 4);
+        if (reversed) xfer(c).d2h_copy(reversed, d_reversed.get(), n);
+        if (head) xfer(c).d2h_copy(head, d_head.get(), nu * 4);
+        if (length) xfer(c).d2h_copy(length, d_length.get(), nu * 4);
+        if (flags) xfer(c).d2h_copy(flags, d_flags.get(), nu);
+    });
+}
+int cblx_biunitigs_text_device(cblx_ctx* c, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs) {
+    return guard(c, [&] {
+        UnitigText t;
+        biunitig_text(c, t, d_buf, [&](u64 need) {
+            if (bytes) *bytes = need;
+            if (n_unitigs) *n_unitigs = t.n_unitigs;
+            if (d_buf && need > cap) throw Error(CBLX_ERANGE, "buffer too small: need " + std::to_string(need) + " bytes");
+            return d_buf != nullptr;  // null: the size is all that was asked for
+        });
+        collect_events(c);
+    });
+}
+int cblx_biunitigs_to_fd(cblx_ctx* c, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes) {
+    return guard(c, [&] {
+        if (fd < 0) throw Error(CBLX_EINVAL, "bad file descriptor");
+        biunitigs_to_fd(c, fd, chunk_bytes, n_unitigs, bytes);
+    });
+}
+int cblx_biunitigs_to_file(cblx_ctx* c, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes) {
+    return guard(c, [&] {
+        if (!path) throw Error(CBLX_EINVAL, "null argument");
+        biunitig_require(c);  // a refusal comes before the file is created or truncated
+        const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) throw Error(CBLX_EINVAL, std::string("Failed to open ") + path);
+        try { biunitigs_to_fd(c, fd, chunk_bytes, n_unitigs, bytes); } catch (...) { (void)::close(fd); throw; }
         if (::close(fd) != 0) throw Error(CBLX_EINVAL, std::string("Failed to write the unitigs to ") + path);
     });
 }

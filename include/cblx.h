@@ -35,7 +35,8 @@ extern "C" {
  * cblx_intersection_count with CBLX_COMMON_STATS, and cblx_intersection_counts; cblx_set_at_least and cblx_occupancy_counts;
  * cblx_contains_seqs_counts_many and cblx_contains_seqs_counts_many_device;
  * cblx_neighbors_kmers, cblx_neighbors_kmers_device, cblx_neighbors_range, cblx_neighbors_range_device and cblx_degree_table;
- * cblx_rank_kmers, cblx_rank_kmers_device, cblx_unitig_table, cblx_unitig_table_device, cblx_unitigs_text_device, cblx_unitigs_to_fd and cblx_unitigs_to_file. */
+ * cblx_rank_kmers, cblx_rank_kmers_device, cblx_unitig_table, cblx_unitig_table_device, cblx_unitigs_text_device, cblx_unitigs_to_fd and cblx_unitigs_to_file;
+ * cblx_biunitig_table, cblx_biunitig_table_device, cblx_biunitigs_text_device, cblx_biunitigs_to_fd and cblx_biunitigs_to_file. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -526,7 +527,7 @@ int cblx_rank_kmers_device(cblx_ctx* ctx, const uint64_t* d_lo, const uint64_t* 
  *   per unitig:  head[u] = the head's ordinal, length[u] = its k-mers, flags[u] bit 0 = circular                   (cap_unitigs elements each)
  * Any array may be NULL and is then not written; with all five NULL the call only counts. *n_kmers = count(), *n_unitigs = U, *n_circular are always
  * set (any may be NULL). A capacity below the need of an array that is given is CBLX_ERANGE: the counts are set and nothing is written. A canonical
- * index is CBLX_EINVAL (bidirected unitigs are not built); 2^32 - 16 k-mers or more are CBLX_ERANGE (ordinals are 32-bit inside). An empty index
+ * index is CBLX_EINVAL (its unitigs are the bidirected ones: cblx_biunitig_table); 2^32 - 16 k-mers or more are CBLX_ERANGE (ordinals are 32-bit inside). An empty index
  * gives U = 0. Numbering and the rotation of a circular unitig follow the iteration order, so they follow the Vec buckets' first-occurrence order.
  * An observer; every call recomputes. Device workspace: about 25 bytes per k-mer. _device: device pointers for the five arrays. */
 int cblx_unitig_table(cblx_ctx* ctx, uint32_t* unitig, uint32_t* offset, uint64_t cap_kmers, uint32_t* head, uint32_t* length, uint8_t* flags,
@@ -542,6 +543,32 @@ int cblx_unitigs_text_device(cblx_ctx* ctx, uint8_t* d_buf, uint64_t cap, uint64
  * cblx_list_to_fd chunk) through two pinned buffers, as the list does; the error rules are cblx_list_to_fd's. */
 int cblx_unitigs_to_fd(cblx_ctx* ctx, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes);
 int cblx_unitigs_to_file(cblx_ctx* ctx, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes);   /* create / truncate, then the above */
+/* ---- bidirected unitigs: the compaction of a CANONICAL index with odd K. Stored k-mer i (ordinal i, x_i its stored form) has two
+ * ORIENTED copies: (i, 0) spells x_i and (i, 1) spells rc(x_i); the mirror of (i, s) is (i, 1 - s). There is an edge (i, s) -> (j, t) when
+ * sigma(j, t) = append(sigma(i, s), c) and x_j is in the set; edges come in mirror pairs, (j, 1 - t) -> (i, 1 - s). Degrees are those of the neighbour
+ * mask m of i: out(i, 0) = popcount(m & 15), in(i, 0) = popcount(m >> 4), out(i, 1) = in(i, 0), in(i, 1) = out(i, 0). An edge is SIMPLE when
+ * out(i, s) = 1, in(j, t) = 1 and j != i. An edge between a stored k-mer and itself — the hairpin (i, s) -> (i, 1 - s), the homopolymer loop — is never
+ * simple, though it counts in the degrees: THIS DIFFERS FROM cblx_unitig_table, where poly-A alone is a circular unitig; here it is a unitig of
+ * length 1 that is not circular. The simple edges cut the oriented k-mers into paths and cycles that come in distinct mirror pairs; a UNITIG is one
+ * image of each pair. Of a path with head (h, s) and tail (t, u) the image with h < t is kept, or with h = t and s = 0 (length 1). Of a cycle of simple
+ * edges only the head is the member with the smallest ordinal, the image kept is the one where that head has s = 0, and the unitig is CIRCULAR.
+ * Unitigs are numbered by ascending ordinal of their heads; every stored k-mer lies on exactly one.
+ *   per k-mer:   unitig[ordinal], offset[ordinal] = the simple edges from the head, reversed[ordinal] = the s of its copy on the kept image (uint8)
+ *   per unitig:  head[u] = the head's ordinal, length[u], flags[u] bit 0 = circular
+ * The conventions of cblx_unitig_table: any array may be NULL, with all six NULL the call only counts; the counts are always set; a short capacity is
+ * CBLX_ERANGE with the need reported and nothing written; an observer; an empty index gives U = 0. A non-canonical index is CBLX_EINVAL (it has
+ * cblx_unitig_table), an even K is CBLX_EINVAL, 2^31 - 8 k-mers or more are CBLX_ERANGE (the ids 2 i + s are 32-bit). Device workspace: about 50 bytes
+ * per k-mer. _device: device pointers for the six arrays. */
+int cblx_biunitig_table(cblx_ctx* ctx, uint32_t* unitig, uint32_t* offset, uint8_t* reversed, uint64_t cap_kmers, uint32_t* head, uint32_t* length, uint8_t* flags,
+                        uint64_t cap_unitigs, uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular);
+int cblx_biunitig_table_device(cblx_ctx* ctx, uint32_t* d_unitig, uint32_t* d_offset, uint8_t* d_reversed, uint64_t cap_kmers, uint32_t* d_head, uint32_t* d_length,
+                               uint8_t* d_flags, uint64_t cap_unitigs, uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular);
+/* The text, lines in unitig order: the K letters of sigma(head), then the last letter of sigma of every following member in offset order (for a reversed
+ * member the complement of its stored form's first base), then '\n': count() + U * K bytes in all. A circular unitig is written open, from its head. The
+ * rules of cblx_unitigs_text_device / cblx_unitigs_to_fd / cblx_unitigs_to_file; a refused cblx_biunitigs_to_file does not create the file. */
+int cblx_biunitigs_text_device(cblx_ctx* ctx, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs);
+int cblx_biunitigs_to_fd(cblx_ctx* ctx, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes);
+int cblx_biunitigs_to_file(cblx_ctx* ctx, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes);
 /* CBL::buckets_nodes (src/cbl.rs:386-390): per non-empty prefix ascending, TrieVec::count_nodes (src/trievec/mod.rs:37-42) — a Vec's length, a Trie's
  * nodes (src/trie.rs:90-102: the root and one node per distinct proper byte prefix of its suffixes). Pairs with cblx_bucket_sizes. */
 int cblx_bucket_nodes(cblx_ctx* ctx, uint64_t* nodes, uint64_t cap, uint64_t* n);

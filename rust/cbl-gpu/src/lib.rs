@@ -289,6 +289,27 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         (u, bytes)
     }
 
+    /// `(k-mers, unitigs, circular unitigs)` of a canonical set with odd `K`: the bidirected unitigs, the paths and cycles that
+    /// the simple edges between oriented k-mers make, one image of each mirror pair. Only the counts come back.
+    pub fn biunitig_counts(&self) -> (u64, u64, u64) {
+        let (mut n, mut u, mut c) = (0u64, 0u64, 0u64);
+        let null32 = std::ptr::null_mut::<u32>();
+        let null8 = std::ptr::null_mut::<u8>();
+        self.check(unsafe {
+            sys::cblx_biunitig_table(self.ctx, null32, null32, null8, 0, null32, null32, null8, 0, &mut n, &mut u, &mut c)
+        });
+        (n, u, c)
+    }
+
+    /// Writes the bidirected unitigs as text to `path` (created or truncated), one line each: the `K` letters the head spells in
+    /// its orientation, then the last letter every following member spells in its own. Returns `(unitigs, bytes)`.
+    pub fn biunitigs_to_file<P: AsRef<Path>>(&self, path: P) -> (u64, u64) {
+        let cpath = Self::cpath(path);
+        let (mut u, mut bytes) = (0u64, 0u64);
+        self.check(unsafe { sys::cblx_biunitigs_to_file(self.ctx, cpath.as_ptr(), 0, &mut u, &mut bytes) });
+        (u, bytes)
+    }
+
     /// Adds a k-mer; returns `true` if it was absent (`src/cbl.rs:226-228`). One device round trip per call: a caller with
     /// many k-mers uses `insert_kmers`.
     #[inline]

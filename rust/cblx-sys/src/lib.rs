@@ -401,6 +401,11 @@ extern "C" {
     pub fn cblx_unitigs_text_device(ctx: *mut cblx_ctx, d_buf: *mut u8, cap: u64, bytes: *mut u64, n_unitigs: *mut u64) -> c_int;
     pub fn cblx_unitigs_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_bytes: u64, n_unitigs: *mut u64, bytes: *mut u64) -> c_int;
     pub fn cblx_unitigs_to_file(ctx: *mut cblx_ctx, path: *const c_char, chunk_bytes: u64, n_unitigs: *mut u64, bytes: *mut u64) -> c_int;
+    pub fn cblx_biunitig_table(ctx: *mut cblx_ctx, unitig: *mut u32, offset: *mut u32, reversed: *mut u8, cap_kmers: u64, head: *mut u32, length: *mut u32, flags: *mut u8, cap_unitigs: u64, n_kmers: *mut u64, n_unitigs: *mut u64, n_circular: *mut u64) -> c_int;
+    pub fn cblx_biunitig_table_device(ctx: *mut cblx_ctx, d_unitig: *mut u32, d_offset: *mut u32, d_reversed: *mut u8, cap_kmers: u64, d_head: *mut u32, d_length: *mut u32, d_flags: *mut u8, cap_unitigs: u64, n_kmers: *mut u64, n_unitigs: *mut u64, n_circular: *mut u64) -> c_int;
+    pub fn cblx_biunitigs_text_device(ctx: *mut cblx_ctx, d_buf: *mut u8, cap: u64, bytes: *mut u64, n_unitigs: *mut u64) -> c_int;
+    pub fn cblx_biunitigs_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_bytes: u64, n_unitigs: *mut u64, bytes: *mut u64) -> c_int;
+    pub fn cblx_biunitigs_to_file(ctx: *mut cblx_ctx, path: *const c_char, chunk_bytes: u64, n_unitigs: *mut u64, bytes: *mut u64) -> c_int;
     pub fn cblx_list_range(ctx: *mut cblx_ctx, first: u64, n: u64, buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_range_device(ctx: *mut cblx_ctx, first: u64, n: u64, d_buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_kmers: u64, n_kmers: *mut u64) -> c_int;
