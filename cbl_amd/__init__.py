@@ -1105,11 +1105,51 @@ class CBL:
         self._chk(self._L.cblx_rank_kmers_device(self._h, _ptr(d_lo), _ptr(d_hi), n, _ptr(d_rank)))
         return d_rank
 
+    # The plain form (a non-canonical index) and the bidirected one (`bi`: a canonical index, section 6l) go through the same four helpers.
+    def _unitig_fn(self, bi: bool, name: str):
+        """The library's cblx_`name`, or its bidirected twin (unitig_table -> cblx_biunitig_table)."""
+        return getattr(self._L, "cblx_" + ("bi" if bi else "") + name)
+
+    def _unitig_counts(self, bi: bool, device: bool = False, per_kmer=None, per_unitig=(None, None, None), cap: int = 0):
+        """(k-mers, unitigs, circular unitigs) from the table call, which fills the arrays it is given (`reversed` exists only with bi)."""
+        per_kmer = per_kmer or (None,) * (3 if bi else 2)
+        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._unitig_fn(bi, "unitig_table_device" if device else "unitig_table")(
+            self._h, *map(_ptr, per_kmer), cap, *map(_ptr, per_unitig), cap, C.byref(n), C.byref(u), C.byref(c)))
+        return n.value, u.value, c.value
+
+    def _unitig_table(self, xp, bi: bool) -> dict:
+        """The compaction table in arrays of `xp`: numpy (host, zeroed) or torch (tensors on the index's device)."""
+        device = xp.__name__ == "torch"
+        cap = max(self.count(), 1)
+        if device:
+            dev = xp.device("cuda", self.device())
+            new, own = (lambda dtype: xp.empty(cap, dtype=dtype, device=dev)), (lambda a: a.clone())
+        else:
+            new, own = (lambda dtype: xp.zeros(cap, dtype=dtype)), (lambda a: a.copy())
+        unitig, offset, head, length = (new(xp.int32 if device else xp.uint32) for _ in range(4))
+        rev, flags = (new(xp.uint8) if bi else None), new(xp.uint8)
+        n, u, c = self._unitig_counts(bi, device, (unitig, offset, rev) if bi else (unitig, offset), (head, length, flags), cap)
+        out = {"unitig": unitig[:n], "offset": offset[:n]}
+        if bi:
+            out["reversed"] = rev[:n]
+        out.update(head=own(head[:u]), length=own(length[:u]), flags=own(flags[:u]), n_circular=c)
+        return out
+
+    def _unitig_sizes(self, bi: bool, name: str, *args):
+        """cblx_`name`(handle, *args, &a, &b) -> (a, b): (bytes, unitigs) of the text-device call, (unitigs, bytes) of the to-file / to-fd calls."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._unitig_fn(bi, name)(self._h, *args, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def _text_lines(self, text_np):
+        """Generator of the lines of the uint8 array text_np() returns, as str."""
+        for line in text_np().tobytes().split(b"\n")[:-1]:
+            yield line.decode("ascii")
+
     def unitig_counts(self):
         """(k-mers, unitigs, circular unitigs) of a non-canonical index; the whole compaction runs on the device, three numbers come back."""
-        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_unitig_table(self._h, None, None, 0, None, None, None, 0, C.byref(n), C.byref(u), C.byref(c)))
-        return n.value, u.value, c.value
+        return self._unitig_counts(False)
 
     def unitig_table_np(self) -> dict:
         """The compaction table of a non-canonical index: per k-mer, by ordinal, `unitig` and `offset` (uint32); per unitig `head` (the
@@ -1118,36 +1158,20 @@ class CBL:
         ascending ordinal of their heads; the head of a cycle is its member with the smallest ordinal."""
         import numpy as np
 
-        cap = max(self.count(), 1)
-        unitig, offset, head, length = (np.zeros(cap, dtype=np.uint32) for _ in range(4))
-        flags = np.zeros(cap, dtype=np.uint8)
-        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_unitig_table(self._h, _ptr(unitig), _ptr(offset), cap, _ptr(head), _ptr(length), _ptr(flags), cap, C.byref(n), C.byref(u), C.byref(c)))
-        return {"unitig": unitig[: n.value], "offset": offset[: n.value], "head": head[: u.value].copy(), "length": length[: u.value].copy(),
-                "flags": flags[: u.value].copy(), "n_circular": c.value}
+        return self._unitig_table(np, False)
 
     def unitig_table_device(self) -> dict:
         """The same table as torch CUDA tensors (int32 holding the unsigned 32-bit values, uint8 for `flags`); nothing crosses to the host but
         the three counts."""
         import torch
 
-        dev = torch.device("cuda", self.device())
-        cap = max(self.count(), 1)
-        unitig, offset, head, length = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(4))
-        flags = torch.empty(cap, dtype=torch.uint8, device=dev)
-        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_unitig_table_device(self._h, _ptr(unitig), _ptr(offset), cap, _ptr(head), _ptr(length), _ptr(flags), cap, C.byref(n), C.byref(u),
-                                                   C.byref(c)))
-        return {"unitig": unitig[: n.value], "offset": offset[: n.value], "head": head[: u.value].clone(), "length": length[: u.value].clone(),
-                "flags": flags[: u.value].clone(), "n_circular": c.value}
+        return self._unitig_table(torch, False)
 
     def unitigs_text_device(self, d_buf=None, cap: int = 0):
         """(bytes, unitigs) of the unitig text: count() + unitigs * K bytes, one line per unitig — the K letters of its head, the last
         letter of every following k-mer, '\n'. With d_buf (a torch uint8 CUDA tensor or raw device address of `cap` bytes) the text is
         written there; without, only the two sizes are computed. A buffer too small raises CblxError(ERANGE) and is left untouched."""
-        nbytes, u = C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_unitigs_text_device(self._h, _ptr(d_buf), cap, C.byref(nbytes), C.byref(u)))
-        return nbytes.value, u.value
+        return self._unitig_sizes(False, "unitigs_text_device", _ptr(d_buf), cap)
 
     def _text_np(self, to_fd):
         """What to_fd(descriptor) writes, as a uint8 array: a pipe, read by a thread while the library streams into it."""
@@ -1177,21 +1201,16 @@ class CBL:
 
     def unitigs(self):
         """Generator of the unitigs as str, in unitig order (the text is built once, before the first one is yielded)."""
-        for line in self.unitigs_text_np().tobytes().split(b"\n")[:-1]:
-            yield line.decode("ascii")
+        return self._text_lines(self.unitigs_text_np)
 
     def unitigs_to_file(self, path, chunk_bytes: int = 0):
         """Writes the unitig text to `path` (created / truncated), streamed from the device in chunks of chunk_bytes (0 = the library's
         default); returns (unitigs, bytes)."""
-        u, nbytes = C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_unitigs_to_file(self._h, os.fsencode(path), chunk_bytes, C.byref(u), C.byref(nbytes)))
-        return u.value, nbytes.value
+        return self._unitig_sizes(False, "unitigs_to_file", os.fsencode(path), chunk_bytes)
 
     def unitigs_to_fd(self, fd: int, chunk_bytes: int = 0):
         """The same to an open file descriptor (flush any Python-level buffer over it first)."""
-        u, nbytes = C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_unitigs_to_fd(self._h, fd, chunk_bytes, C.byref(u), C.byref(nbytes)))
-        return u.value, nbytes.value
+        return self._unitig_sizes(False, "unitigs_to_fd", fd, chunk_bytes)
 
     @staticmethod
     def unitig_summary(length, flags, k: int) -> dict:
@@ -1217,9 +1236,7 @@ class CBL:
     def biunitig_counts(self):
         """(k-mers, unitigs, circular unitigs) of a canonical index with odd K: the compaction over oriented k-mers runs on the device,
         three numbers come back."""
-        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_biunitig_table(self._h, None, None, None, 0, None, None, None, 0, C.byref(n), C.byref(u), C.byref(c)))
-        return n.value, u.value, c.value
+        return self._unitig_counts(True)
 
     def biunitig_table_np(self) -> dict:
         """The compaction table of a canonical index: the dict of unitig_table_np plus `reversed` (uint8 per k-mer, by ordinal): 1 where the
@@ -1229,36 +1246,19 @@ class CBL:
         is kept (a cycle: the one whose smallest member is not reversed)."""
         import numpy as np
 
-        cap = max(self.count(), 1)
-        unitig, offset, head, length = (np.zeros(cap, dtype=np.uint32) for _ in range(4))
-        rev, flags = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype=np.uint8)
-        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_biunitig_table(self._h, _ptr(unitig), _ptr(offset), _ptr(rev), cap, _ptr(head), _ptr(length), _ptr(flags), cap, C.byref(n), C.byref(u),
-                                              C.byref(c)))
-        return {"unitig": unitig[: n.value], "offset": offset[: n.value], "reversed": rev[: n.value], "head": head[: u.value].copy(),
-                "length": length[: u.value].copy(), "flags": flags[: u.value].copy(), "n_circular": c.value}
+        return self._unitig_table(np, True)
 
     def biunitig_table_device(self) -> dict:
         """The same table as torch CUDA tensors (int32 holding the unsigned 32-bit values, uint8 for `reversed` and `flags`); nothing crosses
         to the host but the three counts."""
         import torch
 
-        dev = torch.device("cuda", self.device())
-        cap = max(self.count(), 1)
-        unitig, offset, head, length = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(4))
-        rev, flags = torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(cap, dtype=torch.uint8, device=dev)
-        n, u, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_biunitig_table_device(self._h, _ptr(unitig), _ptr(offset), _ptr(rev), cap, _ptr(head), _ptr(length), _ptr(flags), cap, C.byref(n),
-                                                     C.byref(u), C.byref(c)))
-        return {"unitig": unitig[: n.value], "offset": offset[: n.value], "reversed": rev[: n.value], "head": head[: u.value].clone(),
-                "length": length[: u.value].clone(), "flags": flags[: u.value].clone(), "n_circular": c.value}
+        return self._unitig_table(torch, True)
 
     def biunitigs_text_device(self, d_buf=None, cap: int = 0):
         """(bytes, unitigs) of the bidirected unitig text: count() + unitigs * K bytes, one line per unitig — the K letters its head spells
         in its orientation, the last letter every following member spells in its own, '\n'. d_buf and cap as in unitigs_text_device."""
-        nbytes, u = C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_biunitigs_text_device(self._h, _ptr(d_buf), cap, C.byref(nbytes), C.byref(u)))
-        return nbytes.value, u.value
+        return self._unitig_sizes(True, "unitigs_text_device", _ptr(d_buf), cap)
 
     def biunitigs_text_np(self):
         """The bidirected unitig text as a uint8 array, built on the device and streamed out once."""
@@ -1266,21 +1266,16 @@ class CBL:
 
     def biunitigs(self):
         """Generator of the bidirected unitigs as str, in unitig order (the text is built once, before the first one is yielded)."""
-        for line in self.biunitigs_text_np().tobytes().split(b"\n")[:-1]:
-            yield line.decode("ascii")
+        return self._text_lines(self.biunitigs_text_np)
 
     def biunitigs_to_file(self, path, chunk_bytes: int = 0):
         """Writes the bidirected unitig text to `path` (created / truncated), streamed from the device in chunks of chunk_bytes (0 = the
         library's default); returns (unitigs, bytes)."""
-        u, nbytes = C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_biunitigs_to_file(self._h, os.fsencode(path), chunk_bytes, C.byref(u), C.byref(nbytes)))
-        return u.value, nbytes.value
+        return self._unitig_sizes(True, "unitigs_to_file", os.fsencode(path), chunk_bytes)
 
     def biunitigs_to_fd(self, fd: int, chunk_bytes: int = 0):
         """The same to an open file descriptor (flush any Python-level buffer over it first)."""
-        u, nbytes = C.c_uint64(0), C.c_uint64(0)
-        self._chk(self._L.cblx_biunitigs_to_fd(self._h, fd, chunk_bytes, C.byref(u), C.byref(nbytes)))
-        return u.value, nbytes.value
+        return self._unitig_sizes(True, "unitigs_to_fd", fd, chunk_bytes)
 
     # ---- bucket statistics (src/cbl.rs:364-386) ---------------------------------------------------------------------
     def bucket_table_np(self):

@@ -7,10 +7,7 @@
 // There is no CPU fallback: every data-path step below is a kernel launch.
 #include "comm.hpp"
 #include "host_input.hpp"
-#include "kernels_list.hpp"
-#include "kernels_graph.hpp"
-#include "kernels_unitig.hpp"
-#include "kernels_biunitig.hpp"
+#include "graph.hpp"
 
 namespace {
 
@@ -67,7 +64,7 @@ template <typename C> u64 seq_words_of_host_seq(cblx_ctx* c, const uint8_t* seq,
 // words (get_word, src/cbl.rs:199-206) of n packed host k-mers, on the device
 template <typename C> void words_of_host_kmers(cblx_ctx* c, const uint64_t* lo, const uint64_t* hi, u64 n, Buf<u64>& w_lo, Buf<u8>& w_hi) {
     typedef typename C::HiT HiT;
-    if (!lo || (c->P.wide_kmer() && !hi)) throw Error(CBLX_EINVAL, c->P.wide_kmer() ? "null argument (K >= 33 needs the hi halves of the k-mers)" : "null argument");
+    require_kmer_arrays(c, lo, hi, &w_lo);  // the answer goes into w_lo / w_hi: no third array of the caller's
     if (n >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "too many k-mers in one call");
     Buf<u64> k_lo(c->pool, n + 1), k_hi(c->pool, hi ? n + 1 : 1);
     Buf<u32> bad(c->pool, 1);
@@ -165,500 +162,79 @@ Resident clone_resident(cblx_ctx* dst, const cblx_ctx* src) {
     return copy;
 }
 
-// ---- reading the index out (kernels_list.hpp) --------------------------------------------------------------------------
-// res_off[nb + 1]: where every bucket begins in the iteration order, and the total behind the last one
-u64 iteration_offsets(cblx_ctx* c, Buf<u64>& res_off) {
-    const Resident& r = c->res;
-    res_off = Buf<u64>(c->pool, r.nb + 1);
-    const u64 tot = exclusive_scan<u64>(c, r.cnt.get(), r.nb, res_off.get());
-    hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, res_off.get() + r.nb, tot);
-    CBLX_HIP(hipGetLastError());
-    return tot;
+// ---- the bodies the text-file and unitig entry points share ---------------------------------------------------------------------------
+// `path` is created / truncated, run(fd) writes the text, the file is closed; `what` names the text in the message of a failed close
+template <typename Run> void text_to_file(const char* path, const char* what, Run&& run) {
+    const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) throw Error(CBLX_EINVAL, std::string("Failed to open ") + path);
+    try { run(fd); } catch (...) { (void)::close(fd); throw; }
+    if (::close(fd) != 0) throw Error(CBLX_EINVAL, std::string("Failed to write the ") + what + " to " + path);
 }
-// elements [first, first + n) of the iteration order (n != 0, inside the index) to device arrays, from their index 0; asynchronous on the ctx's stream.
-// d_text != null: lines (16-byte aligned); else packed k-mers, d_hi may be null.
-void export_range_launch(cblx_ctx* c, const u64* res_off, u64 first, u64 n, u64* d_lo, u64* d_hi, u8* d_text) {
-    const Resident& r = c->res;
-    const u64 LINE = c->P.K + 1, STEP = 1ull << 31;  // one launch addresses fewer than 2^32 work items; a multiple of LIST_THREADS keeps every text launch 16-byte aligned
-    const bool ws = c->P.wide_suffix();
-    for (u64 o = 0; o < n; o += STEP) {
-        const u64 m = std::min<u64>(STEP, n - o);
-        const dim3 grid = grid1(m, LIST_THREADS);
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, grid, dim3(LIST_THREADS), 0, c->stream, first + o, m, r.nb, res_off, r.prefix.get(), r.start.get(), r.a_lo.get(),
-                               ws ? r.a_hi.get() : (const u64*)nullptr, c->P, d_text ? (u64*)nullptr : d_lo + o, (d_text || !d_hi) ? (u64*)nullptr : d_hi + o,
-                               d_text ? d_text + o * LINE : (u8*)nullptr);
-        };
-        if (d_text) { if (ws) go(k_export_range<true, true>); else go(k_export_range<true, false>); }
-        else { if (ws) go(k_export_range<false, true>); else go(k_export_range<false, false>); }
-    }
-    CBLX_HIP(hipGetLastError());
-}
-// the checks the range calls share: *m = min(n, count - first)
-void range_clamp(cblx_ctx* c, u64 first, u64 n, u64* m) {
-    flush(c);
-    if (first > c->res.count) throw Error(CBLX_EINVAL, "first = " + std::to_string(first) + " is past the end: the index holds " + std::to_string(c->res.count) + " k-mers");
-    *m = std::min<u64>(n, c->res.count - first);
-}
-
-// ---- de Bruijn neighbourhoods (kernels_graph.hpp) ------------------------------------------------------
-// k-mers per pass: 8 words and 8 flag bytes of scratch each. CBLX_NEIGHBOR_PASS overrides the default; at most 2^28, so that the 8 x pass
-// ordinals of a pass stay below 2^32 - 16 and its lanes fit one grid.
-static const u64 NEIGHBOR_PASS_DEFAULT = 1ull << 22, NEIGHBOR_PASS_MAX = 1ull << 28;
-u64 neighbor_pass() {  // read per call: tests switch it
-    const char* e = std::getenv("CBLX_NEIGHBOR_PASS");
-    const u64 p = e ? std::strtoull(e, nullptr, 10) : NEIGHBOR_PASS_DEFAULT;
-    return std::min(std::max<u64>(p, 1), NEIGHBOR_PASS_MAX);
-}
-// d_masks[i] = the neighbour mask of packed k-mer i of device arrays (d_hi may be null for K <= 31) against c's resident index, in passes of at most
-// neighbor_pass() k-mers: k_neighbor_words makes the 8 m words of a pass, a flags query answers them — by the join on tagged records where
-// query_flags_by_join holds and 8 m >= query_join_min(), by k_contains otherwise and on an empty index — and k_fold_neighbor_flags leaves m bytes.
-// `check`: the arrays are a caller's; all of them are checked before the first pass writes a mask (a refusal writes nothing).
-template <typename C> void neighbor_masks_device(cblx_ctx* c, const u64* d_lo, const u64* d_hi, u64 n, u8* d_masks, bool check = true) {
-    typedef typename C::HiT HiT;
-    const Consts& P = c->P;
-    if (n == 0) return;
-    const char* not_kmer = "k-mer has bits set above 2K (not an IntKmer<K>)";
-    Buf<u32> bad(c->pool, 1);
-    CBLX_HIP(hipMemsetAsync(bad.get(), 0, 4, c->stream));
-    if (check) {
-        for (u64 a = 0; a < n; a += 1ull << 31)
-            hipLaunchKernelGGL((k_kmers_check<C::WIDE>), grid1(std::min<u64>(1ull << 31, n - a), 256), dim3(256), 0, c->stream, d_lo + a, d_hi ? d_hi + a : d_hi,
-                               std::min<u64>(1ull << 31, n - a), P, bad.get());
-        CBLX_HIP(hipGetLastError());
-        if (d2h<u32>(c, bad.get())) throw Error(CBLX_EINVAL, not_kmer);
-    }
-    const u64 pass = std::min(neighbor_pass(), n);
-    const bool by_join = query_flags_by_join(P) && c->res.count != 0;
-    const u64 join_min = query_join_min();
-    Buf<u8> flags(c->pool, 8 * pass + 16);
-    for (u64 a = 0; a < n; a += pass) {
-        const u64 m = std::min(pass, n - a), nw = 8 * m;
-        const u64* k_hi = d_hi ? d_hi + a : d_hi;
-        if (by_join && nw >= join_min) {
-            Records rec;
-            begin_tagged_records(c, rec, nw);
-            hipLaunchKernelGGL((k_neighbor_words<C::WIDE, HiT, true>), grid1(nw, 256), dim3(256), 0, c->stream, d_lo + a, k_hi, m, P, rec.lo.get(), (u64*)rec.hi.get(), bad.get());
-            CBLX_HIP(hipGetLastError());
-            CBLX_HIP(hipMemsetAsync(flags.get(), 0, nw, c->stream));
-            join_tagged_records<C>(c, rec, nw, Buf<u32>(), flags.get());  // no fused histogram: the partition counts its first pass itself
-        } else {
-            Buf<u64> w_lo(c->pool, nw + 2);
-            Buf<u8> w_hi(c->pool, (nw + 2) * std::max<size_t>(1, hi_elem_size(P)));
-            hipLaunchKernelGGL((k_neighbor_words<C::WIDE, HiT, false>), grid1(nw, 256), dim3(256), 0, c->stream, d_lo + a, k_hi, m, P, w_lo.get(), (HiT*)w_hi.get(), bad.get());
-            contains_words<C>(c, w_lo.get(), (const HiT*)w_hi.get(), nw, flags.get());
-            CBLX_HIP(hipStreamSynchronize(c->stream));  // the words die here
-        }
-        hipLaunchKernelGGL(k_fold_neighbor_flags, grid1(m, 256), dim3(256), 0, c->stream, (const u64*)flags.get(), m, d_masks + a);
-        CBLX_HIP(hipGetLastError());
-    }
-    if (d2h<u32>(c, bad.get())) throw Error(CBLX_EINVAL, not_kmer);  // (not after the check, and not on exported k-mers) — also: the flags may go back to the pool
-}
-// The same for elements [first, first + n) of the iteration order (n != 0, inside the index), pass by pass: the export path of
-// cblx_export_kmers_range_device fills a scratch k-mer array, which goes through the device form. d_masks (n bytes) and / or d_table (25 words,
-// zeroed by the caller: k_degree_tally adds every pass's masks) take the result.
-void neighbor_masks_range(cblx_ctx* c, u64 first, u64 n, u8* d_masks, u64* d_table) {
-    const u64 pass = std::min(neighbor_pass(), n);
-    const bool wide = c->P.wide_kmer();
-    Buf<u64> res_off, k_lo(c->pool, pass), k_hi(c->pool, wide ? pass : 1);
-    Buf<u8> tmp;
-    if (!d_masks) tmp = Buf<u8>(c->pool, pass);
-    iteration_offsets(c, res_off);
-    for (u64 a = 0; a < n; a += pass) {
-        const u64 m = std::min(pass, n - a);
-        u8* out = d_masks ? d_masks + a : tmp.get();
-        export_range_launch(c, res_off.get(), first + a, m, k_lo.get(), wide ? k_hi.get() : (u64*)nullptr, nullptr);
-        dispatch(c->P, [&](auto cfg) { neighbor_masks_device<decltype(cfg)>(c, k_lo.get(), wide ? k_hi.get() : (const u64*)nullptr, m, out, false); });
-        if (d_table) {
-            hipLaunchKernelGGL(k_degree_tally, dim3((unsigned)std::min<u64>(1024, ceil_div(m, 256))), dim3(256), 0, c->stream, (const u8*)out, m, d_table);
-            CBLX_HIP(hipGetLastError());
-        }
-    }
-    CBLX_HIP(hipStreamSynchronize(c->stream));  // the scratch k-mers and masks die here
-}
-
-// `cbl list`: the lines of the whole index to a file descriptor, chunk by chunk. Two device buffers and two pinned ones: while the device emits
-// chunk i, chunk i - 1 crosses to its pinned buffer and a writer thread hands chunk i - 2 to write(), in order.
-static const u64 LIST_CHUNK_DEFAULT = 1ull << 21;
-// The stream itself: `total` bytes (not 0) in chunks of `cbytes`. emit(i, len) queues on the ctx's stream whatever makes chunk i and returns where its
-// len bytes will be on the device; what it returned for chunk i - 2 is free again when it is called for chunk i. `what` names the text in the message
-// of a failed write.
-template <typename Emit> void stream_chunks_to_fd(cblx_ctx* c, int fd, u64 total, u64 cbytes, const char* what, Emit&& emit) {
-    const u64 nch = ceil_div(total, cbytes);
-    const u8* src_dev[2] = {nullptr, nullptr};
-    struct Pinned {
-        u8* p[2] = {nullptr, nullptr};
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        ~Pinned() { for (int i = 0; i < 2; ++i) { if (p[i]) (void)hipHostFree(p[i]); if (ev[i]) (void)hipEventDestroy(ev[i]); } }
-    } pin;
-    for (int i = 0; i < (nch > 1 ? 2 : 1); ++i) CBLX_HIP(hipHostMalloc((void**)&pin.p[i], cbytes, hipHostMallocDefault));
-    for (int i = 0; i < 2; ++i) CBLX_HIP(hipEventCreateWithFlags(&pin.ev[i], hipEventDisableTiming));
-    struct Drain {  // on any way out no emitter is still writing into a buffer that goes back to the pool
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{c->stream};
-    // the writer: chunks [0, handed) may be written, `written` are done; it stops at the first error
-    struct Writer {
-        std::mutex mu;
-        std::condition_variable cv;
-        u64 handed = 0, written = 0;
-        bool quit = false;
-        int err = 0;  // errno of a failed write, EIO for one that wrote nothing
-        std::thread th;
-        ~Writer() { { std::lock_guard<std::mutex> g(mu); quit = true; } cv.notify_all(); if (th.joinable()) th.join(); }
-    } wr;
-    auto chunk_len = [&](u64 i) { return std::min<u64>(cbytes, total - i * cbytes); };
-    wr.th = std::thread([&] {
-        for (u64 i = 0;; ++i) {
-            {
-                std::unique_lock<std::mutex> g(wr.mu);
-                wr.cv.wait(g, [&] { return wr.quit || wr.handed > i; });
-                if (wr.handed <= i) return;
-            }
-            const u8* src = pin.p[i & 1];
-            u64 left = chunk_len(i);
-            int err = 0;
-            while (left) {
-                const ssize_t k = ::write(fd, src, left);
-                if (k < 0 && errno == EINTR) continue;
-                if (k <= 0) { err = k < 0 ? errno : EIO; break; }
-                src += k; left -= (u64)k;
-            }
-            std::lock_guard<std::mutex> g(wr.mu);
-            if (err) { wr.err = err; wr.cv.notify_all(); return; }
-            wr.written = i + 1;
-            wr.cv.notify_all();
-        }
-    });
-    auto fail_if_bad = [&] { if (wr.err) throw Error(CBLX_EINVAL, std::string("Failed to write the ") + what + ": " + std::strerror(wr.err)); };
-    for (u64 i = 0; i <= nch; ++i) {
-        if (i < nch) {  // chunk i - 2 was downloaded in the previous round
-            src_dev[i & 1] = emit(i, chunk_len(i));
-            CBLX_HIP(hipEventRecord(pin.ev[i & 1], c->stream));
-        }
-        if (i >= 1) {
-            const u64 j = i - 1;
-            CBLX_HIP(hipEventSynchronize(pin.ev[j & 1]));
-            {
-                std::unique_lock<std::mutex> g(wr.mu);  // the pinned buffer of chunk j still holds chunk j - 2 until that is written
-                wr.cv.wait(g, [&] { return wr.err || wr.written + 2 > j; });
-                fail_if_bad();
-            }
-            xfer(c).d2h_copy(pin.p[j & 1], src_dev[j & 1], chunk_len(j));
-            { std::lock_guard<std::mutex> g(wr.mu); wr.handed = j + 1; }
-            wr.cv.notify_all();
-        }
-    }
-    std::unique_lock<std::mutex> g(wr.mu);
-    wr.cv.wait(g, [&] { return wr.err || wr.written == nch; });
-    fail_if_bad();
-}
-void list_to_fd(cblx_ctx* c, int fd, u64 chunk, u64* n_kmers) {
-    flush(c);
-    const Resident& r = c->res;
-    if (n_kmers) *n_kmers = r.count;
-    if (r.count == 0) return;
-    if (chunk == 0) chunk = LIST_CHUNK_DEFAULT;
-    chunk = std::min<u64>(chunk, r.count);
-    const u64 LINE = c->P.K + 1, cbytes = chunk * LINE, nch = ceil_div(r.count, chunk);
-    Buf<u64> res_off;
-    iteration_offsets(c, res_off);
-    Buf<u8> dev[2] = {Buf<u8>(c->pool, cbytes), Buf<u8>(c->pool, nch > 1 ? cbytes : 1)};
-    stream_chunks_to_fd(c, fd, r.count * LINE, cbytes, "list", [&](u64 i, u64) -> const u8* {
-        export_range_launch(c, res_off.get(), i * chunk, std::min<u64>(chunk, r.count - i * chunk), nullptr, nullptr, dev[i & 1].get());
-        return dev[i & 1].get();
+// the arrays a table call fills (any may be null; `reversed` exists in the bidirected form only) and the three counts it reports
+struct UnitigTableArgs {
+    u32 *unitig, *offset;
+    u8* reversed;
+    u64 cap_kmers;
+    u32 *head, *length;
+    u8* flags;
+    u64 cap_unitigs, *n_kmers, *n_unitigs, *n_circular;
+};
+// cblx_unitig_table* and cblx_biunitig_table*: counts out, the capacities, then numbering into the caller's device arrays (`device`) or into pool
+// arrays copied back
+int unitig_table(cblx_ctx* c, UnitigForm form, bool device, const UnitigTableArgs& o) {
+    return guard(c, [&] {
+        UnitigRun u;
+        unitig_compute(c, u, form);
+        collect_events(c);
+        if (o.n_kmers) *o.n_kmers = u.n;
+        if (o.n_unitigs) *o.n_unitigs = u.n_unitigs;
+        if (o.n_circular) *o.n_circular = u.n_circular;
+        const bool per_kmer = o.unitig || o.offset || o.reversed, per_unitig = o.head || o.length || o.flags;
+        unitig_caps(u, per_kmer, o.cap_kmers, per_unitig, o.cap_unitigs);
+        if (u.n == 0 || !(per_kmer || per_unitig)) return;
+        if (device) { unitig_number(c, u, o.unitig, o.offset, o.reversed, o.head, o.length, o.flags); return; }
+        const u64 n = u.n, nu = u.n_unitigs;
+        Buf<u32> d_unitig(c->pool, o.unitig ? n : 1), d_offset(c->pool, o.offset ? n : 1), d_head(c->pool, o.head ? nu : 1), d_length(c->pool, o.length ? nu : 1);
+        Buf<u8> d_reversed, d_flags(c->pool, o.flags ? nu : 1);
+        if (o.reversed) d_reversed = Buf<u8>(c->pool, n);
+        unitig_number(c, u, o.unitig ? d_unitig.get() : nullptr, o.offset ? d_offset.get() : nullptr, d_reversed.get(), o.head ? d_head.get() : nullptr,
+                      o.length ? d_length.get() : nullptr, o.flags ? d_flags.get() : nullptr);
+        if (o.unitig) xfer(c).d2h_copy(o.unitig, d_unitig.get(), n * 4);
+        if (o.offset) xfer(c).d2h_copy(o.offset, d_offset.get(), n * 4);
+        if (o.reversed) xfer(c).d2h_copy(o.reversed, d_reversed.get(), n);
+        if (o.head) xfer(c).d2h_copy(o.head, d_head.get(), nu * 4);
+        if (o.length) xfer(c).d2h_copy(o.length, d_length.get(), nu * 4);
+        if (o.flags) xfer(c).d2h_copy(o.flags, d_flags.get(), nu);
     });
 }
-// ---- unitigs (kernels_unitig.hpp) ----------------------------------------------------------------------------------
-// rank[i] = the ordinal of word i in the iteration order, ~0 when the index does not hold it (`res_off` of iteration_offsets)
-template <typename C> void rank_words(cblx_ctx* c, const u64* res_off, const u64* w_lo, const typename C::HiT* w_hi, u64 n, u64* d_rank) {
-    typedef typename C::HiT HiT;
-    const u64 step = 1ull << 28;  // QL lanes per query: 2^31 work items per launch
-    for (u64 a = 0; a < n; a += step) {
-        const u64 m = std::min(step, n - a);
-        hipLaunchKernelGGL(k_rank<HiT>, grid1(m * QL, 256), dim3(256), 0, c->stream, w_lo + a, HiTraits<HiT>::has ? w_hi + a : w_hi, m, c->P.SB, c->P.PB, c->res.view(),
-                           c->res.a_lo.get(), c->P.wide_suffix() ? c->res.a_hi.get() : (const u64*)nullptr, res_off, d_rank + a);
-    }
-    CBLX_HIP(hipGetLastError());
+// cblx_unitigs_text_device and cblx_biunitigs_text_device
+int unitigs_text_device(cblx_ctx* c, UnitigForm form, u8* d_buf, u64 cap, u64* bytes, u64* n_unitigs) {
+    return guard(c, [&] {
+        UnitigText t;
+        unitig_text(c, form, t, d_buf, [&](u64 need) {
+            if (bytes) *bytes = need;
+            if (n_unitigs) *n_unitigs = t.n_unitigs;
+            if (d_buf && need > cap) throw Error(CBLX_ERANGE, "buffer too small: need " + std::to_string(need) + " bytes");
+            return d_buf != nullptr;  // null: the size is all that was asked for
+        });
+        collect_events(c);
+    });
 }
-// The ranks of n packed k-mers of device arrays (d_hi may be null for K <= 31; n != 0), in passes of RANK_PASS k-mers: the whole batch is checked
-// before the first pass writes a rank, then k_kmers_to_words (which canonicalises where the index is canonical) and k_rank.
-static const u64 RANK_PASS = 1ull << 24;
-template <typename C> void rank_kmers_device(cblx_ctx* c, const u64* d_lo, const u64* d_hi, u64 n, u64* d_rank) {
-    typedef typename C::HiT HiT;
-    const Consts& P = c->P;
-    Buf<u32> bad(c->pool, 1);
-    CBLX_HIP(hipMemsetAsync(bad.get(), 0, 4, c->stream));
-    for (u64 a = 0; a < n; a += 1ull << 31)
-        hipLaunchKernelGGL((k_kmers_check<C::WIDE>), grid1(std::min<u64>(1ull << 31, n - a), 256), dim3(256), 0, c->stream, d_lo + a, d_hi ? d_hi + a : d_hi,
-                           std::min<u64>(1ull << 31, n - a), P, bad.get());
-    CBLX_HIP(hipGetLastError());
-    if (d2h<u32>(c, bad.get())) throw Error(CBLX_EINVAL, "k-mer has bits set above 2K (not an IntKmer<K>)");
-    const u64 pass = std::min(RANK_PASS, n);
-    Buf<u64> res_off, w_lo(c->pool, pass + 2);
-    Buf<u8> w_hi(c->pool, (pass + 2) * std::max<size_t>(1, hi_elem_size(P)));
-    iteration_offsets(c, res_off);
-    for (u64 a = 0; a < n; a += pass) {
-        const u64 m = std::min(pass, n - a);
-        hipLaunchKernelGGL((k_kmers_to_words<C::WIDE, HiT>), grid1(m, 256), dim3(256), 0, c->stream, d_lo + a, d_hi ? d_hi + a : d_hi, m, P, w_lo.get(), (HiT*)w_hi.get(),
-                           bad.get());
-        rank_words<C>(c, res_off.get(), w_lo.get(), (const HiT*)w_hi.get(), m, d_rank + a);
-    }
-    CBLX_HIP(hipStreamSynchronize(c->stream));  // the words die here
+// cblx_unitigs_to_fd and cblx_biunitigs_to_fd, cblx_unitigs_to_file and cblx_biunitigs_to_file
+int unitigs_to_fd_call(cblx_ctx* c, UnitigForm form, int fd, u64 chunk_bytes, u64* n_unitigs, u64* bytes) {
+    return guard(c, [&] {
+        if (fd < 0) throw Error(CBLX_EINVAL, "bad file descriptor");
+        unitigs_to_fd(c, form, fd, chunk_bytes, n_unitigs, bytes);
+    });
+}
+int unitigs_to_file(cblx_ctx* c, UnitigForm form, const char* path, u64 chunk_bytes, u64* n_unitigs, u64* bytes) {
+    return guard(c, [&] {
+        if (!path) throw Error(CBLX_EINVAL, "null argument");
+        unitig_require(c, form);  // a refusal comes before the file is created or truncated
+        text_to_file(path, "unitigs", [&](int fd) { unitigs_to_fd(c, form, fd, chunk_bytes, n_unitigs, bytes); });
+    });
 }
 
-// The compaction of the resident index: links, list ranking and the cut of the pure cycles (compute), then numbering into whatever arrays the
-// caller has (number). Ordinals are 32-bit inside. Every call recomputes.
-struct UnitigRun {
-    u64 n = 0, n_unitigs = 0, n_circular = 0;
-    u32 rounds = 0;  // jump rounds, the ones after a cycle cut included
-    Buf<u32> next, prev, anc[2], dist[2];
-    Buf<u8> circular;
-    int cur = 0;  // anc[cur] / dist[cur] hold the ranking; the other pair is scratch (the head flags and their scan, in the end)
-};
-// List ranking over u.prev / u.next, arrays of n ids (the k-mers of section 6k, the oriented k-mers of section 6l): pointer jumping, and the cut of the
-// pure cycles when the count of unfinished ids repeats. `counters`: 130 zeroed words — [r] the unfinished ids of round r, [129] the cycles cut.
-void unitig_rank(cblx_ctx* c, UnitigRun& u, u64 n, Buf<u64>& counters) {
-    const dim3 gn = grid1(n, 256), b256(256);
-    hipLaunchKernelGGL(k_unitig_rank_init, gn, b256, 0, c->stream, u.prev.get(), n, u.anc[0].get(), u.dist[0].get());
-    u.cur = 0;
-    u64 last = ~0ull;
-    bool cut = false;
-    for (u32 r = 0;; ++r) {
-        if (r >= 128) throw Error(CBLX_EDEVICE, "unitig ranking did not end (internal error)");
-        const int o = u.cur ^ 1;
-        hipLaunchKernelGGL(k_unitig_jump, gn, b256, 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), n, u.anc[o].get(), u.dist[o].get(), counters.get() + r);
-        CBLX_HIP(hipGetLastError());
-        u.cur = o;
-        ++u.rounds;
-        const u64 open = d2h<u64>(c, counters.get() + r);  // the k-mers that were unfinished when the round began
-        if (open == 0) break;
-        if (open != last) { last = open; continue; }
-        // every path is finished: the `open` unfinished k-mers are the members of the pure cycles
-        if (cut) throw Error(CBLX_EDEVICE, "unitig ranking stalled after the cycle cut (internal error)");
-        cut = true;
-        last = ~0ull;
-        Buf<u32> lo[2] = {Buf<u32>(c->pool, n), Buf<u32>(c->pool, n)}, ptr[2] = {Buf<u32>(c->pool, n), Buf<u32>(c->pool, n)};
-        hipLaunchKernelGGL(k_cycle_init, gn, b256, 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), u.next.get(), n, lo[0].get(), ptr[0].get());
-        int lc = 0;
-        for (u64 span = 1; span < open; span <<= 1, lc ^= 1)  // a cycle has at most `open` members
-            hipLaunchKernelGGL(k_cycle_min, gn, b256, 0, c->stream, lo[lc].get(), ptr[lc].get(), n, lo[lc ^ 1].get(), ptr[lc ^ 1].get());
-        hipLaunchKernelGGL(k_cycle_cut, gn, b256, 0, c->stream, lo[lc].get(), n, u.next.get(), u.prev.get(), u.circular.get(), u.anc[u.cur].get(), u.dist[u.cur].get(),
-                           counters.get() + 129);
-        CBLX_HIP(hipGetLastError());
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // lo / ptr die here
-    }
-}
-void unitig_compute(cblx_ctx* c, UnitigRun& u) {
-    flush(c);
-    if (c->P.canonical) throw Error(CBLX_EINVAL, "unitigs of a canonical index (bidirected unitigs) are not supported");
-    const u64 n = c->res.count;
-    if (n >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "the index holds " + std::to_string(n) + " k-mers: unitigs need fewer than 2^32 - 16");
-    u.n = n;
-    if (n == 0) return;
-    const dim3 gn = grid1(n, 256), b256(256);
-    u.next = Buf<u32>(c->pool, n); u.prev = Buf<u32>(c->pool, n);
-    u.circular = Buf<u8>(c->pool, n);
-    for (int i = 0; i < 2; ++i) { u.anc[i] = Buf<u32>(c->pool, n); u.dist[i] = Buf<u32>(c->pool, n); }
-    Buf<u64> counters(c->pool, 130);  // [r] unfinished k-mers of round r; [129] circular unitigs
-    CBLX_HIP(hipMemsetAsync(u.next.get(), 0xFF, n * 4, c->stream));
-    CBLX_HIP(hipMemsetAsync(u.prev.get(), 0xFF, n * 4, c->stream));
-    CBLX_HIP(hipMemsetAsync(u.circular.get(), 0, n, c->stream));
-    CBLX_HIP(hipMemsetAsync(counters.get(), 0, 130 * 8, c->stream));
-    {   // (a) all masks, (b) the links, pass by pass
-        Buf<u8> masks(c->pool, n + 8);
-        neighbor_masks_range(c, 0, n, masks.get(), nullptr);
-        const u64 pass = std::min(neighbor_pass(), n);
-        const bool wide = c->P.wide_kmer();
-        Buf<u64> res_off, k_lo(c->pool, pass), k_hi(c->pool, wide ? pass : 1);
-        iteration_offsets(c, res_off);
-        for (u64 a = 0; a < n; a += pass) {
-            const u64 m = std::min(pass, n - a);
-            export_range_launch(c, res_off.get(), a, m, k_lo.get(), wide ? k_hi.get() : (u64*)nullptr, nullptr);
-            dispatch(c->P, [&](auto cfg) {
-                typedef decltype(cfg) C;
-                hipLaunchKernelGGL((k_unitig_links<C::WIDE>), grid1(m * QL, 256), b256, 0, c->stream, k_lo.get(), wide ? k_hi.get() : (const u64*)nullptr, a, m, masks.get(), c->P,
-                                   c->res.view(), c->res.a_lo.get(), c->P.wide_suffix() ? c->res.a_hi.get() : (const u64*)nullptr, res_off.get(), u.next.get(), u.prev.get());
-            });
-            CBLX_HIP(hipGetLastError());
-        }
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // the masks and the scratch k-mers die here
-    }
-    // (c) pointer jumping; (d) the cycle cut when the count of unfinished k-mers repeats
-    unitig_rank(c, u, n, counters);
-    u.n_circular = d2h<u64>(c, counters.get() + 129);
-    // (e) head flags -> exclusive scan -> unitig numbers, in the scratch pair
-    const int o = u.cur ^ 1;
-    hipLaunchKernelGGL(k_unitig_heads, gn, b256, 0, c->stream, u.prev.get(), n, u.anc[o].get());
-    CBLX_HIP(hipGetLastError());
-    u.n_unitigs = exclusive_scan<u32>(c, u.anc[o].get(), n, u.dist[o].get());
-}
-// per k-mer unitig / offset, per unitig head / length / flags (device arrays of u.n and u.n_unitigs elements; any may be null); u.n != 0
-void unitig_number(cblx_ctx* c, const UnitigRun& u, u32* d_unitig, u32* d_offset, u32* d_head, u32* d_length, u8* d_flags) {
-    hipLaunchKernelGGL(k_unitig_number, grid1(u.n, 256), dim3(256), 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), u.next.get(), u.dist[u.cur ^ 1].get(),
-                       u.circular.get(), u.n, d_unitig, d_offset, d_head, d_length, d_flags);
-    CBLX_HIP(hipGetLastError());
-    CBLX_HIP(hipStreamSynchronize(c->stream));
-}
-void unitig_caps(const UnitigRun& u, bool per_kmer, u64 cap_kmers, bool per_unitig, u64 cap_unitigs) {
-    if ((per_kmer && cap_kmers < u.n) || (per_unitig && cap_unitigs < u.n_unitigs))
-        throw Error(CBLX_ERANGE, "output capacity too small: the index holds " + std::to_string(u.n) + " k-mers in " + std::to_string(u.n_unitigs) + " unitigs");
-}
-// The text of all unitigs in device memory: n + U K bytes, lines in unitig order (text.get() is null for an empty index).
-struct UnitigText {
-    Buf<u8> text;
-    u64 bytes = 0, n_unitigs = 0;
-};
-// `d_out`: the caller's buffer, or null: t.text is allocated. fits(need) is called once the need is known: it may refuse (throw), or return false when the
-// size is all that is wanted.
-template <typename Fits> void unitig_text(cblx_ctx* c, UnitigText& t, u8* d_out, Fits&& fits) {
-    UnitigRun u;
-    unitig_compute(c, u);
-    const u64 n = u.n, nu = u.n_unitigs, K = c->P.K;
-    t.n_unitigs = nu;
-    t.bytes = n + nu * K;
-    if (!fits(t.bytes) || n == 0) return;
-    if (!d_out) { t.text = Buf<u8>(c->pool, t.bytes); d_out = t.text.get(); }
-    Buf<u32> unitig(c->pool, n), offset(c->pool, n), length(c->pool, nu), line(c->pool, nu);
-    Buf<u64> base(c->pool, nu);
-    unitig_number(c, u, unitig.get(), offset.get(), nullptr, length.get(), nullptr);
-    u = UnitigRun();  // the ranking's arrays go back to the pool
-    hipLaunchKernelGGL(k_unitig_line_bytes, grid1(nu, 256), dim3(256), 0, c->stream, length.get(), nu, (u32)K, line.get());
-    CBLX_HIP(hipGetLastError());
-    if (exclusive_scan<u64>(c, line.get(), nu, base.get()) != t.bytes) throw Error(CBLX_EDEVICE, "unitig lengths do not add up (internal error)");
-    const u64 pass = std::min(neighbor_pass(), n);
-    const bool wide = c->P.wide_kmer();
-    Buf<u64> res_off, k_lo(c->pool, pass), k_hi(c->pool, wide ? pass : 1);
-    iteration_offsets(c, res_off);
-    for (u64 a = 0; a < n; a += pass) {
-        const u64 m = std::min(pass, n - a);
-        export_range_launch(c, res_off.get(), a, m, k_lo.get(), wide ? k_hi.get() : (u64*)nullptr, nullptr);
-        hipLaunchKernelGGL(k_unitig_text, grid1(m, 256), dim3(256), 0, c->stream, k_lo.get(), wide ? k_hi.get() : (const u64*)nullptr, a, m, unitig.get(), offset.get(),
-                           length.get(), base.get(), (u32)K, d_out);
-        CBLX_HIP(hipGetLastError());
-    }
-    CBLX_HIP(hipStreamSynchronize(c->stream));  // the table and the scratch k-mers die here
-}
-// `cbl unitigs`: the text is built once on the device and leaves through the two pinned buffers of the list
-void unitigs_to_fd(cblx_ctx* c, int fd, u64 chunk_bytes, u64* n_unitigs, u64* bytes) {
-    UnitigText t;
-    unitig_text(c, t, nullptr, [](u64) { return true; });
-    if (n_unitigs) *n_unitigs = t.n_unitigs;
-    if (bytes) *bytes = t.bytes;
-    if (t.bytes == 0) return;
-    if (chunk_bytes == 0) chunk_bytes = LIST_CHUNK_DEFAULT * (c->P.K + 1);
-    const u64 cbytes = std::min<u64>(chunk_bytes, t.bytes);
-    stream_chunks_to_fd(c, fd, t.bytes, cbytes, "unitigs", [&](u64 i, u64) -> const u8* { return t.text.get() + i * cbytes; });
-}
-
-// ---- bidirected unitigs (kernels_biunitig.hpp) ----------------------------------------------------------------------
-// The compaction of a canonical index with odd K: section 6k's run on the 2 n oriented k-mers (u.next .. u.circular hold 2 n elements, u.n stays the
-// number of stored k-mers), then the choice of one image of every mirror pair. In the end the scratch pair holds the kept-head flags (anc) and their
-// exclusive scan (dist). About twice the workspace of unitig_compute: six 32-bit arrays and a byte array of 2 n, and the n masks while the links are made.
-void biunitig_require(const cblx_ctx* c) {
-    if (!c->P.canonical) throw Error(CBLX_EINVAL, "bidirected unitigs are those of a canonical index: a non-canonical index has cblx_unitig_table and cblx_unitigs_*");
-    if ((c->P.K & 1u) == 0) throw Error(CBLX_EINVAL, "bidirected unitigs need an odd K (a k-mer of even K can be its own reverse complement)");
-}
-void biunitig_compute(cblx_ctx* c, UnitigRun& u) {
-    flush(c);
-    biunitig_require(c);
-    const u64 n = c->res.count;
-    if (n >= 0x7FFFFFF8ull) throw Error(CBLX_ERANGE, "the index holds " + std::to_string(n) + " k-mers: bidirected unitigs need fewer than 2^31 - 8");
-    u.n = n;
-    if (n == 0) return;
-    const u64 n2 = 2 * n;
-    const dim3 g2 = grid1(n2, 256), b256(256);
-    u.next = Buf<u32>(c->pool, n2); u.prev = Buf<u32>(c->pool, n2);
-    u.circular = Buf<u8>(c->pool, n2);
-    for (int i = 0; i < 2; ++i) { u.anc[i] = Buf<u32>(c->pool, n2); u.dist[i] = Buf<u32>(c->pool, n2); }
-    Buf<u64> counters(c->pool, 130);  // [r] unfinished ids of round r; [129] cycles cut: two per circular unitig
-    CBLX_HIP(hipMemsetAsync(u.next.get(), 0xFF, n2 * 4, c->stream));
-    CBLX_HIP(hipMemsetAsync(u.prev.get(), 0xFF, n2 * 4, c->stream));
-    CBLX_HIP(hipMemsetAsync(u.circular.get(), 0, n2, c->stream));
-    CBLX_HIP(hipMemsetAsync(counters.get(), 0, 130 * 8, c->stream));
-    {   // (a) all masks, (b) the links, pass by pass
-        Buf<u8> masks(c->pool, n + 8);
-        neighbor_masks_range(c, 0, n, masks.get(), nullptr);
-        const u64 pass = std::min(neighbor_pass(), n);
-        const bool wide = c->P.wide_kmer();
-        Buf<u64> res_off, k_lo(c->pool, pass), k_hi(c->pool, wide ? pass : 1);
-        iteration_offsets(c, res_off);
-        for (u64 a = 0; a < n; a += pass) {
-            const u64 m = std::min(pass, n - a);
-            export_range_launch(c, res_off.get(), a, m, k_lo.get(), wide ? k_hi.get() : (u64*)nullptr, nullptr);
-            dispatch(c->P, [&](auto cfg) {
-                typedef decltype(cfg) C;
-                const u64 step = 1ull << 27;  // 2 QL lanes per k-mer: 2^31 work items per launch
-                for (u64 b = 0; b < m; b += step) {
-                    const u64 mb = std::min(step, m - b);
-                    hipLaunchKernelGGL((k_biunitig_links<C::WIDE>), grid1(2 * mb * QL, 256), b256, 0, c->stream, k_lo.get() + b, wide ? k_hi.get() + b : (const u64*)nullptr, a + b, mb,
-                                       masks.get(), c->P, c->res.view(), c->res.a_lo.get(), c->P.wide_suffix() ? c->res.a_hi.get() : (const u64*)nullptr, res_off.get(),
-                                       u.next.get(), u.prev.get());
-                }
-            });
-            CBLX_HIP(hipGetLastError());
-        }
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // the masks and the scratch k-mers die here
-    }
-    // (c) the ranking of section 6k over the 2 n ids: a cycle and its mirror are both cut, in front of the same stored k-mer
-    unitig_rank(c, u, n2, counters);
-    const u64 cuts = d2h<u64>(c, counters.get() + 129);
-    if (cuts & 1) throw Error(CBLX_EDEVICE, "a cycle of oriented k-mers without its mirror (internal error)");
-    u.n_circular = cuts / 2;
-    // (d) tails -> kept heads -> exclusive scan -> unitig numbers, in the scratch pair
-    const int o = u.cur ^ 1;
-    hipLaunchKernelGGL(k_biunitig_tails, g2, b256, 0, c->stream, u.anc[u.cur].get(), u.next.get(), n2, u.anc[o].get());
-    hipLaunchKernelGGL(k_biunitig_keep, g2, b256, 0, c->stream, u.prev.get(), u.circular.get(), n2, u.anc[o].get());
-    CBLX_HIP(hipGetLastError());
-    u.n_unitigs = exclusive_scan<u32>(c, u.anc[o].get(), n2, u.dist[o].get());
-}
-// per stored k-mer unitig / offset / reversed, per unitig head / length / flags (device arrays of u.n and u.n_unitigs elements; any may be null); u.n != 0
-void biunitig_number(cblx_ctx* c, const UnitigRun& u, u32* d_unitig, u32* d_offset, u8* d_reversed, u32* d_head, u32* d_length, u8* d_flags) {
-    hipLaunchKernelGGL(k_biunitig_number, grid1(2 * u.n, 256), dim3(256), 0, c->stream, u.anc[u.cur].get(), u.dist[u.cur].get(), u.next.get(), u.anc[u.cur ^ 1].get(),
-                       u.dist[u.cur ^ 1].get(), u.circular.get(), 2 * u.n, d_unitig, d_offset, d_reversed, d_head, d_length, d_flags);
-    CBLX_HIP(hipGetLastError());
-    CBLX_HIP(hipStreamSynchronize(c->stream));
-}
-// unitig_text for the bidirected form: the same sizes and the same layout
-template <typename Fits> void biunitig_text(cblx_ctx* c, UnitigText& t, u8* d_out, Fits&& fits) {
-    UnitigRun u;
-    biunitig_compute(c, u);
-    const u64 n = u.n, nu = u.n_unitigs, K = c->P.K;
-    t.n_unitigs = nu;
-    t.bytes = n + nu * K;
-    if (!fits(t.bytes) || n == 0) return;
-    if (!d_out) { t.text = Buf<u8>(c->pool, t.bytes); d_out = t.text.get(); }
-    Buf<u32> unitig(c->pool, n), offset(c->pool, n), length(c->pool, nu), line(c->pool, nu);
-    Buf<u8> reversed(c->pool, n);
-    Buf<u64> base(c->pool, nu);
-    biunitig_number(c, u, unitig.get(), offset.get(), reversed.get(), nullptr, length.get(), nullptr);
-    u = UnitigRun();  // the ranking's arrays go back to the pool
-    hipLaunchKernelGGL(k_unitig_line_bytes, grid1(nu, 256), dim3(256), 0, c->stream, length.get(), nu, (u32)K, line.get());
-    CBLX_HIP(hipGetLastError());
-    if (exclusive_scan<u64>(c, line.get(), nu, base.get()) != t.bytes) throw Error(CBLX_EDEVICE, "unitig lengths do not add up (internal error)");
-    const u64 pass = std::min(neighbor_pass(), n);
-    const bool wide = c->P.wide_kmer();
-    Buf<u64> res_off, k_lo(c->pool, pass), k_hi(c->pool, wide ? pass : 1);
-    iteration_offsets(c, res_off);
-    for (u64 a = 0; a < n; a += pass) {
-        const u64 m = std::min(pass, n - a);
-        export_range_launch(c, res_off.get(), a, m, k_lo.get(), wide ? k_hi.get() : (u64*)nullptr, nullptr);
-        hipLaunchKernelGGL(k_biunitig_text, grid1(m, 256), dim3(256), 0, c->stream, k_lo.get(), wide ? k_hi.get() : (const u64*)nullptr, a, m, unitig.get(), offset.get(),
-                           reversed.get(), length.get(), base.get(), (u32)K, d_out);
-        CBLX_HIP(hipGetLastError());
-    }
-    CBLX_HIP(hipStreamSynchronize(c->stream));  // the table and the scratch k-mers die here
-}
-void biunitigs_to_fd(cblx_ctx* c, int fd, u64 chunk_bytes, u64* n_unitigs, u64* bytes) {
-    UnitigText t;
-    biunitig_text(c, t, nullptr, [](u64) { return true; });
-    if (n_unitigs) *n_unitigs = t.n_unitigs;
-    if (bytes) *bytes = t.bytes;
-    if (t.bytes == 0) return;
-    if (chunk_bytes == 0) chunk_bytes = LIST_CHUNK_DEFAULT * (c->P.K + 1);
-    const u64 cbytes = std::min<u64>(chunk_bytes, t.bytes);
-    stream_chunks_to_fd(c, fd, t.bytes, cbytes, "unitigs", [&](u64 i, u64) -> const u8* { return t.text.get() + i * cbytes; });
-}
 }  // namespace
 
 extern "C" {
@@ -2058,7 +1634,7 @@ int cblx_neighbors_kmers_device(cblx_ctx* c, const uint64_t* d_lo, const uint64_
     return guard(c, [&] {
         flush(c);
         if (n == 0) return;
-        if (!d_masks || !d_lo || (c->P.wide_kmer() && !d_hi)) throw Error(CBLX_EINVAL, c->P.wide_kmer() ? "null argument (K >= 33 needs the hi halves of the k-mers)" : "null argument");
+        require_kmer_arrays(c, d_lo, d_hi, d_masks);
         dispatch(c->P, [&](auto cfg) { neighbor_masks_device<decltype(cfg)>(c, d_lo, d_hi, n, d_masks); });
         collect_events(c);
         CBLX_HIP(hipStreamSynchronize(c->stream));
@@ -2068,7 +1644,7 @@ int cblx_neighbors_kmers(cblx_ctx* c, const uint64_t* lo, const uint64_t* hi, ui
     return guard(c, [&] {
         flush(c);
         if (n == 0) return;
-        if (!masks || !lo || (c->P.wide_kmer() && !hi)) throw Error(CBLX_EINVAL, c->P.wide_kmer() ? "null argument (K >= 33 needs the hi halves of the k-mers)" : "null argument");
+        require_kmer_arrays(c, lo, hi, masks);
         Buf<u64> k_lo(c->pool, n + 1), k_hi(c->pool, hi ? n + 1 : 1);
         Buf<u8> d_masks(c->pool, n + 8);
         xfer(c).h2d_copy(k_lo.get(), lo, n * 8);
@@ -2158,10 +1734,7 @@ int cblx_list_to_fd(cblx_ctx* c, int fd, uint64_t chunk_kmers, uint64_t* n_kmers
 int cblx_list_to_file(cblx_ctx* c, const char* path, uint64_t chunk_kmers, uint64_t* n_kmers) {
     return guard(c, [&] {
         if (!path) throw Error(CBLX_EINVAL, "null argument");
-        const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (fd < 0) throw Error(CBLX_EINVAL, std::string("Failed to open ") + path);
-        try { list_to_fd(c, fd, chunk_kmers, n_kmers); } catch (...) { (void)::close(fd); throw; }
-        if (::close(fd) != 0) throw Error(CBLX_EINVAL, std::string("Failed to write the list to ") + path);
+        text_to_file(path, "list", [&](int fd) { list_to_fd(c, fd, chunk_kmers, n_kmers); });
     });
 }
 // ---- unitigs: observers, nothing is modified or sorted
@@ -2169,7 +1742,7 @@ int cblx_rank_kmers_device(cblx_ctx* c, const uint64_t* d_lo, const uint64_t* d_
     return guard(c, [&] {
         flush(c);
         if (n == 0) return;
-        if (!d_rank || !d_lo || (c->P.wide_kmer() && !d_hi)) throw Error(CBLX_EINVAL, c->P.wide_kmer() ? "null argument (K >= 33 needs the hi halves of the k-mers)" : "null argument");
+        require_kmer_arrays(c, d_lo, d_hi, d_rank);
         dispatch(c->P, [&](auto cfg) { rank_kmers_device<decltype(cfg)>(c, d_lo, d_hi, n, d_rank); });
     });
 }
@@ -2177,7 +1750,7 @@ int cblx_rank_kmers(cblx_ctx* c, const uint64_t* lo, const uint64_t* hi, uint64_
     return guard(c, [&] {
         flush(c);
         if (n == 0) return;
-        if (!rank || !lo || (c->P.wide_kmer() && !hi)) throw Error(CBLX_EINVAL, c->P.wide_kmer() ? "null argument (K >= 33 needs the hi halves of the k-mers)" : "null argument");
+        require_kmer_arrays(c, lo, hi, rank);
         Buf<u64> k_lo(c->pool, n + 1), k_hi(c->pool, hi ? n + 1 : 1), d_rank(c->pool, n + 1);
         xfer(c).h2d_copy(k_lo.get(), lo, n * 8);
         if (hi) xfer(c).h2d_copy(k_hi.get(), hi, n * 8);
@@ -2188,134 +1761,38 @@ int cblx_rank_kmers(cblx_ctx* c, const uint64_t* lo, const uint64_t* hi, uint64_
 }
 int cblx_unitig_table_device(cblx_ctx* c, uint32_t* d_unitig, uint32_t* d_offset, uint64_t cap_kmers, uint32_t* d_head, uint32_t* d_length, uint8_t* d_flags,
                              uint64_t cap_unitigs, uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular) {
-    return guard(c, [&] {
-        UnitigRun u;
-        unitig_compute(c, u);
-        collect_events(c);
-        if (n_kmers) *n_kmers = u.n;
-        if (n_unitigs) *n_unitigs = u.n_unitigs;
-        if (n_circular) *n_circular = u.n_circular;
-        unitig_caps(u, d_unitig || d_offset, cap_kmers, d_head || d_length || d_flags, cap_unitigs);
-        if (u.n == 0 || !(d_unitig || d_offset || d_head || d_length || d_flags)) return;
-        unitig_number(c, u, d_unitig, d_offset, d_head, d_length, d_flags);
-    });
+    return unitig_table(c, UnitigForm::Plain, true, {d_unitig, d_offset, nullptr, cap_kmers, d_head, d_length, d_flags, cap_unitigs, n_kmers, n_unitigs, n_circular});
 }
 int cblx_unitig_table(cblx_ctx* c, uint32_t* unitig, uint32_t* offset, uint64_t cap_kmers, uint32_t* head, uint32_t* length, uint8_t* flags, uint64_t cap_unitigs,
                       uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular) {
-    return guard(c, [&] {
-        UnitigRun u;
-        unitig_compute(c, u);
-        collect_events(c);
-        if (n_kmers) *n_kmers = u.n;
-        if (n_unitigs) *n_unitigs = u.n_unitigs;
-        if (n_circular) *n_circular = u.n_circular;
-        unitig_caps(u, unitig || offset, cap_kmers, head || length || flags, cap_unitigs);
-        if (u.n == 0 || !(unitig || offset || head || length || flags)) return;
-        const u64 n = u.n, nu = u.n_unitigs;
-        Buf<u32> d_unitig(c->pool, unitig ? n : 1), d_offset(c->pool, offset ? n : 1), d_head(c->pool, head ? nu : 1), d_length(c->pool, length ? nu : 1);
-        Buf<u8> d_flags(c->pool, flags ? nu : 1);
-        unitig_number(c, u, unitig ? d_unitig.get() : nullptr, offset ? d_offset.get() : nullptr, head ? d_head.get() : nullptr, length ? d_length.get() : nullptr,
-                      flags ? d_flags.get() : nullptr);
-        if (unitig) xfer(c).d2h_copy(unitig, d_unitig.get(), n * 4);
-        if (offset) xfer(c).d2h_copy(offset, d_offset.get(), n * 4);
-        if (head) xfer(c).d2h_copy(head, d_head.get(), nu * 4);
-        if (length) xfer(c).d2h_copy(length, d_length.get(), nu * 4);
-        if (flags) xfer(c).d2h_copy(flags, d_flags.get(), nu);
-    });
+    return unitig_table(c, UnitigForm::Plain, false, {unitig, offset, nullptr, cap_kmers, head, length, flags, cap_unitigs, n_kmers, n_unitigs, n_circular});
 }
 int cblx_unitigs_text_device(cblx_ctx* c, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs) {
-    return guard(c, [&] {
-        UnitigText t;
-        unitig_text(c, t, d_buf, [&](u64 need) {
-            if (bytes) *bytes = need;
-            if (n_unitigs) *n_unitigs = t.n_unitigs;
-            if (d_buf && need > cap) throw Error(CBLX_ERANGE, "buffer too small: need " + std::to_string(need) + " bytes");
-            return d_buf != nullptr;  // null: the size is all that was asked for
-        });
-        collect_events(c);
-    });
+    return unitigs_text_device(c, UnitigForm::Plain, d_buf, cap, bytes, n_unitigs);
 }
 int cblx_unitigs_to_fd(cblx_ctx* c, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes) {
-    return guard(c, [&] {
-        if (fd < 0) throw Error(CBLX_EINVAL, "bad file descriptor");
-        unitigs_to_fd(c, fd, chunk_bytes, n_unitigs, bytes);
-    });
+    return unitigs_to_fd_call(c, UnitigForm::Plain, fd, chunk_bytes, n_unitigs, bytes);
 }
 int cblx_unitigs_to_file(cblx_ctx* c, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes) {
-    return guard(c, [&] {
-        if (!path) throw Error(CBLX_EINVAL, "null argument");
-        const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (fd < 0) throw Error(CBLX_EINVAL, std::string("Failed to open ") + path);
-        try { unitigs_to_fd(c, fd, chunk_bytes, n_unitigs, bytes); } catch (...) { (void)::close(fd); throw; }
-        if (::close(fd) != 0) throw Error(CBLX_EINVAL, std::string("Failed to write the unitigs to ") + path);
-    });
+    return unitigs_to_file(c, UnitigForm::Plain, path, chunk_bytes, n_unitigs, bytes);
 }
 // ---- bidirected unitigs: the same conventions for a canonical index
 int cblx_biunitig_table_device(cblx_ctx* c, uint32_t* d_unitig, uint32_t* d_offset, uint8_t* d_reversed, uint64_t cap_kmers, uint32_t* d_head, uint32_t* d_length,
                                uint8_t* d_flags, uint64_t cap_unitigs, uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular) {
-    return guard(c, [&] {
-        UnitigRun u;
-        biunitig_compute(c, u);
-        collect_events(c);
-        if (n_kmers) *n_kmers = u.n;
-        if (n_unitigs) *n_unitigs = u.n_unitigs;
-        if (n_circular) *n_circular = u.n_circular;
-        unitig_caps(u, d_unitig || d_offset || d_reversed, cap_kmers, d_head || d_length || d_flags, cap_unitigs);
-        if (u.n == 0 || !(d_unitig || d_offset || d_reversed || d_head || d_length || d_flags)) return;
-        biunitig_number(c, u, d_unitig, d_offset, d_reversed, d_head, d_length, d_flags);
-    });
+    return unitig_table(c, UnitigForm::Bidirected, true, {d_unitig, d_offset, d_reversed, cap_kmers, d_head, d_length, d_flags, cap_unitigs, n_kmers, n_unitigs, n_circular});
 }
 int cblx_biunitig_table(cblx_ctx* c, uint32_t* unitig, uint32_t* offset, uint8_t* reversed, uint64_t cap_kmers, uint32_t* head, uint32_t* length, uint8_t* flags,
                         uint64_t cap_unitigs, uint64_t* n_kmers, uint64_t* n_unitigs, uint64_t* n_circular) {
-    return guard(c, [&] {
-        UnitigRun u;
-        biunitig_compute(c, u);
-        collect_events(c);
-        if (n_kmers) *n_kmers = u.n;
-        if (n_unitigs) *n_unitigs = u.n_unitigs;
-        if (n_circular) *n_circular = u.n_circular;
-        unitig_caps(u, unitig || offset || reversed, cap_kmers, head || length || flags, cap_unitigs);
-        if (u.n == 0 || !(unitig || offset || reversed || head || length || flags)) return;
-        const u64 n = u.n, nu = u.n_unitigs;
-        Buf<u32> d_unitig(c->pool, unitig ? n : 1), d_offset(c->pool, offset ? n : 1), d_head(c->pool, head ? nu : 1), d_length(c->pool, length ? nu : 1);
-        Buf<u8> d_reversed(c->pool, reversed ? n : 1), d_flags(c->pool, flags ? nu : 1);
-        biunitig_number(c, u, unitig ? d_unitig.get() : nullptr, offset ? d_offset.get() : nullptr, reversed ? d_reversed.get() : nullptr, head ? d_head.get() : nullptr,
-                        length ? d_length.get() : nullptr, flags ? d_flags.get() : nullptr);
-        if (unitig) xfer(c).d2h_copy(unitig, d_unitig.get(), n * 4);
-        if (offset) xfer(c).d2h_copy(offset, d_offset.get(), n * 4);
-        if (reversed) xfer(c).d2h_copy(reversed, d_reversed.get(), n);
-        if (head) xfer(c).d2h_copy(head, d_head.get(), nu * 4);
-        if (length) xfer(c).d2h_copy(length, d_length.get(), nu * 4);
-        if (flags) xfer(c).d2h_copy(flags, d_flags.get(), nu);
-    });
+    return unitig_table(c, UnitigForm::Bidirected, false, {unitig, offset, reversed, cap_kmers, head, length, flags, cap_unitigs, n_kmers, n_unitigs, n_circular});
 }
 int cblx_biunitigs_text_device(cblx_ctx* c, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs) {
-    return guard(c, [&] {
-        UnitigText t;
-        biunitig_text(c, t, d_buf, [&](u64 need) {
-            if (bytes) *bytes = need;
-            if (n_unitigs) *n_unitigs = t.n_unitigs;
-            if (d_buf && need > cap) throw Error(CBLX_ERANGE, "buffer too small: need " + std::to_string(need) + " bytes");
-            return d_buf != nullptr;  // null: the size is all that was asked for
-        });
-        collect_events(c);
-    });
+    return unitigs_text_device(c, UnitigForm::Bidirected, d_buf, cap, bytes, n_unitigs);
 }
 int cblx_biunitigs_to_fd(cblx_ctx* c, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes) {
-    return guard(c, [&] {
-        if (fd < 0) throw Error(CBLX_EINVAL, "bad file descriptor");
-        biunitigs_to_fd(c, fd, chunk_bytes, n_unitigs, bytes);
-    });
+    return unitigs_to_fd_call(c, UnitigForm::Bidirected, fd, chunk_bytes, n_unitigs, bytes);
 }
 int cblx_biunitigs_to_file(cblx_ctx* c, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes) {
-    return guard(c, [&] {
-        if (!path) throw Error(CBLX_EINVAL, "null argument");
-        biunitig_require(c);  // a refusal comes before the file is created or truncated
-        const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (fd < 0) throw Error(CBLX_EINVAL, std::string("Failed to open ") + path);
-        try { biunitigs_to_fd(c, fd, chunk_bytes, n_unitigs, bytes); } catch (...) { (void)::close(fd); throw; }
-        if (::close(fd) != 0) throw Error(CBLX_EINVAL, std::string("Failed to write the unitigs to ") + path);
-    });
+    return unitigs_to_file(c, UnitigForm::Bidirected, path, chunk_bytes, n_unitigs, bytes);
 }
 int cblx_bucket_nodes(cblx_ctx* c, uint64_t* nodes, uint64_t cap, uint64_t* n) {
     return guard(c, [&] {

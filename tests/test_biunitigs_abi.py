@@ -42,9 +42,11 @@ def test_python_surface_and_kernel_file():
     for kernel in KERNELS:
         assert re.search(r"__global__[^;{]*\b%s\(" % kernel, kb), kernel
     assert "asm" not in kb and "atomic" not in kb  # plain C++ HIP, plain stores: every output element has one writer
-    # the ranking is section 6k's kernels, unchanged, behind one function that both routes call
-    host = _read("cbl_amd", "csrc", "cblx.cpp")
-    assert len(re.findall(r"\bunitig_rank\(c, u, ", host)) == 2 and len(re.findall(r"hipLaunchKernelGGL\(k_unitig_jump\b", host)) == 1
+    # the ranking is section 6k's kernels, unchanged, behind one function; both forms go through one compaction that launches each form's kernels once
+    host = "".join(_read("cbl_amd", "csrc", name) for name in ("cblx.cpp", "list.hpp", "graph.hpp"))
+    assert len(re.findall(r"^void unitig_rank\(", host, flags=re.M)) == 1 and len(re.findall(r"\bunitig_rank\(c, u, ", host)) == 1
+    for kernel in ("k_unitig_jump", "k_unitig_links", "k_biunitig_links", "k_unitig_number", "k_biunitig_number", "k_unitig_text", "k_biunitig_text"):
+        assert len(re.findall(r"hipLaunchKernelGGL\(\(?%s\b" % kernel, host)) == 1, kernel
 
 
 def test_the_unitigs_command_serves_both_forms(capsys):

@@ -447,6 +447,12 @@ def test_refusals_write_nothing(tmp_path):
     with pytest.raises(cbl_amd.CblxError) as e:
         c.unitigs_to_file(tmp_path / "canonical.txt")
     assert e.value.code == cbl_amd.EINVAL
+    assert not (tmp_path / "canonical.txt").exists()  # the refusal comes before the file is created ...
+    (tmp_path / "kept.txt").write_bytes(b"kept\n")
+    with pytest.raises(cbl_amd.CblxError) as e:
+        c.unitigs_to_file(tmp_path / "kept.txt")
+    assert e.value.code == cbl_amd.EINVAL and b"canonical" in _err(c)
+    assert (tmp_path / "kept.txt").read_bytes() == b"kept\n"  # ... or truncated
     assert c.serialize() == cc.blob
     c.close()
 
