@@ -194,6 +194,11 @@ SIGNATURES = {
     "cblx_biunitigs_text_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_biunitigs_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_biunitigs_to_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_gfa_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_gfa_links_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_gfa_text_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_gfa_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_gfa_to_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_list_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -1276,6 +1281,82 @@ class CBL:
     def biunitigs_to_fd(self, fd: int, chunk_bytes: int = 0):
         """The same to an open file descriptor (flush any Python-level buffer over it first)."""
         return self._unitig_sizes(True, "unitigs_to_fd", fd, chunk_bytes)
+
+    # ---- the links between the unitigs and the GFA text of the compacted graph (DESIGN.md section 6m); the form follows the index -----------
+    def _gfa_links(self, device: bool, link_start=None, cap_starts: int = 0, link_to=None, link_rev=None, cap_links: int = 0):
+        u, ln = C.c_uint64(0), C.c_uint64(0)
+        fn = self._L.cblx_gfa_links_device if device else self._L.cblx_gfa_links
+        self._chk(fn(self._h, _ptr(link_start), cap_starts, _ptr(link_to), _ptr(link_rev), cap_links, C.byref(u), C.byref(ln)))
+        return u.value, ln.value
+
+    def _gfa_sizes(self, name: str, *args):
+        """cblx_`name`(handle, *args, &a, &b, &c) -> (a, b, c)."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(getattr(self._L, "cblx_" + name)(self._h, *args, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def gfa_counts(self):
+        """(unitigs, links) of the compacted de Bruijn graph: the unitigs of unitig_table_np (a non-canonical index) or biunitig_table_np (a
+        canonical one), and the edges between them — every edge of the graph that does not join two consecutive k-mers of one unitig."""
+        return self._gfa_links(False)
+
+    def _gfa_table(self, xp) -> dict:
+        device = xp.__name__ == "torch"
+        u, ln = self._gfa_links(device)
+        if device:
+            dev = xp.device("cuda", self.device())
+            new = lambda count, dtype: xp.empty(max(count, 1), dtype=dtype, device=dev)  # noqa: E731
+            start, to, rev = new(2 * u + 1, xp.int64), new(ln, xp.int32), new(ln, xp.uint8)
+        else:
+            start, to, rev = xp.zeros(2 * u + 1, dtype=xp.uint64), xp.zeros(max(ln, 1), dtype=xp.uint32), xp.zeros(max(ln, 1), dtype=xp.uint8)
+        u2, ln2 = self._gfa_links(device, start, 2 * u + 1, to, rev, ln)
+        assert (u2, ln2) == (u, ln)
+        return {"link_start": start[: 2 * u + 1], "link_to": to[:ln], "link_rev": rev[:ln], "n_unitigs": u, "n_links": ln}
+
+    def gfa_links_np(self) -> dict:
+        """The link table between the unitigs. Unitig u has slot 2 u ('+', the image the unitig text spells) and, of a canonical index, slot
+        2 u + 1 ('-', its reverse complement). `link_start` (uint64, 2 U + 1 entries) is the CSR over the slots: the links leaving slot a are
+        [link_start[a], link_start[a + 1]); `link_to` (uint32) is the unitig a link enters and `link_rev` (uint8) is 0 where it enters it at the
+        head of '+' and 1 at the head of '-'. Links of a slot are in ascending code of the appended base. Also `n_unitigs` and `n_links`.
+        Bidirected links come in mirror pairs (see gfa_link_tuples)."""
+        import numpy as np
+
+        return self._gfa_table(np)
+
+    def gfa_links_device(self) -> dict:
+        """The same table as torch CUDA tensors (int64 / int32 holding the unsigned values, uint8 for `link_rev`); only the two counts cross
+        to the host."""
+        import torch
+
+        return self._gfa_table(torch)
+
+    @staticmethod
+    def gfa_link_tuples(link_start, link_to, link_rev):
+        """Generator of (u, '+' | '-', v, '+' | '-') over a link table in table order (host only): the link leaves the end of unitig u read in
+        the first orientation and enters the start of unitig v read in the second. The table of a canonical index holds both members of
+        every mirror pair, (u, a, v, b) and (v, not b, u, not a)."""
+        starts = [int(s) for s in link_start]
+        for slot in range(len(starts) - 1):
+            for ln in range(starts[slot], starts[slot + 1]):
+                yield slot >> 1, "-" if slot & 1 else "+", int(link_to[ln]), "-" if int(link_rev[ln]) else "+"
+
+    def gfa_text_device(self, d_buf=None, cap: int = 0):
+        """(bytes, unitigs, L lines) of the GFA 1.0 text: a header, an S line per unitig carrying its line of the unitig text, an L line per
+        link with the overlap (K - 1)M — of a mirror pair of links one line. d_buf and cap as in unitigs_text_device."""
+        return self._gfa_sizes("gfa_text_device", _ptr(d_buf), cap)
+
+    def gfa_text_np(self):
+        """The GFA text as a uint8 array, built on the device and streamed out once."""
+        return self._text_np(self.gfa_to_fd)
+
+    def gfa_to_file(self, path, chunk_bytes: int = 0):
+        """Writes the GFA text to `path` (created / truncated), streamed from the device in chunks of chunk_bytes (0 = the library's
+        default); returns (unitigs, L lines, bytes)."""
+        return self._gfa_sizes("gfa_to_file", os.fsencode(path), chunk_bytes)
+
+    def gfa_to_fd(self, fd: int, chunk_bytes: int = 0):
+        """The same to an open file descriptor (flush any Python-level buffer over it first)."""
+        return self._gfa_sizes("gfa_to_fd", fd, chunk_bytes)
 
     # ---- bucket statistics (src/cbl.rs:364-386) ---------------------------------------------------------------------
     def bucket_table_np(self):

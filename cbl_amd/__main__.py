@@ -201,7 +201,10 @@ def main(argv=None):
                                         "orientations. The index is not changed")
     un.add_argument("index")
     un.add_argument("-o", "--output")
-    un.add_argument("--stats", action="store_true", help="print a summary (unitigs, circular, k-mers, bases, longest, N50) instead of the lines")
+    un_form = un.add_mutually_exclusive_group()
+    un_form.add_argument("--stats", action="store_true", help="print a summary (unitigs, circular, k-mers, bases, longest, N50) instead of the lines")
+    un_form.add_argument("--gfa", action="store_true", help="write the compacted graph as GFA 1.0 instead of the lines: an S line per unitig and an L line "
+                                                            "per link between two unitigs, with an overlap of K - 1")
     a = ap.parse_args(argv)
 
     if a.cmd == "build":
@@ -359,6 +362,12 @@ def main(argv=None):
                     f.write(out)
             else:
                 sys.stdout.write(out)
+        elif a.gfa:
+            if a.output:
+                cbl.gfa_to_file(a.output)
+            else:
+                sys.stdout.flush()
+                cbl.gfa_to_fd(sys.stdout.fileno())
         elif a.output:
             (cbl.biunitigs_to_file if bi else cbl.unitigs_to_file)(a.output)
         else:

@@ -234,6 +234,44 @@ int unitigs_to_file(cblx_ctx* c, UnitigForm form, const char* path, u64 chunk_by
         text_to_file(path, "unitigs", [&](int fd) { unitigs_to_fd(c, form, fd, chunk_bytes, n_unitigs, bytes); });
     });
 }
+// cblx_gfa_links and cblx_gfa_links_device: counts out, the capacities, then link_start and the fill into the caller's device arrays (`device`) or into
+// pool arrays copied back
+int gfa_links(cblx_ctx* c, bool device, u64* link_start, u64 cap_starts, u32* link_to, u8* link_rev, u64 cap_links, u64* n_unitigs, u64* n_links) {
+    return guard(c, [&] {
+        GfaRun g;
+        gfa_count(c, g);
+        collect_events(c);
+        if (n_unitigs) *n_unitigs = g.n_unitigs;
+        if (n_links) *n_links = g.n_links;
+        const u64 ns = g.slots() + 1, nl = g.n_links;
+        const bool links = link_to || link_rev;
+        if ((link_start && cap_starts < ns) || (links && cap_links < nl))
+            throw Error(CBLX_ERANGE, "output capacity too small: the " + std::to_string(g.n_unitigs) + " unitigs need " + std::to_string(ns) + " starts and have " +
+                                         std::to_string(nl) + " links");
+        if (link_start) {
+            if (device) CBLX_HIP(hipMemcpyAsync(link_start, g.link_start.get(), ns * 8, hipMemcpyDeviceToDevice, c->stream));
+            else xfer(c).d2h_copy(link_start, g.link_start.get(), ns * 8);
+        }
+        if (links && nl) {
+            if (device) gfa_fill(c, g, link_to, link_rev);
+            else {
+                Buf<u32> d_to(c->pool, link_to ? nl : 1);
+                Buf<u8> d_rev(c->pool, link_rev ? nl : 1);
+                gfa_fill(c, g, link_to ? d_to.get() : nullptr, link_rev ? d_rev.get() : nullptr);
+                if (link_to) xfer(c).d2h_copy(link_to, d_to.get(), nl * 4);
+                if (link_rev) xfer(c).d2h_copy(link_rev, d_rev.get(), nl);
+            }
+        }
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+int gfa_to_file(cblx_ctx* c, const char* path, u64 chunk_bytes, u64* n_unitigs, u64* n_links, u64* bytes) {
+    return guard(c, [&] {
+        if (!path) throw Error(CBLX_EINVAL, "null argument");
+        unitig_require(c, gfa_form(c));  // a refusal comes before the file is created or truncated
+        text_to_file(path, "GFA", [&](int fd) { gfa_to_fd(c, fd, chunk_bytes, n_unitigs, n_links, bytes); });
+    });
+}
 
 }  // namespace
 
@@ -1793,6 +1831,37 @@ int cblx_biunitigs_to_fd(cblx_ctx* c, int fd, uint64_t chunk_bytes, uint64_t* n_
 }
 int cblx_biunitigs_to_file(cblx_ctx* c, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes) {
     return unitigs_to_file(c, UnitigForm::Bidirected, path, chunk_bytes, n_unitigs, bytes);
+}
+// ---- links between unitigs and the GFA text: the form follows the index
+int cblx_gfa_links(cblx_ctx* c, uint64_t* link_start, uint64_t cap_starts, uint32_t* link_to, uint8_t* link_rev, uint64_t cap_links, uint64_t* n_unitigs,
+                   uint64_t* n_links) {
+    return gfa_links(c, false, link_start, cap_starts, link_to, link_rev, cap_links, n_unitigs, n_links);
+}
+int cblx_gfa_links_device(cblx_ctx* c, uint64_t* d_link_start, uint64_t cap_starts, uint32_t* d_link_to, uint8_t* d_link_rev, uint64_t cap_links, uint64_t* n_unitigs,
+                          uint64_t* n_links) {
+    return gfa_links(c, true, d_link_start, cap_starts, d_link_to, d_link_rev, cap_links, n_unitigs, n_links);
+}
+int cblx_gfa_text_device(cblx_ctx* c, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs, uint64_t* n_links) {
+    return guard(c, [&] {
+        GfaText t;
+        gfa_text(c, t, d_buf, [&](u64 need) {
+            if (bytes) *bytes = need;
+            if (n_unitigs) *n_unitigs = t.n_unitigs;
+            if (n_links) *n_links = t.n_links;
+            if (d_buf && need > cap) throw Error(CBLX_ERANGE, "buffer too small: need " + std::to_string(need) + " bytes");
+            return d_buf != nullptr;  // null: the sizes are all that was asked for
+        });
+        collect_events(c);
+    });
+}
+int cblx_gfa_to_fd(cblx_ctx* c, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* bytes) {
+    return guard(c, [&] {
+        if (fd < 0) throw Error(CBLX_EINVAL, "bad file descriptor");
+        gfa_to_fd(c, fd, chunk_bytes, n_unitigs, n_links, bytes);
+    });
+}
+int cblx_gfa_to_file(cblx_ctx* c, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* bytes) {
+    return gfa_to_file(c, path, chunk_bytes, n_unitigs, n_links, bytes);
 }
 int cblx_bucket_nodes(cblx_ctx* c, uint64_t* nodes, uint64_t cap, uint64_t* n) {
     return guard(c, [&] {

@@ -1,12 +1,14 @@
 // graph.hpp — the index as a de Bruijn graph, on the host: the checks a batch of packed k-mers goes through, the export of the index pass by pass
 // (export_passes), neighbour masks (neighbor_masks_device, neighbor_masks_range), the rank of a k-mer (rank_words,
 // rank_kmers_device) and the compaction into unitigs, plain (section 6k) and bidirected (section 6l): unitig_compute, unitig_number, unitig_text,
-// unitigs_to_fd. Kernels: kernels_graph.hpp, kernels_unitig.hpp, kernels_biunitig.hpp. Included by cblx.cpp only.
+// unitigs_to_fd; and the links between the unitigs with the GFA text of the compacted graph (section 6m): gfa_count, gfa_fill, gfa_text, gfa_to_fd.
+// Kernels: kernels_graph.hpp, kernels_unitig.hpp, kernels_biunitig.hpp, kernels_gfa.hpp. Included by cblx.cpp only.
 #pragma once
 #include "list.hpp"
 #include "kernels_graph.hpp"
 #include "kernels_unitig.hpp"
 #include "kernels_biunitig.hpp"
+#include "kernels_gfa.hpp"
 
 namespace {
 
@@ -146,6 +148,7 @@ struct UnitigRun {
     u32 rounds = 0;  // jump rounds, the ones after a cycle cut included
     Buf<u32> next, prev, anc[2], dist[2];
     Buf<u8> circular;
+    Buf<u8> masks;  // the n neighbour masks, only where unitig_compute was asked to keep them (section 6m)
     int cur = 0;  // anc[cur] / dist[cur] hold the ranking; the other pair is scratch (the head flags and their scan, in the end)
     u64 ids() const { return form == UnitigForm::Bidirected ? 2 * n : n; }
 };
@@ -192,8 +195,9 @@ void unitig_rank(cblx_ctx* c, UnitigRun& u, u64 n, Buf<u64>& counters) {
     }
 }
 // The workspace is six 32-bit arrays and a byte array of `ids` elements — about twice as much for the bidirected form — and the n masks while the links
-// are made. In the end the scratch pair holds the flags of the (kept) heads (anc) and their exclusive scan (dist).
-void unitig_compute(cblx_ctx* c, UnitigRun& u, UnitigForm form) {
+// are made. In the end the scratch pair holds the flags of the (kept) heads (anc) and their exclusive scan (dist). `keep_masks`: the masks stay in
+// u.masks instead of going back to the pool behind the links.
+void unitig_compute(cblx_ctx* c, UnitigRun& u, UnitigForm form, bool keep_masks = false) {
     flush(c);
     unitig_require(c, form);
     const bool bi = form == UnitigForm::Bidirected;
@@ -232,6 +236,7 @@ void unitig_compute(cblx_ctx* c, UnitigRun& u, UnitigForm form) {
             });
             CBLX_HIP(hipGetLastError());
         });  // the masks die behind its sync
+        if (keep_masks) u.masks = std::move(masks);
     }
     // (c) pointer jumping; (d) the cycle cut when the count of unfinished ids repeats. Bidirected: a cycle and its mirror are both cut, in front of
     // the same stored k-mer
@@ -272,6 +277,17 @@ struct UnitigText {
     Buf<u8> text;
     u64 bytes = 0, n_unitigs = 0;
 };
+// The letters and the '\n' of every unitig's line, K + length[u] bytes from d_out + base[u] (device arrays of a table; `reversed` is null in the plain form)
+void unitig_lines(cblx_ctx* c, u64 n, const u32* unitig, const u32* offset, const u8* reversed, const u32* length, const u64* base, u8* d_out) {
+    const u32 K = c->P.K;
+    export_passes(c, 0, n, [&](u64 a, u64 m, const u64* k_lo, const u64* k_hi, const u64*) {
+        if (!reversed)
+            hipLaunchKernelGGL(k_unitig_text, grid1(m, 256), dim3(256), 0, c->stream, k_lo, k_hi, a, m, unitig, offset, length, base, K, d_out);
+        else
+            hipLaunchKernelGGL(k_biunitig_text, grid1(m, 256), dim3(256), 0, c->stream, k_lo, k_hi, a, m, unitig, offset, reversed, length, base, K, d_out);
+        CBLX_HIP(hipGetLastError());
+    });  // the caller's arrays may die behind its sync
+}
 // `d_out`: the caller's buffer, or null: t.text is allocated. fits(need) is called once the need is known: it may refuse (throw), or return false when the
 // size is all that is wanted.
 template <typename Fits> void unitig_text(cblx_ctx* c, UnitigForm form, UnitigText& t, u8* d_out, Fits&& fits) {
@@ -292,14 +308,7 @@ template <typename Fits> void unitig_text(cblx_ctx* c, UnitigForm form, UnitigTe
     hipLaunchKernelGGL(k_unitig_line_bytes, grid1(nu, 256), dim3(256), 0, c->stream, length.get(), nu, (u32)K, line.get());
     CBLX_HIP(hipGetLastError());
     if (exclusive_scan<u64>(c, line.get(), nu, base.get()) != t.bytes) throw Error(CBLX_EDEVICE, "unitig lengths do not add up (internal error)");
-    export_passes(c, 0, n, [&](u64 a, u64 m, const u64* k_lo, const u64* k_hi, const u64*) {
-        if (!bi)
-            hipLaunchKernelGGL(k_unitig_text, grid1(m, 256), dim3(256), 0, c->stream, k_lo, k_hi, a, m, unitig.get(), offset.get(), length.get(), base.get(), (u32)K, d_out);
-        else
-            hipLaunchKernelGGL(k_biunitig_text, grid1(m, 256), dim3(256), 0, c->stream, k_lo, k_hi, a, m, unitig.get(), offset.get(), reversed.get(), length.get(), base.get(),
-                               (u32)K, d_out);
-        CBLX_HIP(hipGetLastError());
-    });  // the table dies behind its sync
+    unitig_lines(c, n, unitig.get(), offset.get(), reversed.get(), length.get(), base.get(), d_out);  // the table dies behind its sync
 }
 // `cbl unitigs`: the text is built once on the device and leaves through the two pinned buffers of the list
 void unitigs_to_fd(cblx_ctx* c, UnitigForm form, int fd, u64 chunk_bytes, u64* n_unitigs, u64* bytes) {
@@ -311,6 +320,112 @@ void unitigs_to_fd(cblx_ctx* c, UnitigForm form, int fd, u64 chunk_bytes, u64* n
     if (chunk_bytes == 0) chunk_bytes = LIST_CHUNK_DEFAULT * (c->P.K + 1);
     const u64 cbytes = std::min<u64>(chunk_bytes, t.bytes);
     stream_chunks_to_fd(c, fd, t.bytes, cbytes, "unitigs", [&](u64 i, u64) -> const u8* { return t.text.get() + i * cbytes; });
+}
+
+// ---- links between unitigs and the GFA text (kernels_gfa.hpp) ----------------------------------------------------------
+// The form follows the index. What a call holds between its steps: the table's per-k-mer arrays and lengths, the masks the compaction kept, and
+// link_start, the CSR over the 2 U slots (2 U + 1 entries, the last one L).
+struct GfaRun {
+    UnitigForm form = UnitigForm::Plain;
+    u64 n = 0, n_unitigs = 0, n_links = 0;
+    Buf<u32> unitig, offset, length;
+    Buf<u8> reversed, masks;  // reversed: bidirected form only
+    Buf<u64> link_start;
+    u64 slots() const { return 2 * n_unitigs; }
+};
+UnitigForm gfa_form(const cblx_ctx* c) { return c->P.canonical ? UnitigForm::Bidirected : UnitigForm::Plain; }
+// The compaction with its masks kept, the table, the links per slot and their scan: the counts and link_start. An empty index: U = L = 0, link_start = {0}.
+void gfa_count(cblx_ctx* c, GfaRun& g) {
+    UnitigRun u;
+    g.form = gfa_form(c);
+    unitig_compute(c, u, g.form, true);
+    const u64 n = g.n = u.n, nu = g.n_unitigs = u.n_unitigs;
+    g.link_start = Buf<u64>(c->pool, 2 * nu + 1);
+    if (n == 0) {
+        CBLX_HIP(hipMemsetAsync(g.link_start.get(), 0, 8, c->stream));
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+        return;
+    }
+    g.unitig = Buf<u32>(c->pool, n); g.offset = Buf<u32>(c->pool, n); g.length = Buf<u32>(c->pool, nu);
+    if (g.form == UnitigForm::Bidirected) g.reversed = Buf<u8>(c->pool, n);
+    unitig_number(c, u, g.unitig.get(), g.offset.get(), g.reversed.get(), nullptr, g.length.get(), nullptr);
+    g.masks = std::move(u.masks);
+    u = UnitigRun();  // the ranking's arrays go back to the pool
+    Buf<u32> cnt(c->pool, 2 * nu);
+    CBLX_HIP(hipMemsetAsync(cnt.get(), 0, 2 * nu * 4, c->stream));
+    hipLaunchKernelGGL(k_gfa_link_counts, grid1(n, 256), dim3(256), 0, c->stream, g.unitig.get(), g.offset.get(), g.reversed.get(), g.length.get(), g.masks.get(), n, cnt.get());
+    CBLX_HIP(hipGetLastError());
+    g.n_links = exclusive_scan<u64>(c, cnt.get(), 2 * nu, g.link_start.get());
+    h2d(c, g.link_start.get() + 2 * nu, &g.n_links, 1);
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // cnt dies here
+}
+// link_to / link_rev (device arrays of g.n_links elements; either may be null) over export passes; g.n != 0
+void gfa_fill(cblx_ctx* c, const GfaRun& g, u32* d_to, u8* d_rev) {
+    const u64* a_hi = c->P.wide_suffix() ? c->res.a_hi.get() : (const u64*)nullptr;
+    const bool bi = g.form == UnitigForm::Bidirected;
+    export_passes(c, 0, g.n, [&](u64 a, u64 m, const u64* k_lo, const u64* k_hi, const u64* res_off) {
+        dispatch(c->P, [&](auto cfg) {
+            typedef decltype(cfg) C;
+            const u64 step = 1ull << 27;  // bidirected: 2 QL lanes per k-mer, 2^31 work items per launch
+            for (u64 b = 0; b < m; b += step) {
+                const u64 mb = std::min(step, m - b);
+                hipLaunchKernelGGL((k_gfa_link_fill<C::WIDE>), grid1((bi ? 2 : 1) * mb * QL, 256), dim3(256), 0, c->stream, k_lo + b, k_hi ? k_hi + b : k_hi, a + b, mb,
+                                   g.masks.get(), g.unitig.get(), g.offset.get(), g.reversed.get(), g.length.get(), c->P, c->res.view(), c->res.a_lo.get(), a_hi, res_off,
+                                   g.link_start.get(), d_to, d_rev);
+            }
+        });
+        CBLX_HIP(hipGetLastError());
+    });
+}
+// The GFA text in device memory: the header, the S lines, the L lines of the links that are written (of a mirror pair one). `d_out` and fits(need)
+// as in unitig_text; t.n_links = the L lines.
+struct GfaText {
+    Buf<u8> text;
+    u64 bytes = 0, n_unitigs = 0, n_links = 0;
+};
+template <typename Fits> void gfa_text(cblx_ctx* c, GfaText& t, u8* d_out, Fits&& fits) {
+    GfaRun g;
+    gfa_count(c, g);
+    const u64 n = g.n, nu = g.n_unitigs, ns = g.slots(), K = c->P.K;
+    const bool bi = g.form == UnitigForm::Bidirected;
+    const dim3 b256(256);
+    t.n_unitigs = nu;
+    Buf<u32> link_to(c->pool, g.n_links + 1), bytes(c->pool, std::max(ns, nu) + 1), lines(c->pool, ns + 1);
+    Buf<u8> link_rev(c->pool, g.n_links + 1);
+    Buf<u64> s_base(c->pool, nu + 1), l_base(c->pool, ns + 1);
+    u64 s_bytes = 0, l_bytes = 0;
+    if (n) {
+        if (g.n_links) gfa_fill(c, g, link_to.get(), link_rev.get());
+        g.masks.reset();
+        hipLaunchKernelGGL(k_gfa_l_bytes, grid1(ns, 256), b256, 0, c->stream, (const u64*)g.link_start.get(), (const u32*)link_to.get(), (const u8*)link_rev.get(), ns, bi,
+                           (u32)(K - 1), bytes.get(), lines.get());
+        CBLX_HIP(hipGetLastError());
+        t.n_links = exclusive_scan<u64>(c, lines.get(), ns, l_base.get());
+        l_bytes = exclusive_scan<u64>(c, bytes.get(), ns, l_base.get());
+        hipLaunchKernelGGL(k_gfa_s_bytes, grid1(nu, 256), b256, 0, c->stream, (const u32*)g.length.get(), nu, (u32)K, bytes.get());
+        CBLX_HIP(hipGetLastError());
+        s_bytes = exclusive_scan<u64>(c, bytes.get(), nu, s_base.get());
+    }
+    t.bytes = GFA_HEADER_BYTES + s_bytes + l_bytes;
+    if (!fits(t.bytes)) return;
+    if (!d_out) { t.text = Buf<u8>(c->pool, t.bytes); d_out = t.text.get(); }
+    hipLaunchKernelGGL(k_gfa_s_prefix, grid1(nu, 256), b256, 0, c->stream, s_base.get(), nu, (u64)GFA_HEADER_BYTES, d_out);
+    if (n) hipLaunchKernelGGL(k_gfa_l_text, grid1(ns, 256), b256, 0, c->stream, (const u64*)g.link_start.get(), (const u32*)link_to.get(), (const u8*)link_rev.get(),
+                              (const u64*)l_base.get(), ns, bi, (u32)(K - 1), GFA_HEADER_BYTES + s_bytes, d_out);
+    CBLX_HIP(hipGetLastError());
+    if (n) unitig_lines(c, n, g.unitig.get(), g.offset.get(), g.reversed.get(), g.length.get(), s_base.get(), d_out);
+    CBLX_HIP(hipStreamSynchronize(c->stream));  // the tables die here
+}
+// `cbl unitigs --gfa`: the text is built once on the device and leaves as the unitig text does
+void gfa_to_fd(cblx_ctx* c, int fd, u64 chunk_bytes, u64* n_unitigs, u64* n_links, u64* bytes) {
+    GfaText t;
+    gfa_text(c, t, nullptr, [](u64) { return true; });
+    if (n_unitigs) *n_unitigs = t.n_unitigs;
+    if (n_links) *n_links = t.n_links;
+    if (bytes) *bytes = t.bytes;
+    if (chunk_bytes == 0) chunk_bytes = LIST_CHUNK_DEFAULT * (c->P.K + 1);
+    const u64 cbytes = std::min<u64>(chunk_bytes, t.bytes);
+    stream_chunks_to_fd(c, fd, t.bytes, cbytes, "GFA", [&](u64 i, u64) -> const u8* { return t.text.get() + i * cbytes; });
 }
 
 }  // namespace

@@ -36,7 +36,8 @@ extern "C" {
  * cblx_contains_seqs_counts_many and cblx_contains_seqs_counts_many_device;
  * cblx_neighbors_kmers, cblx_neighbors_kmers_device, cblx_neighbors_range, cblx_neighbors_range_device and cblx_degree_table;
  * cblx_rank_kmers, cblx_rank_kmers_device, cblx_unitig_table, cblx_unitig_table_device, cblx_unitigs_text_device, cblx_unitigs_to_fd and cblx_unitigs_to_file;
- * cblx_biunitig_table, cblx_biunitig_table_device, cblx_biunitigs_text_device, cblx_biunitigs_to_fd and cblx_biunitigs_to_file. */
+ * cblx_biunitig_table, cblx_biunitig_table_device, cblx_biunitigs_text_device, cblx_biunitigs_to_fd and cblx_biunitigs_to_file;
+ * cblx_gfa_links, cblx_gfa_links_device, cblx_gfa_text_device, cblx_gfa_to_fd and cblx_gfa_to_file. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -569,6 +570,32 @@ int cblx_biunitig_table_device(cblx_ctx* ctx, uint32_t* d_unitig, uint32_t* d_of
 int cblx_biunitigs_text_device(cblx_ctx* ctx, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs);
 int cblx_biunitigs_to_fd(cblx_ctx* ctx, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes);
 int cblx_biunitigs_to_file(cblx_ctx* ctx, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* bytes);
+/* ---- the links between the unitigs and the GFA text of the compacted graph. The form follows the index: a non-canonical index
+ * gives the links between the unitigs of cblx_unitig_table, a canonical one those between the bidirected unitigs of cblx_biunitig_table; unitig numbers,
+ * offsets and `reversed` are exactly those tables', and so are the refusals (an even K of a canonical index is CBLX_EINVAL, too many k-mers CBLX_ERANGE).
+ * Unitig u has a kept image, side 0 ('+'), and in the bidirected form a mirror image, side 1 ('-'): its oriented k-mers (i, 1 - s) in reverse offset order.
+ * SLOT 2 u + side; in the plain form only even slots hold anything. A LINK is every edge of the graph — self-edges and hairpins included — that does not
+ * join two consecutive offsets of one image (so the cut edge of a circular unitig is a link u+ -> u+). Every link leaves the last oriented k-mer of an image
+ * and enters the first one of an image.
+ *   link_start[slot]   uint64, 2 U + 1 entries: the links that leave `slot` are [link_start[slot], link_start[slot + 1]); link_start[2 U] = L
+ *   link_to[l]         uint32, L entries: the unitig the link enters
+ *   link_rev[l]        uint8, L entries: 0 when it enters the head of that unitig's kept image ('+'), 1 when the head of its mirror ('-'); plain form: 0
+ * Within a slot the links are in ascending code of the base appended. Bidirected links come in mirror pairs: (a -> b) with (b ^ 1 -> a ^ 1) in slot ids; a
+ * link with b = a ^ 1 is its own mirror and occurs once. Any array may be NULL and is then not written; with all three NULL the call only counts.
+ * *n_unitigs = U and *n_links = L are always set. cap_starts < 2 U + 1 (with link_start) or cap_links < L (with link_to or link_rev) is CBLX_ERANGE: the
+ * needs are reported and nothing is written. An empty index gives U = L = 0 and link_start[0] = 0. */
+int cblx_gfa_links(cblx_ctx* ctx, uint64_t* link_start, uint64_t cap_starts, uint32_t* link_to, uint8_t* link_rev, uint64_t cap_links, uint64_t* n_unitigs,
+                   uint64_t* n_links);
+int cblx_gfa_links_device(cblx_ctx* ctx, uint64_t* d_link_start, uint64_t cap_starts, uint32_t* d_link_to, uint8_t* d_link_rev, uint64_t cap_links,
+                          uint64_t* n_unitigs, uint64_t* n_links);
+/* GFA 1.0: "H\tVN:Z:1.0\n", then "S\t<u>\t<line u of the unitig text>\n" for u = 0 .. U - 1, then "L\t<u>\t<+|->\t<v>\t<+|->\t<K - 1>M\n" for the links in table
+ * order; numbers are decimal without padding. Of a mirror pair of links one L line is written — the link whose (from slot, to slot) is lexicographically
+ * <= its mirror's (to slot ^ 1, from slot ^ 1) — and a link that is its own mirror once; the plain form writes every link. *n_links = the L lines written.
+ * An empty index gives the 11 header bytes. d_buf, cap and *bytes as in cblx_unitigs_text_device; fd, path and chunk_bytes (0 = that text's default) as
+ * in cblx_unitigs_to_fd / cblx_unitigs_to_file; a refused cblx_gfa_to_file does not create the file. */
+int cblx_gfa_text_device(cblx_ctx* ctx, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs, uint64_t* n_links);
+int cblx_gfa_to_fd(cblx_ctx* ctx, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* bytes);
+int cblx_gfa_to_file(cblx_ctx* ctx, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* bytes);
 /* CBL::buckets_nodes (src/cbl.rs:386-390): per non-empty prefix ascending, TrieVec::count_nodes (src/trievec/mod.rs:37-42) — a Vec's length, a Trie's
  * nodes (src/trie.rs:90-102: the root and one node per distinct proper byte prefix of its suffixes). Pairs with cblx_bucket_sizes. */
 int cblx_bucket_nodes(cblx_ctx* ctx, uint64_t* nodes, uint64_t cap, uint64_t* n);

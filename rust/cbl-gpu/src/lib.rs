@@ -310,6 +310,25 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         (u, bytes)
     }
 
+    /// `(unitigs, links)` of the compacted de Bruijn graph: the unitigs of `unitig_counts` (a non-canonical set) or
+    /// `biunitig_counts` (a canonical one) and the edges between them. Only the counts come back.
+    pub fn gfa_counts(&self) -> (u64, u64) {
+        let (mut u, mut l) = (0u64, 0u64);
+        self.check(unsafe {
+            sys::cblx_gfa_links(self.ctx, std::ptr::null_mut::<u64>(), 0, std::ptr::null_mut::<u32>(), std::ptr::null_mut::<u8>(), 0, &mut u, &mut l)
+        });
+        (u, l)
+    }
+
+    /// Writes the compacted graph as GFA 1.0 to `path` (created or truncated): an `S` line per unitig, an `L` line per link with
+    /// the overlap `(K - 1)M`, of a mirror pair of links one line. Returns `(unitigs, L lines, bytes)`.
+    pub fn gfa_to_file<P: AsRef<Path>>(&self, path: P) -> (u64, u64, u64) {
+        let cpath = Self::cpath(path);
+        let (mut u, mut l, mut bytes) = (0u64, 0u64, 0u64);
+        self.check(unsafe { sys::cblx_gfa_to_file(self.ctx, cpath.as_ptr(), 0, &mut u, &mut l, &mut bytes) });
+        (u, l, bytes)
+    }
+
     /// Adds a k-mer; returns `true` if it was absent (`src/cbl.rs:226-228`). One device round trip per call: a caller with
     /// many k-mers uses `insert_kmers`.
     #[inline]

@@ -406,6 +406,11 @@ extern "C" {
     pub fn cblx_biunitigs_text_device(ctx: *mut cblx_ctx, d_buf: *mut u8, cap: u64, bytes: *mut u64, n_unitigs: *mut u64) -> c_int;
     pub fn cblx_biunitigs_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_bytes: u64, n_unitigs: *mut u64, bytes: *mut u64) -> c_int;
     pub fn cblx_biunitigs_to_file(ctx: *mut cblx_ctx, path: *const c_char, chunk_bytes: u64, n_unitigs: *mut u64, bytes: *mut u64) -> c_int;
+    pub fn cblx_gfa_links(ctx: *mut cblx_ctx, link_start: *mut u64, cap_starts: u64, link_to: *mut u32, link_rev: *mut u8, cap_links: u64, n_unitigs: *mut u64, n_links: *mut u64) -> c_int;
+    pub fn cblx_gfa_links_device(ctx: *mut cblx_ctx, d_link_start: *mut u64, cap_starts: u64, d_link_to: *mut u32, d_link_rev: *mut u8, cap_links: u64, n_unitigs: *mut u64, n_links: *mut u64) -> c_int;
+    pub fn cblx_gfa_text_device(ctx: *mut cblx_ctx, d_buf: *mut u8, cap: u64, bytes: *mut u64, n_unitigs: *mut u64, n_links: *mut u64) -> c_int;
+    pub fn cblx_gfa_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_bytes: u64, n_unitigs: *mut u64, n_links: *mut u64, bytes: *mut u64) -> c_int;
+    pub fn cblx_gfa_to_file(ctx: *mut cblx_ctx, path: *const c_char, chunk_bytes: u64, n_unitigs: *mut u64, n_links: *mut u64, bytes: *mut u64) -> c_int;
     pub fn cblx_list_range(ctx: *mut cblx_ctx, first: u64, n: u64, buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_range_device(ctx: *mut cblx_ctx, first: u64, n: u64, d_buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_kmers: u64, n_kmers: *mut u64) -> c_int;
