@@ -64,6 +64,13 @@ class BatchView(C.Structure):
     _fields_ = [("n_buckets", C.c_uint64), ("n_words", C.c_uint64), ("d_prefix", C.c_void_p), ("d_count", C.c_void_p), ("d_suffix", C.c_void_p)]
 
 
+class ClipStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("rounds", "tips", "tip_kmers", "isolated", "isolated_kmers", "kmers_left", "fixpoint")]
+
+
+CLIP_ISOLATED = 1  # CBLX_CLIP_ISOLATED of include/cblx.h
+TIP_COUNTS = ("tips", "tip_kmers", "isolated", "isolated_kmers")
+
 BUCKET_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 
 ABI_VERSION = 3  # include/cblx.h CBLX_ABI_VERSION
@@ -199,6 +206,11 @@ SIGNATURES = {
     "cblx_gfa_text_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_gfa_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_gfa_to_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_unitig_ends": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_unitig_ends_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_tips_mark": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_tips_mark_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_clip_tips": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(ClipStats)]),
     "cblx_list_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -1357,6 +1369,90 @@ class CBL:
     def gfa_to_fd(self, fd: int, chunk_bytes: int = 0):
         """The same to an open file descriptor (flush any Python-level buffer over it first)."""
         return self._gfa_sizes("gfa_to_fd", fd, chunk_bytes)
+
+    # ---- tip clipping on the compacted graph (DESIGN.md section 6n); the form follows the index ---------------------------------------------
+    def _max_kmers(self, max_kmers):
+        return self.k - 1 if max_kmers is None else int(max_kmers)
+
+    def _unitig_ends(self, xp) -> dict:
+        device = xp.__name__ == "torch"
+        fn = self._L.cblx_unitig_ends_device if device else self._L.cblx_unitig_ends
+        u = C.c_uint64(0)
+        self._chk(fn(self._h, None, None, 0, C.byref(u)))
+        cap = max(u.value, 1)
+        if device:
+            dev = xp.device("cuda", self.device())
+            left, right = (xp.empty(cap, dtype=xp.uint8, device=dev) for _ in range(2))
+        else:
+            left, right = (xp.zeros(cap, dtype=xp.uint8) for _ in range(2))
+        self._chk(fn(self._h, _ptr(left), _ptr(right), cap, C.byref(u)))
+        return {"left": left[: u.value], "right": right[: u.value], "n_unitigs": u.value}
+
+    def unitig_ends_np(self) -> dict:
+        """The degrees at the two ends of every unitig of unitig_table_np (a non-canonical index) or biunitig_table_np (a canonical one), as uint8
+        arrays: `right` = the out-degree of the last k-mer of the unitig as its text spells it, `left` = the in-degree of its first one — the
+        links that leave and that enter the unitig in the link table of gfa_links_np. Self-edges and hairpins count. Also `n_unitigs`."""
+        import numpy as np
+
+        return self._unitig_ends(np)
+
+    def unitig_ends_device(self) -> dict:
+        """The same as torch uint8 CUDA tensors; only the count crosses to the host."""
+        import torch
+
+        return self._unitig_ends(torch)
+
+    def _tips_mark(self, device: bool, max_kmers, kind=None, cap: int = 0):
+        u, counts = C.c_uint64(0), (C.c_uint64 * 4)()
+        fn = self._L.cblx_tips_mark_device if device else self._L.cblx_tips_mark
+        self._chk(fn(self._h, self._max_kmers(max_kmers), _ptr(kind), cap, C.byref(u), counts))
+        return u.value, dict(zip(TIP_COUNTS, (int(v) for v in counts)))
+
+    def tip_counts(self, max_kmers=None) -> dict:
+        """tips, tip_kmers, isolated, isolated_kmers of tips_np, and n_unitigs: the marks are made on the device, five numbers come back."""
+        u, counts = self._tips_mark(False, max_kmers)
+        return dict(counts, n_unitigs=u)
+
+    def tips_np(self, max_kmers=None) -> dict:
+        """`kind` (uint8 per unitig of the index's compaction table): 1, a tip, where the unitig has at most max_kmers k-mers (None: K - 1, unitigs
+        shorter than K k-mers) and exactly one of its ends (unitig_ends_np) has degree 0; 2, isolated, where it is that short and both have; 0
+        elsewhere. A circular unitig is never marked. Also the counts of tip_counts."""
+        import numpy as np
+
+        u, _ = self._tips_mark(False, max_kmers)
+        kind = np.zeros(max(u, 1), dtype=np.uint8)
+        u, counts = self._tips_mark(False, max_kmers, kind, max(u, 1))
+        return dict(counts, kind=kind[:u], n_unitigs=u)
+
+    def tips_mark_device(self, max_kmers=None, d_kind=None, cap: int = 0) -> dict:
+        """The marks into d_kind (a torch uint8 CUDA tensor or raw device address of `cap` elements; None: counts only); returns the counts of
+        tip_counts. A capacity too small raises CblxError(ERANGE) and leaves d_kind untouched."""
+        u, counts = self._tips_mark(True, max_kmers, d_kind, cap)
+        return dict(counts, n_unitigs=u)
+
+    @staticmethod
+    def tip_kinds(length, flags, left, right, max_kmers: int):
+        """The rule of tips_np restated in numpy on a compaction table's `length` and `flags` and on unitig_ends_np's arrays (host only): a uint8
+        array of kinds. The circular flag is not consulted — a circular unitig has both degrees >= 1 — but a marked circular unitig raises."""
+        import numpy as np
+
+        if max_kmers < 1:
+            raise ValueError("tip_kinds: max_kmers is at least 1")
+        length, left, right = np.asarray(length).astype(np.int64), np.asarray(left).astype(np.int64), np.asarray(right).astype(np.int64)
+        short = length <= max_kmers
+        kind = np.where(short & (left == 0) & (right == 0), 2, np.where(short & ((left == 0) != (right == 0)), 1, 0)).astype(np.uint8)
+        if ((np.asarray(flags) & 1).astype(bool) & (kind != 0)).any():
+            raise ValueError("tip_kinds: a circular unitig without a link")
+        return kind
+
+    def clip_tips(self, max_kmers=None, isolated: bool = False, rounds: int = 1) -> dict:
+        """Removes the k-mers of the tips (tips_np; with `isolated` those of the isolated unitigs too) from the index, on the device: a round
+        compacts, marks and removes every marked unitig of that compaction as one batch, so a short stem that forks into two short dead ends goes
+        whole. `rounds` = 0 repeats until a round finds nothing. Returns rounds (compactions run), tips, tip_kmers, isolated, isolated_kmers (what
+        was removed), kmers_left and fixpoint (1 when the last round found nothing)."""
+        st = ClipStats()
+        self._chk(self._L.cblx_clip_tips(self._h, self._max_kmers(max_kmers), CLIP_ISOLATED if isolated else 0, int(rounds), C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in ClipStats._fields_}
 
     # ---- bucket statistics (src/cbl.rs:364-386) ---------------------------------------------------------------------
     def bucket_table_np(self):

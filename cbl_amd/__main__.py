@@ -3,7 +3,7 @@ reference CLI (/root/reference/examples/cbl.rs:147-167,230-269,270-309,168-229,3
 `CBL::intersect` (src/cbl.rs:106-124) over two or more index files, which the reference's CLI does not expose; `compare` prints the shared k-mers, Jaccard and
 containment of every pair of two or more index files; `classify` assigns every record of a FASTA/Q file to one of two or more index files; `graph` prints
 the degree table of the de Bruijn graph whose nodes are the k-mers of an index; `unitigs` writes the non-branching paths of that graph, one line each
-(of a canonical index: the bidirected unitigs).
+(of a canonical index: the bidirected unitigs); `clip` removes the short dead-end unitigs (tips) of that graph from an index.
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
 here they are flags with the same defaults (K=25, PREFIX_BITS=24). Index files are interchangeable with the reference's.
@@ -205,6 +205,13 @@ def main(argv=None):
     un_form.add_argument("--stats", action="store_true", help="print a summary (unitigs, circular, k-mers, bases, longest, N50) instead of the lines")
     un_form.add_argument("--gfa", action="store_true", help="write the compacted graph as GFA 1.0 instead of the lines: an S line per unitig and an L line "
                                                             "per link between two unitigs, with an overlap of K - 1")
+    cp = sub.add_parser("clip", help="Remove the tips of an index: the unitigs of at most N k-mers that are linked to the rest of the de Bruijn graph at "
+                                     "one end only. A round removes every tip of one compaction together")
+    cp.add_argument("index")
+    cp.add_argument("-o", "--output", required=True)
+    cp.add_argument("--max-kmers", type=int, default=None, metavar="N", help="the longest unitig that counts as a tip, in k-mers (default: K - 1)")
+    cp.add_argument("--isolated", action="store_true", help="also remove the unitigs of at most N k-mers that are linked to nothing")
+    cp.add_argument("--rounds", type=int, default=1, metavar="R", help="compact and clip up to R times (default 1); 0: until a round finds no tip")
     a = ap.parse_args(argv)
 
     if a.cmd == "build":
@@ -373,6 +380,19 @@ def main(argv=None):
         else:
             sys.stdout.flush()
             (cbl.biunitigs_to_fd if bi else cbl.unitigs_to_fd)(sys.stdout.fileno())
+    elif a.cmd == "clip":  # ours (the reference's CLI has no such command): the removal is one WordSet::remove_batch per round (src/wordset/mod.rs:218-237)
+        if (a.max_kmers is not None and a.max_kmers < 1) or a.rounds < 0:
+            ap.error("clip: --max-kmers is at least 1 and --rounds at least 0")
+        print(f"Reading the index stored in {a.index}", file=sys.stderr)
+        cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
+        print(f"Clipping the tips of the {'canonical ' if cbl.is_canonical() else ''}{a.k}-mers contained in {a.index}", file=sys.stderr)
+        st = cbl.clip_tips(a.max_kmers, isolated=a.isolated, rounds=a.rounds)
+        print(f"{st['rounds']} rounds removed {st['tips']} tips of {st['tip_kmers']} k-mers and {st['isolated']} isolated unitigs of {st['isolated_kmers']} "
+              f"k-mers; {st['kmers_left']} k-mers are left{'' if st['fixpoint'] else ' (tips may remain)'}", file=sys.stderr)
+        print(f"Writing the index to {a.output}", file=sys.stderr)
+        cbl.save_to_file(a.output)
+        print("\n".join(f"{key}\t{value}" for key, value in st.items()))
+
 
 if __name__ == "__main__":
     main()

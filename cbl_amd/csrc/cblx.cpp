@@ -273,6 +273,35 @@ int gfa_to_file(cblx_ctx* c, const char* path, u64 chunk_bytes, u64* n_unitigs, 
     });
 }
 
+// cblx_unitig_ends* and cblx_tips_mark*: counts out, the capacity, then the kernels write into the caller's device arrays (`device`) or into pool arrays
+// copied back. `mark`: kind and the four counts (left is `kind`, right unused); otherwise the two ends.
+int tip_observe(cblx_ctx* c, bool device, bool mark, u64 max_kmers, u8* left, u8* right, u64 cap_unitigs, u64* n_unitigs, u64* counts) {
+    return guard(c, [&] {
+        if (mark && max_kmers == 0) throw Error(CBLX_EINVAL, "max_kmers must be at least 1");
+        TipRun t;
+        tip_table(c, t);
+        collect_events(c);
+        const u64 nu = t.n_unitigs;
+        if (n_unitigs) *n_unitigs = nu;
+        if ((left || right) && cap_unitigs < nu)
+            throw Error(CBLX_ERANGE, "output capacity too small: the index holds " + std::to_string(t.n) + " k-mers in " + std::to_string(nu) + " unitigs");
+        u64 h[4] = {0, 0, 0, 0};
+        if (t.n != 0 && (mark || left || right)) {
+            Buf<u8> d_l, d_r;
+            if (!device && left) d_l = Buf<u8>(c->pool, nu);
+            if (!device && right) d_r = Buf<u8>(c->pool, nu);
+            u8* const o_l = device ? left : d_l.get();
+            u8* const o_r = device ? right : d_r.get();
+            if (mark) tip_mark(c, t, max_kmers, o_l, h);
+            else tip_ends(c, t, o_l, o_r);
+            if (!device && left) xfer(c).d2h_copy(left, d_l.get(), nu);
+            if (!device && right) xfer(c).d2h_copy(right, d_r.get(), nu);
+            CBLX_HIP(hipStreamSynchronize(c->stream));
+        }
+        if (counts) for (int k = 0; k < 4; ++k) counts[k] = h[k];
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1862,6 +1891,32 @@ int cblx_gfa_to_fd(cblx_ctx* c, int fd, uint64_t chunk_bytes, uint64_t* n_unitig
 }
 int cblx_gfa_to_file(cblx_ctx* c, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* bytes) {
     return gfa_to_file(c, path, chunk_bytes, n_unitigs, n_links, bytes);
+}
+// ---- tip clipping ----
+int cblx_unitig_ends(cblx_ctx* c, uint8_t* left, uint8_t* right, uint64_t cap_unitigs, uint64_t* n_unitigs) {
+    return tip_observe(c, false, false, 0, left, right, cap_unitigs, n_unitigs, nullptr);
+}
+int cblx_unitig_ends_device(cblx_ctx* c, uint8_t* d_left, uint8_t* d_right, uint64_t cap_unitigs, uint64_t* n_unitigs) {
+    return tip_observe(c, true, false, 0, d_left, d_right, cap_unitigs, n_unitigs, nullptr);
+}
+int cblx_tips_mark(cblx_ctx* c, uint64_t max_kmers, uint8_t* kind, uint64_t cap_unitigs, uint64_t* n_unitigs, uint64_t counts[4]) {
+    return tip_observe(c, false, true, max_kmers, kind, nullptr, cap_unitigs, n_unitigs, counts);
+}
+int cblx_tips_mark_device(cblx_ctx* c, uint64_t max_kmers, uint8_t* d_kind, uint64_t cap_unitigs, uint64_t* n_unitigs, uint64_t counts[4]) {
+    return tip_observe(c, true, true, max_kmers, d_kind, nullptr, cap_unitigs, n_unitigs, counts);
+}
+int cblx_clip_tips(cblx_ctx* c, uint64_t max_kmers, uint32_t flags, uint32_t max_rounds, cblx_clip_stats* stats) {
+    return guard(c, [&] {
+        if (max_kmers == 0) throw Error(CBLX_EINVAL, "max_kmers must be at least 1");
+        if (flags & ~(uint32_t)CBLX_CLIP_ISOLATED) throw Error(CBLX_EINVAL, "unknown flag bits");
+        u64 st[7];
+        try { clip_tips(c, max_kmers, (flags & CBLX_CLIP_ISOLATED) != 0, max_rounds, st); } catch (...) { collect_events(c); throw; }
+        collect_events(c);
+        if (stats) {
+            stats->rounds = st[0]; stats->tips = st[1]; stats->tip_kmers = st[2]; stats->isolated = st[3]; stats->isolated_kmers = st[4];
+            stats->kmers_left = st[5]; stats->fixpoint = st[6];
+        }
+    });
 }
 int cblx_bucket_nodes(cblx_ctx* c, uint64_t* nodes, uint64_t cap, uint64_t* n) {
     return guard(c, [&] {

@@ -1,14 +1,16 @@
 // graph.hpp — the index as a de Bruijn graph, on the host: the checks a batch of packed k-mers goes through, the export of the index pass by pass
 // (export_passes), neighbour masks (neighbor_masks_device, neighbor_masks_range), the rank of a k-mer (rank_words,
 // rank_kmers_device) and the compaction into unitigs, plain (section 6k) and bidirected (section 6l): unitig_compute, unitig_number, unitig_text,
-// unitigs_to_fd; and the links between the unitigs with the GFA text of the compacted graph (section 6m): gfa_count, gfa_fill, gfa_text, gfa_to_fd.
-// Kernels: kernels_graph.hpp, kernels_unitig.hpp, kernels_biunitig.hpp, kernels_gfa.hpp. Included by cblx.cpp only.
+// unitigs_to_fd; the links between the unitigs with the GFA text of the compacted graph (section 6m): gfa_count, gfa_fill, gfa_text, gfa_to_fd; and tip
+// clipping (section 6n): tip_table, tip_ends, tip_mark, clip_tips.
+// Kernels: kernels_graph.hpp, kernels_unitig.hpp, kernels_biunitig.hpp, kernels_gfa.hpp, kernels_tips.hpp. Included by cblx.cpp only.
 #pragma once
 #include "list.hpp"
 #include "kernels_graph.hpp"
 #include "kernels_unitig.hpp"
 #include "kernels_biunitig.hpp"
 #include "kernels_gfa.hpp"
+#include "kernels_tips.hpp"
 
 namespace {
 
@@ -426,6 +428,112 @@ void gfa_to_fd(cblx_ctx* c, int fd, u64 chunk_bytes, u64* n_unitigs, u64* n_link
     if (chunk_bytes == 0) chunk_bytes = LIST_CHUNK_DEFAULT * (c->P.K + 1);
     const u64 cbytes = std::min<u64>(chunk_bytes, t.bytes);
     stream_chunks_to_fd(c, fd, t.bytes, cbytes, "GFA", [&](u64 i, u64) -> const u8* { return t.text.get() + i * cbytes; });
+}
+
+// ---- tip clipping (kernels_tips.hpp) -------------------------------------------------------------------------------------
+// The form follows the index, as in section 6m. What a call holds between its steps: per k-mer `unitig`, per unitig `length` and the degrees at its two
+// ends; the offsets, `reversed` and the masks the compaction kept only until the ends are made.
+struct TipRun {
+    UnitigForm form = UnitigForm::Plain;
+    u64 n = 0, n_unitigs = 0;
+    Buf<u32> unitig, offset, length;
+    Buf<u8> reversed, masks, left, right;
+};
+// The compaction with its masks kept, and the table: the counts. The ranking's arrays are back in the pool on return.
+void tip_table(cblx_ctx* c, TipRun& t) {
+    UnitigRun u;
+    t.form = gfa_form(c);
+    unitig_compute(c, u, t.form, true);
+    const u64 n = t.n = u.n, nu = t.n_unitigs = u.n_unitigs;
+    if (n == 0) return;
+    t.unitig = Buf<u32>(c->pool, n); t.offset = Buf<u32>(c->pool, n); t.length = Buf<u32>(c->pool, nu);
+    if (t.form == UnitigForm::Bidirected) t.reversed = Buf<u8>(c->pool, n);
+    unitig_number(c, u, t.unitig.get(), t.offset.get(), t.reversed.get(), nullptr, t.length.get(), nullptr);
+    t.masks = std::move(u.masks);
+}
+// left / right (device arrays of t.n_unitigs elements; either may be null); t.n != 0. The offsets, `reversed` and the masks go back to the pool.
+void tip_ends(cblx_ctx* c, TipRun& t, u8* d_left, u8* d_right) {
+    hipLaunchKernelGGL(k_tip_ends, grid1(t.n, 256), dim3(256), 0, c->stream, t.unitig.get(), t.offset.get(), t.reversed.get(), t.length.get(), t.masks.get(), t.n, d_left, d_right);
+    CBLX_HIP(hipGetLastError());
+    CBLX_HIP(hipStreamSynchronize(c->stream));
+    t.offset.reset(); t.reversed.reset(); t.masks.reset();
+}
+// kind (a device array of t.n_unitigs elements, or null) and the four counts: tips, their k-mers, isolated unitigs, their k-mers; t.n != 0. The ends
+// are made into t.left / t.right first.
+void tip_mark(cblx_ctx* c, TipRun& t, u64 max_kmers, u8* d_kind, u64 counts[4]) {
+    const u64 nu = t.n_unitigs;
+    t.left = Buf<u8>(c->pool, nu); t.right = Buf<u8>(c->pool, nu);
+    tip_ends(c, t, t.left.get(), t.right.get());
+    Buf<u64> d_counts(c->pool, 4);
+    CBLX_HIP(hipMemsetAsync(d_counts.get(), 0, 4 * 8, c->stream));
+    hipLaunchKernelGGL(k_tip_mark, grid1(nu, 256), dim3(256), 0, c->stream, (const u32*)t.length.get(), (const u8*)t.left.get(), (const u8*)t.right.get(), nu, max_kmers, d_kind,
+                       d_counts.get());
+    CBLX_HIP(hipGetLastError());
+    const std::vector<u64> h = d2h_vec<u64>(c, d_counts.get(), 4);
+    for (int k = 0; k < 4; ++k) counts[k] = h[k];
+}
+// One round of clip_tips: compact, mark, select the k-mers of the wanted kinds in iteration order, and remove their words as one WordSet::remove_batch.
+// Returns the selected k-mers (0: nothing was removed); counts as in tip_mark. Everything the compaction and the marks held is back in the pool before
+// remove_words takes its workspace: only the batch of selected k-mers, then its words, survive.
+u64 clip_round(cblx_ctx* c, u64 max_kmers, bool isolated, u64 counts[4]) {
+    const bool wide = c->P.wide_kmer();
+    Buf<u64> s_lo, s_hi;
+    u64 ns = 0;
+    {
+        TipRun t;
+        tip_table(c, t);
+        for (int k = 0; k < 4; ++k) counts[k] = 0;
+        if (t.n == 0) return 0;
+        const u64 n = t.n;
+        Buf<u8> kind(c->pool, t.n_unitigs);
+        tip_mark(c, t, max_kmers, kind.get(), counts);
+        if (counts[0] + (isolated ? counts[2] : 0) == 0) return 0;
+        t.left.reset(); t.right.reset(); t.length.reset();
+        Buf<u32> sel(c->pool, n), pos(c->pool, n);
+        hipLaunchKernelGGL(k_tip_select, grid1(n, 256), dim3(256), 0, c->stream, (const u32*)t.unitig.get(), (const u8*)kind.get(), n,
+                           (1u << TIP_TIP) | (isolated ? 1u << TIP_ISOLATED : 0u), sel.get());
+        CBLX_HIP(hipGetLastError());
+        ns = exclusive_scan<u32>(c, sel.get(), n, pos.get());
+        if (ns != counts[1] + (isolated ? counts[3] : 0)) throw Error(CBLX_EDEVICE, "the selected k-mers and the marked lengths do not add up (internal error)");
+        t.unitig.reset(); kind.reset();
+        s_lo = Buf<u64>(c->pool, ns + 2);
+        if (wide) s_hi = Buf<u64>(c->pool, ns + 2);
+        export_passes(c, 0, n, [&](u64 a, u64 m, const u64* k_lo, const u64* k_hi, const u64*) {
+            hipLaunchKernelGGL(k_tip_gather, grid1(m, 256), dim3(256), 0, c->stream, k_lo, k_hi, a, m, (const u32*)sel.get(), (const u32*)pos.get(), s_lo.get(), s_hi.get());
+            CBLX_HIP(hipGetLastError());
+        });  // sel / pos die behind its sync
+    }
+    dispatch(c->P, [&](auto cfg) {
+        typedef decltype(cfg) C;
+        typedef typename C::HiT HiT;
+        Buf<u64> w_lo(c->pool, ns + 2);
+        Buf<u8> w_hi(c->pool, (ns + 2) * std::max<size_t>(1, hi_elem_size(c->P)));
+        Buf<u32> bad(c->pool, 1);
+        CBLX_HIP(hipMemsetAsync(bad.get(), 0, 4, c->stream));
+        hipLaunchKernelGGL((k_kmers_to_words<C::WIDE, HiT>), grid1(ns, 256), dim3(256), 0, c->stream, (const u64*)s_lo.get(), (const u64*)s_hi.get(), ns, c->P, w_lo.get(),
+                           (HiT*)w_hi.get(), bad.get());
+        CBLX_HIP(hipGetLastError());
+        if (d2h<u32>(c, bad.get())) throw Error(CBLX_EDEVICE, "an exported k-mer is no IntKmer<K> (internal error)");
+        s_lo.reset(); s_hi.reset();
+        Buf<u32> gstart(c->pool, ns + 1);
+        CBLX_HIP(hipMemsetAsync(gstart.get(), 0, (ns + 1) * 4, c->stream));
+        remove_words<C>(c, w_lo.get(), (const HiT*)w_hi.get(), ns, gstart, false, nullptr);  // groups: the maximal runs of equal prefix, one per bucket
+    });
+    return ns;
+}
+// stats: rounds, tips, tip_kmers, isolated, isolated_kmers, kmers_left, fixpoint (cblx_clip_stats). max_rounds = 0: until nothing is selected.
+void clip_tips(cblx_ctx* c, u64 max_kmers, bool isolated, u32 max_rounds, u64 stats[7]) {
+    for (int k = 0; k < 7; ++k) stats[k] = 0;
+    for (u32 r = 0;; ++r) {
+        u64 counts[4];
+        const u64 ns = clip_round(c, max_kmers, isolated, counts);
+        ++stats[0];
+        if (ns == 0) { stats[6] = 1; break; }
+        stats[1] += counts[0]; stats[2] += counts[1];
+        if (isolated) { stats[3] += counts[2]; stats[4] += counts[3]; }
+        if (r + 1 == max_rounds) break;
+    }
+    stats[5] = c->res.count;
 }
 
 }  // namespace

@@ -37,7 +37,8 @@ extern "C" {
  * cblx_neighbors_kmers, cblx_neighbors_kmers_device, cblx_neighbors_range, cblx_neighbors_range_device and cblx_degree_table;
  * cblx_rank_kmers, cblx_rank_kmers_device, cblx_unitig_table, cblx_unitig_table_device, cblx_unitigs_text_device, cblx_unitigs_to_fd and cblx_unitigs_to_file;
  * cblx_biunitig_table, cblx_biunitig_table_device, cblx_biunitigs_text_device, cblx_biunitigs_to_fd and cblx_biunitigs_to_file;
- * cblx_gfa_links, cblx_gfa_links_device, cblx_gfa_text_device, cblx_gfa_to_fd and cblx_gfa_to_file. */
+ * cblx_gfa_links, cblx_gfa_links_device, cblx_gfa_text_device, cblx_gfa_to_fd and cblx_gfa_to_file;
+ * cblx_unitig_ends, cblx_unitig_ends_device, cblx_tips_mark, cblx_tips_mark_device and cblx_clip_tips with cblx_clip_stats and CBLX_CLIP_ISOLATED. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -596,6 +597,27 @@ int cblx_gfa_links_device(cblx_ctx* ctx, uint64_t* d_link_start, uint64_t cap_st
 int cblx_gfa_text_device(cblx_ctx* ctx, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs, uint64_t* n_links);
 int cblx_gfa_to_fd(cblx_ctx* ctx, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* bytes);
 int cblx_gfa_to_file(cblx_ctx* ctx, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* n_links, uint64_t* bytes);
+/* ---- tip clipping on the compacted graph. The form follows the index as in the link table: unitig numbers, lengths, `reversed` and the
+ * refusals are those of cblx_unitig_table (a non-canonical index) or cblx_biunitig_table (a canonical one).
+ *   right[u]   uint8: the out-degree of the last oriented k-mer of unitig u's kept image = link_start[2 u + 1] - link_start[2 u]
+ *   left[u]    uint8: the in-degree of its first one; bidirected form: link_start[2 u + 2] - link_start[2 u + 1]; plain form: the links whose link_to is u
+ * Self-edges and hairpins count, so a circular unitig has left, right >= 1. With max_kmers >= 1, kind[u] (uint8) is 1, a TIP, when length[u] <= max_kmers and
+ * exactly one of left[u], right[u] is 0; 2, ISOLATED, when length[u] <= max_kmers and both are 0; 0 otherwise. counts = {tips, k-mers of the tips, isolated
+ * unitigs, k-mers of the isolated unitigs}. Observers with the conventions of cblx_unitig_table: any array may be NULL, *n_unitigs (and counts, unless NULL) is
+ * always set, cap_unitigs < U with an array given is CBLX_ERANGE with the need reported and nothing written. max_kmers == 0 is CBLX_EINVAL. */
+int cblx_unitig_ends(cblx_ctx* ctx, uint8_t* left, uint8_t* right, uint64_t cap_unitigs, uint64_t* n_unitigs);
+int cblx_unitig_ends_device(cblx_ctx* ctx, uint8_t* d_left, uint8_t* d_right, uint64_t cap_unitigs, uint64_t* n_unitigs);
+int cblx_tips_mark(cblx_ctx* ctx, uint64_t max_kmers, uint8_t* kind, uint64_t cap_unitigs, uint64_t* n_unitigs, uint64_t counts[4]);
+int cblx_tips_mark_device(cblx_ctx* ctx, uint64_t max_kmers, uint8_t* d_kind, uint64_t cap_unitigs, uint64_t* n_unitigs, uint64_t counts[4]);
+/* A ROUND compacts the index, marks the unitigs, takes the k-mers of the tips — with CBLX_CLIP_ISOLATED those of the isolated unitigs too — in iteration
+ * order and removes their words as ONE WordSet::remove_batch (one group per bucket: the bytes afterwards are what cblx_remove_words_device leaves of that
+ * batch). All marked unitigs of a compaction go together: a short stem that forks into two short dead ends is three tips. Round r stops the call with
+ * fixpoint = 1 when it selects nothing, and with fixpoint = 0 after its removal when r + 1 == max_rounds; max_rounds == 0 runs until the fixpoint.
+ * tips .. isolated_kmers count what was REMOVED, summed over the rounds (the isolated pair stays 0 without the flag); rounds = compactions run. `stats` may be
+ * NULL. max_kmers == 0 and unknown flag bits are CBLX_EINVAL; the form's refusals come before anything changes. An empty index: rounds = 1, fixpoint = 1. */
+#define CBLX_CLIP_ISOLATED 1u
+typedef struct cblx_clip_stats { uint64_t rounds, tips, tip_kmers, isolated, isolated_kmers, kmers_left, fixpoint; } cblx_clip_stats;
+int cblx_clip_tips(cblx_ctx* ctx, uint64_t max_kmers, uint32_t flags, uint32_t max_rounds, cblx_clip_stats* stats);
 /* CBL::buckets_nodes (src/cbl.rs:386-390): per non-empty prefix ascending, TrieVec::count_nodes (src/trievec/mod.rs:37-42) — a Vec's length, a Trie's
  * nodes (src/trie.rs:90-102: the root and one node per distinct proper byte prefix of its suffixes). Pairs with cblx_bucket_sizes. */
 int cblx_bucket_nodes(cblx_ctx* ctx, uint64_t* nodes, uint64_t cap, uint64_t* n);

@@ -329,6 +329,23 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         (u, l, bytes)
     }
 
+    /// `[tips, k-mers of the tips, isolated unitigs, k-mers of the isolated unitigs]` at `max_kmers`: a tip is a unitig of at most
+    /// `max_kmers` k-mers with exactly one end of degree 0, an isolated unitig one with both. Only the counts come back.
+    pub fn tip_counts(&self, max_kmers: u64) -> [u64; 4] {
+        let (mut u, mut counts) = (0u64, [0u64; 4]);
+        self.check(unsafe { sys::cblx_tips_mark(self.ctx, max_kmers, std::ptr::null_mut::<u8>(), 0, &mut u, counts.as_mut_ptr()) });
+        counts
+    }
+
+    /// Removes the k-mers of the tips (with `isolated` those of the isolated unitigs too) on the device. A round compacts, marks and
+    /// removes every marked unitig of that compaction as one batch; `rounds` = 0 repeats until a round finds nothing.
+    pub fn clip_tips(&mut self, max_kmers: u64, isolated: bool, rounds: u32) -> sys::cblx_clip_stats {
+        let mut stats = sys::cblx_clip_stats::default();
+        let flags = if isolated { sys::CBLX_CLIP_ISOLATED } else { 0 };
+        self.check(unsafe { sys::cblx_clip_tips(self.ctx, max_kmers, flags, rounds, &mut stats) });
+        stats
+    }
+
     /// Adds a k-mer; returns `true` if it was absent (`src/cbl.rs:226-228`). One device round trip per call: a caller with
     /// many k-mers uses `insert_kmers`.
     #[inline]

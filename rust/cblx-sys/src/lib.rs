@@ -30,6 +30,7 @@ pub const CBLX_SETOP_SUB: u32 = 2;
 pub const CBLX_SETOP_XOR: u32 = 3;
 pub const CBLX_SETOP_MAX_OPERANDS: u32 = 64;
 pub const CBLX_COMMON_STATS: u32 = 5;
+pub const CBLX_CLIP_ISOLATED: u32 = 1;
 
 #[repr(C)]
 pub struct cblx_ctx {
@@ -102,6 +103,18 @@ pub struct cblx_exchange_stats {
     pub sent_bytes: u64,
     pub recv_bytes: u64,
     pub messages: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct cblx_clip_stats {
+    pub rounds: u64,
+    pub tips: u64,
+    pub tip_kmers: u64,
+    pub isolated: u64,
+    pub isolated_kmers: u64,
+    pub kmers_left: u64,
+    pub fixpoint: u64,
 }
 
 #[repr(C)]
@@ -411,6 +424,11 @@ extern "C" {
     pub fn cblx_gfa_text_device(ctx: *mut cblx_ctx, d_buf: *mut u8, cap: u64, bytes: *mut u64, n_unitigs: *mut u64, n_links: *mut u64) -> c_int;
     pub fn cblx_gfa_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_bytes: u64, n_unitigs: *mut u64, n_links: *mut u64, bytes: *mut u64) -> c_int;
     pub fn cblx_gfa_to_file(ctx: *mut cblx_ctx, path: *const c_char, chunk_bytes: u64, n_unitigs: *mut u64, n_links: *mut u64, bytes: *mut u64) -> c_int;
+    pub fn cblx_unitig_ends(ctx: *mut cblx_ctx, left: *mut u8, right: *mut u8, cap_unitigs: u64, n_unitigs: *mut u64) -> c_int;
+    pub fn cblx_unitig_ends_device(ctx: *mut cblx_ctx, d_left: *mut u8, d_right: *mut u8, cap_unitigs: u64, n_unitigs: *mut u64) -> c_int;
+    pub fn cblx_tips_mark(ctx: *mut cblx_ctx, max_kmers: u64, kind: *mut u8, cap_unitigs: u64, n_unitigs: *mut u64, counts: *mut u64) -> c_int;
+    pub fn cblx_tips_mark_device(ctx: *mut cblx_ctx, max_kmers: u64, d_kind: *mut u8, cap_unitigs: u64, n_unitigs: *mut u64, counts: *mut u64) -> c_int;
+    pub fn cblx_clip_tips(ctx: *mut cblx_ctx, max_kmers: u64, flags: u32, max_rounds: u32, stats: *mut cblx_clip_stats) -> c_int;
     pub fn cblx_list_range(ctx: *mut cblx_ctx, first: u64, n: u64, buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_range_device(ctx: *mut cblx_ctx, first: u64, n: u64, d_buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_kmers: u64, n_kmers: *mut u64) -> c_int;
