@@ -71,6 +71,14 @@ class ClipStats(C.Structure):
 CLIP_ISOLATED = 1  # CBLX_CLIP_ISOLATED of include/cblx.h
 TIP_COUNTS = ("tips", "tip_kmers", "isolated", "isolated_kmers")
 
+
+class ComponentStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("components", "removed_components", "removed_kmers", "kmers_left", "largest_kmers", "rounds")]
+
+
+COMPONENTS_LARGEST = 1  # CBLX_COMPONENTS_LARGEST of include/cblx.h
+COMPONENT_COUNTS = ("kmers", "unitigs", "links", "components", "largest_kmers", "rounds")
+
 BUCKET_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 
 ABI_VERSION = 3  # include/cblx.h CBLX_ABI_VERSION
@@ -211,6 +219,9 @@ SIGNATURES = {
     "cblx_tips_mark": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_tips_mark_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cblx_clip_tips": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(ClipStats)]),
+    "cblx_components": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_components_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_components_filter": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(ComponentStats)]),
     "cblx_list_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -1453,6 +1464,77 @@ class CBL:
         st = ClipStats()
         self._chk(self._L.cblx_clip_tips(self._h, self._max_kmers(max_kmers), CLIP_ISOLATED if isolated else 0, int(rounds), C.byref(st)))
         return {name: int(getattr(st, name)) for name, _ in ClipStats._fields_}
+
+    # ---- connected components of the compacted graph; the form follows the index -------------------------------------
+    def _components(self, device: bool, component=None, cap_unitigs: int = 0, kmer_component=None, cap_kmers: int = 0, first=None, unitigs=None, kmers=None,
+                    cap_components: int = 0) -> dict:
+        counts = (C.c_uint64 * 6)()
+        fn = self._L.cblx_components_device if device else self._L.cblx_components
+        self._chk(fn(self._h, _ptr(component), cap_unitigs, _ptr(kmer_component), cap_kmers, _ptr(first), _ptr(unitigs), _ptr(kmers), cap_components, counts))
+        return dict(zip(COMPONENT_COUNTS, (int(v) for v in counts)))
+
+    def component_counts(self) -> dict:
+        """kmers, unitigs, links, components, largest_kmers and rounds of the connected components of the compacted de Bruijn graph: the labelling
+        runs on the device, six numbers come back. `rounds` is the number of hook-and-compress rounds the labelling took (the last one, which
+        changes nothing, included; 0 for an empty index)."""
+        return self._components(False)
+
+    def _component_table(self, xp, per_kmer: bool) -> dict:
+        device = xp.__name__ == "torch"
+        ct = self._components(device)
+        n, u, nc = ct["kmers"], ct["unitigs"], ct["components"]
+        if device:
+            dev = xp.device("cuda", self.device())
+            new = lambda count, dtype: xp.empty(max(count, 1), dtype=dtype, device=dev)  # noqa: E731
+            i32, i64 = xp.int32, xp.int64
+        else:
+            new = lambda count, dtype: xp.zeros(max(count, 1), dtype=dtype)  # noqa: E731
+            i32, i64 = xp.uint32, xp.uint64
+        component, first, unitigs, kmers = new(u, i32), new(nc, i32), new(nc, i32), new(nc, i64)
+        kc = new(n, i32) if per_kmer else None
+        ct2 = self._components(device, component, u, kc, n if per_kmer else 0, first, unitigs, kmers, nc)
+        assert ct2 == ct
+        out = {"component": component[:u], "first": first[:nc], "unitigs": unitigs[:nc], "kmers": kmers[:nc], "n_kmers": n, "n_unitigs": u, "n_links": ct["links"],
+               "n_components": nc, "largest_kmers": ct["largest_kmers"], "rounds": ct["rounds"]}
+        if per_kmer:
+            out["kmer_component"] = kc[:n]
+        return out
+
+    def components_np(self, per_kmer: bool = False) -> dict:
+        """The connected components of the compacted graph — the weakly connected components of the de Bruijn graph on the stored k-mers; a
+        unitig and its reverse complement are one node. `component` (uint32 per unitig of unitig_table_np / biunitig_table_np), and per
+        component `first` (its smallest unitig; the components are numbered by ascending `first`), `unitigs` (uint32) and `kmers` (uint64, the
+        sum of its unitigs' lengths). With per_kmer also `kmer_component` (uint32 per k-mer, by ordinal). Also n_kmers, n_unitigs, n_links,
+        n_components, largest_kmers and rounds."""
+        import numpy as np
+
+        return self._component_table(np, per_kmer)
+
+    def components_device(self, per_kmer: bool = False) -> dict:
+        """The same table as torch CUDA tensors (int32 / int64 holding the unsigned values); only the six counts cross to the host."""
+        import torch
+
+        return self._component_table(torch, per_kmer)
+
+    def components_filter(self, min_kmers=None, largest: bool = False) -> dict:
+        """Removes whole components from the index, on the device: with min_kmers every component of fewer than min_kmers k-mers, with `largest`
+        every component but the one of most k-mers (a tie: the lower number). Exactly one of the two is given. The k-mers go as one batch, in
+        iteration order. Returns components, removed_components, removed_kmers, kmers_left, largest_kmers (before the removal) and rounds."""
+        st = ComponentStats()
+        self._chk(self._L.cblx_components_filter(self._h, 0 if min_kmers is None else int(min_kmers), COMPONENTS_LARGEST if largest else 0, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in ComponentStats._fields_}
+
+    @staticmethod
+    def component_summary(kmers, unitigs) -> dict:
+        """What the per-component `kmers` and `unitigs` of components_np say (host only): components, largest (the k-mers of the largest one),
+        singletons (components of one unitig) and largest_fraction (the k-mers held by the largest as a fraction of all; 0.0 for no component)."""
+        ks, us = [int(v) for v in kmers], [int(v) for v in unitigs]
+        if len(ks) != len(us):
+            raise ValueError("component_summary: kmers and unitigs differ in length")
+        if any(v < 1 for v in ks) or any(v < 1 for v in us) or any(k < u for k, u in zip(ks, us)):
+            raise ValueError("component_summary: every component has at least one unitig and at least as many k-mers as unitigs")
+        total, big = sum(ks), max(ks, default=0)
+        return {"components": len(ks), "largest": big, "singletons": sum(1 for u in us if u == 1), "largest_fraction": big / total if total else 0.0}
 
     # ---- bucket statistics (src/cbl.rs:364-386) ---------------------------------------------------------------------
     def bucket_table_np(self):

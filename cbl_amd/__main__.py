@@ -3,7 +3,8 @@ reference CLI (/root/reference/examples/cbl.rs:147-167,230-269,270-309,168-229,3
 `CBL::intersect` (src/cbl.rs:106-124) over two or more index files, which the reference's CLI does not expose; `compare` prints the shared k-mers, Jaccard and
 containment of every pair of two or more index files; `classify` assigns every record of a FASTA/Q file to one of two or more index files; `graph` prints
 the degree table of the de Bruijn graph whose nodes are the k-mers of an index; `unitigs` writes the non-branching paths of that graph, one line each
-(of a canonical index: the bidirected unitigs); `clip` removes the short dead-end unitigs (tips) of that graph from an index.
+(of a canonical index: the bidirected unitigs); `clip` removes the short dead-end unitigs (tips) of that graph from an index; `components`
+prints the connected components of that graph, or removes the small ones (or all but the largest) from an index.
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
 here they are flags with the same defaults (K=25, PREFIX_BITS=24). Index files are interchangeable with the reference's.
@@ -212,7 +213,20 @@ def main(argv=None):
     cp.add_argument("--max-kmers", type=int, default=None, metavar="N", help="the longest unitig that counts as a tip, in k-mers (default: K - 1)")
     cp.add_argument("--isolated", action="store_true", help="also remove the unitigs of at most N k-mers that are linked to nothing")
     cp.add_argument("--rounds", type=int, default=1, metavar="R", help="compact and clip up to R times (default 1); 0: until a round finds no tip")
+    cc = sub.add_parser("components", help="Show the connected components of the de Bruijn graph whose nodes are the k-mers of an index, or, with -o, remove "
+                                           "whole components from it: those of fewer than N k-mers, or all but the largest")
+    cc.add_argument("index")
+    cc.add_argument("-o", "--output", help="write the filtered index to OUT (needs --min-kmers or --largest)")
+    cc.add_argument("--sizes", action="store_true", help="also print one line per component: its number, its k-mers and its unitigs, tab-separated")
+    cc_rule = cc.add_mutually_exclusive_group()
+    cc_rule.add_argument("--min-kmers", type=int, default=None, metavar="N", help="remove every component of fewer than N k-mers (N is at least 1)")
+    cc_rule.add_argument("--largest", action="store_true", help="remove every component but the one of most k-mers")
     a = ap.parse_args(argv)
+    if a.cmd == "components":  # refused before anything is loaded
+        if a.min_kmers is not None and a.min_kmers < 1:
+            ap.error("components: --min-kmers is at least 1")
+        if (a.min_kmers is not None or a.largest) != (a.output is not None):
+            ap.error("components: -o needs exactly one of --min-kmers and --largest, and they need -o")
 
     if a.cmd == "build":
         cbl = CBL(a.k, a.prefix_bits, canonical=a.canonical, device=a.device)
@@ -392,6 +406,25 @@ def main(argv=None):
         print(f"Writing the index to {a.output}", file=sys.stderr)
         cbl.save_to_file(a.output)
         print("\n".join(f"{key}\t{value}" for key, value in st.items()))
+    elif a.cmd == "components":  # ours (the reference's CLI has no such command): the removal is one WordSet::remove_batch (src/wordset/mod.rs:218-237)
+        print(f"Reading the index stored in {a.index}", file=sys.stderr)
+        cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
+        if a.output is None:
+            print(f"Labelling the components of the {'canonical ' if cbl.is_canonical() else ''}{a.k}-mers contained in {a.index}", file=sys.stderr)
+            t = cbl.components_np()
+            sm = CBL.component_summary(t["kmers"], t["unitigs"])
+            print(f"kmers\t{t['n_kmers']}\nunitigs\t{t['n_unitigs']}\nlinks\t{t['n_links']}\ncomponents\t{sm['components']}\nlargest\t{sm['largest']}\n"
+                  f"singletons\t{sm['singletons']}\nlargest_fraction\t{sm['largest_fraction']:.6f}")
+            if a.sizes:
+                sys.stdout.write("".join(f"{c}\t{k}\t{u}\n" for c, (k, u) in enumerate(zip(t["kmers"].tolist(), t["unitigs"].tolist()))))
+        else:
+            print(f"Filtering the components of the {'canonical ' if cbl.is_canonical() else ''}{a.k}-mers contained in {a.index}", file=sys.stderr)
+            st = cbl.components_filter(a.min_kmers, largest=a.largest)
+            print(f"Removed {st['removed_components']} of {st['components']} components, {st['removed_kmers']} k-mers; {st['kmers_left']} k-mers are left",
+                  file=sys.stderr)
+            print(f"Writing the index to {a.output}", file=sys.stderr)
+            cbl.save_to_file(a.output)
+            print("\n".join(f"{key}\t{value}" for key, value in st.items()))
 
 
 if __name__ == "__main__":

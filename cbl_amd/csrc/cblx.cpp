@@ -302,6 +302,38 @@ int tip_observe(cblx_ctx* c, bool device, bool mark, u64 max_kmers, u8* left, u8
     });
 }
 
+// cblx_components and cblx_components_device: counts out, the capacities, then the table into the caller's device arrays (`device`) or copied back
+int components(cblx_ctx* c, bool device, u32* component, u64 cap_unitigs, u32* kmer_component, u64 cap_kmers, u32* first, u32* unitigs, u64* kmers, u64 cap_components,
+               u64* counts) {
+    return guard(c, [&] {
+        ComponentRun r;
+        try { component_table(c, r); } catch (...) { collect_events(c); throw; }
+        collect_events(c);
+        const u64 n = r.n, nu = r.n_unitigs, nc = r.n_components;
+        if (counts) { counts[0] = n; counts[1] = nu; counts[2] = r.n_links; counts[3] = nc; counts[4] = r.largest_kmers; counts[5] = r.rounds; }
+        if ((component && cap_unitigs < nu) || (kmer_component && cap_kmers < n) || ((first || unitigs || kmers) && cap_components < nc))
+            throw Error(CBLX_ERANGE, "output capacity too small: the index holds " + std::to_string(n) + " k-mers in " + std::to_string(nu) + " unitigs and " +
+                                         std::to_string(nc) + " components");
+        if (n == 0) return;
+        const auto out = [&](void* dst, const void* src, u64 bytes) {
+            if (!dst) return;
+            if (device) CBLX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+            else xfer(c).d2h_copy(dst, src, bytes);
+        };
+        out(component, r.component.get(), nu * 4);
+        out(first, r.first.get(), nc * 4);
+        out(unitigs, r.unitigs.get(), nc * 4);
+        out(kmers, r.kmers.get(), nc * 8);
+        Buf<u32> d_kc;
+        if (kmer_component) {
+            if (!device) d_kc = Buf<u32>(c->pool, n);
+            component_kmers(c, r, device ? kmer_component : d_kc.get());
+            if (!device) xfer(c).d2h_copy(kmer_component, d_kc.get(), n * 4);
+        }
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1915,6 +1947,30 @@ int cblx_clip_tips(cblx_ctx* c, uint64_t max_kmers, uint32_t flags, uint32_t max
         if (stats) {
             stats->rounds = st[0]; stats->tips = st[1]; stats->tip_kmers = st[2]; stats->isolated = st[3]; stats->isolated_kmers = st[4];
             stats->kmers_left = st[5]; stats->fixpoint = st[6];
+        }
+    });
+}
+// ---- connected components ----
+int cblx_components(cblx_ctx* c, uint32_t* component, uint64_t cap_unitigs, uint32_t* kmer_component, uint64_t cap_kmers, uint32_t* first, uint32_t* unitigs,
+                    uint64_t* kmers, uint64_t cap_components, uint64_t counts[6]) {
+    return components(c, false, component, cap_unitigs, kmer_component, cap_kmers, first, unitigs, kmers, cap_components, counts);
+}
+int cblx_components_device(cblx_ctx* c, uint32_t* d_component, uint64_t cap_unitigs, uint32_t* d_kmer_component, uint64_t cap_kmers, uint32_t* d_first,
+                           uint32_t* d_unitigs, uint64_t* d_kmers, uint64_t cap_components, uint64_t counts[6]) {
+    return components(c, true, d_component, cap_unitigs, d_kmer_component, cap_kmers, d_first, d_unitigs, d_kmers, cap_components, counts);
+}
+int cblx_components_filter(cblx_ctx* c, uint64_t min_kmers, uint32_t flags, cblx_component_stats* stats) {
+    return guard(c, [&] {
+        if (flags & ~(uint32_t)CBLX_COMPONENTS_LARGEST) throw Error(CBLX_EINVAL, "unknown flag bits");
+        const bool largest = (flags & CBLX_COMPONENTS_LARGEST) != 0;
+        if (largest ? min_kmers != 0 : min_kmers == 0)
+            throw Error(CBLX_EINVAL, largest ? "min_kmers must be 0 with CBLX_COMPONENTS_LARGEST" : "min_kmers must be at least 1 (or CBLX_COMPONENTS_LARGEST set)");
+        u64 st[6];
+        try { component_filter(c, min_kmers, largest, st); } catch (...) { collect_events(c); throw; }
+        collect_events(c);
+        if (stats) {
+            stats->components = st[0]; stats->removed_components = st[1]; stats->removed_kmers = st[2]; stats->kmers_left = st[3]; stats->largest_kmers = st[4];
+            stats->rounds = st[5];
         }
     });
 }

@@ -2,8 +2,9 @@
 // (export_passes), neighbour masks (neighbor_masks_device, neighbor_masks_range), the rank of a k-mer (rank_words,
 // rank_kmers_device) and the compaction into unitigs, plain (section 6k) and bidirected (section 6l): unitig_compute, unitig_number, unitig_text,
 // unitigs_to_fd; the links between the unitigs with the GFA text of the compacted graph (section 6m): gfa_count, gfa_fill, gfa_text, gfa_to_fd; and tip
-// clipping (section 6n): tip_table, tip_ends, tip_mark, clip_tips.
-// Kernels: kernels_graph.hpp, kernels_unitig.hpp, kernels_biunitig.hpp, kernels_gfa.hpp, kernels_tips.hpp. Included by cblx.cpp only.
+// clipping (section 6n): tip_table, tip_ends, tip_mark, clip_tips; and the connected components of the compacted graph with their filter (section 6o):
+// component_table, component_filter.
+// Kernels: kernels_graph.hpp, kernels_unitig.hpp, kernels_biunitig.hpp, kernels_gfa.hpp, kernels_tips.hpp, kernels_components.hpp. Included by cblx.cpp only.
 #pragma once
 #include "list.hpp"
 #include "kernels_graph.hpp"
@@ -11,6 +12,7 @@
 #include "kernels_biunitig.hpp"
 #include "kernels_gfa.hpp"
 #include "kernels_tips.hpp"
+#include "kernels_components.hpp"
 
 namespace {
 
@@ -534,6 +536,140 @@ void clip_tips(cblx_ctx* c, u64 max_kmers, bool isolated, u32 max_rounds, u64 st
         if (r + 1 == max_rounds) break;
     }
     stats[5] = c->res.count;
+}
+
+// ---- connected components (kernels_components.hpp) ---------------------------------------------------------------------------
+// The form follows the index, as in section 6m. What a call holds on return: per k-mer `unitig`, per unitig `component`, per component first / unitigs /
+// kmers (the k-mer sums on the host too); the link table, the lengths and the labelling's arrays are back in the pool.
+struct ComponentRun {
+    UnitigForm form = UnitigForm::Plain;
+    u64 n = 0, n_unitigs = 0, n_links = 0, n_components = 0, largest_kmers = 0;
+    u32 rounds = 0, largest = 0;  // hook rounds, the last one (which hooks nothing) included; the number of the largest component
+    Buf<u32> unitig, component, first, unitigs;
+    Buf<u64> kmers;
+    std::vector<u64> h_kmers;
+};
+// The link table, the rounds of hook and compress, the numbering and the sizes. An empty index: everything 0, no round.
+void component_table(cblx_ctx* c, ComponentRun& r) {
+    Buf<u32> length, link_to, par;
+    Buf<u64> link_start;
+    {
+        GfaRun g;
+        gfa_count(c, g);
+        r.form = g.form;
+        r.n = g.n; r.n_unitigs = g.n_unitigs; r.n_links = g.n_links;
+        if (g.n == 0) return;
+        if (g.n_unitigs >= (1ull << 31)) throw Error(CBLX_ERANGE, "the index has " + std::to_string(g.n_unitigs) + " unitigs: components need fewer than 2^31");
+        link_to = Buf<u32>(c->pool, g.n_links + 1);
+        if (g.n_links) gfa_fill(c, g, link_to.get(), nullptr);
+        r.unitig = std::move(g.unitig); length = std::move(g.length); link_start = std::move(g.link_start);
+    }  // the masks, the offsets and `reversed` go back to the pool
+    const u64 nu = r.n_unitigs, ns = 2 * nu;
+    const dim3 gu = grid1(nu, 256), gs = grid1(ns, 256), b256(256);
+    const u32 MAX_ROUNDS = 128, MAX_JUMPS = 33;  // a chain of fewer than 2^31 unitigs is compressed by 31 jumps; one more finds nothing open
+    Buf<u32> nxt(c->pool, nu), tmp(c->pool, nu);
+    Buf<u64> counters(c->pool, MAX_ROUNDS * (1 + MAX_JUMPS));  // [r] the slots that hooked in round r; behind them one word per jump launch
+    CBLX_HIP(hipMemsetAsync(counters.get(), 0, MAX_ROUNDS * (1 + MAX_JUMPS) * 8, c->stream));
+    par = Buf<u32>(c->pool, nu);
+    hipLaunchKernelGGL(k_cc_init, gu, b256, 0, c->stream, nu, par.get());
+    CBLX_HIP(hipGetLastError());
+    u64 jumps = 0;
+    for (u32 rd = 0;; ++rd) {
+        if (rd >= MAX_ROUNDS) throw Error(CBLX_EDEVICE, "component labelling did not end (internal error)");
+        CBLX_HIP(hipMemcpyAsync(nxt.get(), par.get(), nu * 4, hipMemcpyDeviceToDevice, c->stream));
+        hipLaunchKernelGGL(k_cc_hook, gs, b256, 0, c->stream, (const u64*)link_start.get(), (const u32*)link_to.get(), (const u32*)par.get(), ns, nxt.get(),
+                           counters.get() + rd);
+        CBLX_HIP(hipGetLastError());
+        ++r.rounds;
+        if (d2h<u64>(c, counters.get() + rd) == 0) break;  // nothing hooked: nxt == par, and every link joins equal labels
+        for (u32 j = 0;; ++j) {
+            if (j >= MAX_JUMPS) throw Error(CBLX_EDEVICE, "component compression did not end (internal error)");
+            u64* open = counters.get() + MAX_ROUNDS + jumps++;
+            hipLaunchKernelGGL(k_cc_jump, gu, b256, 0, c->stream, (const u32*)nxt.get(), nu, tmp.get(), open);
+            CBLX_HIP(hipGetLastError());
+            std::swap(nxt, tmp);
+            if (d2h<u64>(c, open) == 0) break;
+        }
+        std::swap(par, nxt);
+    }
+    link_to.reset(); link_start.reset(); tmp.reset();
+    // numbering: root flags -> exclusive scan -> component[u], first[c]
+    Buf<u32> scan(c->pool, nu);
+    hipLaunchKernelGGL(k_cc_roots, gu, b256, 0, c->stream, (const u32*)par.get(), nu, nxt.get());
+    CBLX_HIP(hipGetLastError());
+    const u64 nc = r.n_components = exclusive_scan<u32>(c, nxt.get(), nu, scan.get());
+    if (nc == 0 || nc > nu) throw Error(CBLX_EDEVICE, "the component roots do not add up (internal error)");
+    r.component = Buf<u32>(c->pool, nu); r.first = Buf<u32>(c->pool, nc); r.unitigs = Buf<u32>(c->pool, nc); r.kmers = Buf<u64>(c->pool, nc);
+    hipLaunchKernelGGL(k_cc_number, gu, b256, 0, c->stream, (const u32*)par.get(), (const u32*)scan.get(), nu, r.component.get(), r.first.get());
+    CBLX_HIP(hipMemsetAsync(r.unitigs.get(), 0, nc * 4, c->stream));
+    CBLX_HIP(hipMemsetAsync(r.kmers.get(), 0, nc * 8, c->stream));
+    hipLaunchKernelGGL(k_cc_sizes, gu, b256, 0, c->stream, (const u32*)r.component.get(), (const u32*)length.get(), nu, r.unitigs.get(), r.kmers.get());
+    CBLX_HIP(hipGetLastError());
+    r.h_kmers = d2h_vec<u64>(c, r.kmers.get(), nc);  // (the sync: par, scan, nxt and the lengths die here)
+    u64 total = 0;
+    for (u64 k = 0; k < nc; ++k) {
+        total += r.h_kmers[k];
+        if (r.h_kmers[k] > r.largest_kmers) { r.largest_kmers = r.h_kmers[k]; r.largest = (u32)k; }  // a tie goes to the lower number
+    }
+    if (total != r.n) throw Error(CBLX_EDEVICE, "the component sizes do not add up (internal error)");
+}
+// kmer_component (a device array of r.n elements); r.n != 0
+void component_kmers(cblx_ctx* c, const ComponentRun& r, u32* d_kmer_component) {
+    hipLaunchKernelGGL(k_cc_kmer, grid1(r.n, 256), dim3(256), 0, c->stream, (const u32*)r.unitig.get(), (const u32*)r.component.get(), r.n, d_kmer_component);
+    CBLX_HIP(hipGetLastError());
+}
+// cblx_components_filter: the table, the keep bytes, the k-mers of the dropped components in iteration order, and their words removed as one
+// WordSet::remove_batch. stats: components, removed_components, removed_kmers, kmers_left, largest_kmers (before the removal), rounds
+// (cblx_component_stats). `largest`: keep the largest component only (min_kmers is 0 then). Everything the table held is back in the pool before
+// remove_words takes its workspace: only the batch of selected k-mers, then its words, survive.
+void component_filter(cblx_ctx* c, u64 min_kmers, bool largest, u64 stats[6]) {
+    const bool wide = c->P.wide_kmer();
+    Buf<u64> s_lo, s_hi;
+    u64 ns = 0;
+    for (int k = 0; k < 6; ++k) stats[k] = 0;
+    {
+        ComponentRun r;
+        component_table(c, r);
+        if (r.n == 0) return;
+        const u64 n = r.n, nc = r.n_components;
+        stats[0] = nc; stats[3] = n; stats[4] = r.largest_kmers; stats[5] = r.rounds;
+        for (u64 k = 0; k < nc; ++k)
+            if (largest ? k != r.largest : r.h_kmers[k] < min_kmers) { ++stats[1]; stats[2] += r.h_kmers[k]; }
+        if (stats[2] == 0) return;
+        r.first.reset(); r.unitigs.reset();
+        Buf<u8> keep(c->pool, nc);
+        hipLaunchKernelGGL(k_cc_keep, grid1(nc, 256), dim3(256), 0, c->stream, (const u64*)r.kmers.get(), nc, min_kmers, largest ? r.largest : 0xFFFFFFFFu, keep.get());
+        Buf<u32> sel(c->pool, n), pos(c->pool, n);
+        hipLaunchKernelGGL(k_cc_select, grid1(n, 256), dim3(256), 0, c->stream, (const u32*)r.unitig.get(), (const u32*)r.component.get(), (const u8*)keep.get(), n, sel.get());
+        CBLX_HIP(hipGetLastError());
+        ns = exclusive_scan<u32>(c, sel.get(), n, pos.get());
+        if (ns != stats[2]) throw Error(CBLX_EDEVICE, "the selected k-mers and the component sizes do not add up (internal error)");
+        r = ComponentRun();
+        keep.reset();
+        s_lo = Buf<u64>(c->pool, ns + 2);
+        if (wide) s_hi = Buf<u64>(c->pool, ns + 2);
+        export_passes(c, 0, n, [&](u64 a, u64 m, const u64* k_lo, const u64* k_hi, const u64*) {
+            hipLaunchKernelGGL(k_cc_gather, grid1(m, 256), dim3(256), 0, c->stream, k_lo, k_hi, a, m, (const u32*)sel.get(), (const u32*)pos.get(), s_lo.get(), s_hi.get());
+            CBLX_HIP(hipGetLastError());
+        });  // sel / pos die behind its sync
+    }
+    dispatch(c->P, [&](auto cfg) {
+        typedef decltype(cfg) C;
+        typedef typename C::HiT HiT;
+        Buf<u64> w_lo(c->pool, ns + 2);
+        Buf<u8> w_hi(c->pool, (ns + 2) * std::max<size_t>(1, hi_elem_size(c->P)));
+        Buf<u32> bad(c->pool, 1);
+        CBLX_HIP(hipMemsetAsync(bad.get(), 0, 4, c->stream));
+        hipLaunchKernelGGL((k_kmers_to_words<C::WIDE, HiT>), grid1(ns, 256), dim3(256), 0, c->stream, (const u64*)s_lo.get(), (const u64*)s_hi.get(), ns, c->P, w_lo.get(),
+                           (HiT*)w_hi.get(), bad.get());
+        CBLX_HIP(hipGetLastError());
+        if (d2h<u32>(c, bad.get())) throw Error(CBLX_EDEVICE, "an exported k-mer is no IntKmer<K> (internal error)");
+        s_lo.reset(); s_hi.reset();
+        Buf<u32> gstart(c->pool, ns + 1);
+        CBLX_HIP(hipMemsetAsync(gstart.get(), 0, (ns + 1) * 4, c->stream));
+        remove_words<C>(c, w_lo.get(), (const HiT*)w_hi.get(), ns, gstart, false, nullptr);  // groups: the maximal runs of equal prefix, one per bucket
+    });
+    stats[3] = c->res.count;
 }
 
 }  // namespace

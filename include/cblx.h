@@ -38,7 +38,8 @@ extern "C" {
  * cblx_rank_kmers, cblx_rank_kmers_device, cblx_unitig_table, cblx_unitig_table_device, cblx_unitigs_text_device, cblx_unitigs_to_fd and cblx_unitigs_to_file;
  * cblx_biunitig_table, cblx_biunitig_table_device, cblx_biunitigs_text_device, cblx_biunitigs_to_fd and cblx_biunitigs_to_file;
  * cblx_gfa_links, cblx_gfa_links_device, cblx_gfa_text_device, cblx_gfa_to_fd and cblx_gfa_to_file;
- * cblx_unitig_ends, cblx_unitig_ends_device, cblx_tips_mark, cblx_tips_mark_device and cblx_clip_tips with cblx_clip_stats and CBLX_CLIP_ISOLATED. */
+ * cblx_unitig_ends, cblx_unitig_ends_device, cblx_tips_mark, cblx_tips_mark_device and cblx_clip_tips with cblx_clip_stats and CBLX_CLIP_ISOLATED;
+ * cblx_components, cblx_components_device and cblx_components_filter with cblx_component_stats and CBLX_COMPONENTS_LARGEST. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -618,6 +619,28 @@ int cblx_tips_mark_device(cblx_ctx* ctx, uint64_t max_kmers, uint8_t* d_kind, ui
 #define CBLX_CLIP_ISOLATED 1u
 typedef struct cblx_clip_stats { uint64_t rounds, tips, tip_kmers, isolated, isolated_kmers, kmers_left, fixpoint; } cblx_clip_stats;
 int cblx_clip_tips(cblx_ctx* ctx, uint64_t max_kmers, uint32_t flags, uint32_t max_rounds, cblx_clip_stats* stats);
+/* ---- connected components of the compacted graph. The form follows the index as in the link table: unitig numbers, lengths, the
+ * links and the refusals are those of cblx_gfa_links; the index must also have fewer than 2^31 unitigs (CBLX_ERANGE).
+ *   component        a class of the smallest equivalence on the unitigs in which u ~ link_to[l] for every link l that leaves slot 2 u or 2 u + 1: the weakly
+ *                    connected components of the de Bruijn graph on the stored k-mers (a unitig and its mirror are one node). Numbered 0 .. C - 1 by
+ *                    ascending smallest unitig.
+ *   component[u]     uint32, U entries; kmer_component[i] = component[unitig[i]], uint32 per k-mer in iteration order
+ *   first[c]         uint32: the smallest unitig of c (strictly ascending); unitigs[c] uint32; kmers[c] uint64 = the sum of length over its unitigs
+ *   counts           {k-mers, unitigs U, links L, components C, k-mers of the largest component (0 for an empty index), rounds of the labelling}
+ * Observers with the conventions of cblx_unitig_table: any array may be NULL, all NULL counts only, counts (unless NULL) is always set, a capacity below the
+ * need with its array given is CBLX_ERANGE with nothing written; capacities are checked before any output is touched. */
+int cblx_components(cblx_ctx* ctx, uint32_t* component, uint64_t cap_unitigs, uint32_t* kmer_component, uint64_t cap_kmers, uint32_t* first, uint32_t* unitigs,
+                    uint64_t* kmers, uint64_t cap_components, uint64_t counts[6]);
+int cblx_components_device(cblx_ctx* ctx, uint32_t* d_component, uint64_t cap_unitigs, uint32_t* d_kmer_component, uint64_t cap_kmers, uint32_t* d_first,
+                           uint32_t* d_unitigs, uint64_t* d_kmers, uint64_t cap_components, uint64_t counts[6]);
+/* Removes whole components: with min_kmers >= 1 every k-mer of every component with kmers[c] < min_kmers; with CBLX_COMPONENTS_LARGEST (min_kmers must be 0)
+ * every k-mer outside the component of most k-mers (a tie goes to the lower number). The selected k-mers are taken in iteration order and their words removed
+ * as ONE WordSet::remove_batch, as a round of cblx_clip_tips does. One call is the fixpoint: no other component changes. `stats` may be NULL; largest_kmers is
+ * the size before the removal. Unknown flag bits, min_kmers == 0 without the flag and min_kmers != 0 with it are CBLX_EINVAL with nothing removed; min_kmers ==
+ * 1 removes nothing. The form's refusals come before anything changes. An empty index: all-zero stats. */
+#define CBLX_COMPONENTS_LARGEST 1u
+typedef struct cblx_component_stats { uint64_t components, removed_components, removed_kmers, kmers_left, largest_kmers, rounds; } cblx_component_stats;
+int cblx_components_filter(cblx_ctx* ctx, uint64_t min_kmers, uint32_t flags, cblx_component_stats* stats);
 /* CBL::buckets_nodes (src/cbl.rs:386-390): per non-empty prefix ascending, TrieVec::count_nodes (src/trievec/mod.rs:37-42) — a Vec's length, a Trie's
  * nodes (src/trie.rs:90-102: the root and one node per distinct proper byte prefix of its suffixes). Pairs with cblx_bucket_sizes. */
 int cblx_bucket_nodes(cblx_ctx* ctx, uint64_t* nodes, uint64_t cap, uint64_t* n);

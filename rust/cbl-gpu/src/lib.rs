@@ -346,6 +346,24 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         stats
     }
 
+    /// `[k-mers, unitigs, links, components, k-mers of the largest component, rounds]` of the connected components of the compacted
+    /// de Bruijn graph (a unitig and its reverse complement are one node). Only the counts come back.
+    pub fn component_counts(&self) -> [u64; 6] {
+        let mut counts = [0u64; 6];
+        let (n32, n64) = (std::ptr::null_mut::<u32>(), std::ptr::null_mut::<u64>());
+        self.check(unsafe { sys::cblx_components(self.ctx, n32, 0, n32, 0, n32, n32, n64, 0, counts.as_mut_ptr()) });
+        counts
+    }
+
+    /// Removes whole components on the device as one batch: with `largest` every component but the one of most k-mers (`min_kmers`
+    /// must be 0), otherwise every component of fewer than `min_kmers` (at least 1) k-mers.
+    pub fn components_filter(&mut self, min_kmers: u64, largest: bool) -> sys::cblx_component_stats {
+        let mut stats = sys::cblx_component_stats::default();
+        let flags = if largest { sys::CBLX_COMPONENTS_LARGEST } else { 0 };
+        self.check(unsafe { sys::cblx_components_filter(self.ctx, min_kmers, flags, &mut stats) });
+        stats
+    }
+
     /// Adds a k-mer; returns `true` if it was absent (`src/cbl.rs:226-228`). One device round trip per call: a caller with
     /// many k-mers uses `insert_kmers`.
     #[inline]

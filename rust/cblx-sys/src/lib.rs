@@ -31,6 +31,7 @@ pub const CBLX_SETOP_XOR: u32 = 3;
 pub const CBLX_SETOP_MAX_OPERANDS: u32 = 64;
 pub const CBLX_COMMON_STATS: u32 = 5;
 pub const CBLX_CLIP_ISOLATED: u32 = 1;
+pub const CBLX_COMPONENTS_LARGEST: u32 = 1;
 
 #[repr(C)]
 pub struct cblx_ctx {
@@ -115,6 +116,17 @@ pub struct cblx_clip_stats {
     pub isolated_kmers: u64,
     pub kmers_left: u64,
     pub fixpoint: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct cblx_component_stats {
+    pub components: u64,
+    pub removed_components: u64,
+    pub removed_kmers: u64,
+    pub kmers_left: u64,
+    pub largest_kmers: u64,
+    pub rounds: u64,
 }
 
 #[repr(C)]
@@ -429,6 +441,9 @@ extern "C" {
     pub fn cblx_tips_mark(ctx: *mut cblx_ctx, max_kmers: u64, kind: *mut u8, cap_unitigs: u64, n_unitigs: *mut u64, counts: *mut u64) -> c_int;
     pub fn cblx_tips_mark_device(ctx: *mut cblx_ctx, max_kmers: u64, d_kind: *mut u8, cap_unitigs: u64, n_unitigs: *mut u64, counts: *mut u64) -> c_int;
     pub fn cblx_clip_tips(ctx: *mut cblx_ctx, max_kmers: u64, flags: u32, max_rounds: u32, stats: *mut cblx_clip_stats) -> c_int;
+    pub fn cblx_components(ctx: *mut cblx_ctx, component: *mut u32, cap_unitigs: u64, kmer_component: *mut u32, cap_kmers: u64, first: *mut u32, unitigs: *mut u32, kmers: *mut u64, cap_components: u64, counts: *mut u64) -> c_int;
+    pub fn cblx_components_device(ctx: *mut cblx_ctx, d_component: *mut u32, cap_unitigs: u64, d_kmer_component: *mut u32, cap_kmers: u64, d_first: *mut u32, d_unitigs: *mut u32, d_kmers: *mut u64, cap_components: u64, counts: *mut u64) -> c_int;
+    pub fn cblx_components_filter(ctx: *mut cblx_ctx, min_kmers: u64, flags: u32, stats: *mut cblx_component_stats) -> c_int;
     pub fn cblx_list_range(ctx: *mut cblx_ctx, first: u64, n: u64, buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_range_device(ctx: *mut cblx_ctx, first: u64, n: u64, d_buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_kmers: u64, n_kmers: *mut u64) -> c_int;
