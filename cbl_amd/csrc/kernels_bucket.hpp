@@ -841,7 +841,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
     __shared__ u16 s_idx[(PACKED || WP) ? 1 : CAP + 4];
     // sub-bucket counts, then exclusive offsets: 16-bit entries (values <= CAP), counted with 32-bit LDS atomics on the
     // containing dword (LDS is what bounds residency here)
-    __shared__ u32 s_off32[CAP / 2 + 2];
+    static_assert(ITEMS % 2 == 0, "the scan reads a thread's ITEMS 16-bit entries as ITEMS / 2 whole dwords");
+    struct alignas(2 * ITEMS) OffW { u32 v[ITEMS / 2]; };  // a thread's ITEMS entries of the offsets table: one wide LDS access
+    __shared__ alignas(16) u32 s_off32[CAP / 2 + 2];
     u16* s_off = reinterpret_cast<u16*>(s_off32);
     __shared__ u32 s_scan[NW + 1];
     __shared__ u32 s_wtot[NW + 1];
@@ -887,8 +889,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
     // the 2048-slot instantiation four spilled registers and cfg 2 0.3 ms).
     constexpr u32 crowd = (CAP <= (int)VEC_THRESHOLD && !MERGE) ? MSD_LIMIT_HASHED : (WS ? MSD_LIMIT_WIDE : MSD_LIMIT);
 
-    for (u32 i = tid; i < NB / 2 + 1; i += THREADS) s_off32[i] = 0;
-    if (tid == 0) s_max = 0;
+    // (the whole table, one wide store per thread: the scan's fixed layout reads entries behind NB, which stay zero)
+    reinterpret_cast<OffW*>(s_off32)[tid] = OffW{};
+    if (tid == 0) { s_off32[CAP / 2] = 0; s_max = 0; }
     __syncthreads();
     Sfx<WS> key[ITEMS];
     u32 sub[ITEMS], arr[ITEMS];
@@ -960,20 +963,24 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(msd_wav
         }
         return;
     }
-    {   // exclusive scan of the NB counts; each thread owns `per` consecutive entries
-        const u32 per = (NB + THREADS - 1) / THREADS;  // <= ITEMS
-        const u32 b0 = tid * per;
+    {   // exclusive scan of the counts, in k_bucket_sorted's form: thread t owns entries [t ITEMS, t ITEMS + ITEMS) whatever NB is, one wide read
+        // and one wide write, no branch per entry. Entries from NB on count zero and receive the total, c (entry NB is meant to hold it)
+        OffW* own = reinterpret_cast<OffW*>(s_off32) + tid;
+        const OffW in = *own;
         u32 sum = 0, cnt[ITEMS];
 #pragma unroll
         for (int k = 0; k < ITEMS; ++k) {  // counts stay in registers: the write-back below does not re-read them
-            cnt[k] = ((u32)k < per && b0 + k < NB) ? s_off[b0 + k] : 0u;
+            cnt[k] = (k & 1) ? in.v[k / 2] >> 16 : in.v[k / 2] & 0xFFFFu;
             sum += cnt[k];
         }
         u32 ex = block_exclusive_scan<THREADS, u32>(sum, s_scan, nullptr);
+        OffW out;
 #pragma unroll
-        for (int k = 0; k < ITEMS; ++k) {
-            if ((u32)k < per && b0 + k < NB) { s_off[b0 + k] = (u16)ex; ex += cnt[k]; }
+        for (int k = 0; k < ITEMS; k += 2) {
+            out.v[k / 2] = ex | ((ex + cnt[k]) << 16);  // (offsets <= c <= CAP <= 4096: sixteen bits hold them)
+            ex += cnt[k] + cnt[k + 1];
         }
+        *own = out;
     }
     __syncthreads();
     if (tid == 0) s_off[NB] = (u16)c;
@@ -1338,7 +1345,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
     constexpr int ITEMS = CAP / THREADS, NW = THREADS / 64;
     static_assert(!MERGE || 64 * ITEMS < 1024, "the merge epilogue counts a wave's selections in 10-bit fields");
     __shared__ E s_k[EL::slots(CAP)];       // slot p lives at EL::phys(p); + the all-ones slots behind the run
-    __shared__ u32 s_off32[CAP / 2 + 2];    // sub-bucket counts, then exclusive offsets: 16-bit entries, counted with 32-bit atomics on the containing dword
+    static_assert(ITEMS % 2 == 0, "the scan reads a thread's ITEMS 16-bit entries as ITEMS / 2 whole dwords");
+    struct alignas(2 * ITEMS) OffW { u32 v[ITEMS / 2]; };  // a thread's ITEMS entries of the offsets table: one wide LDS access
+    __shared__ alignas(16) u32 s_off32[CAP / 2 + 2];  // sub-bucket counts, then exclusive offsets: 16-bit entries, counted with 32-bit atomics on the containing dword
     u16* s_off = reinterpret_cast<u16*>(s_off32);
     __shared__ u32 s_scan[NW + 1];
     __shared__ u32 s_wtot[NW + 1];
@@ -1370,8 +1379,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
             else retry[atomicAdd(retry_n, 1u)] = dsc;
         }
     };
-    for (u32 i = tid; i < NB / 2 + 1; i += THREADS) s_off32[i] = 0;
-    if (tid == 0) s_max = 0;
+    // (the whole table, one wide store per thread: the scan's fixed layout reads entries behind NB, which stay zero)
+    reinterpret_cast<OffW*>(s_off32)[tid] = OffW{};
+    if (tid == 0) { s_off32[CAP / 2] = 0; s_max = 0; }
     __syncthreads();
     // `per` = slots a lane owns, uniform over the workgroup. Only the walk is instantiated per `per`: a run of 1 300 words on 256 threads issues
     // eight slots per lane in every other phase, and the masked slots cost nothing there (3.471 against 3.449 ms, DESIGN_HISTORY.md §3.13)
@@ -1429,20 +1439,24 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(sorted_
         if (crowded) s_max = crowd + 1u;  // benign race: every writer stores the same value
         __syncthreads();
         if (s_max > crowd) { give_up(); return; }  // repeats (or a cluster beyond the limit): claim table (build) / radix kernel (merge, sub-ranges)
-        {   // exclusive scan of the NB counts; each thread owns `per` consecutive entries
-            const u32 per_nb = (NB + THREADS - 1) / THREADS;  // <= ITEMS
-            const u32 b0 = tid * per_nb;
+        {   // exclusive scan of the counts. Thread t owns entries [t ITEMS, t ITEMS + ITEMS) whatever NB is: one wide read, one wide write and no
+            // branch per entry. Entries from NB on count zero and receive the total, c (entry NB is meant to hold it; nothing reads behind it)
+            OffW* own = reinterpret_cast<OffW*>(s_off32) + tid;
+            const OffW in = *own;
             u32 sum = 0, cnt[ITEMS];
 #pragma unroll
             for (int k = 0; k < ITEMS; ++k) {
-                cnt[k] = ((u32)k < per_nb && b0 + k < NB) ? s_off[b0 + k] : 0u;
+                cnt[k] = (k & 1) ? in.v[k / 2] >> 16 : in.v[k / 2] & 0xFFFFu;
                 sum += cnt[k];
             }
             u32 ex = block_exclusive_scan<THREADS, u32>(sum, s_scan, nullptr);
+            OffW out;
 #pragma unroll
-            for (int k = 0; k < ITEMS; ++k) {
-                if ((u32)k < per_nb && b0 + k < NB) { s_off[b0 + k] = (u16)ex; ex += cnt[k]; }
+            for (int k = 0; k < ITEMS; k += 2) {
+                out.v[k / 2] = ex | ((ex + cnt[k]) << 16);  // (offsets <= c <= CAP <= 4096: sixteen bits hold them)
+                ex += cnt[k] + cnt[k + 1];
             }
+            *own = out;
         }
         __syncthreads();
         if (tid == 0) s_off[NB] = (u16)c;
