@@ -15,6 +15,7 @@
 #include <cstdio>
 
 #include "fastx_parse.hpp"
+#include "query.hpp"
 #include "setops.hpp"
 
 namespace {

@@ -1888,7 +1888,7 @@ __global__ __launch_bounds__(BCL_THREADS) void k_big_claim(const BDesc* __restri
 // sort on the top suffix bits, out of the arena into a TWIN buffer at the same positions. A run then is a sequence of
 // sub-ranges sharing their leading suffix bits; k_bucket_msd sorts + deduplicates every sub-range in place in the twin; and
 // k_big_finish adds up a run's distinct counts (closing the gaps duplicates left). The finished runs are never copied back:
-// the arena becomes whichever of the two buffers holds more words and the other side's buckets move over (pipeline.hpp,
+// the arena becomes whichever of the two buffers holds more words and the other side's buckets move over (bucket_stage.hpp,
 // finish_twin) — on the receiving side of a many-GPU build, where every run is long, nothing is copied at all. The arena run
 // stays untouched, so a run that must stay a Vec (<= 1024 distinct words and no resident Trie: a few words repeated
 // thousands of times) or whose sort gave up still finds its original there (k_bucket_huge).

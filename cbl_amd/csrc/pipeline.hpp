@@ -1,7 +1,9 @@
-// pipeline.hpp — one batch of words into the resident index: KRN-1 front end (chunk plan + encode), KRN-2 stable partition,
-// KRN-4 directory, KRN-3 bucket kernels and the incremental (non-empty index) path. Set algebra and removal build on it in setops.hpp. Included by
-// cblx.cpp only.
+// pipeline.hpp — one batch of words into the resident index: KRN-2 stable partition and KRN-4 directory (partition_and_directory), the batch through them and
+// the bucket stage into an empty or a non-empty index (pipeline, pipeline_group), the KRN-1 front end (chunk plan + encode), the first partition pass of a piece
+// of reads, insert_device, and the sorted batches of the multi-GPU build. The KRN-3 driver is bucket_stage.hpp, the query side query.hpp; set algebra and
+// removal build on this file in setops.hpp. Included by cblx.cpp only.
 #pragma once
+#include "bucket_stage.hpp"
 #include "ctx.hpp"
 #include "kernels_kmer.hpp"
 
@@ -390,408 +392,6 @@ template <typename C> void partition_and_directory(cblx_ctx* c, Records& rec, u6
         hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, c->stream, nr.start.get() + nr.nb, N);
         CBLX_HIP(hipGetLastError());
     }
-}
-
-// general kernel for runs of any length (and the fallback of the big path): one workgroup per run, LSD radix in global scratch
-template <typename C> void huge_stage(cblx_ctx* c, const BDesc* d_list, const u32* d_list_n, u32 nh, u64* a_lo, typename C::HiT* a_hi, Resident& nr, const MergeArgs& ma) {
-    typedef typename C::HiT HiT;
-    if (nh == 0) return;
-    StageTimer t(c, ST_BHUGE);
-    std::vector<BDesc> hl = d2h_vec<BDesc>(c, d_list, nh);
-    std::vector<u64> so(nh);
-    u64 tot = 0;
-    for (u32 i = 0; i < nh; ++i) { so[i] = tot; tot += hl[i].c & ~BDESC_TRIE; }
-    Buf<u64> d_so(c->pool, nh), s_alo(c->pool, tot), s_blo(c->pool, tot), s_ahi(c->pool, C::WS ? tot : 1), s_bhi(c->pool, C::WS ? tot : 1);
-    Buf<u32> s_aidx(c->pool, tot), s_bidx(c->pool, tot);
-    h2d(c, d_so.get(), so.data(), nh);
-    hipLaunchKernelGGL((k_bucket_huge<C::WS, HiT>), dim3(nh), dim3(256), 0, c->stream, d_list, d_list_n, d_so.get(), a_lo, a_hi, c->P.SB, s_alo.get(), s_ahi.get(),
-                       s_aidx.get(), s_blo.get(), s_bhi.get(), s_bidx.get(), nr.cnt.get(), nr.kind.get(), ma);
-    CBLX_HIP(hipGetLastError());
-    CBLX_HIP(hipStreamSynchronize(c->stream));
-}
-// lanes per bucket of the per-bucket copy kernels, from the average run length (words / buckets)
-template <typename F> void with_lpb(u64 words, u64 buckets, F&& f) {
-    const u64 avg = buckets ? words / buckets : 0;
-    if (avg >= 48) f(std::integral_constant<int, 64>());
-    else if (avg >= 12) f(std::integral_constant<int, 16>());
-    else f(std::integral_constant<int, 4>());
-}
-inline dim3 lpb_grid(u64 buckets, int lpb) { return dim3((unsigned)std::max<u64>(1, ceil_div(buckets * (u64)lpb, 256))); }
-
-// The length classes of the one-workgroup bucket kernels (k_bucket_msd, k_bucket_sorted, k_bucket_claim): a run of up to `cap` words takes a workgroup of
-// `threads` — cap / 8 per lane, the two shortest on one wave of two / four slots per lane (kernels_bucket.hpp: CLS_M32).
-struct LenClass { int cls, threads, cap; };
-constexpr int N_LEN_CLASSES = 6;
-constexpr LenClass LEN_CLASSES[N_LEN_CLASSES] = {{CLS_M16, 64, 128}, {CLS_M32, 64, 256}, {CLS_M64, 64, 512}, {CLS_M128, 128, 1024}, {CLS_M256, 256, 2048}, {CLS_M512, 512, 4096}};
-constexpr int len_class_of(u32 cap) {  // entry of that capacity
-    for (int k = 0; k < N_LEN_CLASSES; ++k) if ((u32)LEN_CLASSES[k].cap == cap) return k;
-    return -1;
-}
-// Entry K as an argument: in f(len_class<K>) the entry LEN_CLASSES[decltype(k)::value] is a constant expression. each_len_class visits all in order.
-template <int K> constexpr std::integral_constant<int, K> len_class{};
-template <int K = 0, typename F> void each_len_class(const F& f) {
-    if constexpr (K < N_LEN_CLASSES) { f(len_class<K>); each_len_class<K + 1>(f); }
-}
-// nr.count = the words of all buckets
-inline void count_words(cblx_ctx* c, Resident& nr) {
-    Buf<u64> total(c->pool, 1);
-    CBLX_HIP(hipMemsetAsync(total.get(), 0, 8, c->stream));
-    hipLaunchKernelGGL(k_sum_u32, dim3((unsigned)std::min<u64>(2048, std::max<u64>(1, ceil_div(nr.nb, 256)))), dim3(256), 0, c->stream, nr.cnt.get(), nr.nb, total.get());
-    nr.count = d2h<u64>(c, total.get());
-}
-
-__global__ void k_sum_bdesc_len(const BDesc* __restrict__ list, u32 n, u64* __restrict__ out) {
-    u64 s = 0;
-    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) s += list[i].c & ~BDESC_TRIE;
-    s = wave_reduce_sum(s);
-    if ((threadIdx.x & 63) == 0 && s) atomicAdd((unsigned long long*)out, (unsigned long long)s);
-}
-// (profiling) sum of the final counts of the buckets of a list
-__global__ void k_sum_list_counts(const BDesc* __restrict__ list, u32 n, const u32* __restrict__ cnt, u64* __restrict__ out) {
-    u64 s = 0;
-    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) s += cnt[list[i].r];
-    s = wave_reduce_sum(s);
-    if ((threadIdx.x & 63) == 0 && s) atomicAdd((unsigned long long*)out, (unsigned long long)s);
-}
-// runs of 4097 .. BIG_MAX words (kernels_bucket.hpp: k_big_*): one more partition pass on the top suffix bits with the runs as
-// segments, out of the arena into a twin buffer at the same positions; sub-ranges sorted + deduplicated in place there by
-// k_bucket_msd; what cannot be finished that way takes the general kernel on the (untouched) arena run. The finished runs stay
-// in the twin: finish_twin decides which buffer becomes the arena.
-struct Twin {
-    Buf<u64> lo, hi;   // same positions as the arena; hi only for suffixes wider than 64 bits
-    Buf<u8> in_twin;   // per bucket rank: 1 = its final words are in the twin
-    u64 arrivals = 0;  // words of the runs that went through the twin
-    u64 runs = 0;      // ... and their number
-    bool used() const { return lo.get() != nullptr; }
-};
-__global__ void k_set_u32(u32* p, u32 v) { *p = v; }
-template <typename C> void big_stage(cblx_ctx* c, const BDesc* d_list, const u32* d_list_n, u32 nbig, Resident& nr, const MergeArgs& ma, Twin& tw) {
-    typedef typename C::HiT HiT;
-    constexpr bool WS = C::WS;
-    typedef typename std::conditional<WS, u64, NoHi>::type AH;  // hi part of an arena element as the partition kernels see it
-    if (nbig == 0) return;
-    const Consts& P = c->P;
-    u64* a_lo = nr.a_lo.get();
-    HiT* a_hi = WS ? (HiT*)nr.a_hi.get() : (HiT*)nullptr;
-    if (!tw.used()) {
-        const u64 T = d2h<u64>(c, nr.start.get() + nr.nb);  // every run position lies below the total arrival count
-        try {
-            tw.lo = Buf<u64>(c->pool, T + 2);
-            if (WS) tw.hi = Buf<u64>(c->pool, T + 2);
-            tw.in_twin = Buf<u8>(c->pool, nr.nb + 1);
-        } catch (const Error& e) {
-            // no room for a second arena (an index that fills most of the HBM): the long runs take the general kernel, whose
-            // scratch is only as large as the runs themselves
-            if (e.code != CBLX_ENOMEM) throw;
-            tw = Twin();
-            huge_stage<C>(c, d_list, d_list_n, nbig, a_lo, a_hi, nr, ma);
-            return;
-        }
-        CBLX_HIP(hipMemsetAsync(tw.in_twin.get(), 0, nr.nb + 1, c->stream));
-    }
-    Buf<BDesc> fb(c->pool, nbig);
-    Buf<u32> fb_n(c->pool, 1);
-    {
-        StageTimer t(c, ST_BBIG);
-        Buf<u32> ntile(c->pool, nbig), nv(c->pool, nbig), tile_first(c->pool, nbig + 1);
-        Buf<u64> vb(c->pool, nbig + 1), run_start(c->pool, nbig);
-        hipLaunchKernelGGL(k_big_plan, grid1(nbig, 256), dim3(256), 0, c->stream, d_list, nbig, P.SB, ntile.get(), nv.get());
-        const u64 nt64 = exclusive_scan<u32>(c, ntile.get(), nbig, tile_first.get());
-        const u64 vtot = exclusive_scan<u64>(c, nv.get(), nbig, vb.get());
-        if (nt64 >= 0xFFFFFF00ull / 256) throw Error(CBLX_ERANGE, "too many tiles in the long runs of one batch");
-        const u32 nt = (u32)nt64;
-        hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, c->stream, tile_first.get() + nbig, nt);
-        Buf<u64> t_start(c->pool, nt);
-        Buf<u32> t_count(c->pool, nt), t_seg(c->pool, nt), counts(c->pool, (size_t)256 * nt), colpre(c->pool, (size_t)256 * nt), scratch, coltot(c->pool, 256),
-            adj(c->pool, (size_t)256 * nbig), rel(c->pool, (size_t)256 * nbig);
-        hipLaunchKernelGGL(k_big_tile_table, grid1(std::max<u64>(nt, nbig), 256), dim3(256), 0, c->stream, d_list, nbig, tile_first.get(), t_start.get(), t_count.get(), t_seg.get(),
-                           run_start.get());
-        TileView tv{nullptr, t_count.get(), nullptr, nullptr, nt, 0};
-        tv.start64 = t_start.get();
-        tv.seg32 = t_seg.get();
-        const u32 DB = big_digit_bits(P.SB);
-        const DigitBits dfn{P.SB - DB, DB};
-        const AH* in_hi = (const AH*)a_hi;
-        AH* out_hi = (AH*)tw.hi.get();
-        hipLaunchKernelGGL((k_radix_hist<AH, DigitBits>), dim3(xcd_grid(nt)), dim3(RDX_THREADS), 0, c->stream, (const u64*)a_lo, in_hi, tv, dfn, counts.get());
-        colscan(c, counts.get(), nullptr, nt, colpre.get(), coltot.get(), scratch);
-        hipLaunchKernelGGL(k_seg_adjust, dim3(nbig), dim3(256), 0, c->stream, colpre.get(), coltot.get(), (const u32*)tile_first.get(), (const u32*)nullptr, (const u32*)nullptr, nt, nbig,
-                           adj.get(), rel.get());
-        hipLaunchKernelGGL((k_radix_scatter<AH, AH, DigitBits>), dim3(xcd_grid(nt)), dim3(RDX_THREADS), 0, c->stream, (const u64*)a_lo, in_hi, tv, dfn, (const u32*)colpre.get(),
-                           (const u32*)adj.get(), tw.lo.get(), out_hi, DigitBits{0, 0}, (u8*)nullptr, (u32*)nullptr, 0u, 0u, 0u, (u32*)nullptr, 0u,
-                           OwnWindow{0, 0, nullptr, nullptr, nullptr}, (const u64*)run_start.get());
-        Buf<BDesc> vlist(c->pool, vtot), cls_lists(c->pool, 2 * vtot);
-        Buf<u32> v_count(c->pool, vtot + 1), cls_n(c->pool, 2);
-        Buf<u8> v_kind(c->pool, vtot + 1);
-        Buf<BDesc> retry(c->pool, vtot);  // sub-ranges the sort gives up on (crowded sub-bucket): their runs fall back as a whole
-        Buf<u32> retry_n(c->pool, 1);
-        CBLX_HIP(hipMemsetAsync(retry_n.get(), 0, 4, c->stream));
-        CBLX_HIP(hipMemsetAsync(cls_n.get(), 0, 8, c->stream));
-        CBLX_HIP(hipMemsetAsync(fb_n.get(), 0, 4, c->stream));
-        hipLaunchKernelGGL(k_big_vlist, dim3((nbig + BIG_VLIST_RUNS - 1) / BIG_VLIST_RUNS), dim3(256), 0, c->stream, d_list, nbig, vb.get(), rel.get(), P.SB, vlist.get(), v_count.get(), cls_lists.get(), cls_n.get(), vtot);
-        const std::vector<u32> cn = d2h_vec<u32>(c, cls_n.get(), 2);
-        HiT* th = WS ? (HiT*)tw.hi.get() : (HiT*)nullptr;
-        // sub-ranges of up to 1024 words take the 128-thread workgroup — its `self |= other` instantiation without merge
-        // arguments: that one keeps the top-bit sub-bucket limit (the build's 1024-word class assumes hashed sub-buckets)
-        auto sort = [&](auto pk) {
-            constexpr bool PK = decltype(pk)::value;
-            auto sub = [&](auto kc, u32 i) {  // list i of the sub-ranges, by the kernel of length class kc
-                constexpr int T = LEN_CLASSES[decltype(kc)::value].threads, CAPV = LEN_CLASSES[decltype(kc)::value].cap;
-                if (!cn[i]) return;
-                if constexpr (PK || WS)  // sub-ranges are always asked for the sorted list: the walk kernel (round 6)
-                    hipLaunchKernelGGL((k_bucket_sorted<T, CAPV, WS, HiT>), dim3(cn[i]), dim3(T), 0, c->stream, cls_lists.get() + (size_t)i * vtot, cls_n.get() + i, tw.lo.get(), th, P.SB,
-                                       v_count.get(), v_kind.get(), retry.get(), retry_n.get(), (u8*)nullptr, (u32*)nullptr);
-                else
-                    hipLaunchKernelGGL((k_bucket_msd<T, CAPV, PK, WS, HiT, (CAPV <= 1024)>), dim3(cn[i]), dim3(T), 0, c->stream, cls_lists.get() + (size_t)i * vtot, cls_n.get() + i, tw.lo.get(), th,
-                                       P.SB, v_count.get(), v_kind.get(), retry.get(), retry_n.get(), MergeArgs{});
-            };
-            sub(len_class<len_class_of(BIG_SUB)>, 0);
-            sub(len_class<len_class_of(BIG_VCAP)>, 1);
-        };
-        if constexpr (!WS) { if (P.SB + PK_BITS <= 64) sort(std::true_type()); else sort(std::false_type()); }
-        else sort(std::false_type());
-        hipLaunchKernelGGL((k_big_finish<WS>), dim3(nbig), dim3(256), 0, c->stream, d_list, d_list_n, vb.get(), vlist.get(), v_count.get(), P.SB, tw.lo.get(), tw.hi.get(), nr.cnt.get(),
-                           nr.kind.get(), tw.in_twin.get(), fb.get(), fb_n.get());
-        CBLX_HIP(hipGetLastError());
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // the pass tables die here
-    }
-    {   // arrivals of the runs that went through the twin = their lengths (the fallback runs are few)
-        Buf<u64> tot(c->pool, 1);
-        CBLX_HIP(hipMemsetAsync(tot.get(), 0, 8, c->stream));
-        hipLaunchKernelGGL(k_sum_bdesc_len, dim3((unsigned)std::min<u64>(1024, ceil_div(nbig, 256))), dim3(256), 0, c->stream, d_list, nbig, tot.get());
-        tw.arrivals += d2h<u64>(c, tot.get());
-    }
-    const u32 nfb = d2h<u32>(c, fb_n.get());
-    tw.runs += nbig - nfb;
-    huge_stage<C>(c, fb.get(), fb_n.get(), nfb, a_lo, a_hi, nr, ma);
-}
-// After every bucket kernel of the stage: the finished long runs sit in the twin, everything else in the arena. The buffer that
-// holds more words becomes the arena; the other side's buckets are copied over (count[r] words at the same positions).
-// `force`: -1 = the rule above; 0 / 1 = the result must end up in the arena / in the twin (a group of the grouped receiver, whose
-// two buffers are a slot of the final arena and a scratch area: pipeline_group)
-template <typename C> void finish_twin(cblx_ctx* c, Resident& nr, Twin& tw, int force = -1) {
-    constexpr bool WS = C::WS;
-    if (!tw.used()) return;
-    if (force == 0 && tw.runs == 0) { tw = Twin(); return; }  // a preset twin nothing went through
-    StageTimer t(c, ST_BBIG);
-    const u64 T = d2h<u64>(c, nr.start.get() + nr.nb);
-    const bool to_twin = force < 0 ? tw.arrivals * 2 > T : force == 1;
-    const u64* src_lo = to_twin ? nr.a_lo.get() : tw.lo.get();
-    const u64* src_hi = to_twin ? nr.a_hi.get() : tw.hi.get();
-    u64* dst_lo = to_twin ? tw.lo.get() : nr.a_lo.get();
-    u64* dst_hi = to_twin ? tw.hi.get() : nr.a_hi.get();
-    // lanes per bucket: the long runs take a wave each; the others follow the average bucket length
-    auto copy = [&](auto lpb) {
-        constexpr int LPB = decltype(lpb)::value;
-        hipLaunchKernelGGL((k_copy_buckets<WS, LPB>), lpb_grid(nr.nb, LPB), dim3(256), 0, c->stream, nr.nb, nr.start.get(), nr.cnt.get(), tw.in_twin.get(), to_twin ? 0u : 1u, src_lo, src_hi,
-                           dst_lo, dst_hi);
-    };
-    if (to_twin) with_lpb(T - tw.arrivals, nr.nb - std::min<u64>(tw.runs, nr.nb), copy); else copy(std::integral_constant<int, 64>());
-    CBLX_HIP(hipGetLastError());
-    CBLX_HIP(hipStreamSynchronize(c->stream));
-    if (to_twin) {
-        nr.a_lo = std::move(tw.lo);
-        if (WS) nr.a_hi = std::move(tw.hi);
-    }
-    tw = Twin();
-}
-
-// KRN-3 over the runs of `nr` (run of a prefix = [its resident suffixes as stored][the new words in stream order]) in the
-// arena a_lo / a_hi: per-bucket dedup / sort by size class; fills nr.cnt, nr.kind, nr.count. `old` = the resident index
-// the runs were built against (tells which buckets are untouched and which are Tries already).
-// `preset` (optional): the twin buffer of the long-run path, supplied by the caller (lo / hi set, same positions as the arena) instead of
-// allocated here; `force`: see finish_twin
-template <typename C> void bucket_stage(cblx_ctx* c, Resident& nr, const DirView& old, Twin* preset = nullptr, int force = -1) {
-    typedef typename C::HiT HiT;
-    const Consts& P = c->P;
-    u64* a_lo = nr.a_lo.get();  // the arena (the long runs may move it to a twin buffer at the end: finish_twin)
-    HiT* a_hi = C::WS ? (HiT*)nr.a_hi.get() : (HiT*)nullptr;
-    Twin tw;
-    if (preset) {
-        tw = std::move(*preset);
-        tw.in_twin = Buf<u8>(c->pool, nr.nb + 1);
-        CBLX_HIP(hipMemsetAsync(tw.in_twin.get(), 0, nr.nb + 1, c->stream));
-    }
-    {
-    const u64 nb = nr.nb;
-    Buf<BDesc> lists(c->pool, (size_t)CLS_N * std::max<u64>(nb, 1));
-    Buf<u32> list_n(c->pool, CLS_N);
-    Buf<u32> res_count(c->pool, nb + 1);
-    Buf<u8> res_kind(c->pool, nb + 1);
-    CBLX_HIP(hipMemsetAsync(list_n.get(), 0, CLS_N * 4, c->stream));
-    // (suffixes wider than 64 bits: an element takes 18 bytes of LDS, the 4096-word workgroup 82 KB = one per CU, and the Trie
-    // classes cost 60 ps per word on 2000-word buckets against 10 on short ones. Sending runs over 2048 / 1024 words down the
-    // long-run path instead was measured and is slower: 134 -> 143 / 165 ms per 1.2 G words at K = 59, the cost is the ranking
-    // inside clusters of up to K mates, whatever the workgroup — so k_classify's `lds_max` is 4096 for every suffix width)
-    hipLaunchKernelGGL(k_classify, grid1(nb, CLASSIFY_THREADS), dim3(CLASSIFY_THREADS), 0, c->stream, nb, 4096u, nr.prefix.get(), nr.start.get(), old,
-                       res_count.get(), res_kind.get(), nr.cnt.get(), nr.kind.get(), lists.get(), list_n.get());
-    std::vector<u32> ln = d2h_vec<u32>(c, list_n.get(), CLS_N);
-    if (ln[CLS_S32] | ln[CLS_S16]) {
-        StageTimer t(c, ST_BSMALL);
-        if (ln[CLS_S16])
-            hipLaunchKernelGGL((k_bucket_small<16, C::WS, HiT>), grid1((u64)ln[CLS_S16] * 16, 256), dim3(256), 0, c->stream,
-                               lists.get() + (size_t)CLS_S16 * nb, list_n.get() + CLS_S16, a_lo, a_hi, P.SB, nr.cnt.get(), nr.kind.get());
-        if (ln[CLS_S32])
-            hipLaunchKernelGGL((k_bucket_small<32, C::WS, HiT>), grid1((u64)ln[CLS_S32] * 32, 256), dim3(256), 0, c->stream,
-                               lists.get() + (size_t)CLS_S32 * nb, list_n.get() + CLS_S32, a_lo, a_hi, P.SB, nr.cnt.get(), nr.kind.get());
-    }
-    // whether the batch looks like one full of repeats: some shorter run gave up in the counting sort (unknown = yes when
-    // there are no shorter runs at all). Long runs of distinct words — the receiving side of a many-GPU build — then skip
-    // the pre-pass below altogether.
-    bool saw_repeats = true;
-    {
-        StageTimer t(c, ST_BMED);
-        // fast path (counting sort on the top suffix bits + in-sub-bucket ranking); a run with a crowded sub-bucket marks its
-        // list entry and takes the claim-table kernel of its length class (runs full of repeats); what needs the sorted layout
-        // after that goes to the LDS radix sort
-        constexpr int NM = N_LEN_CLASSES;
-        u64 roff[NM + 1] = {0};
-        for (int k = 0; k < NM; ++k) roff[k + 1] = roff[k] + ln[LEN_CLASSES[k].cls];
-        Buf<u8> bail(c->pool, roff[NM] + 8);
-        Buf<u32> bail_any(c->pool, NM + 1);  // one word per class, then the radix kernel's list counter
-        Buf<BDesc> retry2(c->pool, std::max<u64>(roff[NM], 1));
-        CBLX_HIP(hipMemsetAsync(bail.get(), 0, roff[NM] + 8, c->stream));
-        CBLX_HIP(hipMemsetAsync(bail_any.get(), 0, (NM + 1) * 4, c->stream));
-        u32* r2n = bail_any.get() + NM;
-        // The classes up to 1024 words (hashed sub-buckets) never give up without repeats in the batch: once one of them did
-        // — the shortest is asked first — the classes after it start with the claim table (`repeat_mode`) instead of a
-        // counting sort that is going to give up.
-        bool repeat_mode = false;
-        std::vector<u32> any(NM, 0u);
-        bool used_msd[NM] = {false};
-        auto any_of = [&](const std::vector<u32>& v) { u32 a = 0; for (u32 x : v) a |= x; return a != 0; };
-        // suffixes too wide for the counting-sort kernel's 16-byte elements (SUFFIX_BITS > 116: K >= 57 with a handful of prefix
-        // bits): every class takes the LDS radix kernel
-        const bool radix_only = !msd_takes<C::WS>(P.SB);
-        if (radix_only) {
-            for (const LenClass& lc : LEN_CLASSES)
-                if (ln[lc.cls])
-                    hipLaunchKernelGGL((k_bucket_medium<512, C::WS, HiT>), dim3(ln[lc.cls]), dim3(512), 0, c->stream, lists.get() + (size_t)lc.cls * nb, list_n.get() + lc.cls, a_lo, a_hi,
-                                       P.SB, nr.cnt.get(), nr.kind.get(), MergeArgs{});
-            CBLX_HIP(hipGetLastError());
-        }
-        auto stage = [&](auto packed_tag) {
-            constexpr bool PK = decltype(packed_tag)::value;
-            if (radix_only) return;
-            auto go = [&](auto kc) {
-                constexpr int k = decltype(kc)::value, T = LEN_CLASSES[k].threads, CAPV = LEN_CLASSES[k].cap, cls = LEN_CLASSES[k].cls;
-                if (!ln[cls]) return;
-                // (the claim table as FIRST kernel of every run <= 1024 words, measured: cfg 2, no repeats, +0.25 ms; the 30x-coverage workload -2.4 ms)
-                if (repeat_mode) {
-                    hipLaunchKernelGGL((k_bucket_claim<T, CAPV, C::WS, HiT>), dim3(ln[cls]), dim3(T), 0, c->stream, lists.get() + (size_t)cls * nb, list_n.get() + cls, a_lo, a_hi, P.SB,
-                                       nr.cnt.get(), nr.kind.get(), retry2.get(), r2n, (const u8*)nullptr);
-                    return;
-                }
-                used_msd[k] = true;
-                if constexpr ((PK || C::WS) && CAPV > (int)VEC_THRESHOLD)  // runs of more than 1024 words end up sorted (or give up: repeats): the walk kernel (round 6)
-                    hipLaunchKernelGGL((k_bucket_sorted<T, CAPV, C::WS, HiT>), dim3(ln[cls]), dim3(T), 0, c->stream, lists.get() + (size_t)cls * nb, list_n.get() + cls, a_lo, a_hi, P.SB,
-                                       nr.cnt.get(), nr.kind.get(), (BDesc*)nullptr, (u32*)nullptr, bail.get() + roff[k], bail_any.get() + k);
-                else
-                    hipLaunchKernelGGL((k_bucket_msd<T, CAPV, PK, C::WS, HiT>), dim3(ln[cls]), dim3(T), 0, c->stream, lists.get() + (size_t)cls * nb, list_n.get() + cls, a_lo, a_hi, P.SB,
-                                       nr.cnt.get(), nr.kind.get(), (BDesc*)nullptr, (u32*)nullptr, MergeArgs{}, bail.get() + roff[k], bail_any.get() + k);
-            };
-            go(len_class<0>);
-            if (used_msd[0] && (ln[CLS_M32] | ln[CLS_M64] | ln[CLS_M128] | ln[CLS_M256] | ln[CLS_M512]))  // the shortest class is the cheapest witness
-                repeat_mode = d2h<u32>(c, bail_any.get() + 0) != 0;
-            go(len_class<1>);
-            go(len_class<2>);
-            go(len_class<3>);
-            if (!repeat_mode && (ln[CLS_M256] | ln[CLS_M512]) && (used_msd[1] | used_msd[2] | used_msd[3]))
-                repeat_mode = any_of(d2h_vec<u32>(c, bail_any.get(), 4));
-            go(len_class<4>);
-            go(len_class<5>);
-            if (!roff[NM]) return;
-            any = d2h_vec<u32>(c, bail_any.get(), NM);
-            each_len_class([&](auto kc) {
-                constexpr int k = decltype(kc)::value, T = LEN_CLASSES[k].threads, CAPV = LEN_CLASSES[k].cap, cls = LEN_CLASSES[k].cls;
-                if (!used_msd[k] || !any[k]) return;
-                hipLaunchKernelGGL((k_bucket_claim<T, CAPV, C::WS, HiT>), dim3((ln[cls] + 63) / 64), dim3(T), 0, c->stream, lists.get() + (size_t)cls * nb, list_n.get() + cls, a_lo, a_hi,
-                                   P.SB, nr.cnt.get(), nr.kind.get(), retry2.get(), r2n, (const u8*)(bail.get() + roff[k]));
-            });
-            if (repeat_mode || any_of(any)) {
-                // what the claim tables left for the sorted layout: distinct words now, at most 4096 per run
-                const u32 n2 = d2h<u32>(c, r2n);
-                if (n2) {
-                    Buf<BDesc> retry3(c->pool, n2);
-                    Buf<u32> r3n(c->pool, 1);
-                    CBLX_HIP(hipMemsetAsync(r3n.get(), 0, 4, c->stream));
-                    if constexpr (PK || C::WS)
-                        hipLaunchKernelGGL((k_bucket_sorted<512, 4096, C::WS, HiT>), dim3(n2), dim3(512), 0, c->stream, retry2.get(), r2n, a_lo, a_hi, P.SB, nr.cnt.get(), nr.kind.get(), retry3.get(),
-                                           r3n.get(), (u8*)nullptr, (u32*)nullptr);
-                    else
-                        hipLaunchKernelGGL((k_bucket_msd<512, 4096, PK, C::WS, HiT>), dim3(n2), dim3(512), 0, c->stream, retry2.get(), r2n, a_lo, a_hi, P.SB, nr.cnt.get(), nr.kind.get(),
-                                           retry3.get(), r3n.get(), MergeArgs{});
-                    const u32 n3 = d2h<u32>(c, r3n.get());
-                    if (n3)
-                        hipLaunchKernelGGL((k_bucket_medium<512, C::WS, HiT>), dim3(n3), dim3(512), 0, c->stream, retry3.get(), r3n.get(), a_lo, a_hi, P.SB, nr.cnt.get(), nr.kind.get(), MergeArgs{});
-                    CBLX_HIP(hipStreamSynchronize(c->stream));  // retry3 dies here
-                }
-            }
-        };
-        if constexpr (!C::WS) {
-            if (P.SB + PK_BITS <= 64) stage(std::true_type()); else stage(std::false_type());
-        } else {
-            stage(std::false_type());
-        }
-        saw_repeats = roff[NM] ? repeat_mode : true;  // no shorter runs at all: unknown = yes
-        if (roff[NM] && !repeat_mode && (ln[CLS_BIG] | ln[CLS_HUGE]) && any_of(any)) {
-            // no shorter hashed runs to tell: a sizeable share of the runs that went through the counting sort must have given up
-            // (a few do without a single repeat — necklace clusters)
-            Buf<u64> nbail(c->pool, 1);
-            CBLX_HIP(hipMemsetAsync(nbail.get(), 0, 8, c->stream));
-            hipLaunchKernelGGL(k_sum_u8, dim3((unsigned)std::min<u64>(1024, ceil_div(roff[NM], 256))), dim3(256), 0, c->stream, bail.get(), roff[NM], nbail.get());
-            saw_repeats = d2h<u64>(c, nbail.get()) * 8 >= roff[NM];
-        }
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // retry buffers die here
-    }
-    bool long_done = false;
-    if constexpr (!C::WS) {
-        if (P.SB < 64 && ln[CLS_BIG] + ln[CLS_HUGE] > 0 && saw_repeats) {
-            // runs too long for one workgroup's sort: first the pre-pass that shrinks the ones full of repeats to their first
-            // occurrences (k_big_claim); what it passes on takes the paths below, what it shrank to more than 1024 distinct
-            // words is sorted by one workgroup
-            const u32 nbig = ln[CLS_BIG], nhuge = ln[CLS_HUGE];
-            Buf<BDesc> next_big(c->pool, std::max<u32>(nbig, 1)), next_huge(c->pool, std::max<u32>(nhuge, 1)), srt(c->pool, (size_t)nbig + nhuge), retry(c->pool, (size_t)nbig + nhuge);
-            Buf<u32> cnts(c->pool, 4);  // next_big, next_huge, sorted, retry
-            std::vector<u32> cn;
-            {
-            StageTimer t(c, ST_BBIG);
-            CBLX_HIP(hipMemsetAsync(cnts.get(), 0, 16, c->stream));
-            if (nbig)
-                hipLaunchKernelGGL((k_big_claim<HiT>), dim3(nbig), dim3(BCL_THREADS), 0, c->stream, lists.get() + (size_t)CLS_BIG * nb, list_n.get() + CLS_BIG, a_lo, P.SB, nr.cnt.get(),
-                                   nr.kind.get(), next_big.get(), cnts.get() + 0, srt.get(), cnts.get() + 2);
-            if (nhuge)
-                hipLaunchKernelGGL((k_big_claim<HiT>), dim3(nhuge), dim3(BCL_THREADS), 0, c->stream, lists.get() + (size_t)CLS_HUGE * nb, list_n.get() + CLS_HUGE, a_lo, P.SB, nr.cnt.get(),
-                                   nr.kind.get(), next_huge.get(), cnts.get() + 1, srt.get(), cnts.get() + 2);
-            cn = d2h_vec<u32>(c, cnts.get(), 3);
-            if (cn[2]) {
-                if (P.SB + PK_BITS <= 64)
-                    hipLaunchKernelGGL((k_bucket_sorted<256, 2048, false, HiT>), dim3(cn[2]), dim3(256), 0, c->stream, srt.get(), cnts.get() + 2, a_lo, a_hi, P.SB, nr.cnt.get(), nr.kind.get(),
-                                       retry.get(), cnts.get() + 3, (u8*)nullptr, (u32*)nullptr);
-                else
-                    hipLaunchKernelGGL((k_bucket_msd<256, 2048, false, false, HiT>), dim3(cn[2]), dim3(256), 0, c->stream, srt.get(), cnts.get() + 2, a_lo, a_hi, P.SB,
-                                       nr.cnt.get(), nr.kind.get(), retry.get(), cnts.get() + 3, MergeArgs{});
-                const u32 nre = d2h<u32>(c, cnts.get() + 3);
-                if (nre)
-                    hipLaunchKernelGGL((k_bucket_medium<512, false, HiT>), dim3(nre), dim3(512), 0, c->stream, retry.get(), cnts.get() + 3, a_lo, a_hi, P.SB, nr.cnt.get(), nr.kind.get(), MergeArgs{});
-            }
-            CBLX_HIP(hipGetLastError());
-            }
-            big_stage<C>(c, next_big.get(), cnts.get() + 0, cn[0], nr, MergeArgs{}, tw);
-            huge_stage<C>(c, next_huge.get(), cnts.get() + 1, cn[1], a_lo, a_hi, nr, MergeArgs{});
-            CBLX_HIP(hipStreamSynchronize(c->stream));  // the lists die here
-            long_done = true;
-        }
-    }
-    if (!long_done) {
-        if (msd_takes<C::WS>(P.SB)) big_stage<C>(c, lists.get() + (size_t)CLS_BIG * nb, list_n.get() + CLS_BIG, ln[CLS_BIG], nr, MergeArgs{}, tw);
-        else huge_stage<C>(c, lists.get() + (size_t)CLS_BIG * nb, list_n.get() + CLS_BIG, ln[CLS_BIG], a_lo, a_hi, nr, MergeArgs{});
-        huge_stage<C>(c, lists.get() + (size_t)CLS_HUGE * nb, list_n.get() + CLS_HUGE, ln[CLS_HUGE], a_lo, a_hi, nr, MergeArgs{});
-    }
-    }
-    CBLX_HIP(hipGetLastError());
-    finish_twin<C>(c, nr, tw, force);
-    count_words(c, nr);
 }
 
 // rows of k_merge_table's `other` side for a freshly partitioned batch: every run is a Vec of its raw length
@@ -1240,335 +840,6 @@ void insert_device_one(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64
         encode<C>(c, d_bases, pl, rec.lo.get(), (typename C::HiT*)rec.hi.get(), base, eh);
         pipeline<C>(c, rec, base + pl.n_kmers, std::move(countsA));
         c->kmers_inserted += pl.n_kmers;
-    });
-    collect_events(c);
-}
-
-// membership flags of n device words against the resident index (WordSet::contains_batch)
-// (`res`: the index asked, on c's stream — c's own, or another operand's of a panel query)
-template <typename C> void contains_words(cblx_ctx* c, const Resident& res, const u64* w_lo, const typename C::HiT* w_hi, u64 n, u8* d_out) {
-    typedef typename C::HiT HiT;
-    const u64 step = 1ull << 28;  // QL lanes per query: 2^31 work items per launch
-    for (u64 a = 0; a < n; a += step) {
-        const u64 m = std::min(step, n - a);
-        hipLaunchKernelGGL(k_contains<HiT>, grid1(m * QL, 256), dim3(256), 0, c->stream, w_lo + a, HiTraits<HiT>::has ? w_hi + a : w_hi, m, c->P.SB, c->P.PB, res.view(),
-                           res.a_lo.get(), c->P.wide_suffix() ? res.a_hi.get() : (const u64*)nullptr, d_out + a);
-    }
-    CBLX_HIP(hipGetLastError());
-}
-template <typename C> void contains_words(cblx_ctx* c, const u64* w_lo, const typename C::HiT* w_hi, u64 n, u8* d_out) {
-    contains_words<C>(c, c->res, w_lo, w_hi, n, d_out);
-}
-// Tallies of a big query batch by join (k_query_join): KRN-1 + the stable partition of the query words + one workgroup per
-// prefix run. CBLX_QUERY_JOIN_MIN overrides the batch size (k-mers) from which it replaces the per-query kernel.
-u64 query_join_min() {  // read per call: tests switch it
-    const char* e = std::getenv("CBLX_QUERY_JOIN_MIN");
-    return e ? std::strtoull(e, nullptr, 10) : (u64)(4u << 20);
-}
-// as insert_device: KRN-1 accumulates the first partition pass's tile histogram (countsA: zero-filled here, it goes to the partition)
-inline EncHist query_hist(cblx_ctx* c, u64 nk, Buf<u32>& countsA) {
-    const Consts& P = c->P;
-    EncHist eh{};
-    const size_t ntmax = (size_t)ceil_div(nk, RDX_TILE) + 256;
-    countsA = Buf<u32>(c->pool, 256 * ntmax);
-    CBLX_HIP(hipMemsetAsync(countsA.get(), 0, 256 * ntmax * 4, c->stream));
-    const u32 nA = std::min(8u, P.PB);
-    eh.counts = countsA.get();
-    eh.shift = P.SB + (P.PB - nA);
-    eh.nbits = nA;
-    return eh;
-}
-// Queries that keep their positions (words of at most 96 bits, narrow suffix): 16-byte records (lo, ordinal << 32 | hi bits) through the
-// partition of the 64-bit-hi layout. rec.lo / rec.hi end up as the partitioned records, qd as the batch's directory (prefixes, run starts).
-// the four buffers of nk tagged records (rec.hi / hi2 hold 64-bit hi parts)
-inline void begin_tagged_records(cblx_ctx* c, Records& rec, u64 nk) {
-    rec.lo = Buf<u64>(c->pool, nk + 2);
-    rec.lo2 = Buf<u64>(c->pool, nk + 2);
-    rec.hi = Buf<u8>(c->pool, (nk + 2) * 8);
-    rec.hi2 = Buf<u8>(c->pool, (nk + 2) * 8);
-}
-// nk tagged records in rec.lo / rec.hi, already encoded (by KRN-1 + k_query_tag, or by k_neighbor_words), through the partition. `countsA`: the first pass's
-// tile histogram where the encoder accumulated it (KRN-1), empty where it did not: the partition then counts it itself.
-template <typename C> void partition_tagged(cblx_ctx* c, Records& rec, u64 nk, Buf<u32>&& countsA, Resident& qd) {
-    typedef Cfg<C::WIDE, u64, false> QC;
-    partition_and_directory<QC>(c, rec, nk, std::move(countsA), qd);
-}
-template <typename C> void query_partition_tagged(cblx_ctx* c, const u8* d_bases, const ChunkPlan& pl, Buf<u32>&& countsA, const EncHist& eh, Records& rec, Resident& qd) {
-    typedef typename C::HiT HiT;
-    const Consts& P = c->P;
-    const u64 nk = pl.n_kmers;
-    begin_tagged_records(c, rec, nk);
-    {
-        Buf<u8> hi_tmp(c->pool, (nk + 2) * std::max<size_t>(1, hi_elem_size(P)));
-        encode<C>(c, d_bases, pl, rec.lo.get(), (HiT*)hi_tmp.get(), 0, eh);
-        hipLaunchKernelGGL(k_query_tag<HiT>, grid1(nk, 256), dim3(256), 0, c->stream, nk, (const HiT*)hi_tmp.get(), (u64*)rec.hi.get());
-        CBLX_HIP(hipGetLastError());
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // hi_tmp dies here
-    }
-    partition_tagged<C>(c, rec, nk, std::move(countsA), qd);
-}
-// One workgroup per prefix run of the partitioned query records (rec, directory qd) against c's resident index: pos[0] (device, zeroed by the caller) += the
-// queries found; `flags` (zero-filled, or null) takes flag 1 at the ordinal of every query found — tagged records, H = u64, only.
-template <typename C, typename H> void join_runs(cblx_ctx* c, const Records& rec, const Resident& qd, u8* flags, u64* pos) {
-    const Consts& P = c->P;
-    const u64 step = 1ull << 23;  // workgroups per launch (x 256 threads < 2^32 work items)
-    Buf<u32> per_run(c->pool, qd.nb + 1);
-    CBLX_HIP(hipMemsetAsync(per_run.get(), 0, (qd.nb + 1) * 4, c->stream));
-    for (u64 b0 = 0; b0 < qd.nb; b0 += step)
-        hipLaunchKernelGGL((k_query_join<C::WS, H>), dim3((unsigned)std::min(step, qd.nb - b0)), dim3(JOIN_THREADS), 0, c->stream, qd.nb, b0, qd.prefix.get(),
-                           qd.start.get(), rec.lo.get(), (const H*)rec.hi.get(), P.SB, c->res.view(), c->res.a_lo.get(),
-                           P.wide_suffix() ? c->res.a_hi.get() : (const u64*)nullptr, per_run.get(), flags);
-    hipLaunchKernelGGL(k_sum_u32, dim3((unsigned)std::min<u64>(2048, std::max<u64>(1, ceil_div(qd.nb, 256)))), dim3(256), 0, c->stream, per_run.get(), qd.nb, pos);
-    CBLX_HIP(hipGetLastError());
-    CBLX_HIP(hipStreamSynchronize(c->stream));  // per_run dies here
-}
-// The flag join on records that are already encoded and tagged (rec.lo / rec.hi of begin_tagged_records, ordinals 0 .. nk - 1 in the upper halves): partition,
-// then one workgroup per run. d_flags: nk bytes, zero-filled by the caller; returns the number of records found. Narrow suffixes only (query_flags_by_join).
-template <typename C> u64 join_tagged_records(cblx_ctx* c, Records& rec, u64 nk, Buf<u32>&& countsA, u8* d_flags) {
-    if constexpr (!C::WS) {
-        Resident qd;  // directory of the query batch: prefixes and run starts
-        Buf<u64> pos(c->pool, 1);
-        CBLX_HIP(hipMemsetAsync(pos.get(), 0, 8, c->stream));
-        partition_tagged<C>(c, rec, nk, std::move(countsA), qd);
-        join_runs<C, u64>(c, rec, qd, d_flags, pos.get());
-        return d2h<u64>(c, pos.get());  // also: the temporaries may go back to the pool
-    } else {
-        throw Error(CBLX_EDEVICE, "flag join of a wide suffix (internal error)");
-    }
-}
-template <typename C> u64 query_join(cblx_ctx* c, const u8* d_bases /* as left by plan_chunks */, const ChunkPlan& pl, u8* d_flags /* nk bytes or null */) {
-    typedef typename C::HiT HiT;
-    const u64 nk = pl.n_kmers;
-    if (d_flags && nk) CBLX_HIP(hipMemsetAsync(d_flags, 0, nk, c->stream));
-    if (nk == 0 || c->res.count == 0) return 0;
-    Buf<u32> countsA;
-    const EncHist eh = query_hist(c, nk, countsA);
-    Records rec;
-    Resident qd;  // directory of the query batch: prefixes and run starts
-    Buf<u64> pos(c->pool, 1);
-    CBLX_HIP(hipMemsetAsync(pos.get(), 0, 8, c->stream));
-    if constexpr (!C::WS) {
-        if (d_flags) {
-            query_partition_tagged<C>(c, d_bases, pl, std::move(countsA), eh, rec, qd);
-            join_runs<C, u64>(c, rec, qd, d_flags, pos.get());
-            return d2h<u64>(c, pos.get());
-        }
-    }
-    begin_records<C>(c, rec, nk);
-    encode<C>(c, d_bases, pl, rec.lo.get(), (HiT*)rec.hi.get(), 0, eh);
-    partition_and_directory<C>(c, rec, nk, std::move(countsA), qd);
-    join_runs<C, HiT>(c, rec, qd, (u8*)nullptr, pos.get());
-    return d2h<u64>(c, pos.get());  // also: the temporaries may go back to the pool
-}
-// words whose hi part leaves 32 bits for the query's ordinal, and whose suffix fits 64 bits: flags can come from the join
-inline bool query_flags_by_join(const Consts& P) { return !P.wide_suffix() && P.WB <= 96; }
-// Per-sequence tallies from the flags of a planned batch (kernels_kmer.hpp): seq_total[s] / seq_pos[s] for every sequence of the plan
-// (pl.seq_chunk kept). The flags stay on the device.
-void seq_tallies(cblx_ctx* c, const ChunkPlan& pl, u64 nseq, const u8* d_flags, u32* d_seq_total, u32* d_seq_pos) {
-    Buf<u32> chunk_pos(c->pool, pl.nchunks + 1);
-    const u32 long_cap = (u32)std::min<u64>(nseq, pl.nchunks / (SEQ_TALLY_LANE_MAX + 1) + 1);  // sequences of more than SEQ_TALLY_LANE_MAX chunks
-    Buf<u32> long_list(c->pool, long_cap), long_n(c->pool, 1);
-    CBLX_HIP(hipMemsetAsync(long_n.get(), 0, 4, c->stream));
-    if (d_seq_pos)
-        for (u64 c0 = 0; c0 < pl.nchunks; c0 += 1ull << 25)  // one wave per chunk, fewer than 2^32 work items per launch
-            hipLaunchKernelGGL(k_chunk_tally, grid1(std::min<u64>(1ull << 25, pl.nchunks - c0) * 64, 256), dim3(256), 0, c->stream, d_flags, (const u64*)pl.kmer_off.get(), c0,
-                               pl.nchunks, chunk_pos.get());
-    hipLaunchKernelGGL(k_seq_tally, grid1(nseq, 256), dim3(256), 0, c->stream, (const u64*)pl.seq_chunk.get(), (const u64*)pl.kmer_off.get(), (const u32*)chunk_pos.get(), nseq,
-                       d_seq_total, d_seq_pos, long_list.get(), long_n.get(), long_cap);
-    if (d_seq_pos && pl.nchunks > SEQ_TALLY_LANE_MAX)  // else no sequence is long
-        hipLaunchKernelGGL(k_seq_tally_long, dim3(long_cap), dim3(SEQ_TALLY_LONG_THREADS), 0, c->stream, (const u32*)long_list.get(), (const u32*)long_n.get(),
-                           (const u64*)pl.seq_chunk.get(), (const u32*)chunk_pos.get(), d_seq_pos);
-    CBLX_HIP(hipGetLastError());
-    CBLX_HIP(hipStreamSynchronize(c->stream));  // chunk_pos and the list die here
-}
-// CBL::contains_seq over a batch of device-resident sequences: KRN-1, then one membership flag per k-mer (sequence after
-// sequence, each in get_seq_words order) into d_out[cap] when given; *total / *positive count the flags.
-// d_seq_total / d_seq_pos (device, nseq entries each, either may be null): k-mers queried and k-mers found of every sequence. They are
-// tallied on the device from the flags, which then go to scratch unless d_out takes them: by the join with ordinals where
-// query_flags_by_join holds and the batch is big enough, by k_contains otherwise — the routes of a query with d_out.
-void query_device(cblx_ctx* c, const u8* d_bases, const u64* d_offsets, u64 nseq, u8* d_out, u64 cap, u64* total, u64* positive, u32* d_seq_total = nullptr,
-                  u32* d_seq_pos = nullptr) {
-    if (total) *total = 0;
-    if (positive) *positive = 0;
-    if (nseq == 0) return;
-    check_aligned16(d_bases, "d_bases");
-    const bool per_seq = d_seq_total || d_seq_pos;
-    dispatch(c->P, [&](auto cfg) {
-        typedef decltype(cfg) C;
-        typedef typename C::HiT HiT;
-        ChunkPlan pl;
-        pl.keep_seq_chunk = per_seq;
-        plan_chunks(c, d_bases, d_offsets, nseq, pl);
-        const u64 nk = pl.n_kmers;
-        if (total) *total = nk;
-        if (nk == 0) {  // (not with nseq > 0 today: every chunk holds at least its first k-mer)
-            if (d_seq_total) CBLX_HIP(hipMemsetAsync(d_seq_total, 0, nseq * 4, c->stream));
-            if (d_seq_pos) CBLX_HIP(hipMemsetAsync(d_seq_pos, 0, nseq * 4, c->stream));
-            return;
-        }
-        if (nk >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "too many k-mers in one query batch");
-        if (d_out && nk > cap) throw Error(CBLX_ERANGE, "output capacity too small: " + std::to_string(nk) + " k-mers");
-        Buf<u8> flags;
-        if (d_seq_pos && !d_out) { flags = Buf<u8>(c->pool, nk + 16); d_out = flags.get(); }
-        if (nk >= query_join_min() && (!d_out || query_flags_by_join(c->P))) {  // big batch: join instead of one bucket read per query
-            const u64 p = query_join<C>(c, d_bases, pl, d_out);
-            if (positive) *positive = p;
-        } else {
-            Buf<u64> w_lo(c->pool, nk + 2);
-            Buf<u8> w_hi(c->pool, (nk + 2) * std::max<size_t>(1, hi_elem_size(c->P)));
-            if (!d_out) { flags = Buf<u8>(c->pool, nk + 8); d_out = flags.get(); }
-            Buf<u32> zeros(c->pool, 1);
-            CBLX_HIP(hipMemsetAsync(zeros.get(), 0, 4, c->stream));
-            encode<C>(c, d_bases, pl, w_lo.get(), (HiT*)w_hi.get(), 0);
-            contains_words<C>(c, w_lo.get(), (const HiT*)w_hi.get(), nk, d_out);
-            hipLaunchKernelGGL(k_count_zero_u8, dim3((unsigned)std::min<u64>(4096, ceil_div(nk, 256))), dim3(256), 0, c->stream, (const u8*)d_out, nk, zeros.get());
-            CBLX_HIP(hipGetLastError());
-            const u64 z = d2h<u32>(c, zeros.get());  // also: the temporaries may go back to the pool
-            if (positive) *positive = nk - z;
-        }
-        if (per_seq) seq_tallies(c, pl, nseq, d_out, d_seq_total, d_seq_pos);
-    });
-    collect_events(c);
-}
-
-// ---- a batch against a PANEL of indexes (cblx_contains_seqs_counts_many*) ---------------------------------------------------
-// The panel join: plan, KRN-1, ordinal tags and the partition of the query words run ONCE (query_join's flag branch); k_panel_join then takes every
-// query run through its bucket in each index. d_mask: nk words, zero-filled. srcs[j] with an empty index keeps its place (bit j stays 0).
-template <typename C> void panel_join(cblx_ctx* c, cblx_ctx* const* srcs, u32 n, const u8* d_bases, const ChunkPlan& pl, u64* d_mask) {
-    if constexpr (!C::WS) {
-        const Consts& P = c->P;
-        const u64 nk = pl.n_kmers;
-        Buf<u32> countsA;
-        const EncHist eh = query_hist(c, nk, countsA);
-        Records rec;
-        Resident qd;
-        query_partition_tagged<C>(c, d_bases, pl, std::move(countsA), eh, rec, qd);
-        std::vector<PanelEntry> h(n);
-        for (u32 j = 0; j < n; ++j) {
-            const Resident& r = srcs[j]->res;
-            h[j] = r.count ? PanelEntry{r.view(), r.a_lo.get(), (const u64*)nullptr} : PanelEntry{DirView{nullptr, nullptr, nullptr, nullptr, nullptr, 0}, nullptr, nullptr};
-        }
-        Buf<PanelEntry> d_panel(c->pool, n);
-        h2d(c, d_panel.get(), h.data(), n);
-        const u64 step = 1ull << 23;  // workgroups per launch (x 256 threads < 2^32 work items)
-        for (u64 b0 = 0; b0 < qd.nb; b0 += step)
-            hipLaunchKernelGGL(k_panel_join, dim3((unsigned)std::min(step, qd.nb - b0)), dim3(JOIN_THREADS), 0, c->stream, qd.nb, b0, (const u32*)qd.prefix.get(),
-                               (const u64*)qd.start.get(), (const u64*)rec.lo.get(), (const u64*)rec.hi.get(), P.SB, (const PanelEntry*)d_panel.get(), n, d_mask);
-        CBLX_HIP(hipGetLastError());
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // the records, the directory and the panel table die here (h was read by then)
-    } else {
-        throw Error(CBLX_EDEVICE, "panel join of a wide suffix (internal error)");
-    }
-}
-// The two tally levels from masks (kernels_kmer.hpp): d_seq_pos[j * nseq + s] for every index j and sequence s of the plan (pl.seq_chunk kept).
-void mask_tallies(cblx_ctx* c, const ChunkPlan& pl, u64 nseq, u32 n, const u64* d_mask, u32* d_seq_pos) {
-    Buf<u32> chunk_pos(c->pool, (size_t)pl.nchunks * n + 1);
-    const u32 long_cap = (u32)std::min<u64>(nseq, pl.nchunks / (SEQ_TALLY_LANE_MAX + 1) + 1);  // sequences of more than SEQ_TALLY_LANE_MAX chunks
-    Buf<u32> long_list(c->pool, long_cap), long_n(c->pool, 1);
-    CBLX_HIP(hipMemsetAsync(long_n.get(), 0, 4, c->stream));
-    for (u64 c0 = 0; c0 < pl.nchunks; c0 += 1ull << 25)  // one wave per chunk, fewer than 2^32 work items per launch
-        hipLaunchKernelGGL(k_chunk_tally_mask, grid1(std::min<u64>(1ull << 25, pl.nchunks - c0) * 64, 256), dim3(256), 0, c->stream, d_mask, (const u64*)pl.kmer_off.get(), c0,
-                           pl.nchunks, n, chunk_pos.get());
-    const u64 per = (1ull << 31) / n;  // sequences per launch: fewer than 2^32 lanes
-    for (u64 s0 = 0; s0 < nseq; s0 += per) {
-        const u64 m = std::min(per, nseq - s0);
-        hipLaunchKernelGGL(k_seq_tally_mask, grid1(m * n, 256), dim3(256), 0, c->stream, (const u64*)pl.seq_chunk.get(), (const u32*)chunk_pos.get(), s0, s0 + m, nseq, n,
-                           d_seq_pos, long_list.get(), long_n.get(), long_cap);
-    }
-    if (pl.nchunks > SEQ_TALLY_LANE_MAX)  // else no sequence is long
-        hipLaunchKernelGGL(k_seq_tally_long_mask, dim3(long_cap, n), dim3(SEQ_TALLY_LONG_THREADS), 0, c->stream, (const u32*)long_list.get(), (const u32*)long_n.get(),
-                           (const u64*)pl.seq_chunk.get(), (const u32*)chunk_pos.get(), nseq, n, d_seq_pos);
-    CBLX_HIP(hipGetLastError());
-    CBLX_HIP(hipStreamSynchronize(c->stream));  // chunk_pos and the list die here
-}
-// contains_seq of a device-resident batch against n indexes at once: d_seq_total[nseq], d_seq_pos[n * nseq] (row j = srcs[j]) and one membership mask per
-// k-mer in d_mask[cap] (bit j = srcs[j] holds it), any of them null; *total k-mers, positive[j] = the sum of row j (host, n entries, or null).
-// `c`: the first non-empty operand (srcs[0] when all are empty) — its stream, pool and mailbox; every operand is flushed and idle.
-// Routes: at most one non-empty operand -> query_device on it (byte for byte today's result); the panel join where query_flags_by_join holds and the batch
-// is big enough; else KRN-1 once and k_contains per non-empty operand (only the encode is shared).
-void query_panel_device(cblx_ctx* c, cblx_ctx* const* srcs, u32 n, const u8* d_bases, const u64* d_offsets, u64 nseq, u32* d_seq_total, u32* d_seq_pos, u64* d_mask,
-                        u64 cap, u64* total, u64* positive) {
-    if (total) *total = 0;
-    if (positive) for (u32 j = 0; j < n; ++j) positive[j] = 0;
-    if (nseq == 0) return;
-    check_aligned16(d_bases, "d_bases");
-    u32 nlive = 0, j0 = 0;
-    for (u32 j = n; j-- > 0;)
-        if (srcs[j]->res.count) { ++nlive; j0 = j; }  // j0: the first non-empty one
-    if (nlive <= 1) {
-        Buf<u8> flags;
-        u64 fcap = 0;
-        if (d_mask) {  // the flags of the one index, then bit j0 of every mask word
-            fcap = std::min(kmers_upper_bound(c, d_offsets, 0, nseq), cap);
-            flags = Buf<u8>(c->pool, fcap + 16);
-        }
-        u64 tot = 0, pos = 0;
-        query_device(c, d_bases, d_offsets, nseq, d_mask ? flags.get() : nullptr, fcap, &tot, &pos, d_seq_total, d_seq_pos ? d_seq_pos + (size_t)j0 * nseq : nullptr);
-        if (total) *total = tot;
-        if (positive) positive[j0] = pos;
-        if (d_seq_pos)
-            for (u32 j = 0; j < n; ++j)
-                if (j != j0) CBLX_HIP(hipMemsetAsync(d_seq_pos + (size_t)j * nseq, 0, nseq * 4, c->stream));
-        if (d_mask && tot) {
-            CBLX_HIP(hipMemsetAsync(d_mask, 0, tot * 8, c->stream));
-            if (nlive) hipLaunchKernelGGL(k_mask_or_flags, grid1(tot, 256), dim3(256), 0, c->stream, (const u8*)flags.get(), tot, j0, d_mask);
-            CBLX_HIP(hipGetLastError());
-        }
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // the flags die here
-        return;
-    }
-    dispatch(c->P, [&](auto cfg) {
-        typedef decltype(cfg) C;
-        typedef typename C::HiT HiT;
-        ChunkPlan pl;
-        pl.keep_seq_chunk = true;
-        plan_chunks(c, d_bases, d_offsets, nseq, pl);
-        const u64 nk = pl.n_kmers;
-        if (total) *total = nk;
-        if (nk == 0) {  // (not with nseq > 0 today: every chunk holds at least its first k-mer)
-            if (d_seq_total) CBLX_HIP(hipMemsetAsync(d_seq_total, 0, nseq * 4, c->stream));
-            if (d_seq_pos) CBLX_HIP(hipMemsetAsync(d_seq_pos, 0, (size_t)n * nseq * 4, c->stream));
-            return;
-        }
-        if (nk >= 0xFFFFFFF0ull) throw Error(CBLX_ERANGE, "too many k-mers in one query batch");
-        if (d_mask && nk > cap) throw Error(CBLX_ERANGE, "mask capacity too small: " + std::to_string(nk) + " k-mers");
-        Buf<u64> mask_tmp;
-        if (!d_mask) { mask_tmp = Buf<u64>(c->pool, nk + 2); d_mask = mask_tmp.get(); }
-        CBLX_HIP(hipMemsetAsync(d_mask, 0, nk * 8, c->stream));
-        if (query_flags_by_join(c->P) && nk >= query_join_min()) {
-            panel_join<C>(c, srcs, n, d_bases, pl, d_mask);
-        } else {  // wide suffix, a word of more than 96 bits, or a small batch: one k_contains per non-empty index on the words encoded once
-            Buf<u64> w_lo(c->pool, nk + 2);
-            Buf<u8> w_hi(c->pool, (nk + 2) * std::max<size_t>(1, hi_elem_size(c->P))), flags(c->pool, nk + 8);
-            encode<C>(c, d_bases, pl, w_lo.get(), (HiT*)w_hi.get(), 0);
-            for (u32 j = 0; j < n; ++j) {
-                if (!srcs[j]->res.count) continue;
-                contains_words<C>(c, srcs[j]->res, w_lo.get(), (const HiT*)w_hi.get(), nk, flags.get());
-                hipLaunchKernelGGL(k_mask_or_flags, grid1(nk, 256), dim3(256), 0, c->stream, (const u8*)flags.get(), nk, j, d_mask);
-            }
-            CBLX_HIP(hipGetLastError());
-            CBLX_HIP(hipStreamSynchronize(c->stream));  // the words and the flags die here
-        }
-        Buf<u32> pos_tmp;
-        u32* rows = d_seq_pos;
-        if (!rows && positive) { pos_tmp = Buf<u32>(c->pool, (size_t)n * nseq); rows = pos_tmp.get(); }
-        if (d_seq_total) {  // k_seq_tally with no positives to sum: the totals alone
-            hipLaunchKernelGGL(k_seq_tally, grid1(nseq, 256), dim3(256), 0, c->stream, (const u64*)pl.seq_chunk.get(), (const u64*)pl.kmer_off.get(), (const u32*)nullptr, nseq,
-                               d_seq_total, (u32*)nullptr, (u32*)nullptr, (u32*)nullptr, 0u);
-            CBLX_HIP(hipGetLastError());
-        }
-        if (rows) mask_tallies(c, pl, nseq, n, d_mask, rows);
-        if (positive) {
-            Buf<u64> sums(c->pool, n);
-            CBLX_HIP(hipMemsetAsync(sums.get(), 0, n * 8, c->stream));
-            for (u32 j = 0; j < n; ++j)
-                hipLaunchKernelGGL(k_sum_u32, dim3((unsigned)std::min<u64>(2048, std::max<u64>(1, ceil_div(nseq, 256)))), dim3(256), 0, c->stream, (const u32*)rows + (size_t)j * nseq,
-                                   nseq, sums.get() + j);
-            CBLX_HIP(hipGetLastError());
-            const std::vector<u64> s = d2h_vec<u64>(c, sums.get(), n);
-            for (u32 j = 0; j < n; ++j) positive[j] = s[j];
-        }
-        CBLX_HIP(hipStreamSynchronize(c->stream));  // the scratch mask and rows die here
     });
     collect_events(c);
 }

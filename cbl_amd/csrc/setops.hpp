@@ -1,6 +1,6 @@
 // setops.hpp — set algebra between resident indexes and k-mer removal, on the host: `self |= other` (merge_direct), `a OP b` into a new index and the
 // assigning forms (set_op_build), CBL::merge / CBL::intersect of n operands (set_op_many_build), the k-mers at least t of n hold and the occupancy histogram (at_least_build), |a AND b| alone (intersection_count), WordSet::remove_batch (remove_words). They share the
-// bucket stages of pipeline.hpp and the end of a result (set_op_tail). Kernels: kernels_setops.hpp, kernels_remove.hpp. Included by cblx.cpp only.
+// bucket stages of bucket_stage.hpp and the end of a result (set_op_tail). Kernels: kernels_setops.hpp, kernels_remove.hpp. Included by cblx.cpp only.
 #pragma once
 #include "kernels_remove.hpp"
 #include "kernels_setops.hpp"
@@ -118,31 +118,17 @@ template <typename C> void merge_direct(cblx_ctx* c, const Resident& s, const Re
         Buf<BDesc> retry(c->pool, std::max<u64>(nb, 1));
         Buf<u32> retry_n(c->pool, 1);
         CBLX_HIP(hipMemsetAsync(retry_n.get(), 0, 4, c->stream));
-        auto msd = [&](auto packed_tag) {
-            constexpr bool PK = decltype(packed_tag)::value;
-            each_len_class([&](auto kc) {
-                constexpr int k = decltype(kc)::value, T = LEN_CLASSES[k].threads, CAPV = LEN_CLASSES[k].cap, cls = LEN_CLASSES[k].cls;
-                if constexpr (cls != CLS_M32) {  // (k_classify_merge has no such class)
-                    if (!ln[cls]) return;
-                    if constexpr (PK || WS)  // packed elements: the walk kernel in its merge mode (round 6)
-                        hipLaunchKernelGGL((k_bucket_sorted<T, CAPV, WS, HiT, true>), dim3(ln[cls]), dim3(T), 0, c->stream, lists.get() + (size_t)cls * nb, list_n.get() + cls, a_lo, a_hi, P.SB,
-                                           nr.cnt.get(), nr.kind.get(), retry.get(), retry_n.get(), (u8*)nullptr, (u32*)nullptr, ma_msd);
-                    else
-                        hipLaunchKernelGGL((k_bucket_msd<T, CAPV, PK, WS, HiT, true>), dim3(ln[cls]), dim3(T), 0, c->stream, lists.get() + (size_t)cls * nb, list_n.get() + cls, a_lo, a_hi, P.SB,
-                                           nr.cnt.get(), nr.kind.get(), retry.get(), retry_n.get(), ma_msd);
-                }
+        if (!msd_takes<WS>(P.SB)) radix_only_classes<C>(c, lists.get(), list_n.get(), ln, nb, nr, ma);
+        else
+            with_packed<C>(P, [&](auto pk) {
+                each_len_class([&](auto kc) {
+                    constexpr int cls = LEN_CLASSES[decltype(kc)::value].cls;
+                    if constexpr (cls != CLS_M32)  // (k_classify_merge has no such class)
+                        if (ln[cls])
+                            launch_run_sort<C, SORT_MERGE, decltype(pk)::value>(c, kc, lists.get() + (size_t)cls * nb, list_n.get() + cls, ln[cls], a_lo, a_hi, nr.cnt.get(), nr.kind.get(),
+                                                                                SortOut{retry.get(), retry_n.get()}, ma_msd);
+                });
             });
-        };
-        if constexpr (!WS) {
-            if (P.SB + PK_BITS <= 64) msd(std::true_type()); else msd(std::false_type());
-        } else {
-            if (msd_takes<WS>(P.SB)) msd(std::false_type());
-            else  // (see bucket_stage) every class to the LDS radix kernel
-                for (int cls : {CLS_M16, CLS_M64, CLS_M128, CLS_M256, CLS_M512})
-                    if (ln[cls])
-                        hipLaunchKernelGGL((k_bucket_medium<512, WS, HiT>), dim3(ln[cls]), dim3(512), 0, c->stream, lists.get() + (size_t)cls * nb, list_n.get() + cls, a_lo, a_hi, P.SB,
-                                           nr.cnt.get(), nr.kind.get(), ma);
-        }
         const u32 nretry = (ln[CLS_M16] || ln[CLS_M64] || ln[CLS_M128] || ln[CLS_M256] || ln[CLS_M512]) ? d2h<u32>(c, retry_n.get()) : 0u;
         if (nretry) {
             if (direct)  // (these buckets were not gathered: the radix kernel works on the run)
@@ -158,9 +144,7 @@ template <typename C> void merge_direct(cblx_ctx* c, const Resident& s, const Re
     }
     {
         Twin tw;
-        if (msd_takes<WS>(P.SB)) big_stage<C>(c, lists.get() + (size_t)CLS_BIG * nb, list_n.get() + CLS_BIG, ln[CLS_BIG], nr, ma, tw);
-        else huge_stage<C>(c, lists.get() + (size_t)CLS_BIG * nb, list_n.get() + CLS_BIG, ln[CLS_BIG], a_lo, a_hi, nr, ma);
-        huge_stage<C>(c, lists.get() + (size_t)CLS_HUGE * nb, list_n.get() + CLS_HUGE, ln[CLS_HUGE], a_lo, a_hi, nr, ma);
+        long_runs_stage<C>(c, lists.get(), list_n.get(), ln, nb, nr, ma, tw);
         finish_twin<C>(c, nr, tw);
     }
     count_words(c, nr);

@@ -31,7 +31,7 @@ SMALL_MAX = 32             # kernels_bucket.hpp: SMALL_MAX, all-pairs in a slice
 MED_ITEMS = 8              # kernels_bucket.hpp: MED_ITEMS, slots per lane of the counting-sort classes
 BIG_MAX = 1 << 18          # kernels_bucket.hpp: BIG_MAX, longest run of the split path
 BIG_SUB = 1024             # kernels_bucket.hpp: BIG_SUB, words per sub-range big_bits aims at
-LDS_MAX = 4096             # pipeline.hpp: bucket_stage, k_classify's lds_max, the same for every suffix width
+LDS_MAX = 4096             # bucket_stage.hpp: bucket_stage, k_classify's lds_max, the same for every suffix width
 PK_BITS = 12               # kernels_bucket.hpp: PK_BITS, a packed element is suffix + 12-bit position in 64 bits
 MSD_MAX_BITS = 128         # kernels_bucket.hpp: msd_takes, wide suffixes up to SB + 12 <= 128 take the counting sort, wider ones the radix kernel
 DIRECT_UPTO = 512 * MED_ITEMS  # setops.hpp: merge_direct, direct_upto, both-sided buckets `|=` reads in place
@@ -111,9 +111,9 @@ def props(name):
     k, pb = CONFIGS[name]
     sb = pyref.params(k, pb)["SB"]
     wide = sb > 64                                           # common.hpp:26 wide_suffix
-    return dict(k=k, pb=pb, sb=sb, wide=wide, packed=not wide and sb + PK_BITS <= 64,  # pipeline.hpp: bucket_stage, `stage`
+    return dict(k=k, pb=pb, sb=sb, wide=wide, packed=not wide and sb + PK_BITS <= 64,  # bucket_stage.hpp: with_packed
                 msd=not wide or sb + 12 <= MSD_MAX_BITS,     # msd_takes
-                prepass=not wide and sb < 64)                # pipeline.hpp: bucket_stage, the pre-pass of the long runs
+                prepass=not wide and sb < 64)                # bucket_stage.hpp: bucket_stage, the pre-pass of the long runs
 
 
 # ---- the model -------------------------------------------------------------------------------------------------------------------------------
