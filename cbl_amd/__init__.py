@@ -79,6 +79,13 @@ class ComponentStats(C.Structure):
 COMPONENTS_LARGEST = 1  # CBLX_COMPONENTS_LARGEST of include/cblx.h
 COMPONENT_COUNTS = ("kmers", "unitigs", "links", "components", "largest_kmers", "rounds")
 
+
+class AbundanceStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("kmers", "removed_kmers", "unitigs", "removed_unitigs", "kmers_left", "min_count")]
+
+
+ABUNDANCE_UNITIGS = 1  # CBLX_ABUNDANCE_UNITIGS of include/cblx.h
+
 BUCKET_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 
 ABI_VERSION = 3  # include/cblx.h CBLX_ABI_VERSION
@@ -222,6 +229,17 @@ SIGNATURES = {
     "cblx_components": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_components_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_components_filter": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(ComponentStats)]),
+    "cblx_abundance_seqs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_abundance_seqs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_abundance_histogram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_unitig_coverage": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_unitig_coverage_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cblx_gfa_tagged_text_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_uint64)]),
+    "cblx_gfa_tagged_to_fd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_gfa_tagged_to_file": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64)]),
+    "cblx_abundance_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(AbundanceStats)]),
     "cblx_list_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -1535,6 +1553,114 @@ class CBL:
             raise ValueError("component_summary: every component has at least one unitig and at least as many k-mers as unitigs")
         total, big = sum(ks), max(ks, default=0)
         return {"components": len(ks), "largest": big, "singletons": sum(1 for u in us if u == 1), "largest_fraction": big / total if total else 0.0}
+
+    # ---- k-mer abundances from reads: the counts are the caller's tensor, one uint32 per stored k-mer by ordinal ---------
+    def _counts(self, counts):
+        """(tensor, address, length) of an abundance array: a torch int32 CUDA tensor holding the unsigned values; None -> zero-filled, count() long."""
+        import torch
+
+        if counts is None:
+            counts = torch.zeros(self.count(), dtype=torch.int32, device=torch.device("cuda", self.device()))
+        if not (counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous()):
+            raise ValueError("counts is a contiguous torch int32 CUDA tensor (it holds the unsigned 32-bit values)")
+        return counts, (counts.data_ptr() if counts.numel() else None), counts.numel()
+
+    def abundance_seqs(self, bases, offsets, counts=None):
+        """Adds to counts[i] the occurrences of stored k-mer i (by ordinal, the index in the iteration order) in a host batch of reads (bases: uint8
+        array, offsets: uint64 array of n + 1 entries), saturating at 2^32 - 1: k-mers as contains_seqs enumerates them, both strands for a
+        canonical index; a read shorter than K gives none. The call accumulates into `counts` (None: a zero-filled tensor made here) and refuses
+        a tensor whose length is not count(). Returns (counts, k-mers of the batch, those the index holds). The index is not modified."""
+        counts, p, m = self._counts(counts)
+        tot, found = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_abundance_seqs(self._h, _ptr(bases), _ptr(offsets), max(len(offsets) - 1, 0), p, m, C.byref(tot), C.byref(found)))
+        return counts, tot.value, found.value
+
+    def abundance_seqs_device(self, d_bases, d_offsets, n: int, counts=None):
+        """The same for a device-resident batch (d_bases 16-byte aligned); nothing crosses to the host but the two totals."""
+        counts, p, m = self._counts(counts)
+        tot, found = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.cblx_abundance_seqs_device(self._h, _ptr(d_bases), _ptr(d_offsets), n, p, m, C.byref(tot), C.byref(found)))
+        return counts, tot.value, found.value
+
+    def abundance_histogram(self, counts):
+        """The abundance spectrum as a uint64 array of 256: hist[j] = the stored k-mers with counts[i] == j for j < 255, hist[255] = those with
+        counts[i] >= 255."""
+        import numpy as np
+
+        counts, p, m = self._counts(counts)
+        hist = np.zeros(256, dtype=np.uint64)
+        self._chk(self._L.cblx_abundance_histogram(self._h, p, m, hist.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return hist
+
+    def _unitig_coverage(self, xp, counts):
+        device = xp.__name__ == "torch"
+        counts, p, m = self._counts(counts)
+        fn = self._L.cblx_unitig_coverage_device if device else self._L.cblx_unitig_coverage
+        u = C.c_uint64(0)
+        self._chk(fn(self._h, p, m, None, 0, C.byref(u)))
+        cap = max(u.value, 1)
+        kc = xp.zeros(cap, dtype=xp.int64, device=counts.device) if device else xp.zeros(cap, dtype=xp.uint64)
+        self._chk(fn(self._h, p, m, _ptr(kc), cap, C.byref(u)))
+        return kc[: u.value]
+
+    def unitig_coverage_np(self, counts):
+        """kc (uint64 per unitig of unitig_table_np / biunitig_table_np): the sum of counts over the unitig's k-mers. Mean coverage is kc / length."""
+        import numpy as np
+
+        return self._unitig_coverage(np, counts)
+
+    def unitig_coverage_device(self, counts):
+        """The same as a torch int64 CUDA tensor holding the unsigned values; only the number of unitigs crosses to the host."""
+        import torch
+
+        return self._unitig_coverage(torch, counts)
+
+    def _counts_or_none(self, counts):
+        return (None, 0) if counts is None else self._counts(counts)[1:]
+
+    def gfa_tagged_text_device(self, counts=None, d_buf=None, cap: int = 0):
+        """(bytes, unitigs, L lines) of the tagged GFA text; d_buf and cap as in gfa_text_device."""
+        p, m = self._counts_or_none(counts)
+        return self._gfa_sizes("gfa_tagged_text_device", p, m, _ptr(d_buf), cap)
+
+    def gfa_tagged_to_fd(self, fd: int, counts=None, chunk_bytes: int = 0):
+        """The tagged GFA text to an open file descriptor; returns (unitigs, L lines, bytes)."""
+        p, m = self._counts_or_none(counts)
+        return self._gfa_sizes("gfa_tagged_to_fd", p, m, fd, chunk_bytes)
+
+    def gfa_tagged_to_file(self, path, counts=None, chunk_bytes: int = 0):
+        """Writes the GFA text of gfa_to_file with the tags LN:i:<bases> and, with `counts`, KC:i:<the unitig's coverage sum> on every S line."""
+        p, m = self._counts_or_none(counts)
+        return self._gfa_sizes("gfa_tagged_to_file", p, m, os.fsencode(path), chunk_bytes)
+
+    def gfa_tagged_text_np(self, counts=None):
+        """The tagged GFA text as a uint8 array, built on the device and streamed out once."""
+        return self._text_np(lambda fd: self.gfa_tagged_to_fd(fd, counts))
+
+    def abundance_filter(self, counts, min_count: int, unitigs: bool = False) -> dict:
+        """Removes the weakly supported k-mers, on the device, as one batch in iteration order: every k-mer with counts[i] < min_count, or with
+        `unitigs` every k-mer of every unitig whose mean coverage is below min_count (kc < min_count * length). `counts` is only read; after a
+        call that removed something it no longer matches the index: tally again. Returns kmers, removed_kmers, unitigs, removed_unitigs (both 0
+        under the k-mer rule), kmers_left and min_count."""
+        counts, p, m = self._counts(counts)
+        st = AbundanceStats()
+        self._chk(self._L.cblx_abundance_filter(self._h, p, m, int(min_count), ABUNDANCE_UNITIGS if unitigs else 0, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in AbundanceStats._fields_}
+
+    @staticmethod
+    def solid_threshold(hist):
+        """The first local minimum of an abundance spectrum after bin 0 (host only): the smallest j >= 1 whose bin is followed by a higher one,
+        moved back to the first bin of a plateau of equal bins — where the descent from the error peak ends and the rise to the coverage peak
+        begins. Bin 0 is not looked at. None when no bin from 1 on is followed by a higher one."""
+        h = [int(v) for v in hist]
+        j = 1
+        while j + 1 < len(h):
+            if h[j + 1] > h[j]:  # the spectrum rises behind j: j ends a descent or a plateau
+                while j > 1 and h[j - 1] == h[j]:
+                    j -= 1  # the first bin of the plateau
+                return j
+            j += 1
+        return None
 
     # ---- bucket statistics (src/cbl.rs:364-386) ---------------------------------------------------------------------
     def bucket_table_np(self):

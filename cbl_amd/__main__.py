@@ -4,7 +4,8 @@ reference CLI (/root/reference/examples/cbl.rs:147-167,230-269,270-309,168-229,3
 containment of every pair of two or more index files; `classify` assigns every record of a FASTA/Q file to one of two or more index files; `graph` prints
 the degree table of the de Bruijn graph whose nodes are the k-mers of an index; `unitigs` writes the non-branching paths of that graph, one line each
 (of a canonical index: the bidirected unitigs); `clip` removes the short dead-end unitigs (tips) of that graph from an index; `components`
-prints the connected components of that graph, or removes the small ones (or all but the largest) from an index.
+prints the connected components of that graph, or removes the small ones (or all but the largest) from an index; `abundance` counts how often
+the reads of FASTA/Q files hold every k-mer of an index, and prints the spectrum, writes the GFA text with LN / KC tags or removes the weak k-mers.
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
 here they are flags with the same defaults (K=25, PREFIX_BITS=24). Index files are interchangeable with the reference's.
@@ -134,6 +135,19 @@ def unitigs_report(summary):
     return lines, human
 
 
+def abundance_report(total, found, hist):
+    """What `cbl abundance` prints, from the totals of CBL.abundance_seqs* and the spectrum of CBL.abundance_histogram: the machine-readable lines and a
+    human summary. `solid_threshold` is the first valley of the spectrum (CBL.solid_threshold), `none` when it has none."""
+    h = [int(v) for v in hist]
+    kmers = sum(h)
+    solid = CBL.solid_threshold(h)
+    lines = [f"total\t{int(total)}", f"found\t{int(found)}", f"kmers\t{kmers}", f"unseen\t{h[0]}", f"once\t{h[1]}", f"saturated_bin\t{h[255]}",
+             f"solid_threshold\t{'none' if solid is None else solid}"]
+    human = [f"# k-mers of the reads: {int(total)}", f"# of them in the index: {int(found)} ({int(found) * 100 / total if total else float('nan'):.2f}%)",
+             f"# k-mers of the index never seen: {h[0]} of {kmers}"]
+    return lines, human
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cbl_amd")
     ap.add_argument("-k", type=int, default=25, help="k-mer size (odd, <= 59); the reference bakes it in at build time")
@@ -221,7 +235,24 @@ def main(argv=None):
     cc_rule = cc.add_mutually_exclusive_group()
     cc_rule.add_argument("--min-kmers", type=int, default=None, metavar="N", help="remove every component of fewer than N k-mers (N is at least 1)")
     cc_rule.add_argument("--largest", action="store_true", help="remove every component but the one of most k-mers")
+    ab = sub.add_parser("abundance", help="Count how often the reads of one or more FASTA/Q files hold every k-mer of an index (both strands for a canonical "
+                                          "index), print the abundance spectrum, write the compacted graph as GFA with LN and KC tags, or, with "
+                                          "--min-count and -o, remove the weakly supported k-mers. Every file is staged in device memory at once")
+    ab.add_argument("index")
+    ab.add_argument("reads", nargs="+", help="FASTA/Q files, tallied one after the other into one array of counts")
+    ab.add_argument("--hist", action="store_true", help="print the spectrum: a line `j<TAB>k-mers` for j = 0 .. 255 (the last one: 255 and more)")
+    ab.add_argument("--min-count", type=int, default=None, metavar="N", help="remove every k-mer counted fewer than N times (N is at least 1; needs -o)")
+    ab.add_argument("--unitigs", action="store_true", help="with --min-count: remove whole unitigs, those whose mean count is below N")
+    ab.add_argument("-o", "--output", help="write the filtered index to OUT (needs --min-count)")
+    ab.add_argument("--gfa", metavar="OUT.gfa", help="write the compacted graph of the index as loaded as GFA 1.0 with LN:i: and KC:i: tags on the S lines")
     a = ap.parse_args(argv)
+    if a.cmd == "abundance":  # refused before anything is loaded
+        if a.min_count is not None and a.min_count < 1:
+            ap.error("abundance: --min-count is at least 1")
+        if a.unitigs and a.min_count is None:
+            ap.error("abundance: --unitigs needs --min-count")
+        if (a.min_count is not None) != (a.output is not None):
+            ap.error("abundance: --min-count needs -o, and -o needs --min-count")
     if a.cmd == "components":  # refused before anything is loaded
         if a.min_kmers is not None and a.min_kmers < 1:
             ap.error("components: --min-kmers is at least 1")
@@ -422,6 +453,40 @@ def main(argv=None):
             st = cbl.components_filter(a.min_kmers, largest=a.largest)
             print(f"Removed {st['removed_components']} of {st['components']} components, {st['removed_kmers']} k-mers; {st['kmers_left']} k-mers are left",
                   file=sys.stderr)
+            print(f"Writing the index to {a.output}", file=sys.stderr)
+            cbl.save_to_file(a.output)
+            print("\n".join(f"{key}\t{value}" for key, value in st.items()))
+
+    elif a.cmd == "abundance":  # ours (the reference's CLI has no such command): the counts live beside the index, never in it
+        import torch
+
+        print(f"Reading the index stored in {a.index}", file=sys.stderr)
+        cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
+        counts = torch.zeros(cbl.count(), dtype=torch.int32, device=torch.device("cuda", cbl.device()))
+        total = found = 0
+        for reads in a.reads:
+            print(f"Counting the {'canonical ' if cbl.is_canonical() else ''}{a.k}-mers of {reads}", file=sys.stderr)
+            nrec = cbl.count_fastx_records(reads)  # the whole file at once: one rank, one block no smaller than the record count
+            d_bases, d_offsets, n, _ = cbl.stage_fastx_blocks(reads, max(nrec, 1), 0, 1)
+            try:
+                if n:
+                    _, t, f = cbl.abundance_seqs_device(d_bases, d_offsets, n, counts)
+                    total, found = total + t, found + f
+            finally:
+                cbl.stage_release()
+        hist = cbl.abundance_histogram(counts)
+        lines, human = abundance_report(total, found, hist)
+        print("\n".join(human), file=sys.stderr)
+        print("\n".join(lines))
+        if a.hist:
+            sys.stdout.write("".join(f"{j}\t{v}\n" for j, v in enumerate(hist.tolist())))
+        if a.gfa:
+            print(f"Writing the tagged GFA text to {a.gfa}", file=sys.stderr)
+            cbl.gfa_tagged_to_file(a.gfa, counts)
+        if a.output:
+            st = cbl.abundance_filter(counts, a.min_count, unitigs=a.unitigs)
+            print(f"Removed {st['removed_kmers']} of {st['kmers']} k-mers counted below {a.min_count}{' on average over their unitig' if a.unitigs else ''}; "
+                  f"{st['kmers_left']} k-mers are left", file=sys.stderr)
             print(f"Writing the index to {a.output}", file=sys.stderr)
             cbl.save_to_file(a.output)
             print("\n".join(f"{key}\t{value}" for key, value in st.items()))

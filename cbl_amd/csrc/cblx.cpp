@@ -8,6 +8,7 @@
 #include "comm.hpp"
 #include "host_input.hpp"
 #include "graph.hpp"
+#include "abundance.hpp"
 
 namespace {
 
@@ -1971,6 +1972,89 @@ int cblx_components_filter(cblx_ctx* c, uint64_t min_kmers, uint32_t flags, cblx
         if (stats) {
             stats->components = st[0]; stats->removed_components = st[1]; stats->removed_kmers = st[2]; stats->kmers_left = st[3]; stats->largest_kmers = st[4];
             stats->rounds = st[5];
+        }
+    });
+}
+// ---- k-mer abundances from reads: the counts are the caller's device array
+int cblx_abundance_seqs(cblx_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint64_t n, uint32_t* d_counts, uint64_t n_counts, uint64_t* total, uint64_t* found) {
+    return guard(c, [&] {
+        if (total) *total = 0;
+        if (found) *found = 0;
+        if (n == 0) { abundance_tally(c, nullptr, nullptr, nullptr, 0, d_counts, n_counts, total, found); return; }  // (the guard on n_counts still holds)
+        if (!bases || !offsets) throw Error(CBLX_EINVAL, "null argument");
+        for (u64 i = 0; i < n; ++i)
+            if (offsets[i + 1] < offsets[i]) throw Error(CBLX_EINVAL, "offsets must be non-decreasing");
+        const u64 b0 = offsets[0], nb = offsets[n] - b0;
+        Buf<u8> d_b(c->pool, nb + 64);
+        Buf<u64> d_o(c->pool, n + 1);
+        std::vector<u64> rel(n + 1);
+        for (u64 i = 0; i <= n; ++i) rel[i] = offsets[i] - b0;
+        xfer(c).h2d_copy(d_b.get(), bases + b0, nb);  // pinned lanes: the caller's buffers are pageable
+        xfer(c).h2d_copy(d_o.get(), rel.data(), (n + 1) * 8);
+        xfer(c).sync();
+        abundance_tally(c, d_b.get(), d_o.get(), rel.data(), n, d_counts, n_counts, total, found);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+int cblx_abundance_seqs_device(cblx_ctx* c, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n, uint32_t* d_counts, uint64_t n_counts, uint64_t* total,
+                               uint64_t* found) {
+    return guard(c, [&] {
+        abundance_tally(c, d_bases, d_offsets, nullptr, n, d_counts, n_counts, total, found);
+        CBLX_HIP(hipStreamSynchronize(c->stream));
+    });
+}
+int cblx_abundance_histogram(cblx_ctx* c, const uint32_t* d_counts, uint64_t n_counts, uint64_t hist[256]) {
+    return guard(c, [&] {
+        if (!hist) throw Error(CBLX_EINVAL, "null argument");
+        abundance_hist(c, d_counts, n_counts, hist);
+    });
+}
+int cblx_unitig_coverage(cblx_ctx* c, const uint32_t* d_counts, uint64_t n_counts, uint64_t* kc, uint64_t cap_unitigs, uint64_t* n_unitigs) {
+    return guard(c, [&] { unitig_kc(c, false, d_counts, n_counts, kc, cap_unitigs, n_unitigs); });
+}
+int cblx_unitig_coverage_device(cblx_ctx* c, const uint32_t* d_counts, uint64_t n_counts, uint64_t* d_kc, uint64_t cap_unitigs, uint64_t* n_unitigs) {
+    return guard(c, [&] { unitig_kc(c, true, d_counts, n_counts, d_kc, cap_unitigs, n_unitigs); });
+}
+int cblx_gfa_tagged_text_device(cblx_ctx* c, const uint32_t* d_counts, uint64_t n_counts, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs,
+                                uint64_t* n_links) {
+    return guard(c, [&] {
+        GfaText t;
+        gfa_text_tagged(c, t, d_counts, n_counts, d_buf, [&](u64 need) {
+            if (bytes) *bytes = need;
+            if (n_unitigs) *n_unitigs = t.n_unitigs;
+            if (n_links) *n_links = t.n_links;
+            if (d_buf && need > cap) throw Error(CBLX_ERANGE, "buffer too small: need " + std::to_string(need) + " bytes");
+            return d_buf != nullptr;  // null: the sizes are all that was asked for
+        });
+        collect_events(c);
+    });
+}
+int cblx_gfa_tagged_to_fd(cblx_ctx* c, const uint32_t* d_counts, uint64_t n_counts, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* n_links,
+                          uint64_t* bytes) {
+    return guard(c, [&] {
+        if (fd < 0) throw Error(CBLX_EINVAL, "bad file descriptor");
+        gfa_tagged_to_fd(c, d_counts, n_counts, fd, chunk_bytes, n_unitigs, n_links, bytes);
+    });
+}
+int cblx_gfa_tagged_to_file(cblx_ctx* c, const uint32_t* d_counts, uint64_t n_counts, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* n_links,
+                            uint64_t* bytes) {
+    return guard(c, [&] {
+        if (!path) throw Error(CBLX_EINVAL, "null argument");
+        if (d_counts) abundance_require(c, d_counts, n_counts);  // a refusal comes before the file is created or truncated
+        unitig_require(c, gfa_form(c));
+        text_to_file(path, "GFA", [&](int fd) { gfa_tagged_to_fd(c, d_counts, n_counts, fd, chunk_bytes, n_unitigs, n_links, bytes); });
+    });
+}
+int cblx_abundance_filter(cblx_ctx* c, const uint32_t* d_counts, uint64_t n_counts, uint32_t min_count, uint32_t flags, cblx_abundance_stats* stats) {
+    return guard(c, [&] {
+        if (min_count == 0) throw Error(CBLX_EINVAL, "min_count must be at least 1");
+        if (flags & ~(uint32_t)CBLX_ABUNDANCE_UNITIGS) throw Error(CBLX_EINVAL, "unknown flag bits");
+        u64 st[6];
+        try { abundance_filter(c, d_counts, n_counts, min_count, (flags & CBLX_ABUNDANCE_UNITIGS) != 0, st); } catch (...) { collect_events(c); throw; }
+        collect_events(c);
+        if (stats) {
+            stats->kmers = st[0]; stats->removed_kmers = st[1]; stats->unitigs = st[2]; stats->removed_unitigs = st[3]; stats->kmers_left = st[4];
+            stats->min_count = st[5];
         }
     });
 }

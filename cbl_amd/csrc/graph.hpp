@@ -387,7 +387,13 @@ struct GfaText {
     Buf<u8> text;
     u64 bytes = 0, n_unitigs = 0, n_links = 0;
 };
-template <typename Fits> void gfa_text(cblx_ctx* c, GfaText& t, u8* d_out, Fits&& fits) {
+// `tags`: what a caller adds to the S lines (abundance.hpp, section 6p). s_bytes(c, g, bytes) fills bytes[u] of its own S lines, or returns false: the plain
+// ones. s_tags(c, g, s_base, d_out) is queued behind the letters.
+struct GfaNoTags {
+    bool s_bytes(cblx_ctx*, const GfaRun&, u32*) { return false; }
+    void s_tags(cblx_ctx*, const GfaRun&, const u64*, u8*) {}
+};
+template <typename Fits, typename Tags = GfaNoTags> void gfa_text(cblx_ctx* c, GfaText& t, u8* d_out, Fits&& fits, Tags&& tags = Tags()) {
     GfaRun g;
     gfa_count(c, g);
     const u64 n = g.n, nu = g.n_unitigs, ns = g.slots(), K = c->P.K;
@@ -406,7 +412,7 @@ template <typename Fits> void gfa_text(cblx_ctx* c, GfaText& t, u8* d_out, Fits&
         CBLX_HIP(hipGetLastError());
         t.n_links = exclusive_scan<u64>(c, lines.get(), ns, l_base.get());
         l_bytes = exclusive_scan<u64>(c, bytes.get(), ns, l_base.get());
-        hipLaunchKernelGGL(k_gfa_s_bytes, grid1(nu, 256), b256, 0, c->stream, (const u32*)g.length.get(), nu, (u32)K, bytes.get());
+        if (!tags.s_bytes(c, g, bytes.get())) hipLaunchKernelGGL(k_gfa_s_bytes, grid1(nu, 256), b256, 0, c->stream, (const u32*)g.length.get(), nu, (u32)K, bytes.get());
         CBLX_HIP(hipGetLastError());
         s_bytes = exclusive_scan<u64>(c, bytes.get(), nu, s_base.get());
     }
@@ -418,6 +424,7 @@ template <typename Fits> void gfa_text(cblx_ctx* c, GfaText& t, u8* d_out, Fits&
                               (const u64*)l_base.get(), ns, bi, (u32)(K - 1), GFA_HEADER_BYTES + s_bytes, d_out);
     CBLX_HIP(hipGetLastError());
     if (n) unitig_lines(c, n, g.unitig.get(), g.offset.get(), g.reversed.get(), g.length.get(), s_base.get(), d_out);
+    if (n) tags.s_tags(c, g, s_base.get(), d_out);
     CBLX_HIP(hipStreamSynchronize(c->stream));  // the tables die here
 }
 // `cbl unitigs --gfa`: the text is built once on the device and leaves as the unitig text does

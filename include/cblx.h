@@ -39,7 +39,9 @@ extern "C" {
  * cblx_biunitig_table, cblx_biunitig_table_device, cblx_biunitigs_text_device, cblx_biunitigs_to_fd and cblx_biunitigs_to_file;
  * cblx_gfa_links, cblx_gfa_links_device, cblx_gfa_text_device, cblx_gfa_to_fd and cblx_gfa_to_file;
  * cblx_unitig_ends, cblx_unitig_ends_device, cblx_tips_mark, cblx_tips_mark_device and cblx_clip_tips with cblx_clip_stats and CBLX_CLIP_ISOLATED;
- * cblx_components, cblx_components_device and cblx_components_filter with cblx_component_stats and CBLX_COMPONENTS_LARGEST. */
+ * cblx_components, cblx_components_device and cblx_components_filter with cblx_component_stats and CBLX_COMPONENTS_LARGEST;
+ * cblx_abundance_seqs, cblx_abundance_seqs_device, cblx_abundance_histogram, cblx_unitig_coverage, cblx_unitig_coverage_device, cblx_gfa_tagged_text_device,
+ * cblx_gfa_tagged_to_fd, cblx_gfa_tagged_to_file and cblx_abundance_filter with cblx_abundance_stats and CBLX_ABUNDANCE_UNITIGS. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -641,6 +643,48 @@ int cblx_components_device(cblx_ctx* ctx, uint32_t* d_component, uint64_t cap_un
 #define CBLX_COMPONENTS_LARGEST 1u
 typedef struct cblx_component_stats { uint64_t components, removed_components, removed_kmers, kmers_left, largest_kmers, rounds; } cblx_component_stats;
 int cblx_components_filter(cblx_ctx* ctx, uint64_t min_kmers, uint32_t flags, cblx_component_stats* stats);
+/* ---- k-mer abundances from reads. The index stays a set: the counts belong to the CALLER, a DEVICE array `d_counts` of n_counts
+ * uint32, one per stored k-mer by ORDINAL (its index in the iteration order of the moment, as in cblx_rank_kmers). Every call applies pending inserts first and
+ * then refuses n_counts != the number of stored k-mers with CBLX_EINVAL and nothing written or removed: the guard against an array from before a change of
+ * the index. Nothing in the index is modified or sorted by the observers: cblx_serialize gives the same bytes afterwards.
+ *   occurrence   one k-mer of the batch as cblx_contains_seqs enumerates it: sequence after sequence, get_seq_words order; bytes that are not ACGT are skipped
+ *                as there; a sequence shorter than K gives none (it is not refused); a canonical index counts both strands for the one stored k-mer
+ *   tally        d_counts[i] = min(2^32 - 1, d_counts[i] + occ_i), occ_i = the occurrences whose word has ordinal i. The call ACCUMULATES; the caller zeroes.
+ *                *total = the occurrences, *found = those the index holds. `bases` / `offsets` are host arrays in cblx_abundance_seqs and device arrays (d_bases
+ *                16-byte aligned) in the _device form, with the conventions of cblx_contains_seqs*; a batch takes fewer than 2^32 - 16 k-mers (CBLX_ERANGE,
+ *                nothing written). An empty index with n_counts == 0 tallies nothing: *found = 0.
+ *   spectrum     hist[j] (256 uint64 on the host) = the ordinals with d_counts[i] == j for j < 255; hist[255] = those with d_counts[i] >= 255 */
+int cblx_abundance_seqs(cblx_ctx* ctx, const uint8_t* bases, const uint64_t* offsets, uint64_t n, uint32_t* d_counts, uint64_t n_counts, uint64_t* total,
+                        uint64_t* found);
+int cblx_abundance_seqs_device(cblx_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n, uint32_t* d_counts, uint64_t n_counts, uint64_t* total,
+                               uint64_t* found);
+int cblx_abundance_histogram(cblx_ctx* ctx, const uint32_t* d_counts, uint64_t n_counts, uint64_t hist[256]);
+/* Unitig coverage. The form follows the index as in cblx_gfa_links: unitig numbers, lengths and the refusals are those of cblx_unitig_table (a non-canonical
+ * index) or cblx_biunitig_table (a canonical one). kc[u] (uint64; a host array, a device array in the _device form) = the sum of d_counts[i] over the k-mers of
+ * unitig u, so the sum of kc is the sum of the counts and kc[u] <= length[u] (2^32 - 1); mean coverage is kc[u] / length[u]. *n_unitigs = U is always set. A NULL
+ * kc only counts; cap_unitigs < U with kc given is CBLX_ERANGE with the need reported and nothing written. */
+int cblx_unitig_coverage(cblx_ctx* ctx, const uint32_t* d_counts, uint64_t n_counts, uint64_t* kc, uint64_t cap_unitigs, uint64_t* n_unitigs);
+int cblx_unitig_coverage_device(cblx_ctx* ctx, const uint32_t* d_counts, uint64_t n_counts, uint64_t* d_kc, uint64_t cap_unitigs, uint64_t* n_unitigs);
+/* The GFA text of cblx_gfa_text_device byte for byte, except that every S line reads "S\t<u>\t<letters>\tLN:i:<length[u] + K - 1>\tKC:i:<kc[u]>\n" (decimal without
+ * padding). With d_counts NULL the KC tag and its tab are absent, LN stays, and n_counts is not looked at. The H line and the L lines are as they were, and
+ * *n_links keeps its meaning. The other parameters as in cblx_gfa_text_device / cblx_gfa_to_fd / cblx_gfa_to_file; a refused cblx_gfa_tagged_to_file does not
+ * create the file. */
+int cblx_gfa_tagged_text_device(cblx_ctx* ctx, const uint32_t* d_counts, uint64_t n_counts, uint8_t* d_buf, uint64_t cap, uint64_t* bytes, uint64_t* n_unitigs,
+                                uint64_t* n_links);
+int cblx_gfa_tagged_to_fd(cblx_ctx* ctx, const uint32_t* d_counts, uint64_t n_counts, int fd, uint64_t chunk_bytes, uint64_t* n_unitigs, uint64_t* n_links,
+                          uint64_t* bytes);
+int cblx_gfa_tagged_to_file(cblx_ctx* ctx, const uint32_t* d_counts, uint64_t n_counts, const char* path, uint64_t chunk_bytes, uint64_t* n_unitigs,
+                            uint64_t* n_links, uint64_t* bytes);
+/* Removes the weakly supported k-mers, min_count >= 1. K-mer rule (flags == 0): every ordinal with d_counts[i] < min_count; it works on any index and runs no
+ * compaction (unitigs and removed_unitigs stay 0). Unitig rule (CBLX_ABUNDANCE_UNITIGS): every k-mer of every unitig with kc[u] < min_count * length[u], that is
+ * mean coverage below min_count in integers. The selected k-mers are taken in iteration order and their words removed as ONE WordSet::remove_batch, as a round
+ * of cblx_clip_tips does. d_counts is read, never written; after a call that removed something it no longer matches the index (a Vec bucket loses by
+ * swap_remove, so ordinals move): tally again — the n_counts guard refuses the stale array. `stats` may be NULL; kmers is the count before. min_count == 0,
+ * unknown flag bits and n_counts != the stored k-mers are CBLX_EINVAL with nothing removed; the form's refusals (unitig rule only) come before anything changes.
+ * An empty index: all-zero stats. */
+#define CBLX_ABUNDANCE_UNITIGS 1u
+typedef struct cblx_abundance_stats { uint64_t kmers, removed_kmers, unitigs, removed_unitigs, kmers_left, min_count; } cblx_abundance_stats;
+int cblx_abundance_filter(cblx_ctx* ctx, const uint32_t* d_counts, uint64_t n_counts, uint32_t min_count, uint32_t flags, cblx_abundance_stats* stats);
 /* CBL::buckets_nodes (src/cbl.rs:386-390): per non-empty prefix ascending, TrieVec::count_nodes (src/trievec/mod.rs:37-42) — a Vec's length, a Trie's
  * nodes (src/trie.rs:90-102: the root and one node per distinct proper byte prefix of its suffixes). Pairs with cblx_bucket_sizes. */
 int cblx_bucket_nodes(cblx_ctx* ctx, uint64_t* nodes, uint64_t cap, uint64_t* n);

@@ -364,6 +364,20 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         stats
     }
 
+    /// Removes the weakly supported k-mers on the device as one batch. `d_counts` is the caller's device array of `n_counts` = `count()`
+    /// abundances, one `u32` per stored k-mer by ordinal (what `cblx_abundance_seqs*` tallied). Every k-mer counted fewer than `min_count`
+    /// (at least 1) times goes, or with `unitigs` every k-mer of every unitig whose mean count is below `min_count`. The array is only read,
+    /// and no longer matches the index after a call that removed something.
+    ///
+    /// # Safety
+    /// `d_counts` must be a device allocation of at least `n_counts` `u32` on the index's device.
+    pub unsafe fn abundance_filter(&mut self, d_counts: *const u32, n_counts: u64, min_count: u32, unitigs: bool) -> sys::cblx_abundance_stats {
+        let mut stats = sys::cblx_abundance_stats::default();
+        let flags = if unitigs { sys::CBLX_ABUNDANCE_UNITIGS } else { 0 };
+        self.check(sys::cblx_abundance_filter(self.ctx, d_counts, n_counts, min_count, flags, &mut stats));
+        stats
+    }
+
     /// Adds a k-mer; returns `true` if it was absent (`src/cbl.rs:226-228`). One device round trip per call: a caller with
     /// many k-mers uses `insert_kmers`.
     #[inline]

@@ -32,6 +32,7 @@ pub const CBLX_SETOP_MAX_OPERANDS: u32 = 64;
 pub const CBLX_COMMON_STATS: u32 = 5;
 pub const CBLX_CLIP_ISOLATED: u32 = 1;
 pub const CBLX_COMPONENTS_LARGEST: u32 = 1;
+pub const CBLX_ABUNDANCE_UNITIGS: u32 = 1;
 
 #[repr(C)]
 pub struct cblx_ctx {
@@ -127,6 +128,17 @@ pub struct cblx_component_stats {
     pub kmers_left: u64,
     pub largest_kmers: u64,
     pub rounds: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct cblx_abundance_stats {
+    pub kmers: u64,
+    pub removed_kmers: u64,
+    pub unitigs: u64,
+    pub removed_unitigs: u64,
+    pub kmers_left: u64,
+    pub min_count: u64,
 }
 
 #[repr(C)]
@@ -444,6 +456,15 @@ extern "C" {
     pub fn cblx_components(ctx: *mut cblx_ctx, component: *mut u32, cap_unitigs: u64, kmer_component: *mut u32, cap_kmers: u64, first: *mut u32, unitigs: *mut u32, kmers: *mut u64, cap_components: u64, counts: *mut u64) -> c_int;
     pub fn cblx_components_device(ctx: *mut cblx_ctx, d_component: *mut u32, cap_unitigs: u64, d_kmer_component: *mut u32, cap_kmers: u64, d_first: *mut u32, d_unitigs: *mut u32, d_kmers: *mut u64, cap_components: u64, counts: *mut u64) -> c_int;
     pub fn cblx_components_filter(ctx: *mut cblx_ctx, min_kmers: u64, flags: u32, stats: *mut cblx_component_stats) -> c_int;
+    pub fn cblx_abundance_seqs(ctx: *mut cblx_ctx, bases: *const u8, offsets: *const u64, n: u64, d_counts: *mut u32, n_counts: u64, total: *mut u64, found: *mut u64) -> c_int;
+    pub fn cblx_abundance_seqs_device(ctx: *mut cblx_ctx, d_bases: *const u8, d_offsets: *const u64, n: u64, d_counts: *mut u32, n_counts: u64, total: *mut u64, found: *mut u64) -> c_int;
+    pub fn cblx_abundance_histogram(ctx: *mut cblx_ctx, d_counts: *const u32, n_counts: u64, hist: *mut u64) -> c_int;
+    pub fn cblx_unitig_coverage(ctx: *mut cblx_ctx, d_counts: *const u32, n_counts: u64, kc: *mut u64, cap_unitigs: u64, n_unitigs: *mut u64) -> c_int;
+    pub fn cblx_unitig_coverage_device(ctx: *mut cblx_ctx, d_counts: *const u32, n_counts: u64, d_kc: *mut u64, cap_unitigs: u64, n_unitigs: *mut u64) -> c_int;
+    pub fn cblx_gfa_tagged_text_device(ctx: *mut cblx_ctx, d_counts: *const u32, n_counts: u64, d_buf: *mut u8, cap: u64, bytes: *mut u64, n_unitigs: *mut u64, n_links: *mut u64) -> c_int;
+    pub fn cblx_gfa_tagged_to_fd(ctx: *mut cblx_ctx, d_counts: *const u32, n_counts: u64, fd: c_int, chunk_bytes: u64, n_unitigs: *mut u64, n_links: *mut u64, bytes: *mut u64) -> c_int;
+    pub fn cblx_gfa_tagged_to_file(ctx: *mut cblx_ctx, d_counts: *const u32, n_counts: u64, path: *const c_char, chunk_bytes: u64, n_unitigs: *mut u64, n_links: *mut u64, bytes: *mut u64) -> c_int;
+    pub fn cblx_abundance_filter(ctx: *mut cblx_ctx, d_counts: *const u32, n_counts: u64, min_count: u32, flags: u32, stats: *mut cblx_abundance_stats) -> c_int;
     pub fn cblx_list_range(ctx: *mut cblx_ctx, first: u64, n: u64, buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_range_device(ctx: *mut cblx_ctx, first: u64, n: u64, d_buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_kmers: u64, n_kmers: *mut u64) -> c_int;
