@@ -86,6 +86,13 @@ class AbundanceStats(C.Structure):
 
 ABUNDANCE_UNITIGS = 1  # CBLX_ABUNDANCE_UNITIGS of include/cblx.h
 
+
+class BubbleStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("rounds", "bubbles", "popped", "popped_kmers", "kmers_left", "fixpoint")]
+
+
+BUBBLE_COUNTS = ("bubbles", "popped", "popped_kmers")
+
 BUCKET_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 
 ABI_VERSION = 3  # include/cblx.h CBLX_ABI_VERSION
@@ -240,6 +247,9 @@ SIGNATURES = {
     "cblx_gfa_tagged_to_file": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_uint64)]),
     "cblx_abundance_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(AbundanceStats)]),
+    "cblx_bubbles_mark": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_bubbles_mark_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cblx_pop_bubbles": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(BubbleStats)]),
     "cblx_list_range": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_range_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cblx_list_to_fd": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -1646,6 +1656,91 @@ class CBL:
         st = AbundanceStats()
         self._chk(self._L.cblx_abundance_filter(self._h, p, m, int(min_count), ABUNDANCE_UNITIGS if unitigs else 0, C.byref(st)))
         return {name: int(getattr(st, name)) for name, _ in AbundanceStats._fields_}
+
+    # ---- bubble popping on the compacted graph; the form follows the index ------------------------------------------
+    def _bubble_max(self, max_kmers):
+        return 2 * self.k if max_kmers is None else int(max_kmers)
+
+    def _bubbles_mark(self, device: bool, max_kmers, counts=None, kind=None, cap: int = 0):
+        p, m = self._counts_or_none(counts)
+        u, out = C.c_uint64(0), (C.c_uint64 * 3)()
+        fn = self._L.cblx_bubbles_mark_device if device else self._L.cblx_bubbles_mark
+        self._chk(fn(self._h, self._bubble_max(max_kmers), p, m, _ptr(kind), cap, C.byref(u), out))
+        return u.value, dict(zip(BUBBLE_COUNTS, (int(v) for v in out)))
+
+    def bubble_counts(self, max_kmers=None, counts=None) -> dict:
+        """bubbles, popped, popped_kmers of bubbles_np, and n_unitigs: the marks are made on the device, four numbers come back."""
+        u, out = self._bubbles_mark(False, max_kmers, counts)
+        return dict(out, n_unitigs=u)
+
+    def bubbles_np(self, max_kmers=None, counts=None):
+        """(kind, counts_dict). `kind` (uint8 per unitig of the index's compaction table) marks the simple bubbles of the compacted graph: arms are
+        unitigs of at most max_kmers k-mers (None: 2 K — the arms of a SNP have K k-mers, those of a small indel a few more) with one link in and one
+        link out, and the arms that share their source and their target are a group. In a group of two or more, kind = 2 (kept) for the arm of the
+        highest mean coverage kc / length under `counts` (a tensor as abundance_seqs fills it; ties and counts=None: the longest, then the lowest
+        number) and 1 (popped) for the others; 0 elsewhere. counts_dict: bubbles (kept arms), popped, popped_kmers, n_unitigs."""
+        import numpy as np
+
+        u, _ = self._bubbles_mark(False, max_kmers, counts)
+        kind = np.zeros(max(u, 1), dtype=np.uint8)
+        u, out = self._bubbles_mark(False, max_kmers, counts, kind, max(u, 1))
+        return kind[:u], dict(out, n_unitigs=u)
+
+    def bubbles_mark_device(self, max_kmers=None, counts=None, d_kind=None, cap: int = 0) -> dict:
+        """The marks into d_kind (a torch uint8 CUDA tensor or raw device address of `cap` elements; None: counts only); returns the counts of
+        bubble_counts. A capacity too small raises CblxError(ERANGE) and leaves d_kind untouched."""
+        u, out = self._bubbles_mark(True, max_kmers, counts, d_kind, cap)
+        return dict(out, n_unitigs=u)
+
+    @staticmethod
+    def bubble_kinds(link_start, link_to, link_rev, length, left, kc, max_kmers: int):
+        """The rule of bubbles_np restated on the arrays of gfa_links_np and a compaction table's `length` (host only): a uint8 array of kinds.
+        `left` (unitig_ends_np) is given for a non-canonical index and None for a canonical one, where the in-degree of an image is the out-degree
+        of its other image; `kc` (unitig_coverage_np) or None for the length rule."""
+        import numpy as np
+
+        if max_kmers < 1:
+            raise ValueError("bubble_kinds: max_kmers is at least 1")
+        start = [int(v) for v in link_start]
+        to, rev, length = [int(v) for v in link_to], [int(v) for v in link_rev], [int(v) for v in length]
+        cov = None if kc is None else [int(v) for v in kc]
+        links = lambda x: [2 * to[j] + rev[j] for j in range(start[x], start[x + 1])]  # noqa: E731
+        indeg = (lambda x: start[(x ^ 1) + 1] - start[x ^ 1]) if left is None else (lambda x: int(left[x >> 1]))
+        groups = {}
+        for a in range(len(start) - 1):
+            for x in links(a):
+                p = x >> 1
+                if indeg(x) != 1 or len(links(x)) != 1 or length[p] > max_kmers:
+                    continue
+                t = links(x)[0]
+                if p in (a >> 1, t >> 1):
+                    continue
+                key = (a, t) if left is not None else min((a, t), (t ^ 1, a ^ 1))
+                groups.setdefault(key, set()).add(p)
+
+        def above(u, v):
+            if cov is not None and cov[u] * length[v] != cov[v] * length[u]:
+                return cov[u] * length[v] > cov[v] * length[u]
+            return (length[u], -u) > (length[v], -v)
+
+        kind = np.zeros(len(length), dtype=np.uint8)
+        for members in groups.values():
+            if len(members) >= 2:
+                for u in members:
+                    kind[u] = 1 if any(above(v, u) for v in members if v != u) else 2
+        return kind
+
+    def pop_bubbles(self, max_kmers=None, counts=None, rounds: int = 1):
+        """Removes the k-mers of the popped arms (bubbles_np) from the index, on the device: a round compacts, marks and removes every popped arm of
+        that compaction as one batch. `rounds` = 0 repeats until a round pops nothing. Returns rounds (compactions run), bubbles, popped,
+        popped_kmers (what was removed), kmers_left and fixpoint (1 when the last round popped nothing). With `counts` the coverage rule decides
+        and the tensor is carried through the removals in place: returns (stats, counts[:kmers_left]), a view of the caller's tensor whose element
+        j is the count of the k-mer of the new ordinal j; the elements behind it are 0."""
+        p, m = self._counts_or_none(counts)
+        st = BubbleStats()
+        self._chk(self._L.cblx_pop_bubbles(self._h, self._bubble_max(max_kmers), p, m, 0, int(rounds), C.byref(st)))
+        out = {name: int(getattr(st, name)) for name, _ in BubbleStats._fields_}
+        return out if counts is None else (out, counts[: out["kmers_left"]])
 
     @staticmethod
     def solid_threshold(hist):

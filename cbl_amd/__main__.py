@@ -5,7 +5,8 @@ containment of every pair of two or more index files; `classify` assigns every r
 the degree table of the de Bruijn graph whose nodes are the k-mers of an index; `unitigs` writes the non-branching paths of that graph, one line each
 (of a canonical index: the bidirected unitigs); `clip` removes the short dead-end unitigs (tips) of that graph from an index; `components`
 prints the connected components of that graph, or removes the small ones (or all but the largest) from an index; `abundance` counts how often
-the reads of FASTA/Q files hold every k-mer of an index, and prints the spectrum, writes the GFA text with LN / KC tags or removes the weak k-mers.
+the reads of FASTA/Q files hold every k-mer of an index, and prints the spectrum, writes the GFA text with LN / KC tags or removes the weak k-mers; `pop`
+removes the weaker arms of the simple bubbles of that graph from an index, judged by the coverage of reads where they are given, by length otherwise.
 
 K and PREFIX_BITS are compile-time constants of the reference (env K / PREFIX_BITS at cargo build time, build.rs:9-56);
 here they are flags with the same defaults (K=25, PREFIX_BITS=24). Index files are interchangeable with the reference's.
@@ -245,7 +246,17 @@ def main(argv=None):
     ab.add_argument("--unitigs", action="store_true", help="with --min-count: remove whole unitigs, those whose mean count is below N")
     ab.add_argument("-o", "--output", help="write the filtered index to OUT (needs --min-count)")
     ab.add_argument("--gfa", metavar="OUT.gfa", help="write the compacted graph of the index as loaded as GFA 1.0 with LN:i: and KC:i: tags on the S lines")
+    pb = sub.add_parser("pop", help="Pop the simple bubbles of an index: where two to four unitigs of at most N k-mers each lead from one end of a unitig to "
+                                    "the same end of another, keep the one of the highest mean coverage in the reads (without reads: the longest) and "
+                                    "remove the others. A round removes every such arm of one compaction together")
+    pb.add_argument("index")
+    pb.add_argument("reads", nargs="*", help="FASTA/Q files, tallied one after the other into one array of counts; none: the longer arm is kept")
+    pb.add_argument("-o", "--output", required=True)
+    pb.add_argument("--max-kmers", type=int, default=None, metavar="N", help="the longest unitig that counts as an arm, in k-mers (default: 2 K)")
+    pb.add_argument("--rounds", type=int, default=1, metavar="R", help="compact and pop up to R times (default 1); 0: until a round pops nothing")
     a = ap.parse_args(argv)
+    if a.cmd == "pop" and ((a.max_kmers is not None and a.max_kmers < 1) or a.rounds < 0):  # refused before anything is loaded
+        ap.error("pop: --max-kmers is at least 1 and --rounds at least 0")
     if a.cmd == "abundance":  # refused before anything is loaded
         if a.min_count is not None and a.min_count < 1:
             ap.error("abundance: --min-count is at least 1")
@@ -490,6 +501,34 @@ def main(argv=None):
             print(f"Writing the index to {a.output}", file=sys.stderr)
             cbl.save_to_file(a.output)
             print("\n".join(f"{key}\t{value}" for key, value in st.items()))
+
+    elif a.cmd == "pop":  # ours (the reference's CLI has no such command): the removal is one WordSet::remove_batch per round (src/wordset/mod.rs:218-237)
+        if a.reads:
+            import torch  # (before the index is loaded, as in `abundance`: the counts are a torch tensor)
+
+        print(f"Reading the index stored in {a.index}", file=sys.stderr)
+        cbl = CBL.load_from_file(a.index, a.k, a.prefix_bits, device=a.device)
+        counts = None
+        if a.reads:
+            counts = torch.zeros(cbl.count(), dtype=torch.int32, device=torch.device("cuda", cbl.device()))
+            for reads in a.reads:
+                print(f"Counting the {'canonical ' if cbl.is_canonical() else ''}{a.k}-mers of {reads}", file=sys.stderr)
+                nrec = cbl.count_fastx_records(reads)  # the whole file at once, as `abundance` stages it
+                d_bases, d_offsets, n, _ = cbl.stage_fastx_blocks(reads, max(nrec, 1), 0, 1)
+                try:
+                    if n:
+                        cbl.abundance_seqs_device(d_bases, d_offsets, n, counts)
+                finally:
+                    cbl.stage_release()
+        print(f"Popping the bubbles of the {'canonical ' if cbl.is_canonical() else ''}{a.k}-mers contained in {a.index}, by "
+              f"{'coverage' if a.reads else 'length'}", file=sys.stderr)
+        st = cbl.pop_bubbles(a.max_kmers, counts, rounds=a.rounds)
+        st = st[0] if a.reads else st
+        print(f"{st['rounds']} rounds popped {st['popped']} arms of {st['popped_kmers']} k-mers in {st['bubbles']} bubbles; {st['kmers_left']} k-mers are "
+              f"left{'' if st['fixpoint'] else ' (bubbles may remain)'}", file=sys.stderr)
+        print(f"Writing the index to {a.output}", file=sys.stderr)
+        cbl.save_to_file(a.output)
+        print("\n".join(f"{key}\t{value}" for key, value in st.items()))
 
 
 if __name__ == "__main__":

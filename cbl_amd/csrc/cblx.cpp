@@ -9,6 +9,7 @@
 #include "host_input.hpp"
 #include "graph.hpp"
 #include "abundance.hpp"
+#include "bubbles.hpp"
 
 namespace {
 
@@ -2055,6 +2056,27 @@ int cblx_abundance_filter(cblx_ctx* c, const uint32_t* d_counts, uint64_t n_coun
         if (stats) {
             stats->kmers = st[0]; stats->removed_kmers = st[1]; stats->unitigs = st[2]; stats->removed_unitigs = st[3]; stats->kmers_left = st[4];
             stats->min_count = st[5];
+        }
+    });
+}
+// ---- bubble popping ----
+int cblx_bubbles_mark(cblx_ctx* c, uint64_t max_kmers, const uint32_t* d_counts, uint64_t n_counts, uint8_t* kind, uint64_t cap_unitigs, uint64_t* n_unitigs,
+                      uint64_t counts[3]) {
+    return guard(c, [&] { bubbles_observe(c, false, max_kmers, d_counts, n_counts, kind, cap_unitigs, n_unitigs, counts); });
+}
+int cblx_bubbles_mark_device(cblx_ctx* c, uint64_t max_kmers, const uint32_t* d_counts, uint64_t n_counts, uint8_t* d_kind, uint64_t cap_unitigs,
+                             uint64_t* n_unitigs, uint64_t counts[3]) {
+    return guard(c, [&] { bubbles_observe(c, true, max_kmers, d_counts, n_counts, d_kind, cap_unitigs, n_unitigs, counts); });
+}
+int cblx_pop_bubbles(cblx_ctx* c, uint64_t max_kmers, uint32_t* d_counts, uint64_t n_counts, uint32_t flags, uint32_t max_rounds, cblx_bubble_stats* stats) {
+    return guard(c, [&] {
+        if (max_kmers == 0) throw Error(CBLX_EINVAL, "max_kmers must be at least 1");
+        if (flags != 0) throw Error(CBLX_EINVAL, "unknown flag bits");
+        u64 st[6];
+        try { pop_bubbles(c, max_kmers, d_counts, n_counts, max_rounds, st); } catch (...) { collect_events(c); throw; }
+        collect_events(c);
+        if (stats) {
+            stats->rounds = st[0]; stats->bubbles = st[1]; stats->popped = st[2]; stats->popped_kmers = st[3]; stats->kmers_left = st[4]; stats->fixpoint = st[5];
         }
     });
 }

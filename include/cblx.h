@@ -41,7 +41,8 @@ extern "C" {
  * cblx_unitig_ends, cblx_unitig_ends_device, cblx_tips_mark, cblx_tips_mark_device and cblx_clip_tips with cblx_clip_stats and CBLX_CLIP_ISOLATED;
  * cblx_components, cblx_components_device and cblx_components_filter with cblx_component_stats and CBLX_COMPONENTS_LARGEST;
  * cblx_abundance_seqs, cblx_abundance_seqs_device, cblx_abundance_histogram, cblx_unitig_coverage, cblx_unitig_coverage_device, cblx_gfa_tagged_text_device,
- * cblx_gfa_tagged_to_fd, cblx_gfa_tagged_to_file and cblx_abundance_filter with cblx_abundance_stats and CBLX_ABUNDANCE_UNITIGS. */
+ * cblx_gfa_tagged_to_fd, cblx_gfa_tagged_to_file and cblx_abundance_filter with cblx_abundance_stats and CBLX_ABUNDANCE_UNITIGS;
+ * cblx_bubbles_mark, cblx_bubbles_mark_device and cblx_pop_bubbles with cblx_bubble_stats. */
 #define CBLX_ABI_VERSION 3
 
 enum {
@@ -685,6 +686,31 @@ int cblx_gfa_tagged_to_file(cblx_ctx* ctx, const uint32_t* d_counts, uint64_t n_
 #define CBLX_ABUNDANCE_UNITIGS 1u
 typedef struct cblx_abundance_stats { uint64_t kmers, removed_kmers, unitigs, removed_unitigs, kmers_left, min_count; } cblx_abundance_stats;
 int cblx_abundance_filter(cblx_ctx* ctx, const uint32_t* d_counts, uint64_t n_counts, uint32_t min_count, uint32_t flags, cblx_abundance_stats* stats);
+/* ---- bubble popping on the compacted graph. The form, the unitig numbers, `length`, the slots and the link table are those of
+ * cblx_gfa_links; kc is cblx_unitig_coverage's. For an image slot x = 2 p + s: out(x) = the links of slot x, in(x) = the in-degree of that image's head (the
+ * links of slot x ^ 1 in the bidirected form, `left` of cblx_unitig_ends in the plain one). Image x of unitig p is a qualified arm from source slot a to target
+ * slot T when a -> x is a link, in(x) == out(x) == 1, the one link of x enters T, length[p] <= max_kmers, and p is neither the unitig of a nor that of T. The
+ * qualified arms that share (a, T) form a group of distinct unitigs (at most 4; in the bidirected form (a, T) and its mirror (T ^ 1, a ^ 1) are one group, and a
+ * unitig is never compared with its own other image). With counts (d_counts: one uint32 per stored k-mer by ordinal, n_counts == the stored k-mers, as in
+ * cblx_abundance_seqs) u ranks above v when kc[u] length[v] > kc[v] length[u] (mean coverage, compared exactly in 128-bit integers), then when it is longer,
+ * then when u < v; d_counts == NULL with n_counts == 0 selects the length rule, which starts at the second clause. kind[u] = 2 (kept) when u is in a group of
+ * two or more unitigs and ranks above all the others, 1 (popped) when another member ranks above it, 0 elsewhere: every such group has exactly one kept arm.
+ * counts = { kept arms, popped arms, the k-mers of the popped arms }, always reported. kind may be NULL (counts only); cap_unitigs below the unitigs is
+ * CBLX_ERANGE with the need in *n_unitigs and nothing written. The index is not modified. max_kmers == 0, NULL counts with n_counts != 0 and n_counts != the
+ * stored k-mers are CBLX_EINVAL. */
+int cblx_bubbles_mark(cblx_ctx* ctx, uint64_t max_kmers, const uint32_t* d_counts, uint64_t n_counts, uint8_t* kind, uint64_t cap_unitigs, uint64_t* n_unitigs,
+                      uint64_t counts[3]);
+int cblx_bubbles_mark_device(cblx_ctx* ctx, uint64_t max_kmers, const uint32_t* d_counts, uint64_t n_counts, uint8_t* d_kind, uint64_t cap_unitigs,
+                             uint64_t* n_unitigs, uint64_t counts[3]);
+/* Pops the bubbles: a round compacts, marks, takes the k-mers of ALL popped arms of that compaction in iteration order and removes their words as ONE
+ * WordSet::remove_batch, as a round of cblx_clip_tips does. max_rounds = 0 repeats until a round pops nothing. stats (may be NULL): rounds = compactions run,
+ * bubbles / popped / popped_kmers = what was removed, summed over the rounds, kmers_left, fixpoint = 1 when the last round popped nothing; an empty index gives
+ * rounds = 1, fixpoint = 1. With counts the array is carried: behind every removing round d_counts[j], j < kmers_left, is the count the surviving k-mer of NEW
+ * ordinal j had before, and the elements from kmers_left up to the n_counts given are 0; the caller goes on with n_counts = kmers_left. A call that removes
+ * nothing does not write the array. flags must be 0. max_kmers == 0, flags != 0, NULL counts with n_counts != 0 and n_counts != the stored k-mers are
+ * CBLX_EINVAL with nothing changed; the form's refusals come from the first compaction, before anything changes. */
+typedef struct cblx_bubble_stats { uint64_t rounds, bubbles, popped, popped_kmers, kmers_left, fixpoint; } cblx_bubble_stats;
+int cblx_pop_bubbles(cblx_ctx* ctx, uint64_t max_kmers, uint32_t* d_counts, uint64_t n_counts, uint32_t flags, uint32_t max_rounds, cblx_bubble_stats* stats);
 /* CBL::buckets_nodes (src/cbl.rs:386-390): per non-empty prefix ascending, TrieVec::count_nodes (src/trievec/mod.rs:37-42) — a Vec's length, a Trie's
  * nodes (src/trie.rs:90-102: the root and one node per distinct proper byte prefix of its suffixes). Pairs with cblx_bucket_sizes. */
 int cblx_bucket_nodes(cblx_ctx* ctx, uint64_t* nodes, uint64_t cap, uint64_t* n);

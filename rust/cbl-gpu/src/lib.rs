@@ -378,6 +378,20 @@ impl<const K: usize, T: PackedInt, const PREFIX_BITS: usize> CBL<K, T, PREFIX_BI
         stats
     }
 
+    /// Pops the simple bubbles of the compacted graph on the device: where two to four unitigs of at most `max_kmers` k-mers lead from one unitig end
+    /// to the same other end, the one of the highest mean coverage stays and the others are removed, every popped arm of a compaction as one batch;
+    /// `rounds` = 0 repeats until a round pops nothing. `d_counts` is the caller's device array of `n_counts` = `count()` abundances (what
+    /// `cblx_abundance_seqs*` tallied), carried in place through every removal: afterwards its first `kmers_left` elements are the counts of the
+    /// survivors by their new ordinals and the rest is 0. A null `d_counts` with `n_counts` = 0 keeps the longest arm instead.
+    ///
+    /// # Safety
+    /// `d_counts` must be null or a device allocation of at least `n_counts` `u32` on the index's device.
+    pub unsafe fn pop_bubbles(&mut self, max_kmers: u64, d_counts: *mut u32, n_counts: u64, rounds: u32) -> sys::cblx_bubble_stats {
+        let mut stats = sys::cblx_bubble_stats::default();
+        self.check(sys::cblx_pop_bubbles(self.ctx, max_kmers, d_counts, n_counts, 0, rounds, &mut stats));
+        stats
+    }
+
     /// Adds a k-mer; returns `true` if it was absent (`src/cbl.rs:226-228`). One device round trip per call: a caller with
     /// many k-mers uses `insert_kmers`.
     #[inline]

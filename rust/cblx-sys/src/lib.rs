@@ -143,6 +143,17 @@ pub struct cblx_abundance_stats {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
+pub struct cblx_bubble_stats {
+    pub rounds: u64,
+    pub bubbles: u64,
+    pub popped: u64,
+    pub popped_kmers: u64,
+    pub kmers_left: u64,
+    pub fixpoint: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
 pub struct cblx_consts {
     pub kmer_bits: u32,
     pub pos_bits: u32,
@@ -465,6 +476,9 @@ extern "C" {
     pub fn cblx_gfa_tagged_to_fd(ctx: *mut cblx_ctx, d_counts: *const u32, n_counts: u64, fd: c_int, chunk_bytes: u64, n_unitigs: *mut u64, n_links: *mut u64, bytes: *mut u64) -> c_int;
     pub fn cblx_gfa_tagged_to_file(ctx: *mut cblx_ctx, d_counts: *const u32, n_counts: u64, path: *const c_char, chunk_bytes: u64, n_unitigs: *mut u64, n_links: *mut u64, bytes: *mut u64) -> c_int;
     pub fn cblx_abundance_filter(ctx: *mut cblx_ctx, d_counts: *const u32, n_counts: u64, min_count: u32, flags: u32, stats: *mut cblx_abundance_stats) -> c_int;
+    pub fn cblx_bubbles_mark(ctx: *mut cblx_ctx, max_kmers: u64, d_counts: *const u32, n_counts: u64, kind: *mut u8, cap_unitigs: u64, n_unitigs: *mut u64, counts: *mut u64) -> c_int;
+    pub fn cblx_bubbles_mark_device(ctx: *mut cblx_ctx, max_kmers: u64, d_counts: *const u32, n_counts: u64, d_kind: *mut u8, cap_unitigs: u64, n_unitigs: *mut u64, counts: *mut u64) -> c_int;
+    pub fn cblx_pop_bubbles(ctx: *mut cblx_ctx, max_kmers: u64, d_counts: *mut u32, n_counts: u64, flags: u32, max_rounds: u32, stats: *mut cblx_bubble_stats) -> c_int;
     pub fn cblx_list_range(ctx: *mut cblx_ctx, first: u64, n: u64, buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_range_device(ctx: *mut cblx_ctx, first: u64, n: u64, d_buf: *mut u8, cap: u64, written_bytes: *mut u64) -> c_int;
     pub fn cblx_list_to_fd(ctx: *mut cblx_ctx, fd: c_int, chunk_kmers: u64, n_kmers: *mut u64) -> c_int;
